@@ -530,6 +530,12 @@ def gen_inbatch(rh):
         out[f"B{B}_k{k}_seed{seed}.0"], out[f"B{B}_k{k}_seed{seed}.1"] = npy(first), npy(second)
     np.savez_compressed(os.path.join(OUT, "inbatch_random.npz"), **out)
     print("inbatch_random.npz", len(out), "arrays")
+    more = {}
+    for B, k, seed in [(5, 2, 11), (17, 16, 12), (40, 7, 13)]:  # one call each, k up to B - 1
+        more[f"B{B}_k{k}_seed{seed}"] = npy(inbatch_negative_sampling(torch.zeros((B, B)), neg_ratio=k,
+                                                                       generator=torch.Generator().manual_seed(seed)))
+    np.savez_compressed(os.path.join(OUT, "inbatch_random_more.npz"), **more)
+    print("inbatch_random_more.npz", len(more), "arrays")
 
 
 CONFIGS = ["deepfm_tutorial", "deepfm_criteo", "widedeep", "dcn", "dcnv2_mix", "dcnv2_full_stacked", "din",

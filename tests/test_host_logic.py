@@ -250,15 +250,15 @@ def test_inbatch_random_stream_is_the_references_bit_for_bit():
         random_inbatch_negatives(3, 4, torch.device("cpu"), row_offset=2)
 
 
-def test_inbatch_random_stream_against_the_live_reference():
-    from oracle.ref_import import available, import_reference
-    if not available():
-        pytest.skip("reference checkout not present (GPU box)")
-    import_reference()
-    from torch_rechub.utils.match import inbatch_negative_sampling as ref_fn
+def test_inbatch_random_stream_against_recorded_reference_draws():
+    """Three more shapes, one call each: the unmodified reference's draws recorded by oracle/gen_golden.py::gen_inbatch
+    in tests/golden/inbatch_random_more.npz."""
     from torch_rechub_amd.utils.match import inbatch_negative_sampling
-    for B, k, seed in [(5, 2, 11), (17, 16, 12), (40, 7, 13)]:
-        a = ref_fn(torch.zeros(B, B), neg_ratio=k, generator=torch.Generator().manual_seed(seed))
+    gold = load_golden("inbatch_random_more.npz")
+    cases = [(5, 2, 11), (17, 16, 12), (40, 7, 13)]
+    assert sorted(gold.files) == sorted(f"B{B}_k{k}_seed{seed}" for B, k, seed in cases)
+    for B, k, seed in cases:
+        a = torch.from_numpy(gold[f"B{B}_k{k}_seed{seed}"])
         b = inbatch_negative_sampling(torch.zeros(B, B), neg_ratio=k, generator=torch.Generator().manual_seed(seed))
         assert torch.equal(a, b)
 
@@ -486,6 +486,24 @@ def test_bench_lazy_k_default_follows_the_trainers_rule(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py", "--batch", "32768", "--lazy-k", "96"])
     a = bench.parse()
     assert a.lazy_k == 96 and a.lazy_k_explicit is True
+
+
+def test_bench_plain_full_and_dump_arguments(monkeypatch):
+    """bench.py: a plain run is the default, --full opts into the extra passes, --dump-outputs takes a directory; --steps
+    below 1 and --dump-outputs with --full (the dump resets the trainer the --full passes check) are refused."""
+    import sys
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    assert bench.parse().full is True
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--dump-outputs", "out"])
+    assert bench.parse().dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--full", "--dump-outputs", "out"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + bad)
+        with pytest.raises(SystemExit):
+            bench.parse()
 
 
 def test_step_form_candidates_carry_form_grid_and_hold_back():

@@ -1,11 +1,11 @@
 """INTEGRATION.md section B executed for real: ``torch_rechub_amd.integration.enable()`` against the imported,
-UNMODIFIED reference package (only present in the build container; skipped on the GPU box)."""
+UNMODIFIED reference package, a checkout outside this repository (RECHUB_REFERENCE): the module skips where it is absent."""
 import pytest
 import torch
 
 from oracle.ref_import import available, import_reference
 
-pytestmark = pytest.mark.skipif(not available(), reason="reference checkout not present (GPU box)")
+pytestmark = pytest.mark.skipif(not available(), reason="needs the unmodified reference torch_rechub package (RECHUB_REFERENCE): not present")
 
 
 @pytest.fixture()

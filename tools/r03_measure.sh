@@ -8,10 +8,10 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp PYTHONUNBUFFERED=1
 STAGES=${STAGES:-"bench bench300 prof pmc"}
 for s in $STAGES; do case $s in
-bench) echo "== bench default (driver's command)"; ( time timeout 600 python bench.py --steps 20 --warmup 10 > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" ) 2>&1 | grep real; echo "rc=$?";;
-bench300) echo "== bench 300"; timeout 300 python bench.py --steps 300 --warmup 10 --no-cpu-baseline --brief > "$OUT/bench_300.json" 2> "$OUT/bench_300.err"; echo "rc=$?";;
+bench) echo "== bench default (--full)"; ( time timeout 600 python bench.py --full --steps 20 --warmup 10 > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" ) 2>&1 | grep real; echo "rc=$?";;
+bench300) echo "== bench 300"; timeout 300 python bench.py --full --steps 300 --warmup 10 --no-cpu-baseline --brief > "$OUT/bench_300.json" 2> "$OUT/bench_300.err"; echo "rc=$?";;
 prof) echo "== rocprof kernel stats of the default command"
-  (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OLDPWD/$OUT/prof" -o bench -- python "$OLDPWD/bench.py" --steps 20 --warmup 10 --no-cpu-baseline --brief > "$OLDPWD/$OUT/prof_bench.json" 2> "$OLDPWD/$OUT/prof.err"); echo "rc=$?"
+  (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OLDPWD/$OUT/prof" -o bench -- python "$OLDPWD/bench.py" --full --steps 20 --warmup 10 --no-cpu-baseline --brief > "$OLDPWD/$OUT/prof_bench.json" 2> "$OLDPWD/$OUT/prof.err"); echo "rc=$?"
   python tools/prof_summary.py "$OUT/prof" > "$OUT/prof_summary.txt" 2>&1
   cp "$OUT"/prof/*kernel_stats.csv "$OUT/kernel_stats.csv" 2>/dev/null
   (cd /tmp && rm -rf /tmp/tl_r03 && timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/tl_r03 -o t -- python "$OLDPWD/bench.py" --trace-inner --steps 30 --warmup 10 --rows 4000000 > /dev/null 2> "$OLDPWD/$OUT/tl.err"); python tools/timeline.py /tmp/tl_r03 2 > "$OUT/step_timeline.txt" 2>&1

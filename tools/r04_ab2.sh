@@ -4,7 +4,7 @@ out=$1; shift; mkdir -p $out
 for spec in "$@"; do
   IFS='|' read -r tag envs args <<< "$spec"
   envs=$(echo "$envs" | tr ';' ' ')
-  env $envs timeout 300 python bench.py --steps 200 --warmup 10 --no-cpu-baseline --brief --no-kernel-sweep --no-step-accounting $args > $out/$tag.json 2> $out/$tag.err
+  env $envs timeout 300 python bench.py --full --steps 200 --warmup 10 --no-cpu-baseline --brief --no-kernel-sweep --no-step-accounting $args > $out/$tag.json 2> $out/$tag.err
   python - <<PY
 import json
 try:

@@ -45,7 +45,7 @@ tests) for i in $(seq 1 ${TESTS_REPEAT:-1}); do
 testsall) timeout 1500 python -m pytest tests -m gpu -q > "$OUT/pytest_gpu_all.log" 2>&1; echo "rc=$?"; grep -E "^(FAILED|ERROR)|passed|failed" "$OUT/pytest_gpu_all.log" | tail -40;;
 probe) timeout 600 python tools/bitwise_probe.py ${PROBE_ARGS:-} > "$OUT/bitwise_probe.txt" 2> "$OUT/bitwise_probe.err"; echo "rc=$?"; grep -v "^ " "$OUT/bitwise_probe.txt" | tail -40; tail -5 "$OUT/bitwise_probe.err";;
 noise) timeout 600 python tools/noise_budget.py --runs ${NOISE_RUNS:-24} > "$OUT/noise_budget.txt" 2> "$OUT/noise_budget.err"; echo "rc=$?"; tail -30 "$OUT/noise_budget.txt"; tail -3 "$OUT/noise_budget.err";;
-bench) ( time timeout 900 python bench.py --steps 20 --warmup 5 > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" ) 2>&1 | grep real; echo "rc=$?"
+bench) ( time timeout 900 python bench.py --full --steps 20 --warmup 5 > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" ) 2>&1 | grep real; echo "rc=$?"
   python - "$OUT/bench_default.json" <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -56,13 +56,13 @@ acct=d.get("step_accounting") or {}
 print("acct", {k:acct.get(k) for k in ("wall_us_per_step","groups")})
 PY
   tail -5 "$OUT/bench_default.err";;
-bench300) timeout 400 python bench.py --steps 300 --warmup 10 --no-cpu-baseline --brief ${BENCH300_ARGS:-} > "$OUT/bench_300.json" 2> "$OUT/bench_300.err"; echo "rc=$?"; python -c "
+bench300) timeout 400 python bench.py --full --steps 300 --warmup 10 --no-cpu-baseline --brief ${BENCH300_ARGS:-} > "$OUT/bench_300.json" 2> "$OUT/bench_300.err"; echo "rc=$?"; python -c "
 import json,sys; d=json.loads(open('$OUT/bench_300.json').read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d.get('dense_twin_check'))";;
 dp) for pl in replicate shard; do
-    timeout 400 python bench.py --force-dp --tables $pl --steps 100 --warmup 10 --no-cpu-baseline --brief > "$OUT/bench_dp_$pl.json" 2> "$OUT/bench_dp_$pl.err"; echo "dp $pl rc=$?"
+    timeout 400 python bench.py --full --force-dp --tables $pl --steps 100 --warmup 10 --no-cpu-baseline --brief > "$OUT/bench_dp_$pl.json" 2> "$OUT/bench_dp_$pl.err"; echo "dp $pl rc=$?"
     python -c "
 import json,sys; d=json.loads(open('$OUT/bench_dp_$pl.json').read().strip().splitlines()[-1]); print('$pl', d['value'], d['ms_per_step'], d.get('comm_us_per_step'))" || tail -5 "$OUT/bench_dp_$pl.err"; done;;
-prof) (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OLDPWD/$OUT/prof" -o bench -- python "$OLDPWD/bench.py" --steps 20 --warmup 5 --no-cpu-baseline --brief --no-twin-check > "$OLDPWD/$OUT/prof_bench.json" 2> "$OLDPWD/$OUT/prof.err"); echo "rc=$?"
+prof) (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OLDPWD/$OUT/prof" -o bench -- python "$OLDPWD/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline --brief --no-twin-check > "$OLDPWD/$OUT/prof_bench.json" 2> "$OLDPWD/$OUT/prof.err"); echo "rc=$?"
   python tools/prof_summary.py "$OUT/prof" > "$OUT/prof_summary.txt" 2>&1; head -30 "$OUT/prof_summary.txt"
   cp "$OUT"/prof/*kernel_stats.csv "$OUT/kernel_stats.csv" 2>/dev/null
   (cd /tmp && rm -rf /tmp/tl_r05 && timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/tl_r05 -o t -- python "$OLDPWD/bench.py" --trace-inner --steps 30 --warmup 10 --rows 4000000 > /dev/null 2> "$OLDPWD/$OUT/tl.err"); python tools/timeline.py /tmp/tl_r05 2 > "$OUT/step_timeline.txt" 2>&1
@@ -90,9 +90,9 @@ for st,en,n,q in rows[lo:hi]:
 PY
   head -60 "$OUT/dp_${pl}_step_kernels.txt"; done;;
 sweepalone) timeout 300 python tools/sweep_alone_probe.py ${SWEEP_K:-128} > "$OUT/sweep_alone.txt" 2> "$OUT/sweep_alone.err"; echo "rc=$?"; cat "$OUT/sweep_alone.txt";;
-twin) timeout 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --brief --twin-repeat --no-kernel-sweep > "$OUT/bench_twin.json" 2> "$OUT/bench_twin.err"; echo "rc=$?"; grep "dense twin check" "$OUT/bench_twin.err" | tail -2; tail -3 "$OUT/bench_twin.err";;
+twin) timeout 400 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --brief --twin-repeat --no-kernel-sweep > "$OUT/bench_twin.json" 2> "$OUT/bench_twin.err"; echo "rc=$?"; grep "dense twin check" "$OUT/bench_twin.err" | tail -2; tail -3 "$OUT/bench_twin.err";;
 sec) for m in ${MODELS:-dssm dcnv2 din}; do
-    timeout 400 python bench.py --model $m --steps 30 --warmup 5 --no-cpu-baseline --brief > "$OUT/bench_$m.json" 2> "$OUT/bench_$m.err"; echo "$m rc=$?"
+    timeout 400 python bench.py --full --model $m --steps 30 --warmup 5 --no-cpu-baseline --brief > "$OUT/bench_$m.json" 2> "$OUT/bench_$m.err"; echo "$m rc=$?"
     python -c "
 import json; d=json.loads(open('$OUT/bench_$m.json').read().strip().splitlines()[-1]); print('$m', d['ms_per_step'], d['config'].get('step_form'))" || tail -5 "$OUT/bench_$m.err"; done;;
 models) for m in ${MODELS:-dcnv2 din dssm}; do model_table $m > "$OUT/${m}_step_kernels.txt" 2>&1; head -3 "$OUT/${m}_step_kernels.txt"; done;;

@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp PYTHONUNBUFFERED=1
 OUT=gpurun_out/r05_dp24; mkdir -p $OUT
 run() { tag=$1; envs=$2; shift 2
-  env $envs timeout 200 python bench.py --force-dp --tables shard --steps 150 --warmup 10 --no-cpu-baseline --brief --no-kernel-sweep --no-step-accounting --no-pmc --no-twin-check "$@" > $OUT/$tag.json 2> $OUT/$tag.err
+  env $envs timeout 200 python bench.py --full --force-dp --tables shard --steps 150 --warmup 10 --no-cpu-baseline --brief --no-kernel-sweep --no-step-accounting --no-pmc --no-twin-check "$@" > $OUT/$tag.json 2> $OUT/$tag.err
   python - <<PY
 import json
 try:

@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp PYTHONUNBUFFERED=1
 OUT=gpurun_out/r05_rep; mkdir -p $OUT
 for n in 8 4; do
-  RECHUB_EMULATE_WORLD=$n timeout 150 python bench.py --force-dp --tables replicate --steps 150 --warmup 10 --no-cpu-baseline --brief --no-kernel-sweep --no-step-accounting --no-pmc --no-twin-check > $OUT/rep_$n.json 2> $OUT/rep_$n.err
+  RECHUB_EMULATE_WORLD=$n timeout 150 python bench.py --full --force-dp --tables replicate --steps 150 --warmup 10 --no-cpu-baseline --brief --no-kernel-sweep --no-step-accounting --no-pmc --no-twin-check > $OUT/rep_$n.json 2> $OUT/rep_$n.err
   python - <<PY
 import json
 try:

@@ -57,27 +57,27 @@ for s in $STAGES; do echo "=== stage $s $(date +%T)"; case $s in
 integ) RECHUB_REFERENCE=$PWD/_refmount timeout 900 python -m pytest -m gpu tests/test_integration_patch.py -v > "$OUT/integration_gpu.log" 2>&1; echo "rc=$?"; tail -15 "$OUT/integration_gpu.log";;
 tests) timeout 1500 python -m pytest tests -m gpu -x -q > "$OUT/pytest_gpu.log" 2>&1; echo "rc=$?"; tail -5 "$OUT/pytest_gpu.log";;
 testsel) timeout 1200 python -m pytest -m gpu -x -q ${TEST_SEL:-tests} ${TEST_K:+-k "$TEST_K"} > "$OUT/pytest_sel${SELTAG:-}.log" 2>&1; echo "rc=$?"; tail -15 "$OUT/pytest_sel${SELTAG:-}.log";;
-bench) ( time timeout 900 python bench.py --steps 20 --warmup 5 > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" ) 2>&1 | grep real
+bench) ( time timeout 900 python bench.py --full --steps 20 --warmup 5 > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" ) 2>&1 | grep real
   brief "$OUT/bench_default.json"; tail -5 "$OUT/bench_default.err";;
-bench300) timeout 400 python bench.py --steps 300 --warmup 10 --no-cpu-baseline --brief ${BENCH300_ARGS:-} > "$OUT/bench_300.json" 2> "$OUT/bench_300.err"; echo "rc=$?"; brief "$OUT/bench_300.json";;
+bench300) timeout 400 python bench.py --full --steps 300 --warmup 10 --no-cpu-baseline --brief ${BENCH300_ARGS:-} > "$OUT/bench_300.json" 2> "$OUT/bench_300.err"; echo "rc=$?"; brief "$OUT/bench_300.json";;
 timeline) (cd /tmp && rm -rf /tmp/tl_r06 && timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/tl_r06 -o t -- python "$OLDPWD/bench.py" --trace-inner --steps 30 --warmup 10 --rows 4000000 ${TL_ARGS:-} > /dev/null 2> "$OLDPWD/$OUT/tl.err"); python tools/timeline.py /tmp/tl_r06 2 > "$OUT/step_timeline${TLTAG:-}.txt" 2>&1; head -40 "$OUT/step_timeline${TLTAG:-}.txt";;
-prof) (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OLDPWD/$OUT/prof" -o bench -- python "$OLDPWD/bench.py" --steps 20 --warmup 5 --no-cpu-baseline --brief --no-twin-check > "$OLDPWD/$OUT/prof_bench.json" 2> "$OLDPWD/$OUT/prof.err"); echo "rc=$?"
+prof) (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OLDPWD/$OUT/prof" -o bench -- python "$OLDPWD/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline --brief --no-twin-check > "$OLDPWD/$OUT/prof_bench.json" 2> "$OLDPWD/$OUT/prof.err"); echo "rc=$?"
   python tools/prof_summary.py "$OUT/prof" > "$OUT/prof_summary.txt" 2>&1; head -30 "$OUT/prof_summary.txt"
   cp "$OUT"/prof/*kernel_stats.csv "$OUT/kernel_stats.csv" 2>/dev/null
   find "$OUT/prof" -name '*kernel_trace.csv' -size +20M -delete;;
 dp) for pl in replicate shard; do
-    timeout 400 python bench.py --force-dp --tables $pl --steps 100 --warmup 10 --no-cpu-baseline --brief > "$OUT/bench_dp_$pl.json" 2> "$OUT/bench_dp_$pl.err"; echo "dp $pl rc=$?"
+    timeout 400 python bench.py --full --force-dp --tables $pl --steps 100 --warmup 10 --no-cpu-baseline --brief > "$OUT/bench_dp_$pl.json" 2> "$OUT/bench_dp_$pl.err"; echo "dp $pl rc=$?"
     brief "$OUT/bench_dp_$pl.json" || tail -5 "$OUT/bench_dp_$pl.err"; done;;
 dptrace) for pl in ${DP_PLACEMENTS:-shard replicate}; do
   (cd /tmp && rm -rf /tmp/dp_prof_$pl && MASTER_ADDR=127.0.0.1 MASTER_PORT=29577 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/dp_prof_$pl -o dp -- python $OLDPWD/bench.py --force-dp --tables $pl --trace-inner --steps 10 --warmup 5 --rows 4000000 ${DP_ARGS:-} > /dev/null 2> $OLDPWD/$OUT/dp_prof_$pl.err)
   python tools/timeline.py /tmp/dp_prof_$pl 2 > "$OUT/dp_${pl}_step_timeline.txt" 2>&1; head -45 "$OUT/dp_${pl}_step_timeline.txt"; done;;
 models) for m in $MODELS; do model_table $m > "$OUT/${m}_step_kernels.txt" 2>&1; head -45 "$OUT/${m}_step_kernels.txt"; done;;
-modelbench) for m in $MODELS; do timeout 300 python bench.py --model $m --steps 100 --warmup 10 --no-cpu-baseline --brief > "$OUT/bench_$m.json" 2> "$OUT/bench_$m.err"; echo "$m rc=$?"; brief "$OUT/bench_$m.json"; done;;
+modelbench) for m in $MODELS; do timeout 300 python bench.py --full --model $m --steps 100 --warmup 10 --no-cpu-baseline --brief > "$OUT/bench_$m.json" 2> "$OUT/bench_$m.err"; echo "$m rc=$?"; brief "$OUT/bench_$m.json"; done;;
 ab) IFS=' ' read -r -a cases <<< "${AB_CASES:-base||}"
   for rep in $(seq 1 ${AB_REPEAT:-2}); do for c in "${cases[@]}"; do
     name=${c%%|*}; rest=${c#*|}; envs=${rest%%|*}; args=${rest#*|}; args=${args//;/ }  # (bench args: ';' for ' ')
     ( IFS=';'; for e in $envs; do [ -n "$e" ] && export "$e"; done; unset IFS
-      timeout 300 python bench.py --steps ${AB_STEPS:-200} --warmup 10 --no-cpu-baseline --brief --no-kernel-sweep --no-step-accounting --no-pmc --no-twin-check $args > "$OUT/ab_${name}_$rep.json" 2> "$OUT/ab_${name}_$rep.err" )
+      timeout 300 python bench.py --full --steps ${AB_STEPS:-200} --warmup 10 --no-cpu-baseline --brief --no-kernel-sweep --no-step-accounting --no-pmc --no-twin-check $args > "$OUT/ab_${name}_$rep.json" 2> "$OUT/ab_${name}_$rep.err" )
     python - "$OUT/ab_${name}_$rep.json" "$name" "$rep" <<'PY' | tee -a "$OUT/ab_table.txt"
 import json,sys
 try:
