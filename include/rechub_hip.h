@@ -747,6 +747,43 @@ int rh_augru_fwd(const float* xw, const float* attn, const float* U, const float
 int rh_augru_bwd(const float* xw, const float* attn, const float* U, const float* state_bias, const float* h_all,
                  const float* g_hall, int B, int T, int D, float* d_xw, float* d_huh, float* d_attn, void* stream);
 
+/* ---- field-aware FM (DeepFFM / FAT-DeepFFM) ------------------------------------------------------------------------
+ * F fields (2 .. 64), P = F(F-1)/2 pairs in the reference's order (i outer, j > i inner), D logical width (1 .. 128),
+ * Dp physical row width of the tables (D <= Dp <= 128: PaddedEmbedding).  Pair side (i, j) is row x_i * F + j of field
+ * i's table.  Two row-addressing modes, one kernel each way:
+ *   table mode (fdesc, idesc as above, x = null): the raw (B,) index columns of the F fields;
+ *   dense mode (fdesc = idesc = null, x (B, F, F, D) with sample stride x_stride): the layer-level FFM.
+ * rh_ffm_fwd: out[b, p*D + d] = row(i,j)[d] * row(j,i)[d] (one product: bit-exact), or with reduce_sum out[b, p] = the sum
+ *   over d; row stride out_stride.  An index whose row falls outside [0, vocab) sets RH_FLAG_INDEX_OOB.
+ * rh_ffm_bwd: g (B, P*D) or (B, P) with reduce_sum, row stride g_stride.  Table mode: g * row(j,i) float-atomically added
+ *   to row (i,j) of field i's gradient buffer (fdesc[F + i]; logical columns only, rows at padding_idx dropped), or with
+ *   sink = 1 written to rows (B, F(F-1), Dp) at virtual field v(i,j) = i(F-1) + (j < i ? j : j - 1), padding columns 0.
+ *   Dense mode: g_x (B, F, F, D), sample stride gx_stride, every element written once (diagonal 0).
+ * rh_ffm_expand_index: out (B, F(F-1)) of the index dtype = x_i * F + j at v(i,j): the lookups of the table mode as
+ *   ordinary index columns (optimizer touch records, the data-parallel exchange).
+ * replaces: DeepFFM.forward torch_rechub/models/ranking/deepffm.py:57-62 (x * F + fields_offset, (B, F, F, D) lookup),
+ *           FFM.forward torch_rechub/basic/layers.py:736-746 and their autograd. */
+int rh_ffm_expand_index(const int64_t* idesc, int idx_is_i64, int B, int F, void* out, void* stream);
+int rh_ffm_fwd(const int64_t* fdesc, const int64_t* idesc, int idx_is_i64, const float* x, int64_t x_stride, int B, int F,
+               int D, int Dp, int reduce_sum, float* out, int64_t out_stride, int32_t* err_flag, void* stream);
+int rh_ffm_bwd(const int64_t* fdesc, const int64_t* idesc, int idx_is_i64, const float* x, int64_t x_stride, int B, int F,
+               int D, int Dp, int reduce_sum, const float* g, int64_t g_stride, float* g_x, int64_t gx_stride, int sink,
+               float* rows, int32_t* err_flag, void* stream);
+/* CEN field attention on em (B, P*D), row stride ld (FAT-DeepFFM).
+ * rh_cen_desc_fwd: d (B, P) = relu(sum_d u[p,d] em[b,p,d]).
+ * rh_cen_desc_bwd: g_em (B, P*D) contiguous = relu'(d) g_d u; u_partial (rh_cen_nchunks(B), P*D) per-chunk sums of
+ *   relu'(d) g_d em over consecutive samples in a fixed order (g_u = rh_colsum of it: bitwise reproducible).
+ * rh_cen_rescale_fwd: out (B, P*D) contiguous = s[b,p] em[b,p,:].
+ * rh_cen_rescale_bwd: g_em (B, P*D) contiguous = s g; g_s (B, P) = sum_d g em.  g row stride ldg.
+ * replaces: CEN.forward torch_rechub/basic/layers.py:777-786 (the attention MLP between d and s stays an MLP). */
+int rh_cen_nchunks(int B);
+int rh_cen_desc_fwd(const float* em, int64_t ld, const float* u, int B, int P, int D, float* d_out, void* stream);
+int rh_cen_desc_bwd(const float* em, int64_t ld, const float* u, const float* d, const float* g_d, int B, int P, int D,
+                    float* g_em, float* u_partial, void* stream);
+int rh_cen_rescale_fwd(const float* em, int64_t ld, const float* s, int B, int P, int D, float* out, void* stream);
+int rh_cen_rescale_bwd(const float* em, int64_t ld, const float* s, const float* g, int64_t ldg, int B, int P, int D,
+                       float* g_em, float* g_s, void* stream);
+
 /* ---- row-sharded tables (one shard per rank) -----------------------------------------------------------------------
  * Global row g of a table lives on rank g % world as local row g / world.  rh_shard_localize rewrites an index matrix
  * idx (n_rows, F) (int64 / int32, contiguous: the all-gathered indices of the global batch) for this rank's shards:

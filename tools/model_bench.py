@@ -5,6 +5,10 @@
   dien / bst  : the same tables and histories through DIEN (GRU + AUGRU recurrences, auxiliary loss) / BST (1 encoder layer)
   dssm        : configs[4] shape (100 M-item + 10 M-user tables, history L=50 mean-pooled, towers [256,128,64] prelu,
                 in-batch negatives)
+  deepffm / fatdeepffm : the Criteo example's DeepFFM / FAT-DeepFFM (examples/ranking/run_criteo.py:77-80: 26 sparse fields,
+                field-aware tables of v * 26 rows x 10, width-1 linear tables, MLP [1600, 1600] dropout 0.5); --scale 0.04
+                gives field-aware tables of about as many rows as the DeepFM headline's.  Also times a plain-PyTorch eager
+                restatement of the same model on the same GPU (nn.Embedding lookups, indexed pair products, torch.optim.Adam).
     python tools/model_bench.py --models dcn,dcnv2,din,dssm --steps 30
 """
 import argparse
@@ -80,10 +84,70 @@ def build(name, dev, B, scale):
              "hist_item": torch.randint(1, ni, (B, L), device=dev, generator=g).masked_fill(pad, 0)}
         trainer = MatchTrainer(model, mode=0, in_batch_neg=True, in_batch_neg_ratio=20, device=str(dev),
                                show_progress=False)
+    elif name in ("deepffm", "fatdeepffm"):
+        from torch_rechub_amd.models.ranking import DeepFFM, FatDeepFFM
+        vocabs = [max(3, int(v * scale)) for v in CRITEO_VOCABS]
+        F = len(vocabs)
+        linear = [SparseFeature(f"C{i}", v, 1) for i, v in enumerate(vocabs)]
+        cross = [SparseFeature(f"C{i}", v * F, 10) for i, v in enumerate(vocabs)]
+        ffm_mlp = {"dims": [1600, 1600], "dropout": 0.5, "activation": "relu"}
+        with torch.device(dev):
+            model = DeepFFM(linear, cross, 10, ffm_mlp) if name == "deepffm" else FatDeepFFM(linear, cross, 10, 3, ffm_mlp)
+        x = {f.name: torch.randint(0, v, (B,), device=dev, generator=g) for f, v in zip(linear, vocabs)}
+        trainer = CTRTrainer(model, device=str(dev), show_progress=False)
     else:
         raise ValueError(name)
     y = (torch.rand(B, device=dev, generator=g) < 0.25).float()
     return trainer, x, y
+
+
+def torch_ffm_ms(name, dev, B, scale, steps):
+    """ms/step of a plain-PyTorch eager DeepFFM / FAT-DeepFFM train step at the same shape (the comparison line)."""
+    from torch import nn
+    vocabs = [max(3, int(v * scale)) for v in CRITEO_VOCABS]
+    F, D = len(vocabs), 10
+    I, J = torch.triu_indices(F, F, 1, device=dev)
+    P = I.numel()
+    lin = nn.ModuleList([nn.Embedding(v, 1) for v in vocabs]).to(dev)
+    ffm = nn.ModuleList([nn.Embedding(v * F, D) for v in vocabs]).to(dev)
+
+    def blocks(d_in, dims, p_drop):
+        out = []
+        for a, w in zip([d_in] + dims, dims):
+            out += [nn.Linear(a, w), nn.BatchNorm1d(w), nn.ReLU(), nn.Dropout(p_drop)]
+        return out
+
+    mlp = nn.Sequential(*blocks(P * D, [1600, 1600], 0.5), nn.Linear(1600, 1)).to(dev)
+    fat = name == "fatdeepffm"
+    u = nn.Parameter(torch.rand(P, D, device=dev))
+    att = nn.Sequential(*blocks(P, [P // 3, P], 0.0)).to(dev)
+    params = list(lin.parameters()) + list(ffm.parameters()) + list(mlp.parameters()) + ([u] + list(att.parameters()) if fat else [])
+    opt = torch.optim.Adam(params, lr=1e-3)
+    g = torch.Generator(device=dev).manual_seed(0)
+    x = torch.stack([torch.randint(0, v, (B,), device=dev, generator=g) for v in vocabs], 1)
+    y = (torch.rand(B, device=dev, generator=g) < 0.25).float()
+    off = torch.arange(F, device=dev)
+
+    def step():
+        y_lin = sum(t(x[:, f]) for f, t in enumerate(lin))
+        e = torch.stack([t(x[:, f:f + 1] * F + off) for f, t in enumerate(ffm)], 1)  # (B, F, F, D)
+        em = e[:, I, J] * e[:, J, I]
+        if fat:
+            em = att(torch.relu((u * em).sum(-1))).unsqueeze(-1) * em
+        p = torch.sigmoid((mlp(em.flatten(1)) + y_lin).squeeze(1))
+        loss = nn.functional.binary_cross_entropy(p, y)
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+
+    for _ in range(3):
+        step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        step()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / steps * 1e3
 
 
 def main():
@@ -147,6 +211,10 @@ def main():
         from torch_rechub_amd import ops
         ops.check_errors()
         del trainer, x, y
+        if name in ("deepffm", "fatdeepffm"):
+            torch.cuda.empty_cache()
+            ms = torch_ffm_ms(name, dev, a.batch, a.scale, a.steps)
+            print(f"{name:6s} B={a.batch} plain PyTorch eager {ms:8.3f} ms/step ({a.batch / ms:9.1f} k samples/s)", flush=True)
         torch.cuda.reset_peak_memory_stats()
 
 

@@ -12,6 +12,8 @@
 | CrossNetwork     | :390-420                    | ops.cross_network: one wavefront per sample, all layers in registers |
 | CrossNetV2       | :423-444                    | library GEMM + ONE fused Hadamard/bias/residual kernel (ops.cross_v2_epilogue) |
 | CrossNetMix      | :447-506                    | experts batched into 3 GEMMs per layer (was 150 mm per step) + ONE fused bias/Hadamard/gate-mix/residual kernel |
+| FFM              | :736-746                    | ops.ffm: one pass each way over the (B, F, F, D) input (DeepFFM fuses it into the lookup) |
+| CEN              | :777-786                    | descriptor and rescale kernels (ops.cen_descriptor / cen_rescale) around the attention MLP |
 
 Tables stay ``nn.Embedding`` modules inside ``embed_dict`` (checkpoint ABI:
 ``embedding.embed_dict.<feature>.weight``); kernels read them in place.
@@ -184,6 +186,8 @@ class EmbeddingLayer(nn.Module):
             return False
         for fea in features:
             if isinstance(fea, SparseFeature):
+                if x[fea.name].dim() != 1:
+                    return False  # (B, K) indices: forward's multi-lookup path
                 dims.add(self.phys_dim(fea))
             elif isinstance(fea, SequenceFeature):
                 return False
@@ -210,6 +214,43 @@ class EmbeddingLayer(nn.Module):
         """(B, F*D) rows of row-sharded tables for the local batch (index all-gather, shard gather, reduce-scatter)."""
         return sharding.lookup([self.table_of(f) for f in sparse_feas], [_as_index(x[f.name]) for f in sparse_feas])
 
+    def _multi_lookup(self, x, table_feas, dense_feas, squeeze_dim):
+        """(B, K) index per sparse feature (the field-aware lookup of the reference's DeepFFM, deepffm.py:57-58): (B, n, K, D),
+        flattened for squeeze_dim.  ONE fused gather launch over n*K columns, each table repeated K times.  The indices
+        are usually computed inside the step (x * F + offset), so the gather is announced as not replayable (EmbedCall)."""
+        idx = [_as_index(x[f.name]) if isinstance(f, SparseFeature) else None for f in table_feas]
+        if any(t is None or t.dim() != 2 for t in idx) or len({t.shape[1] for t in idx}) != 1:
+            raise ValueError("torch_rechub_amd: (B, K) indices need every table feature to be a SparseFeature with the same K")
+        if len({f.embed_dim for f in table_feas}) != 1 or len({self.phys_dim(f) for f in table_feas}) != 1:
+            raise RuntimeError("torch_rechub_amd: a (B, K) lookup needs one embed_dim across its features")
+        if self.is_sharded(table_feas):
+            raise RuntimeError("torch_rechub_amd: (B, K) lookups on row-sharded tables are not supported")
+        dim = self.phys_dim(table_feas[0])
+        if not _fusable_dim(dim):
+            raise RuntimeError(f"torch_rechub_amd: embed_dim={dim} has no HIP gather kernel")
+        K = int(idx[0].shape[1])
+        feas = [f for f in table_feas for _ in range(K)]
+        # the indices land in ONE buffer owned by this layer (its address, hence its cached descriptor, stays fixed from the
+        # eager steps into a hipGraph capture, where the computed index tensor lives elsewhere): one (B, K) lookup per layer
+        # and step -- the backward reads the indices from it
+        B = int(idx[0].shape[0])
+        key = (B, len(idx), K, idx[0].dtype, str(idx[0].device))
+        buf = self.__dict__.setdefault("_bk_index", {}).get(key)
+        if buf is None:
+            if idx[0].is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("torch_rechub_amd: run the step eagerly once before capturing a hipGraph")
+            buf = self._bk_index[key] = torch.empty((B, len(idx), K), dtype=idx[0].dtype, device=idx[0].device)
+        buf.copy_(torch.stack(idx, 1))
+        call = ops.EmbedCall([self.table_of(f).weight for f in feas], [self.table_of(f).padding_idx for f in feas],
+                             [buf[:, n, k] for n in range(len(idx)) for k in range(K)], replay=False)
+        out, _, _ = ops.fused_embedding(call)
+        out = self.compact(out, feas)
+        if not squeeze_dim:
+            return out.reshape(out.shape[0], len(table_feas), K, table_feas[0].embed_dim)
+        if dense_feas:
+            return torch.cat([out] + self._dense_columns(x, dense_feas), dim=1)
+        return out
+
     def pieces(self, x, features):
         """The per-feature tensors of ``forward(x, features)`` as a list -- (B, D) per sparse feature, (B, L, D) per
         concat-pooled sequence feature -- for callers that take the (B, n, ...) result apart again feature by feature
@@ -233,6 +274,8 @@ class EmbeddingLayer(nn.Module):
             raise ValueError("If keep the original shape:[batch_size, num_features, embed_dim], expected %s in feature "
                              "list, got %s" % ("SparseFeatures", features))
 
+        if any(isinstance(f, SparseFeature) and x[f.name].dim() == 2 for f in table_feas):
+            return self._multi_lookup(x, table_feas, dense_feas, squeeze_dim)
         if self.can_fuse(x, features):
             sparse = table_feas
             out, _, _ = self.fused(x, sparse, dense_feas if squeeze_dim else ())
@@ -438,6 +481,35 @@ class FM(nn.Module):
 
     def forward(self, x):
         return ops.fm(x, self.reduce_sum)
+
+
+class FFM(nn.Module):
+    """Field-aware pairwise products of a (B, F, F, D) input: (B, P, D), or (B, P, 1) with reduce_sum (reference
+    layers.py:714-746).  One HIP pass each way (ops.ffm); DeepFFM's fused path never builds the input at all."""
+
+    def __init__(self, num_fields, reduce_sum=True):
+        super().__init__()
+        self.num_fields = num_fields
+        self.reduce_sum = reduce_sum
+
+    def forward(self, x):
+        return ops.ffm(x, self.reduce_sum)
+
+
+class CEN(nn.Module):
+    """Compose-Excitation Network field attention of FAT-DeepFFM (reference layers.py:749-786): d = relu(sum_d u * em),
+    s = mlp_att(d), aem = s * em flattened to (B, P*D).  ``u`` and ``mlp_att.mlp.*`` are the reference's parameters."""
+
+    def __init__(self, embed_dim, num_field_crosses, reduction_ratio):
+        super().__init__()
+        self.u = torch.nn.Parameter(torch.rand(num_field_crosses, embed_dim), requires_grad=True)
+        self.mlp_att = MLP(num_field_crosses, dims=[num_field_crosses // reduction_ratio, num_field_crosses],
+                           output_layer=False, activation="relu")
+
+    def forward(self, em):
+        d = ops.cen_descriptor(em, self.u)
+        s = self.mlp_att(d)
+        return ops.cen_rescale(em, s)
 
 
 class CrossNetwork(nn.Module):

@@ -8,6 +8,7 @@ _EXPORTS = {
     "bst": ("BST",),
     "dcn": ("DCN",),
     "dcn_v2": ("DCNv2",),
+    "deepffm": ("DeepFFM", "FatDeepFFM"),
     "deepfm": ("DeepFM",),
     "dien": ("DIEN", "AUGRU", "AUGRU_Cell"),
     "din": ("DIN", "ActivationUnit"),

@@ -190,8 +190,11 @@ class EmbedCall(object):
     _dcache = _DescCache()
 
     def __init__(self, weights, pads, idx, dense=(), want_fm=False, want_lr=False, slots=None, width=None,
-                 field_split=0, samples_per_block=0, local_grads=False):
-        self.local_grads = bool(local_grads)  # True: never hand the gradient rows to the data-parallel exchange
+                 field_split=0, samples_per_block=0, local_grads=False, replay=True):
+        self.local_grads = bool(local_grads)
+        # False: the index columns are computed inside the step (x * F + j of a field-aware lookup), so an optimizer must
+        # not replay this gather's record ahead of the step that recomputes them (optim.TableAdam: ordinary refresh only)
+        self.replay = bool(replay)  # True: never hand the gradient rows to the data-parallel exchange
         self.weights = list(weights)
         self.idx = list(idx)
         self.dense = list(dense)
@@ -282,16 +285,17 @@ def _log_touch(weights, pads, idesc, idx_is_i64, B, F, D, keep):
                           keep=keep))
 
 
-def _pre_gather(weights, pads, idesc, idx_is_i64, B, F, D, training=None, keep=None):
+def _pre_gather(weights, pads, idesc, idx_is_i64, B, F, D, training=None, keep=None, replay=True):
     """``training``: the lookup is part of a differentiated forward (a backward / optimizer step follows).  Inside an
     autograd.Function.forward grad mode is off, so the callers pass ctx.needs_input_grad; None = ask grad mode.
     ``keep``: the index tensor(s) behind ``idesc`` -- a listener that keeps the record (TableAdam's refresh-ahead replays the
-    previous step's records) keeps the memory the descriptor points at alive with it."""
+    previous step's records) keeps the memory the descriptor points at alive with it.
+    ``replay``: False when the index buffer behind ``idesc`` is computed inside the step (EmbedCall.replay)."""
     if training is None:
         training = torch.is_grad_enabled()
     for lst in _listeners():
         lst.on_gather(dict(weights=list(weights), pads=list(pads), idesc=idesc, idx_is_i64=idx_is_i64, B=B, F=F, D=D,
-                           training=bool(training), keep=keep))
+                           training=bool(training), keep=keep, replay=bool(replay)))
 
 
 # data-parallel exchange hook: set by torch_rechub_amd.distributed when world_size > 1
@@ -344,7 +348,7 @@ class _EmbedFused(torch.autograd.Function):
             require_hip(lr_w, lr_b)
         ddesc = call.ddesc()
         _pre_gather(call.weights, call.pads, call.idesc(), call.idx_is_i64, B, F, D, training=any(ctx.needs_input_grad),
-                    keep=call.idx)
+                    keep=call.idx, replay=call.replay)
         _lib.call("rh_embed_fwd", _p(call.fdesc(False)), _p(call.idesc()), call.idx_is_i64, B, F, D, _p(ddesc),
                   len(call.dense), call.dense_col, _p(out), out.stride(0), _p(lr_w if call.want_lr else None),
                   _p(lr_b if call.want_lr else None), _p(lr), _p(fm), _p(s_sum), call.field_split,
@@ -527,6 +531,246 @@ def scatter_rows(call, idx_all, rows_all):
     _lib.call("rh_embed_scatter_rows", _p(call.fdesc(True)), _p(idesc), 1 if idx_all.dtype == torch.int64 else 0,
               N, F, D, _p(rows_all), 1.0, call.samples_per_block, _p(err_flag(call.device)), _stream())
     _log_touch(call.weights, call.pads, idesc, 1 if idx_all.dtype == torch.int64 else 0, N, F, D, [idx_all])
+
+
+# --------------------------------------------------------------------------------------------
+# field-aware FM (DeepFFM / FAT-DeepFFM, csrc/ffm.hip)
+FFM_MAX_FIELDS = 64
+FFM_MAX_DIM = 128
+
+
+_ffm_xv = OrderedDict()
+_ffm_xv_pinned = {}
+
+
+def _ffm_index_buffer(idesc, B, V, dtype, device):
+    """The (B, F(F-1)) expanded-index buffer of one set of raw index columns (keyed by their descriptor tensor, itself cached
+    by the columns' addresses): its contents are a function of those columns alone, and its address stays fixed from the
+    eager steps into a hipGraph capture (its own descriptor is then already uploaded).  Buffers a capture used are kept."""
+    key = (idesc.data_ptr(), B, V, dtype, str(device))
+    t = _ffm_xv_pinned.get(key)
+    if t is None:
+        t = _ffm_xv.get(key)
+        capturing = device.type == "cuda" and torch.cuda.is_current_stream_capturing()
+        if t is None:
+            if capturing:
+                raise RuntimeError("torch_rechub_amd: run the step eagerly once before capturing a hipGraph")
+            t = _ffm_xv[key] = torch.empty((B, V), dtype=dtype, device=device)
+            if len(_ffm_xv) > 16:
+                _ffm_xv.popitem(last=False)
+        else:
+            _ffm_xv.move_to_end(key)
+        if capturing:
+            _ffm_xv_pinned[key] = t
+    return t
+
+
+class FfmCall(object):
+    """The fused field-aware lookup of F fields: tables (vocab_f, Dp) whose row x_f * F + j is field f's embedding towards
+    field j, the raw (B,) index columns (EmbedCall's rules) and the logical width D <= Dp."""
+
+    def __init__(self, weights, pads, idx, embed_dim):
+        self.base = EmbedCall(weights, pads, idx)
+        self.F, self.B, self.Dp = self.base.F, self.base.B, self.base.D
+        self.D = int(embed_dim)
+        if not 2 <= self.F <= FFM_MAX_FIELDS or not 1 <= self.D <= min(self.Dp, FFM_MAX_DIM):
+            raise RuntimeError(f"torch_rechub_amd: field-aware FM with {self.F} fields of width {self.D} (row {self.Dp}) "
+                               f"has no HIP kernel (2 .. {FFM_MAX_FIELDS} fields, width 1 .. {FFM_MAX_DIM})")
+        self.P = self.F * (self.F - 1) // 2
+        self.V = self.F * (self.F - 1)
+        self.device = self.base.device
+        self.weights = self.base.weights
+
+    def virtual_call(self):
+        """(EmbedCall over the F(F-1) virtual fields v(i, j) = i (F-1) + (j < i ? j : j - 1), xv): the lookups of the fused
+        kernel as ordinary index columns x_i * F + j (rh_ffm_expand_index), for the optimizer's records and the exchange."""
+        F, V, B = self.F, self.V, self.B
+        base = self.base
+        xv = _ffm_index_buffer(base.idesc(), B, V, base.idx[0].dtype, self.device)
+        _lib.call("rh_ffm_expand_index", _p(base.idesc()), base.idx_is_i64, B, F, _p(xv), _stream())
+        owner = [i for i in range(F) for _ in range(F - 1)]
+        vcall = EmbedCall([base.weights[i] for i in owner], [base.pads[i] for i in owner], list(xv.unbind(1)),
+                          replay=False)
+        return vcall, xv
+
+
+class _FfmFused(torch.autograd.Function):
+    """em (B, P*D) = the pairwise field-aware products read straight from the tables (rh_ffm_fwd, table mode)."""
+
+    @staticmethod
+    def forward(ctx, call, *weights):
+        B, F, D, Dp, P = call.B, call.F, call.D, call.Dp, call.P
+        dev = call.device
+        base = call.base
+        training = any(ctx.needs_input_grad)
+        vcall = xv = None
+        if _listeners() or (training and _sparse_exchange is not None):
+            vcall, xv = call.virtual_call()
+            _pre_gather(vcall.weights, vcall.pads, vcall.idesc(), vcall.idx_is_i64, B, call.V, Dp, training=training,
+                        keep=[xv], replay=False)
+        em = torch.empty((B, P * D), dtype=torch.float32, device=dev)
+        _lib.call("rh_ffm_fwd", _p(base.fdesc(False)), _p(base.idesc()), base.idx_is_i64, _NULL, 0, B, F, D, Dp, 0, _p(em),
+                  em.stride(0), _p(err_flag(dev)), _stream())
+        ctx.call, ctx.vcall, ctx.xv = call, vcall, xv
+        return em
+
+    @staticmethod
+    def backward(ctx, g_em):
+        call, vcall, xv = ctx.call, ctx.vcall, ctx.xv
+        base = call.base
+        B, F, D, Dp = call.B, call.F, call.D, call.Dp
+        dev = call.device
+        nones = (None,) * (1 + len(base.weights))
+        if g_em is None or not any(w.requires_grad for w in base.weights):
+            return nones
+        for hook in list(_pre_backward_hooks):
+            hook()
+        if g_em.stride(1) != 1:
+            g_em = g_em.contiguous()
+        exchange = _sparse_exchange
+        if exchange is not None and vcall is None:
+            raise RuntimeError("torch_rechub_amd: the data-parallel exchange was switched on between forward and backward")
+        rows = None
+        if exchange is None:
+            fdesc = base.fdesc(True)
+        else:
+            fdesc = base.fdesc(False)
+            rows = torch.empty((B, call.V, Dp), dtype=torch.float32, device=dev)
+        _lib.call("rh_ffm_bwd", _p(fdesc), _p(base.idesc()), base.idx_is_i64, _NULL, 0, B, F, D, Dp, 0, _p(g_em),
+                  g_em.stride(0), _NULL, 0, 0 if rows is None else 1, _p(rows), _p(err_flag(dev)), _stream())
+        if exchange is not None:
+            gathered = exchange(vcall, rows)
+            if gathered is not None:
+                scatter_rows(vcall, gathered[0], gathered[1])
+        elif vcall is not None:
+            _log_touch(vcall.weights, vcall.pads, vcall.idesc(), vcall.idx_is_i64, B, call.V, Dp, [xv])
+        for w in {id(w): w for w in base.weights if w.requires_grad}.values():
+            _publish_grad(w)
+        return nones
+
+
+def ffm_fused(call):
+    """em (B, P*D) of a FfmCall: the MLP input of DeepFFM (deepffm.py:57-65 of the reference) without the (B, F, F, D)
+    lookup; the backward scatters into the tables' gradient buffers (or hands rows to the data-parallel exchange)."""
+    return _FfmFused.apply(call, *call.weights)
+
+
+class _FfmDenseFn(torch.autograd.Function):
+    """FFM.forward on a (B, F, F, D) tensor (rh_ffm_fwd / rh_ffm_bwd, dense mode): (B, P, D) or (B, P, 1)."""
+
+    @staticmethod
+    def forward(ctx, x, reduce_sum):
+        require_hip(x)
+        B, F, F2, D = (int(v) for v in x.shape)
+        if F != F2 or x.dtype != torch.float32:
+            raise ValueError("ffm: input must be float32 (B, F, F, D)")
+        if x.stride(3) != 1 or x.stride(2) != D or x.stride(1) != F * D:
+            x = x.contiguous()
+        P = F * (F - 1) // 2
+        out = torch.empty((B, P, 1 if reduce_sum else D), dtype=torch.float32, device=x.device)
+        _lib.call("rh_ffm_fwd", _NULL, _NULL, 0, _p(x), x.stride(0), B, F, D, D, int(reduce_sum), _p(out), out.stride(0),
+                  _NULL, _stream())
+        ctx.reduce_sum = bool(reduce_sum)
+        ctx.save_for_backward(x)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, = ctx.saved_tensors
+        B, F, _, D = (int(v) for v in x.shape)
+        g = g.contiguous()
+        gx = torch.empty((B, F, F, D), dtype=torch.float32, device=x.device)
+        _lib.call("rh_ffm_bwd", _NULL, _NULL, 0, _p(x), x.stride(0), B, F, D, D, int(ctx.reduce_sum), _p(g), g.stride(0),
+                  _p(gx), gx.stride(0), 0, _NULL, _NULL, _stream())
+        return gx, None
+
+
+def ffm(x, reduce_sum=True):
+    """The reference's FFM layer (basic/layers.py:736-746) on a (B, F, F, D) input."""
+    return _FfmDenseFn.apply(x, bool(reduce_sum))
+
+
+def _em_2d(em, P, D):
+    """(B, P*D) view with unit column stride of a (B, P, D) / (B, P*D) tensor, and its row stride."""
+    if em.dim() == 3:
+        em = em.reshape(em.shape[0], P * D)
+    if em.stride(1) != 1:
+        em = em.contiguous()
+    return em
+
+
+class _CenDescFn(torch.autograd.Function):
+    """d (B, P) = relu(sum_d u * em) (CEN.forward, basic/layers.py:779 of the reference); u gradient without atomics."""
+
+    @staticmethod
+    def forward(ctx, em, u):
+        require_hip(em, u)
+        P, D = int(u.shape[0]), int(u.shape[1])
+        ctx.in_shape = em.shape
+        em = _em_2d(em, P, D)
+        u = u.contiguous()
+        B = int(em.shape[0])
+        d = torch.empty((B, P), dtype=torch.float32, device=em.device)
+        _lib.call("rh_cen_desc_fwd", _p(em), em.stride(0), _p(u), B, P, D, _p(d), _stream())
+        ctx.save_for_backward(em, u, d)
+        return d
+
+    @staticmethod
+    def backward(ctx, g_d):
+        em, u, d = ctx.saved_tensors
+        B, P, D = int(em.shape[0]), int(u.shape[0]), int(u.shape[1])
+        g_d = g_d.contiguous()
+        g_em = torch.empty((B, P * D), dtype=torch.float32, device=em.device)
+        nch = _lib.call("rh_cen_nchunks", B)
+        part = torch.empty((max(nch, 1), P * D), dtype=torch.float32, device=em.device)
+        _lib.call("rh_cen_desc_bwd", _p(em), em.stride(0), _p(u), _p(d), _p(g_d), B, P, D, _p(g_em), _p(part), _stream())
+        g_u = torch.empty((P, D), dtype=torch.float32, device=em.device)
+        if B == 0:
+            g_u.zero_()
+        else:
+            _lib.call("rh_colsum", _p(part), nch, P * D, _p(g_u), _NULL, 0, _NULL, _stream())
+        return g_em.view(ctx.in_shape), g_u
+
+
+class _CenRescaleFn(torch.autograd.Function):
+    """aem (B, P*D) = s[b, p] * em[b, p, :] (CEN.forward, basic/layers.py:785-786 of the reference)."""
+
+    @staticmethod
+    def forward(ctx, em, s, P, D):
+        require_hip(em, s)
+        ctx.in_shape = em.shape
+        em = _em_2d(em, P, D)
+        s = s.contiguous()
+        B = int(em.shape[0])
+        out = torch.empty((B, P * D), dtype=torch.float32, device=em.device)
+        _lib.call("rh_cen_rescale_fwd", _p(em), em.stride(0), _p(s), B, P, D, _p(out), _stream())
+        ctx.dims = (P, D)
+        ctx.save_for_backward(em, s)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        em, s = ctx.saved_tensors
+        P, D = ctx.dims
+        B = int(em.shape[0])
+        if g.stride(1) != 1:
+            g = g.contiguous()
+        g_em = torch.empty((B, P * D), dtype=torch.float32, device=em.device)
+        g_s = torch.empty((B, P), dtype=torch.float32, device=em.device)
+        _lib.call("rh_cen_rescale_bwd", _p(em), em.stride(0), _p(s), _p(g), g.stride(0), B, P, D, _p(g_em), _p(g_s),
+                  _stream())
+        return g_em.view(ctx.in_shape), g_s, None, None
+
+
+def cen_descriptor(em, u):
+    """relu(sum_d u * em): (B, P) from em (B, P, D) or (B, P*D)."""
+    return _CenDescFn.apply(em, u)
+
+
+def cen_rescale(em, s):
+    """s.unsqueeze(-1) * em, flattened to (B, P*D)."""
+    B, P = int(s.shape[0]), int(s.shape[1])
+    return _CenRescaleFn.apply(em, s, P, int(em.shape[-1]) if em.dim() == 3 else int(em.shape[1]) // P)
 
 
 # --------------------------------------------------------------------------------------------

@@ -314,8 +314,11 @@ class TableAdam(torch.optim.Adam):
         seg = graphs.active()
         capturing = torch.cuda.is_current_stream_capturing()
         training = rec.get("training", torch.is_grad_enabled())
-        if training:
-            # "keep": the index tensors behind idesc stay alive as long as the record does (refresh-ahead replays it)
+        if training and rec.get("replay", True):
+            # "keep": the index tensors behind idesc stay alive as long as the record does (refresh-ahead replays it).
+            # A record over indices computed inside the step (replay False: field-aware lookups) is left out, so the step
+            # has fewer records than gathers and no refresh-ahead / assemble-with-refresh form is chosen: every gather of
+            # it takes the ordinary refresh in front of its kernel, after its indices exist.
             self._step_recs.append({k: rec.get(k) for k in ("weights", "pads", "idesc", "idx_is_i64", "B", "F", "D", "keep")})
         if capturing and seg is not None and self.overlap_sweep:
             # segmented replay: EVERY replay joins the sweep forked by the previous one before its first segment (the
