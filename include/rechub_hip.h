@@ -784,6 +784,45 @@ int rh_cen_rescale_fwd(const float* em, int64_t ld, const float* s, int B, int P
 int rh_cen_rescale_bwd(const float* em, int64_t ld, const float* s, const float* g, int64_t ldg, int B, int P, int D,
                        float* g_em, float* g_s, void* stream);
 
+/* ---- multi-interest user towers and list-wise scoring (YoutubeDNN / MIND / ComiRec) ----------------------------------
+ * Capsule routing (CapsuleNetwork, bilinear types 0 / 1 / 2), B samples, L positions, I interests, width D (D <= 64,
+ * I*D <= 256; type 2 also I*D*D <= 4096).  mask (B, L) int32, nonzero = kept.  Types 0 / 1: U (B, L, Iu*D) the Linear's
+ * output (Iu = 1 / I; type 0 repeats it over the interests); type 2: E (B, L, D) and W (L, I*D, D) (w[0, :L]).
+ * init (B, I, L) the initial routing logits, or null for zeros.  Writes cap (B, I, D), and when not null the last
+ * iteration's masked softmax weights sw (B, I, L) and pre-squash sums s (B, I, D) for the backward.
+ * rh_capsule_bwd (through the last iteration only): types 0 / 1: g_u (B, L, Iu*D); type 2: g_e (B, L, D) and g_s (B, I, D).
+ * rh_capsule_wgrad (type 2): partial (rh_capsule_wgrad_nchunks(B), L*I*D*D) per-chunk sums of the weight gradient in a
+ *   fixed order (g_w = rh_colsum of it: bitwise reproducible).
+ * replaces: CapsuleNetwork.forward torch_rechub/basic/layers.py:657-712 and its autograd. */
+int rh_capsule_supported(int L, int I, int D, int type);
+int rh_capsule_fwd(const float* U, const float* E, const float* W, const int32_t* mask, const float* init, int B, int L,
+                   int I, int D, int type, int routing_times, float* cap, float* sw, float* s, void* stream);
+int rh_capsule_bwd(const float* g_cap, const float* s, const float* sw, const float* W, int B, int L, int I, int D, int type,
+                   float* g_u, float* g_e, float* g_s, void* stream);
+int rh_capsule_wgrad_nchunks(int B);
+int rh_capsule_wgrad(const float* g_s, const float* sw, const float* E, int B, int L, int I, int D, float* partial,
+                     void* stream);
+/* Self-attentive pooling (MultiInterestSA after A = tanh(E W1) W2): A (B, L, I), E (B, L, D), mask (B, L) int32 or null.
+ * rh_sa_pool_fwd: P (B, L, I) = softmax over L of A + -1e9 (1 - mask); out (B, I, D) = P^T E.
+ * rh_sa_pool_bwd: g (B, I, D) -> gA (B, L, I), gE (B, L, D).  D <= 64, L*I <= 1024, I*D <= 1024.
+ * replaces: MultiInterestSA.forward torch_rechub/basic/layers.py:601-609 (softmax, mask term, matmul) and its autograd. */
+int rh_sa_supported(int L, int I, int D);
+int rh_sa_pool_fwd(const float* A, const float* E, const int32_t* mask, int B, int L, int I, int D, float* P, float* out,
+                   void* stream);
+int rh_sa_pool_bwd(const float* P, const float* E, const float* g, int B, int L, int I, int D, float* gA, float* gE,
+                   void* stream);
+/* List-wise scoring: u (B, I, D) normalised user vectors (I <= 16, D <= 64), pos (B, D) row stride ldp and neg (B, K, D)
+ * raw item rows (K < 1024).  Rows are L2-normalised (F.normalize, eps 1e-12); best[b] = first argmax_i u_i . pos_hat;
+ * logits (B, 1 + K) = u_best . [pos_hat, neg_hat] / temperature; nrm (B, 1 + K) the row norms for the backward.
+ * rh_listwise_bwd: g (B, 1 + K) -> g_u (B, I, D) (zero but the chosen interest), g_pos (B, D), g_neg (B, K, D).
+ * replaces: the item towers' F.normalize + torch.cat and the bmm / argmax / gather / mul-sum of YoutubeDNN, MIND,
+ *           ComirecDR and ComirecSA.forward (torch_rechub/models/matching/youtube_dnn.py, mind.py, comirec.py). */
+int rh_listwise_fwd(const float* u, const float* pos, int64_t ldp, const float* neg, int B, int I, int D, int K,
+                    float temperature, float* logits, int32_t* best, float* nrm, void* stream);
+int rh_listwise_bwd(const float* u, const float* pos, int64_t ldp, const float* neg, const int32_t* best, const float* nrm,
+                    const float* g, int B, int I, int D, int K, float temperature, float* g_u, float* g_pos, float* g_neg,
+                    void* stream);
+
 /* ---- row-sharded tables (one shard per rank) -----------------------------------------------------------------------
  * Global row g of a table lives on rank g % world as local row g / world.  rh_shard_localize rewrites an index matrix
  * idx (n_rows, F) (int64 / int32, contiguous: the all-gathered indices of the global batch) for this rank's shards:

@@ -9,6 +9,9 @@
                 field-aware tables of v * 26 rows x 10, width-1 linear tables, MLP [1600, 1600] dropout 0.5); --scale 0.04
                 gives field-aware tables of about as many rows as the DeepFM headline's.  Also times a plain-PyTorch eager
                 restatement of the same model on the same GPU (nn.Embedding lookups, indexed pair products, torch.optim.Adam).
+  youtubednn / mind / comirec_dr / comirec_sa : the retrieval examples' list-wise models (MatchTrainer(mode=2)) at B = 4096,
+                history L = 50, D = 16, I = 4 interests, K = 3 negatives, a 10 M-row item table (--scale scales it), five
+                user fields.  Also times a plain-PyTorch eager restatement (the reference's op chain, torch.optim.Adam).
     python tools/model_bench.py --models dcn,dcnv2,din,dssm --steps 30
 """
 import argparse
@@ -95,10 +98,137 @@ def build(name, dev, B, scale):
             model = DeepFFM(linear, cross, 10, ffm_mlp) if name == "deepffm" else FatDeepFFM(linear, cross, 10, 3, ffm_mlp)
         x = {f.name: torch.randint(0, v, (B,), device=dev, generator=g) for f, v in zip(linear, vocabs)}
         trainer = CTRTrainer(model, device=str(dev), show_progress=False)
+    elif name in RETRIEVAL:
+        model, x = build_retrieval(name, dev, B, scale, g)
+        return MatchTrainer(model, mode=2, device=str(dev), show_progress=False), x, torch.zeros(B, dtype=torch.long,
+                                                                                                  device=dev)
     else:
         raise ValueError(name)
     y = (torch.rand(B, device=dev, generator=g) < 0.25).float()
     return trainer, x, y
+
+
+RETRIEVAL = ("youtubednn", "mind", "comirec_dr", "comirec_sa")
+R_L, R_D, R_I, R_K, R_ITEMS, R_USERS = 50, 16, 4, 3, 10_000_000, [1_000_000, 3, 8, 22, 4000]
+
+
+def retrieval_batch(dev, B, n_item, g):
+    lens = torch.randint(1, R_L + 1, (B,), device=dev, generator=g)
+    pad = torch.arange(R_L, device=dev)[None, :] >= lens[:, None]
+    x = {f"u{i}": torch.randint(0, v, (B,), device=dev, generator=g) for i, v in enumerate(R_USERS)}
+    x["hist_movie_id"] = torch.randint(1, n_item, (B, R_L), device=dev, generator=g).masked_fill(pad, 0)
+    x["movie_id"] = torch.randint(1, n_item, (B,), device=dev, generator=g)
+    x["neg_items"] = torch.randint(1, n_item, (B, R_K), device=dev, generator=g)
+    return x
+
+
+def build_retrieval(name, dev, B, scale, g):
+    from torch_rechub_amd.basic.features import SequenceFeature, SparseFeature
+    from torch_rechub_amd.models.matching import MIND, ComirecDR, ComirecSA, YoutubeDNN
+    n_item = max(1000, int(R_ITEMS * scale))
+    user = [SparseFeature(f"u{i}", v, R_D) for i, v in enumerate(R_USERS)]
+    hist = [SequenceFeature("hist_movie_id", n_item, R_D, pooling="concat", shared_with="movie_id")]
+    item = [SparseFeature("movie_id", n_item, R_D)]
+    neg = [SequenceFeature("neg_items", n_item, R_D, pooling="concat", shared_with="movie_id")]
+    with torch.device(dev):
+        if name == "youtubednn":
+            mean_hist = [SequenceFeature("hist_movie_id", n_item, R_D, pooling="mean", shared_with="movie_id")]
+            model = YoutubeDNN(user + mean_hist, item, neg, user_params={"dims": [128, 64, 16]}, temperature=0.02)
+        elif name == "mind":
+            model = MIND(user, hist, item, neg, max_length=R_L, temperature=0.02)
+        elif name == "comirec_dr":
+            model = ComirecDR(user, hist, item, neg, max_length=R_L, temperature=0.02)
+            torch.nn.init.normal_(model.capsule.w, 0, 0.3)
+        else:
+            model = ComirecSA(user, hist, item, neg, temperature=0.02)
+    return model, retrieval_batch(dev, B, n_item, g)
+
+
+def torch_retrieval_ms(name, dev, B, scale, steps):
+    """ms/step of a plain-PyTorch eager restatement of the reference's list-wise step at the same shape."""
+    from torch import nn
+    F_ = nn.functional
+    n_item = max(1000, int(R_ITEMS * scale))
+    g = torch.Generator(device=dev).manual_seed(0)
+    x = retrieval_batch(dev, B, n_item, g)
+    users = nn.ModuleList([nn.Embedding(v, R_D) for v in R_USERS]).to(dev)
+    items = nn.Embedding(n_item, R_D).to(dev)
+    nu = len(R_USERS) * R_D
+    params = list(users.parameters()) + list(items.parameters())
+    if name == "youtubednn":
+        dims = [nu + R_D, 128, 64, 16]
+        mlp = []
+        for a, w in zip(dims, dims[1:]):
+            mlp += [nn.Linear(a, w), nn.BatchNorm1d(w), nn.ReLU()]
+        mlp = nn.Sequential(*mlp).to(dev)
+        params += list(mlp.parameters())
+    else:
+        conv = nn.Parameter(torch.rand(nu + R_D, R_D, device=dev))
+        params.append(conv)
+        if name == "comirec_sa":
+            W1 = nn.Parameter(torch.rand(R_D, 4 * R_D, device=dev))
+            W2 = nn.Parameter(torch.rand(4 * R_D, R_I, device=dev))
+            params += [W1, W2]
+        elif name == "mind":
+            lin = nn.Linear(R_D, R_D, bias=False).to(dev)
+            params += list(lin.parameters())
+        else:
+            w = nn.Parameter(0.3 * torch.randn(1, R_L, R_I * R_D, R_D, device=dev))
+            params.append(w)
+    opt = torch.optim.Adam(params, lr=1e-3)
+    y = torch.zeros(B, dtype=torch.long, device=dev)
+
+    def capsule(e, mask, kind):
+        uh = lin(e).repeat(1, 1, R_I) if kind == 0 else torch.sum(w[:, :R_L] * e.unsqueeze(2), dim=3)
+        uh = uh.reshape(-1, R_L, R_I, R_D).transpose(1, 2).contiguous()
+        uh_it = uh.detach()
+        cw = torch.randn(B, R_I, R_L, device=dev) if kind == 0 else torch.zeros(B, R_I, R_L, device=dev)
+        am = mask.unsqueeze(1).repeat(1, R_I, 1)
+        for i in range(3):
+            sw = torch.where(am == 0, torch.zeros_like(cw), F_.softmax(cw, dim=-1)).unsqueeze(2)
+            cap = torch.matmul(sw, uh_it if i < 2 else uh)
+            n = torch.sum(torch.square(cap), -1, True)
+            cap = n / (1 + n) / torch.sqrt(n + 1e-9) * cap
+            if i < 2:
+                cw = cw + torch.matmul(uh_it, cap.transpose(2, 3)).reshape(-1, R_I, R_L)
+        return cap.reshape(-1, R_I, R_D)
+
+    def step():
+        u_in = torch.cat([t(x[f"u{i}"]) for i, t in enumerate(users)], 1)
+        his = x["hist_movie_id"]
+        e = items(his)
+        if name == "youtubednn":
+            hmask = (his > 0).float().unsqueeze(-1)
+            u = F_.normalize(mlp(torch.cat([u_in, (e * hmask).sum(1) / (hmask.sum(1) + 1e-16)], 1)), dim=-1).unsqueeze(1)
+        else:
+            mask = (his > 0).long()
+            if name == "comirec_sa":
+                A = torch.einsum("bsd,dk->bsk", torch.einsum("bse,ed->bsd", e, W1).tanh(), W2)
+                A = F_.softmax(A + -1.e9 * (1 - mask.unsqueeze(-1).float()), dim=1)
+                interests = torch.matmul(A.permute(0, 2, 1), e)
+            else:
+                interests = capsule(e, mask, 0 if name == "mind" else 2)
+            u = torch.cat([u_in.unsqueeze(1).expand(B, R_I, nu), interests], -1)
+            u = F_.normalize(torch.matmul(u, conv), p=2, dim=-1)
+        it = F_.normalize(torch.cat([items(x["movie_id"]).unsqueeze(1), items(x["neg_items"])], 1), p=2, dim=-1)
+        if name == "youtubednn":
+            logits = (u * it).sum(2) / 0.02
+        else:
+            k = torch.argmax(torch.bmm(u, it[:, 0].unsqueeze(-1)), dim=1).squeeze(-1)
+            logits = (u[torch.arange(B, device=dev), k].unsqueeze(1) * it).sum(-1)
+        loss = F_.cross_entropy(logits, y)
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+
+    for _ in range(3):
+        step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        step()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / steps * 1e3
 
 
 def torch_ffm_ms(name, dev, B, scale, steps):
@@ -211,9 +341,10 @@ def main():
         from torch_rechub_amd import ops
         ops.check_errors()
         del trainer, x, y
-        if name in ("deepffm", "fatdeepffm"):
+        if name in ("deepffm", "fatdeepffm") + RETRIEVAL:
             torch.cuda.empty_cache()
-            ms = torch_ffm_ms(name, dev, a.batch, a.scale, a.steps)
+            ms = (torch_ffm_ms if name in ("deepffm", "fatdeepffm") else torch_retrieval_ms)(name, dev, a.batch, a.scale,
+                                                                                            a.steps)
             print(f"{name:6s} B={a.batch} plain PyTorch eager {ms:8.3f} ms/step ({a.batch / ms:9.1f} k samples/s)", flush=True)
         torch.cuda.reset_peak_memory_stats()
 

@@ -14,6 +14,8 @@
 | CrossNetMix      | :447-506                    | experts batched into 3 GEMMs per layer (was 150 mm per step) + ONE fused bias/Hadamard/gate-mix/residual kernel |
 | FFM              | :736-746                    | ops.ffm: one pass each way over the (B, F, F, D) input (DeepFFM fuses it into the lookup) |
 | CEN              | :777-786                    | descriptor and rescale kernels (ops.cen_descriptor / cen_rescale) around the attention MLP |
+| MultiInterestSA  | :568-609                    | GEMM path for tanh(E W1) W2, ONE masked-softmax + pooling launch each way (ops.sa_pool) |
+| CapsuleNetwork   | :612-712                    | ONE routing launch with the projections in LDS (ops.capsule_routing); type 2 never forms (B, L, I*D, D) |
 
 Tables stay ``nn.Embedding`` modules inside ``embed_dict`` (checkpoint ABI:
 ``embedding.embed_dict.<feature>.weight``); kernels read them in place.
@@ -683,3 +685,97 @@ class CrossLayer(nn.Module):
 
     def forward(self, x_0, x_i):
         return self.w(x_i) * x_0 + self.b
+
+
+def _interest_mask(mask, B, L):
+    """(B, L) int32, nonzero = kept: the reference's ``mask == 0`` test of a (B, L) mask."""
+    return (mask.reshape(B, L) != 0).to(torch.int32).contiguous()
+
+
+class MultiInterestSA(nn.Module):
+    """Self-attentive multi-interest extractor of ComiRec (reference layers.py:568-609), same parameters and init order.
+
+    ``H = tanh(E W1)`` and ``H W2`` run on the GEMM path (ops.linear); the masked softmax over L and the pooling
+    ``A^T E`` are one HIP launch each way (ops.sa_pool).  ``W3`` is built and never used, as in the reference."""
+
+    def __init__(self, embedding_dim, interest_num, hidden_dim=None):
+        super().__init__()
+        self.embedding_dim = embedding_dim
+        self.interest_num = interest_num
+        if hidden_dim is None:  # (as in the reference, an explicit hidden_dim leaves self.hidden_dim unset)
+            self.hidden_dim = self.embedding_dim * 4
+        self.W1 = torch.nn.Parameter(torch.rand(self.embedding_dim, self.hidden_dim), requires_grad=True)
+        self.W2 = torch.nn.Parameter(torch.rand(self.hidden_dim, self.interest_num), requires_grad=True)
+        self.W3 = torch.nn.Parameter(torch.rand(self.embedding_dim, self.embedding_dim), requires_grad=True)
+
+    def forward(self, seq_emb, mask=None):
+        ops.require_hip(seq_emb)
+        B, L, D = (int(v) for v in seq_emb.shape)
+        if not ops.sa_supported(L, self.interest_num, D):
+            raise RuntimeError(f"torch_rechub_amd: MultiInterestSA with L={L}, interest_num={self.interest_num}, "
+                               f"embed_dim={D} has no HIP kernel (D <= 64, L * interest_num <= 1024)")
+        H = torch.tanh(ops.linear(seq_emb.reshape(B * L, D), self.W1.t()))
+        A = ops.linear(H, self.W2.t()).view(B, L, self.interest_num)
+        return ops.sa_pool(A, seq_emb, None if mask is None else _interest_mask(mask, B, L))
+
+
+class CapsuleNetwork(nn.Module):
+    """Dynamic-routing multi-interest extractor of MIND / ComiRec-DR (reference layers.py:612-712), same constructor,
+    parameters, init order and routing semantics (iterations 0 and 1 route the detached projections; the output is the
+    last iteration's; masked positions are zeroed after the softmax without renormalising).
+
+    The routing runs in one HIP launch (ops.capsule_routing) with the per-sample projections in LDS; bilinear type 2
+    never forms the reference's (B, L, I*D, D) product.  Types 0 / 1 project with ops.linear first.  MIND's (type 0)
+    initial logits are ``torch.randn(B, interest_num, seq_len)`` drawn as the reference draws them; ``routing_init``, a
+    callable ``(B, interest_num, seq_len, device) -> tensor``, replaces that draw (tests replay recorded draws through it)."""
+
+    def __init__(self, embedding_dim, seq_len, bilinear_type=2, interest_num=4, routing_times=3, relu_layer=False):
+        super().__init__()
+        self.embedding_dim = embedding_dim
+        self.seq_len = seq_len
+        self.bilinear_type = bilinear_type
+        self.interest_num = interest_num
+        self.routing_times = routing_times
+        self.relu_layer = relu_layer
+        self.stop_grad = True
+        self.relu = nn.Sequential(nn.Linear(self.embedding_dim, self.embedding_dim, bias=False), nn.ReLU())
+        if self.bilinear_type == 0:
+            self.linear = nn.Linear(self.embedding_dim, self.embedding_dim, bias=False)
+        elif self.bilinear_type == 1:
+            self.linear = nn.Linear(self.embedding_dim, self.embedding_dim * self.interest_num, bias=False)
+        else:  # uninitialised storage, as the reference's torch.Tensor(...): no random draws
+            self.w = nn.Parameter(torch.empty(1, self.seq_len, self.interest_num * self.embedding_dim, self.embedding_dim))
+        self.routing_init = None
+
+    def _init_logits(self, B, device):
+        if self.bilinear_type != 0:
+            return None
+        if self.routing_init is not None:
+            t = self.routing_init(B, self.interest_num, self.seq_len, device)
+        else:
+            t = torch.randn(B, self.interest_num, self.seq_len, device=device, requires_grad=False)
+        return t.to(device=device, dtype=torch.float32).contiguous()
+
+    def forward(self, item_eb, mask):
+        ops.require_hip(item_eb)
+        B, L, D = (int(v) for v in item_eb.shape)
+        I = self.interest_num
+        if L != self.seq_len or D != self.embedding_dim:
+            raise RuntimeError(f"CapsuleNetwork: input of shape {tuple(item_eb.shape)} does not match seq_len={self.seq_len}, "
+                               f"embedding_dim={self.embedding_dim}")
+        if self.bilinear_type not in (0, 1, 2) or not ops.capsule_supported(L, I, D, self.bilinear_type) or \
+                self.routing_times < 1:
+            raise RuntimeError(f"torch_rechub_amd: CapsuleNetwork(bilinear_type={self.bilinear_type}, seq_len={L}, "
+                               f"interest_num={I}, embedding_dim={D}, routing_times={self.routing_times}) has no HIP kernel")
+        m = _interest_mask(mask, B, L)
+        init = self._init_logits(B, item_eb.device)
+        # with routing_times <= 2 the output comes from the detached projections: no gradient reaches them
+        with torch.set_grad_enabled(torch.is_grad_enabled() and self.routing_times > 2):
+            if self.bilinear_type == 2:
+                cap = ops.capsule_routing(item_eb, self.w, m, init, 2, I, D, self.routing_times)
+            else:
+                U = ops.linear(item_eb.reshape(B * L, D), self.linear.weight).view(B, L, -1)
+                cap = ops.capsule_routing(U, None, m, init, self.bilinear_type, I, D, self.routing_times)
+        if self.relu_layer:
+            cap = self.relu(cap)
+        return cap

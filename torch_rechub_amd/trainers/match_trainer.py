@@ -123,7 +123,14 @@ class MatchTrainer(CTRTrainer):
             pos_score, neg_score = self.model(x_dict)
             loss = self.criterion(pos_score, neg_score)
         else:
-            loss = self.criterion(self.model(x_dict), y)
+            pred = self.model(x_dict)
+            if self.mode == 2 and y.dtype != torch.long:  # (a DeviceDataLoader's label column is float32)
+                y = y.long()
+            if self.mode == 2 and ops.cross_entropy_ok(self.criterion, pred, y):
+                # list-wise softmax over the (B, 1 + K) logits (YoutubeDNN / MIND / ComiRec): one launch each way
+                loss = ops.cross_entropy_mean(pred, y)
+            else:
+                loss = self.criterion(pred, y)
         return self._add_reg(loss)
 
     def evaluate(self, model, data_loader):
