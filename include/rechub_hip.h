@@ -46,6 +46,7 @@ extern "C" {
 
 /* err_flag bits */
 #define RH_FLAG_INDEX_OOB 1 /* an index was <0 or >= vocab (reference: IndexError / device assert) */
+#define RH_FLAG_TARGET_OOB 2 /* a class label was < 0 or >= the class count (reference: IndexError) */
 
 int rh_abi_version(void);
 const char* rh_last_error(void);
@@ -822,6 +823,46 @@ int rh_listwise_fwd(const float* u, const float* pos, int64_t ldp, const float* 
 int rh_listwise_bwd(const float* u, const float* pos, int64_t ldp, const float* neg, const int32_t* best, const float* nrm,
                     const float* g, int B, int I, int D, int K, float temperature, float* g_u, float* g_pos, float* g_neg,
                     void* stream);
+
+/* ---- HSTU generative model: pointwise relative-bias attention and the next-token head --------------------------------
+ * Attention of one HSTULayer on proj (B, L, ld) = silu(proj1(LN(x))) (row stride ld >= 2 H (dqk + dv)): per head h,
+ * q at columns h dqk, k at H dqk + h dqk, v at 2 H dqk + H dv + h dv.  td (B, L) int64 seconds or null (position-only
+ * bias), kmask (B, L) int32 nonzero = kept key or null.  pos_w (2 N - 1, H), ts_w (nb + 1, H) contiguous; N = max_seq_len,
+ * nb = num_time_buckets, fn_log 0 sqrt / 1 log, minutes 0 / 1, alpha = 1 / sqrt(dqk).
+ * rh_hstu_attn_fwd: out (B, L, H dv) = (silu(alpha q k^T + pos + ts) / N, masked to 0 above the diagonal and at dropped
+ *   keys) v.  1 <= L <= min(N, 1024), dqk, dv <= 64, nb <= 1023, else RH_E_UNSUPPORTED.
+ * rh_hstu_attn_bwd: g_out (B, L, H dv) -> the q / k / v columns of g_proj (B, L, ld) (the other columns are not
+ *   written), g_pos_w (2 N - 1, H) and g_ts_w (nb + 1, H), through per-workgroup partials pos_part
+ *   (rh_hstu_attn_nparts(B, L, H), L) and ts_part (same rows, nb + 1; may be null when td is) summed in a fixed order.
+ *   No atomics: bitwise reproducible.
+ * replaces: HSTULayer.forward torch_rechub/basic/layers.py:916-933 (matmul, rab, tril, masked_fill, silu, /N, matmul) with
+ *           RelativeBucketedTimeAndPositionBias.forward utils/hstu_utils.py:150-185, and their autograd. */
+int rh_hstu_attn_nparts(int B, int L, int H);
+int rh_hstu_attn_fwd(const float* proj, int64_t ld, int B, int L, int H, int dqk, int dv, const int64_t* td,
+                     const int32_t* kmask, const float* pos_w, const float* ts_w, int N, int nb, int fn_log, int minutes,
+                     float divisor, float alpha, float* out, void* stream);
+int rh_hstu_attn_bwd(const float* proj, int64_t ld, int B, int L, int H, int dqk, int dv, const int64_t* td,
+                     const int32_t* kmask, const float* pos_w, const float* ts_w, int N, int nb, int fn_log, int minutes,
+                     float divisor, float alpha, const float* g_out, float* g_proj, float* pos_part, float* ts_part,
+                     float* g_pos_w, float* g_ts_w, void* stream);
+/* Next-token cross entropy over the item table: h (M, D), W (V, D), bias (V,) or null, labels (M,) int64 (0 = ignored,
+ * else in [1, V)).  z = ((h W^T + bias) / t1) / t2, column 0 excluded from the normaliser; loss (1,) = mean over rows with
+ * a label of lse - z[label] (NaN when there is none; nce = 1: then the mean over every row of lse + 1e9 / t2).
+ * rh_hstu_head_fwd: part (M, rh_hstu_head_nsplit(M, V), 2) workspace; zlab, lse, wrow (M,) for the backward; a label
+ *   outside [0, V) ORs RH_FLAG_TARGET_OOB into *err (when not null) and its row's loss is undefined.
+ * rh_hstu_head_bwd: g_loss (1,) device scalar -> g_h (M, D), g_W (V, D), g_bias (V,) (null: not wanted); part
+ *   (rh_hstu_head_rsplit(M, D, V), V, D + 1) workspace, unused when that count is 1.  Logits recomputed tile by tile;
+ *   no atomics.  M >= 1, V >= 2, any D.
+ * replaces: HSTUModel.forward's F.linear / temperature (models/generative/hstu.py:266-271), SeqTrainer's logits.clone()
+ *           and CrossEntropyLoss / NCELoss (trainers/seq_trainer.py:177-194, basic/loss_func.py:141-175), and autograd. */
+int rh_hstu_head_nsplit(int M, int V);
+int rh_hstu_head_rsplit(int M, int D, int V);
+int rh_hstu_head_fwd(const float* h, const float* W, const float* bias, const int64_t* labels, int M, int D, int V, float t1,
+                     float t2, int nce, float* part, float* zlab, float* lse, float* wrow, float* loss, int32_t* err,
+                     void* stream);
+int rh_hstu_head_bwd(const float* h, const float* W, const float* bias, const int64_t* labels, const float* lse,
+                     const float* wrow, const float* g_loss, int M, int D, int V, float t1, float t2, float* part, float* g_h,
+                     float* g_W, float* g_bias, void* stream);
 
 /* ---- row-sharded tables (one shard per rank) -----------------------------------------------------------------------
  * Global row g of a table lives on rank g % world as local row g / world.  rh_shard_localize rewrites an index matrix

@@ -12,6 +12,11 @@
   youtubednn / mind / comirec_dr / comirec_sa : the retrieval examples' list-wise models (MatchTrainer(mode=2)) at B = 4096,
                 history L = 50, D = 16, I = 4 interests, K = 3 negatives, a 10 M-row item table (--scale scales it), five
                 user fields.  Also times a plain-PyTorch eager restatement (the reference's op chain, torch.optim.Adam).
+  hstu / hstu_large : HSTUModel + SeqTrainer on synthetic sequences: the MovieLens-1M example shape (B 128, L 200, d 50,
+                H 1, dqk = dv = 50, 2 layers, V 3707, l2 scoring, temperature 0.05, log buckets / 0.301 / seconds) and the
+                reference defaults (d 512, H 8, dqk = dv = 64, 4 layers, L 256) at B 64, V 100 k.  Times the HIP step
+                (fused attention and next-token loss), a plain-PyTorch eager restatement of the reference's op chain
+                (dense (B, H, L, L) attention, (B, L, V) logits, clone, CrossEntropyLoss) and the kernels' device times.
     python tools/model_bench.py --models dcn,dcnv2,din,dssm --steps 30
 """
 import argparse
@@ -280,6 +285,113 @@ def torch_ffm_ms(name, dev, B, scale, steps):
     return (time.perf_counter() - t0) / steps * 1e3
 
 
+HSTU = {"hstu": dict(B=128, L=200, V=3707, d_model=50, n_heads=1, n_layers=2, dqk=50, dv=50, score_norm="l2",
+                     temperature=0.05, time_bucket_fn="log", time_bucket_divisor=0.301, time_bucket_unit="seconds"),
+        "hstu_large": dict(B=64, L=256, V=100000, d_model=512, n_heads=8, n_layers=4, dqk=64, dv=64)}
+
+
+def hstu_bench(name, dev, steps):
+    """ms/step of the HIP SeqTrainer step and of a plain-PyTorch eager restatement of the reference's step."""
+    import torch.nn.functional as F
+
+    from torch_rechub_amd.models.generative import HSTUModel
+    from torch_rechub_amd.trainers import SeqTrainer
+    cfg = dict(HSTU[name])
+    B, L, V = cfg.pop("B"), cfg.pop("L"), cfg.pop("V")
+    torch.manual_seed(0)
+    model = HSTUModel(V, max_seq_len=L, dropout=0.0, **cfg)
+    trainer = SeqTrainer(model, device=str(dev))
+    g = torch.Generator().manual_seed(0)
+    lens = torch.randint(L // 4, L + 1, (B,), generator=g)
+    tok = torch.randint(1, V, (B, L), generator=g) * (torch.arange(L)[None, :] >= L - lens[:, None])  # left padded
+    td = torch.sort(torch.randint(0, 10**8, (B, L), generator=g), 1, descending=True).values
+    tok, td, tg = tok.to(dev), td.to(dev), torch.randint(1, V, (B,), generator=g).to(dev)
+
+    def timed(fn):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / steps * 1e3
+
+    hip = timed(lambda: trainer.train_step(tok, td, tg))
+    kernels = {}
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            trainer.train_step(tok, td, tg)
+            torch.cuda.synchronize()
+        import re
+        for ev in prof.key_averages():
+            m = re.search(r"\b(hstu_\w+_kernel|head_\w+_kernel)", ev.key)
+            if m:
+                us, n = kernels.get(m.group(1), (0.0, 0))
+                kernels[m.group(1)] = (us + ev.device_time_total, n + ev.count)
+    except Exception as e:  # noqa: BLE001
+        print(f"  [{name}] profiler unavailable: {type(e).__name__}: {e}")
+    mem_hip = torch.cuda.max_memory_allocated() / 2**30
+    torch.cuda.reset_peak_memory_stats()
+
+    def eager_loss():
+        padding = tok.ne(0)
+        x = model.token_embedding(tok) + model.position_embedding(torch.arange(L, device=dev))[None]
+        x = x + model.time_embedding(model._time_diff_to_bucket(td))
+        x = x * padding[..., None]
+        causal = torch.tril(torch.ones(L, L, device=dev, dtype=torch.bool))[None, None] & padding[:, None, None, :]
+        for layer in model.hstu_block.layers:
+            H, dqk, dv = layer.n_heads, layer.dqk, layer.dv
+            p = F.silu(layer.proj1(layer.norm_in(x)))
+            q = p[..., :H * dqk].reshape(B, L, H, dqk).transpose(1, 2)
+            k = p[..., H * dqk:2 * H * dqk].reshape(B, L, H, dqk).transpose(1, 2)
+            u = p[..., 2 * H * dqk:2 * H * dqk + H * dv]
+            v = p[..., 2 * H * dqk + H * dv:].reshape(B, L, H, dv).transpose(1, 2)
+            s = torch.matmul(q, k.transpose(-2, -1)) * layer.attn_alpha + layer.rab(time_diffs=td, seq_len=L)
+            a = F.silu(s.masked_fill(~causal, -1e4)) / layer.max_seq_len
+            o = torch.matmul(a, v).transpose(1, 2).reshape(B, L, H * dv)
+            x = x + layer.proj2(layer.norm_attn(o) * u)
+        x = x * padding[..., None]
+        w, b = model.token_embedding.weight, model.output_bias
+        if model.score_norm == "l2":
+            x, w = F.normalize(x, dim=-1, eps=model.l2_norm_eps), F.normalize(w, dim=-1, eps=model.l2_norm_eps)
+        logits = F.linear(x, w, b)
+        if model.temperature != 1.0:
+            logits = logits / model.temperature
+        return trainer._compute_next_token_loss(logits, tok, tg)
+
+    def eager_step():
+        loss = eager_loss()
+        model.zero_grad()
+        loss.backward()
+        trainer.optimizer.step()
+
+    eager_top = []
+    try:
+        eager = timed(eager_step)
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            eager_step()
+            torch.cuda.synchronize()
+        evs = [ev for ev in prof.key_averages() if ev.device_time_total > 0]
+        total = sum(ev.device_time_total for ev in evs)
+        eager_top = [(ev.key[:70], ev.device_time_total, ev.count) for ev in
+                     sorted(evs, key=lambda ev: -ev.device_time_total)[:8]] + [("(all device work)", total, 0)]
+    except torch.cuda.OutOfMemoryError:
+        eager = float("nan")
+        print(f"  [{name}] eager restatement does not fit")
+    mem_eager = torch.cuda.max_memory_allocated() / 2**30
+    print(f"{name:10s} B={B} L={L} V={V}  HIP {hip:8.3f} ms/step (peak {mem_hip:.1f} GiB)   plain PyTorch eager "
+          f"{eager:8.3f} ms/step (peak {mem_eager:.1f} GiB)   speedup {eager / hip:.2f}x", flush=True)
+    for k, (us, n) in sorted(kernels.items(), key=lambda kv: -kv[1][0]):
+        print(f"    {k:32s} {us:10.1f} us per step ({n} launches)", flush=True)
+    for k, us, n in eager_top:
+        print(f"    eager: {k:70s} {us:12.1f} us per step ({n} launches)", flush=True)
+    from torch_rechub_amd import ops
+    ops.check_errors()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", default="dcn,dcnv2,din,dssm")
@@ -290,6 +402,10 @@ def main():
     dev = torch.device("cuda:0")
     for name in a.models.split(","):
         torch.cuda.empty_cache()
+        if name in HSTU:
+            hstu_bench(name, dev, a.steps)
+            torch.cuda.reset_peak_memory_stats()
+            continue
         trainer, x, y = build(name, dev, a.batch, a.scale)
         trainer.model.train()
         trainer.optimizer.sync_hyper()

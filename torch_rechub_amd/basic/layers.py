@@ -16,10 +16,13 @@
 | CEN              | :777-786                    | descriptor and rescale kernels (ops.cen_descriptor / cen_rescale) around the attention MLP |
 | MultiInterestSA  | :568-609                    | GEMM path for tanh(E W1) W2, ONE masked-softmax + pooling launch each way (ops.sa_pool) |
 | CapsuleNetwork   | :612-712                    | ONE routing launch with the projections in LDS (ops.capsule_routing); type 2 never forms (B, L, I*D, D) |
+| HSTULayer / HSTUBlock | :792-972               | LayerNorms / proj1 / proj2 on the library, attention ONE launch each way (ops.hstu_attention) |
 
 Tables stay ``nn.Embedding`` modules inside ``embed_dict`` (checkpoint ABI:
 ``embedding.embed_dict.<feature>.weight``); kernels read them in place.
 """
+import math
+
 import torch
 from torch import nn
 
@@ -779,3 +782,65 @@ class CapsuleNetwork(nn.Module):
         if self.relu_layer:
             cap = self.relu(cap)
         return cap
+
+
+class HSTULayer(nn.Module):
+    """One HSTU layer (reference basic/layers.py:792-933): U, V, Q, K = split(silu(proj1(LN(x)))), then
+    proj2(dropout(LN(A V) * U)) with A = silu(alpha Q K^T + rab) / N under the causal and key-padding masks.  The
+    attention is ONE HIP launch each way (ops.hstu_attention) that never forms the (B, H, L, L) scores or bias; the
+    LayerNorms and the two projections stay on the library."""
+
+    def __init__(self, d_model=512, n_heads=8, dqk=64, dv=64, dropout=0.1, max_seq_len=200, num_time_buckets=128,
+                 time_bucket_fn='sqrt', time_bucket_divisor=1.0, time_bucket_unit='minutes'):
+        super().__init__()
+        if d_model % n_heads != 0:
+            raise ValueError(f"d_model ({d_model}) must be divisible by n_heads ({n_heads}).")
+        from ..utils.hstu_utils import RelativeBucketedTimeAndPositionBias
+        self.d_model = d_model
+        self.n_heads = n_heads
+        self.dqk = dqk
+        self.dv = dv
+        self.max_seq_len = max_seq_len
+        self.attn_alpha = 1.0 / math.sqrt(dqk)
+        self.norm_in = nn.LayerNorm(d_model)
+        self.proj1 = nn.Linear(d_model, 2 * n_heads * dqk + 2 * n_heads * dv)
+        self.rab = RelativeBucketedTimeAndPositionBias(n_heads=n_heads, max_seq_len=max_seq_len,
+                                                       num_time_buckets=num_time_buckets, time_bucket_fn=time_bucket_fn,
+                                                       time_bucket_divisor=time_bucket_divisor,
+                                                       time_bucket_unit=time_bucket_unit)
+        self.norm_attn = nn.LayerNorm(n_heads * dv)
+        self.proj2 = nn.Linear(n_heads * dv, d_model)
+        self.dropout = nn.Dropout(dropout)
+
+    def forward(self, x, padding_mask=None, time_diffs=None):
+        H, dqk, dv = self.n_heads, self.dqk, self.dv
+        proj = torch.nn.functional.silu(self.proj1(self.norm_in(x)))
+        u = proj[..., 2 * H * dqk:2 * H * dqk + H * dv]
+        rab = self.rab
+        attn = ops.hstu_attention(proj, rab.pos_w, rab.ts_w, H, dqk, dv, self.max_seq_len, time_diffs=time_diffs,
+                                  padding_mask=padding_mask, num_time_buckets=rab.num_time_buckets,
+                                  time_bucket_fn=rab.time_bucket_fn, time_bucket_divisor=rab.time_bucket_divisor,
+                                  time_bucket_unit=rab.time_bucket_unit)
+        return self.proj2(self.dropout(self.norm_attn(attn) * u))
+
+
+class HSTUBlock(nn.Module):
+    """``n_layers`` HSTULayers with the external residual x = x + layer(x) (reference basic/layers.py:936-972)."""
+
+    def __init__(self, d_model=512, n_heads=8, n_layers=4, dqk=64, dv=64, dropout=0.1, max_seq_len=200,
+                 num_time_buckets=128, time_bucket_fn='sqrt', time_bucket_divisor=1.0, time_bucket_unit='minutes'):
+        super().__init__()
+        self.d_model = d_model
+        self.n_heads = n_heads
+        self.n_layers = n_layers
+        self.layers = nn.ModuleList([
+            HSTULayer(d_model=d_model, n_heads=n_heads, dqk=dqk, dv=dv, dropout=dropout, max_seq_len=max_seq_len,
+                      num_time_buckets=num_time_buckets, time_bucket_fn=time_bucket_fn,
+                      time_bucket_divisor=time_bucket_divisor, time_bucket_unit=time_bucket_unit)
+            for _ in range(n_layers)
+        ])
+
+    def forward(self, x, padding_mask=None, time_diffs=None):
+        for layer in self.layers:
+            x = x + layer(x, padding_mask=padding_mask, time_diffs=time_diffs)
+        return x

@@ -4,6 +4,8 @@ Same classification rules: parameters of normalisation layers are skipped, param
 ``nn.Embedding`` / ``nn.EmbeddingBag`` modules use the embedding coefficients, everything else the
 dense ones.  Returns the python float 0.0 when nothing applies (the trainer adds it to the loss).
 """
+import torch
+import torch.nn.functional as F
 from torch import nn
 
 _NORMS = (nn.BatchNorm1d, nn.BatchNorm2d, nn.BatchNorm3d, nn.LayerNorm, nn.GroupNorm, nn.InstanceNorm1d,
@@ -72,3 +74,26 @@ class BPRLoss(nn.Module):
         pos_score = pos_score.view(-1)
         diff = pos_score - neg_score if neg_score.dim() == 1 else pos_score.view(-1, 1) - neg_score
         return -diff.sigmoid().log().mean()
+
+
+class NCELoss(nn.Module):
+    """Temperature-scaled softmax cross entropy with an ignored target id (reference basic/loss_func.py:110-175): the
+    mean / sum over rows whose target is not ``ignore_index``, or over every row when there is none."""
+
+    def __init__(self, temperature=1.0, ignore_index=0, reduction='mean'):
+        super().__init__()
+        self.temperature = temperature
+        self.ignore_index = ignore_index
+        self.reduction = reduction
+
+    def forward(self, logits, targets):
+        log_probs = F.log_softmax(logits / self.temperature, dim=-1)
+        loss = -log_probs[torch.arange(targets.shape[0], device=targets.device), targets]
+        keep = targets != self.ignore_index
+        if keep.any():
+            loss = loss[keep]
+        if self.reduction == 'mean':
+            return loss.mean()
+        if self.reduction == 'sum':
+            return loss.sum()
+        return loss

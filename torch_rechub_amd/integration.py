@@ -20,14 +20,15 @@ import sys
 
 _LAYERS = ("EmbeddingLayer", "InputMask", "SumPooling", "AveragePooling", "ConcatPooling", "LR", "MLP", "FM",
            "CrossNetwork", "CrossNetV2", "CrossNetMix", "SENETLayer", "BiLinearInteractionLayer", "InteractingLayer",
-           "CrossLayer", "FFM", "CEN", "MultiInterestSA", "CapsuleNetwork")
+           "CrossLayer", "FFM", "CEN", "MultiInterestSA", "CapsuleNetwork", "HSTULayer", "HSTUBlock")
 _FEATURES = ("DenseFeature", "SparseFeature", "SequenceFeature")
 _ACTIVATIONS = ("Dice", "activation_layer")
 _MODELS = {"ranking": ("DeepFM", "WideDeep", "DCN", "DCNv2", "DIN", "DIEN", "BST", "AFM", "AutoInt", "EDCN", "FiBiNet",
                        "DeepFFM", "FatDeepFFM"),
            "matching": ("DSSM", "YoutubeDNN", "MIND", "ComirecSA", "ComirecDR"),
-           "multi_task": ("SharedBottom", "ESMM", "MMOE", "PLE", "AITM")}
-_TRAINERS = ("CTRTrainer", "MatchTrainer", "MTLTrainer")
+           "multi_task": ("SharedBottom", "ESMM", "MMOE", "PLE", "AITM"),
+           "generative": ("HSTUModel",)}
+_TRAINERS = ("CTRTrainer", "MatchTrainer", "MTLTrainer", "SeqTrainer")
 
 _undo = []  # (module, attribute, original object)
 

@@ -1,1 +1,1 @@
-from . import matching, ranking  # noqa: F401
+from . import generative, matching, ranking  # noqa: F401

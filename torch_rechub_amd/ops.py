@@ -11,6 +11,7 @@ backward scatter-adds into it and publishes it as ``weight.grad``; ``FusedDenseA
 touched rows inside its own pass.  A stock ``torch.optim`` optimizer sees an ordinary dense ``.grad``.
 """
 import ctypes
+import math
 import os
 from collections import OrderedDict
 
@@ -138,6 +139,8 @@ def check_errors(device=None):
             f.zero_()
             if v & 1:
                 raise IndexError("torch_rechub_amd: an embedding index was out of range (index < 0 or >= vocab_size)")
+            if v & 2:  # RH_FLAG_TARGET_OOB
+                raise IndexError("torch_rechub_amd: a target label was out of range (label < 0 or >= the number of classes)")
             if v & 64:  # RH_ERR_GATE_TIMEOUT
                 raise RuntimeError("torch_rechub_amd: a deferred table sweep waited 2 s for a training step that never started "
                                    "(rh_adam_sweep_gate); the tables may be inconsistent")
@@ -2890,3 +2893,121 @@ def listwise_logits(u, pos, neg, temperature=1.0):
         raise RuntimeError(f"torch_rechub_amd: list-wise scoring of user {tuple(u.shape)}, items {tuple(pos.shape)} / "
                            f"{tuple(neg.shape)} has no HIP kernel (I <= 16, D <= 64, K < 1024, float32)")
     return _ListwiseFn.apply(u, pos, neg, float(temperature))
+
+
+# --------------------------------------------------------------------------------------------
+# HSTU: pointwise relative-bias attention and the next-token head (csrc/hstu.hip)
+# --------------------------------------------------------------------------------------------
+class _HstuAttnFn(torch.autograd.Function):
+    """(B, L, H dv) = (silu(alpha q k^T + rab) / N, causal and key-padding masked) v, q / k / v read from proj."""
+
+    @staticmethod
+    def forward(ctx, proj, pos_w, ts_w, td, kmask, cfg):
+        proj = proj.contiguous()
+        B, L, ld = (int(v) for v in proj.shape)
+        H, dqk, dv, N, nb, fn_log, minutes, divisor, alpha = cfg
+        out = torch.empty((B, L, H * dv), dtype=torch.float32, device=proj.device)
+        _lib.call("rh_hstu_attn_fwd", _p(proj), ld, B, L, H, dqk, dv, _p(td), _p(kmask), _p(pos_w), _p(ts_w), N, nb,
+                  fn_log, minutes, divisor, alpha, _p(out), _stream())
+        ctx.cfg = cfg
+        ctx.save_for_backward(proj, pos_w, ts_w, td, kmask)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        proj, pos_w, ts_w, td, kmask = ctx.saved_tensors
+        B, L, ld = (int(v) for v in proj.shape)
+        H, dqk, dv, N, nb, fn_log, minutes, divisor, alpha = ctx.cfg
+        g = g.contiguous()
+        dev = g.device
+        g_proj = torch.zeros((B, L, ld), dtype=torch.float32, device=dev)  # the u columns stay zero
+        if B == 0:
+            return g_proj, torch.zeros_like(pos_w), torch.zeros_like(ts_w), None, None, None
+        nparts = _lib.call("rh_hstu_attn_nparts", B, L, H)
+        pos_part = torch.empty((nparts, L), dtype=torch.float32, device=dev)
+        ts_part = torch.empty((nparts, nb + 1), dtype=torch.float32, device=dev) if td is not None else None
+        g_pos = torch.empty_like(pos_w)
+        g_ts = torch.empty_like(ts_w)
+        _lib.call("rh_hstu_attn_bwd", _p(proj), ld, B, L, H, dqk, dv, _p(td), _p(kmask), _p(pos_w), _p(ts_w), N, nb,
+                  fn_log, minutes, divisor, alpha, _p(g), _p(g_proj), _p(pos_part), _p(ts_part), _p(g_pos), _p(g_ts),
+                  _stream())
+        return g_proj, g_pos, g_ts, None, None, None
+
+
+def hstu_attention(proj, pos_w, ts_w, n_heads, dqk, dv, max_seq_len, time_diffs=None, padding_mask=None,
+                   num_time_buckets=128, time_bucket_fn="sqrt", time_bucket_divisor=1.0, time_bucket_unit="minutes"):
+    """HSTU attention output (B, L, H dv) from ``proj`` (B, L, 2 H (dqk + dv)) = silu(proj1(LN(x))) laid out [q | k | u | v],
+    the rab tables pos_w (2 N - 1, H) / ts_w (nb + 1, H), time_diffs (B, L) int64 seconds or None (position-only bias) and
+    padding_mask (B, L) bool (True = valid key) or None."""
+    require_hip(proj, pos_w, ts_w, time_diffs, padding_mask)
+    if proj.dtype != torch.float32 or pos_w.dtype != torch.float32 or ts_w.dtype != torch.float32:
+        raise RuntimeError("torch_rechub_amd: HSTU attention runs in float32 only")
+    B, L, W = (int(v) for v in proj.shape)
+    if W != 2 * n_heads * (dqk + dv):
+        raise RuntimeError(f"torch_rechub_amd: HSTU projection width {W} != 2 * {n_heads} * ({dqk} + {dv})")
+    if not (1 <= L <= min(int(max_seq_len), 1024) and 1 <= dqk <= 64 and 1 <= dv <= 64 and num_time_buckets <= 1023):
+        raise RuntimeError(f"torch_rechub_amd: HSTU attention with L={L}, dqk={dqk}, dv={dv}, "
+                           f"num_time_buckets={num_time_buckets} has no HIP kernel (L <= min(max_seq_len, 1024), "
+                           "dqk, dv <= 64, num_time_buckets <= 1023)")
+    if time_bucket_fn not in ("sqrt", "log") or time_bucket_unit not in ("minutes", "seconds"):
+        raise ValueError(f"Unsupported time bucketing {time_bucket_fn!r} / {time_bucket_unit!r}")
+    td = None if time_diffs is None else time_diffs.to(torch.int64).contiguous()
+    km = None if padding_mask is None else padding_mask.to(torch.int32).contiguous()
+    cfg = (int(n_heads), int(dqk), int(dv), int(max_seq_len), int(num_time_buckets), int(time_bucket_fn == "log"),
+           int(time_bucket_unit == "minutes"), float(time_bucket_divisor), 1.0 / math.sqrt(dqk))
+    return _HstuAttnFn.apply(proj, pos_w.contiguous(), ts_w.contiguous(), td, km, cfg)
+
+
+class _NextTokenLossFn(torch.autograd.Function):
+    """Mean next-token cross entropy over the item table without the (M, V) logits."""
+
+    @staticmethod
+    def forward(ctx, h, w, bias, labels, t1, t2, nce):
+        h, w = h.contiguous(), w.contiguous()
+        M, D = (int(v) for v in h.shape)
+        V = int(w.shape[0])
+        dev = h.device
+        nsplit = _lib.call("rh_hstu_head_nsplit", M, V)
+        part = torch.empty((M, nsplit, 2), dtype=torch.float32, device=dev)
+        zlab = torch.empty((M,), dtype=torch.float32, device=dev)
+        lse = torch.empty((M,), dtype=torch.float32, device=dev)
+        wrow = torch.empty((M,), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        _lib.call("rh_hstu_head_fwd", _p(h), _p(w), _p(bias), _p(labels), M, D, V, t1, t2, int(nce), _p(part), _p(zlab),
+                  _p(lse), _p(wrow), _p(loss), _p(err_flag(dev)), _stream())
+        ctx.t = (t1, t2)
+        ctx.has_bias = bias is not None
+        ctx.save_for_backward(h, w, bias, labels, lse, wrow)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        h, w, bias, labels, lse, wrow = ctx.saved_tensors
+        M, D = (int(v) for v in h.shape)
+        V = int(w.shape[0])
+        t1, t2 = ctx.t
+        dev = h.device
+        R = _lib.call("rh_hstu_head_rsplit", M, D, V)
+        part = torch.empty((R, V, D + 1) if R > 1 else (1,), dtype=torch.float32, device=dev)
+        g_h = torch.empty_like(h)
+        g_w = torch.empty_like(w)
+        g_b = torch.empty((V,), dtype=torch.float32, device=dev) if ctx.has_bias else None
+        _lib.call("rh_hstu_head_bwd", _p(h), _p(w), _p(bias), _p(labels), _p(lse), _p(wrow), _p(g.reshape(1).contiguous()),
+                  M, D, V, t1, t2, _p(part), _p(g_h), _p(g_w), _p(g_b), _stream())
+        return g_h, g_w, g_b, None, None, None, None
+
+
+def next_token_loss(h, weight, bias, labels, temperature=1.0, nce_temperature=None):
+    """Mean cross entropy of the next-token logits z = ((h weight^T + bias) / temperature) [/ nce_temperature] over the
+    rows whose label is not 0, column 0 excluded (SeqTrainer._compute_next_token_loss with ignore_index 0).  h (M, D),
+    weight (V, D), bias (V,) or None, labels (M,) int64.  nce_temperature given: NCELoss (mean over every row when no
+    label is set); else nn.CrossEntropyLoss (NaN then)."""
+    require_hip(h, weight, bias, labels)
+    if h.dim() != 2 or weight.dim() != 2 or h.shape[1] != weight.shape[1] or weight.shape[0] < 2 or h.shape[0] < 1:
+        raise RuntimeError(f"torch_rechub_amd: next-token head of h {tuple(h.shape)} and weight {tuple(weight.shape)} "
+                           "unsupported (h (M, D), weight (V, D), M >= 1, V >= 2)")
+    if h.dtype != torch.float32 or weight.dtype != torch.float32:
+        raise RuntimeError("torch_rechub_amd: the next-token head runs in float32 only")
+    nce = nce_temperature is not None
+    return _NextTokenLossFn.apply(h, weight, bias, labels.to(torch.int64).contiguous(), float(temperature),
+                                  float(nce_temperature) if nce else 1.0, nce)

@@ -1,1 +1,1 @@
-from . import data, match  # noqa: F401
+from . import data, hstu_utils, match  # noqa: F401

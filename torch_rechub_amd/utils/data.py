@@ -334,3 +334,27 @@ class DeviceDataLoader(object):
             yield self.load_next()
         if rem and not self.drop_last:
             yield self.load_next(rem)
+
+
+class SeqDataset(Dataset):
+    """Next-item samples (reference torch_rechub/utils/data.py:396-452): yields int64
+    ``(seq_tokens, seq_positions, seq_time_diffs, target)`` rows of the given (N, L) / (N,) arrays."""
+
+    def __init__(self, seq_tokens, seq_positions, targets, seq_time_diffs):
+        super().__init__()
+        self.seq_tokens = seq_tokens
+        self.seq_positions = seq_positions
+        self.targets = targets
+        self.seq_time_diffs = seq_time_diffs
+        assert len(seq_tokens) == len(targets), "seq_tokens and targets must have same length"
+        assert len(seq_tokens) == len(seq_positions), "seq_tokens and seq_positions must have same length"
+        assert len(seq_tokens) == len(seq_time_diffs), "seq_tokens and seq_time_diffs must have same length"
+        assert seq_tokens.shape[1] == seq_positions.shape[1], "seq_tokens and seq_positions must have same seq_len"
+        assert seq_tokens.shape[1] == seq_time_diffs.shape[1], "seq_tokens and seq_time_diffs must have same seq_len"
+
+    def __getitem__(self, index):
+        return (torch.LongTensor(self.seq_tokens[index]), torch.LongTensor(self.seq_positions[index]),
+                torch.LongTensor(self.seq_time_diffs[index]), torch.tensor(self.targets[index], dtype=torch.long))
+
+    def __len__(self):
+        return len(self.targets)
