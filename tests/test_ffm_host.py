@@ -167,3 +167,76 @@ def test_ffm_entry_points_reject_unsupported_shapes():
     with pytest.raises(RuntimeError, match="either"):
         _lib.call("rh_ffm_fwd", fake, null, 1, null, 0, 4, 3, 4, 4, 0, fake, 12, null, null)
     assert _lib.call("rh_cen_nchunks", 4096) == 64
+
+
+def np_ffm_bwd(x, g, reduce_sum):
+    """dX (B, F, F, D) of np_ffm for upstream g (B, P, D) or (B, P, 1): dX[:, i, j] = g_p x[:, j, i], the diagonal zero.
+    Each element is one product, so in float32 it is what a float32 kernel must produce bit for bit."""
+    B, F, _, D = x.shape
+    gx = np.zeros_like(x)
+    for p, (i, j) in enumerate((i, j) for i in range(F - 1) for j in range(i + 1, F)):
+        gp = g[:, p, :] if not reduce_sum else np.broadcast_to(g[:, p, :1], (B, D))
+        gx[:, i, j] = gp * x[:, j, i]
+        gx[:, j, i] = gp * x[:, i, j]
+    return gx
+
+
+def np_cen_desc(em, u):
+    """CEN descriptor d (B, P) = relu(sum_d u * em) for em (B, P, D), u (P, D)."""
+    return np.maximum((u[None] * em).sum(-1), 0)
+
+
+def np_cen_desc_bwd(em, u, g_d, d=None):
+    """(g_em (B, P, D), g_u (P, D)) of np_cen_desc; a tie at d = 0 passes no gradient, as torch's ReLU.  ``d``: the
+    descriptor whose ReLU mask to use (default: the float64 one)."""
+    gg = np.where((np_cen_desc(em, u) if d is None else d) > 0, g_d, 0.0)
+    return gg[..., None] * u[None], (gg[..., None] * em).sum(0)
+
+
+def np_cen_rescale_bwd(em, s, g):
+    """(g_em (B, P, D), g_s (B, P)) of aem = s[..., None] * em for upstream g (B, P, D)."""
+    return s[..., None] * g, (g * em).sum(-1)
+
+
+@pytest.mark.parametrize("rs", [0, 1])
+def test_numpy_ffm_backward_matches_autograd(rs):
+    g = torch.Generator().manual_seed(7 + rs)
+    B, F, D = 5, 4, 3
+    x = torch.randn(B, F, F, D, generator=g, dtype=torch.float64, requires_grad=True)
+    out = torch.stack([x[:, i, j, :] * x[:, j, i, :] for i in range(F - 1) for j in range(i + 1, F)], dim=1)
+    if rs:
+        out = out.sum(-1, keepdim=True)
+    np.testing.assert_allclose(np_ffm(x.detach().numpy(), rs), out.detach().numpy(), rtol=1e-15, atol=0)
+    gy = torch.randn(out.shape, generator=g, dtype=torch.float64)
+    out.backward(gy)
+    want = x.grad.numpy()
+    got = np_ffm_bwd(x.detach().numpy(), gy.numpy(), rs)
+    np.testing.assert_allclose(got, want, rtol=1e-15, atol=0)
+    assert not got[:, range(F), range(F)].any()
+
+
+def test_numpy_cen_backward_matches_autograd():
+    g = torch.Generator().manual_seed(9)
+    B, P, D = 7, 6, 5
+    em = torch.randn(B, P, D, generator=g, dtype=torch.float64)
+    em[0, 1] = 0.0  # d = 0 exactly: a tie of the ReLU
+    em[2, 3] = 0.0
+    em.requires_grad_(True)
+    u = torch.randn(P, D, generator=g, dtype=torch.float64, requires_grad=True)
+    d = torch.relu((u * em).sum(-1))
+    assert d[0, 1] == 0 and d[2, 3] == 0 and (d == 0).sum() > 2  # ties and negative sums both present
+    np.testing.assert_allclose(np_cen_desc(em.detach().numpy(), u.detach().numpy()), d.detach().numpy(), rtol=1e-14)
+    gd = torch.randn(B, P, generator=g, dtype=torch.float64)
+    d.backward(gd)
+    g_em, g_u = np_cen_desc_bwd(em.detach().numpy(), u.detach().numpy(), gd.numpy())
+    np.testing.assert_allclose(g_em, em.grad.numpy(), rtol=1e-14, atol=1e-15)
+    np.testing.assert_allclose(g_u, u.grad.numpy(), rtol=1e-14, atol=1e-15)
+    assert not g_em[0, 1].any() and not g_em[2, 3].any()
+    em2 = em.detach().clone().requires_grad_(True)
+    s = torch.randn(B, P, generator=g, dtype=torch.float64, requires_grad=True)
+    out = (s.unsqueeze(-1) * em2).reshape(B, -1)
+    gy = torch.randn(out.shape, generator=g, dtype=torch.float64)
+    out.backward(gy)
+    g_em, g_s = np_cen_rescale_bwd(em2.detach().numpy(), s.detach().numpy(), gy.numpy().reshape(B, P, D))
+    np.testing.assert_allclose(g_em.reshape(B, -1), em2.grad.numpy().reshape(B, -1), rtol=1e-15, atol=0)
+    np.testing.assert_allclose(g_s, s.grad.numpy(), rtol=1e-14, atol=1e-15)

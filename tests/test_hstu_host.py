@@ -261,3 +261,31 @@ def test_seq_trainer_rejects_unsupported_loss_params_at_construction():
             SeqTrainer(m, device="cuda:0", loss_params=lp)
     with pytest.raises(ValueError, match="loss_type"):
         SeqTrainer(m, device="cuda:0", loss_type="bpr")
+
+
+def test_hstu_entry_points_reject_unsupported_shapes():
+    """Argument validation of csrc/hstu.hip at the first shape past each limit: nothing is launched (the pointers are
+    never dereferenced)."""
+    import ctypes
+
+    from torch_rechub_amd import _lib
+    f, n = ctypes.c_void_p(4096), ctypes.c_void_p(0)
+
+    def attn(L, H, dqk, dv, N, nb, td=f):
+        ld = 2 * H * (dqk + dv)
+        fwd = ("rh_hstu_attn_fwd", f, ld, 2, L, H, dqk, dv, td, f, f, f, N, nb, 0, 1, 1.0, 0.5, f, n)
+        bwd = ("rh_hstu_attn_bwd", f, ld, 2, L, H, dqk, dv, td, f, f, f, N, nb, 0, 1, 1.0, 0.5, f, f, f, f, f, f, n)
+        return fwd, bwd
+
+    for args, what in ((attn(1025, 1, 8, 8, 1025, 16), "L=1025"), (attn(65, 1, 8, 8, 64, 16), "L=65"),
+                       (attn(8, 1, 65, 8, 8, 16), "dqk=65"), (attn(8, 1, 8, 65, 8, 16), "dv=65"),
+                       (attn(8, 1, 0, 8, 8, 16), "dqk=0"), (attn(8, 1, 8, 8, 8, 1024), "num_time_buckets=1024")):
+        for call in args:
+            with pytest.raises(RuntimeError, match=what):
+                _lib.call(*call)
+    assert _lib.call("rh_hstu_attn_nparts", 3, 65, 2) == 3 * 2 * 2
+    for M, D, V, t1 in ((0, 8, 10, 1.0), (4, 0, 10, 1.0), (4, 8, 1, 1.0), (4, 8, 10, 0.0)):
+        with pytest.raises(RuntimeError, match="unsupported"):
+            _lib.call("rh_hstu_head_fwd", f, f, n, f, M, D, V, t1, 1.0, 0, f, f, f, f, f, n, n)
+        with pytest.raises(RuntimeError, match="unsupported"):
+            _lib.call("rh_hstu_head_bwd", f, f, n, f, f, f, f, M, D, V, t1, 1.0, f, f, f, n, n)

@@ -259,3 +259,60 @@ def test_models_refuse_cpu_tensors():
     x = {k[3:]: torch.from_numpy(gold[k]) for k in gold.files if k.startswith("x0.")}
     with pytest.raises(RuntimeError):
         model(x)
+
+
+def test_interest_entry_points_reject_unsupported_shapes():
+    """Argument validation of csrc/interest.hip at the first shape past each limit: nothing is launched (the pointers are
+    never dereferenced), and the support queries agree with the checks."""
+    import ctypes
+
+    from torch_rechub_amd import _lib
+    f, n = ctypes.c_void_p(4096), ctypes.c_void_p(0)
+
+    def caps_fwd(L, I, D, kind):
+        return _lib.call("rh_capsule_fwd", f, f, f, f, n, 4, L, I, D, kind, 3, f, f, f, n)
+
+    def caps_bwd(L, I, D, kind):
+        return _lib.call("rh_capsule_bwd", f, f, f, f, 4, L, I, D, kind, f, f, f, n)
+
+    for call in (caps_fwd, caps_bwd):
+        with pytest.raises(RuntimeError, match="no HIP kernel|unsupported"):
+            call(8, 1, 65, 0)                      # D = 65
+        with pytest.raises(RuntimeError, match="no HIP kernel|unsupported"):
+            call(8, 257, 1, 1)                     # I*D = 257
+        with pytest.raises(RuntimeError, match="no HIP kernel|unsupported"):
+            call(8, 5, 29, 2)                      # type 2: I*D*D = 4205 > 4096 (I*D = 145)
+        with pytest.raises(RuntimeError, match="no HIP kernel|unsupported"):
+            call(8, 17, 16, 2)                     # I*D = 272
+        for I, D, kind in ((16, 16, 0), (1, 64, 2), (4, 32, 2), (4, 1, 1)):
+            L = 1
+            while _lib.call("rh_capsule_supported", 2 * L, I, D, kind):
+                L *= 2
+            lo, hi = L, 2 * L                      # supported(lo), not supported(hi)
+            while hi - lo > 1:
+                mid = (lo + hi) // 2
+                lo, hi = (mid, hi) if _lib.call("rh_capsule_supported", mid, I, D, kind) else (lo, mid)
+            with pytest.raises(RuntimeError, match="no HIP kernel|unsupported"):
+                call(hi, I, D, kind)               # one position past the LDS limit
+    assert _lib.call("rh_capsule_supported", 8, 1, 64, 2) == 1 and _lib.call("rh_capsule_supported", 8, 4, 32, 2) == 1
+    assert _lib.call("rh_capsule_supported", 8, 5, 29, 2) == 0 and _lib.call("rh_capsule_supported", 8, 4, 33, 2) == 0
+    with pytest.raises(RuntimeError, match="unsupported"):
+        _lib.call("rh_capsule_wgrad", f, f, f, 4, 8, 4, 33, f, n)   # I*D*D = 4356
+    with pytest.raises(RuntimeError, match="unsupported"):
+        _lib.call("rh_capsule_wgrad", f, f, f, 4, 8, 1, 65, f, n)
+    with pytest.raises(RuntimeError, match="unsupported"):
+        _lib.call("rh_capsule_wgrad", f, f, f, 0, 8, 4, 16, f, n)   # nothing to sum: the caller zeroes instead
+    for L, I, D in ((1025, 1, 1), (257, 4, 16), (1, 1, 65), (4, 1025, 1), (2, 17, 61)):
+        assert not _lib.call("rh_sa_supported", L, I, D)
+        with pytest.raises(RuntimeError, match="no HIP kernel"):
+            _lib.call("rh_sa_pool_fwd", f, f, f, 4, L, I, D, f, f, n)
+        with pytest.raises(RuntimeError, match="unsupported"):
+            _lib.call("rh_sa_pool_bwd", f, f, f, 4, L, I, D, f, f, n)
+    assert _lib.call("rh_sa_supported", 1024, 1, 64) and _lib.call("rh_sa_supported", 64, 16, 64)
+    for I, D, K in ((17, 16, 3), (4, 65, 3), (4, 16, 1024)):
+        with pytest.raises(RuntimeError, match="no HIP kernel"):
+            _lib.call("rh_listwise_fwd", f, f, D, f, 4, I, D, K, 1.0, f, f, f, n)
+        with pytest.raises(RuntimeError, match="unsupported"):
+            _lib.call("rh_listwise_bwd", f, f, D, f, f, f, f, 4, I, D, K, 1.0, f, f, f, n)
+    with pytest.raises(RuntimeError, match="bad arguments"):  # a row stride below D
+        _lib.call("rh_listwise_fwd", f, f, 15, f, 4, 4, 16, 3, 1.0, f, f, f, n)
