@@ -47,6 +47,8 @@ extern "C" {
 /* err_flag bits */
 #define RH_FLAG_INDEX_OOB 1 /* an index was <0 or >= vocab (reference: IndexError / device assert) */
 #define RH_FLAG_TARGET_OOB 2 /* a class label was < 0 or >= the class count (reference: IndexError) */
+#define RH_FLAG_SESSION_EMPTY 128 /* a session row holds no item (reference: pack_padded_sequence raises) */
+#define RH_FLAG_SESSION_SHORT 256 /* no session row reaches the padded length L (reference NARM: broadcast error) */
 
 int rh_abi_version(void);
 const char* rh_last_error(void);
@@ -863,6 +865,57 @@ int rh_hstu_head_fwd(const float* h, const float* W, const float* bias, const in
 int rh_hstu_head_bwd(const float* h, const float* W, const float* bias, const int64_t* labels, const float* lse,
                      const float* wrow, const float* g_loss, int M, int D, int V, float t1, float t2, float* part, float* g_h,
                      float* g_W, float* g_bias, void* stream);
+
+/* Full-catalogue cross entropy (the same streaming head, every column and every row counted, no bias / temperature):
+ * u (B, D), E (V, D), labels (B,) int64 in [0, V).  loss (1,) = mean over rows of lse(u E^T) - (u E^T)[label].
+ * rh_catalogue_ce_fwd: part (B, rh_hstu_head_nsplit(B, V), 2) workspace; zlab, lse, wrow (B,) for the backward; a label
+ *   outside [0, V) ORs RH_FLAG_TARGET_OOB into *err (when not null) and its row's loss is undefined.
+ * rh_catalogue_ce_bwd: g_loss (1,) device scalar -> g_u (B, D), dense g_E (V, D); part (rh_hstu_head_rsplit(B, D, V), V,
+ *   D + 1) workspace (unused when that count is 1), part_h (rh_catalogue_ce_vsplit(B, D, V), B, D) workspace (unused when 1).
+ *   B >= 1, 2 <= V <= 2^30, any D; the (B, V) logits never exist; no atomics.
+ * replaces: nn.CrossEntropyLoss over NARM / STAMP's (B, V) scores (models/matching/narm.py:111, stamp.py:99 with
+ *           MatchTrainer(mode=2), examples/matching/run_sbr.py), and autograd. */
+int rh_catalogue_ce_vsplit(int B, int D, int V);
+int rh_catalogue_ce_fwd(const float* u, const float* E, const int64_t* labels, int B, int D, int V, float* part, float* zlab,
+                        float* lse, float* wrow, float* loss, int32_t* err, void* stream);
+int rh_catalogue_ce_bwd(const float* u, const float* E, const int64_t* labels, const float* lse, const float* wrow,
+                        const float* g_loss, int B, int D, int V, float* part, float* part_h, float* g_u, float* g_E,
+                        void* stream);
+
+/* ---- session-based retrieval (csrc/session.hip) ---------------------------------------------------------------------
+ * GRU recurrence of nn.GRU (gate order r, z, n) from the zero state: xw (B, T, 3H) = x W_ih^T (+ b_ih) for every step,
+ * w_hh (3H, H) = weight_hh, b_hh (3H,) or null.  1 <= H <= rh_gru_max_hidden() (128), else RH_E_UNSUPPORTED.
+ * rh_gru_fwd: h_all (B, T, H) every state; hu (B, T, 3H) the state products h_{t-1} W_hh^T + b_hh (for the backward).
+ * rh_gru_bwd: g (B, T, H) gradient of h_all -> d_xw (B, T, 3H) the input-side pre-activation gradients
+ *   [r | z | n] and d_s (B, T, 3H) the state-side ones [r | z | hu_n] (weight gradients: d_s^T h_prev, d_xw^T x).
+ * replaces: nn.GRU / pack_padded_sequence (models/matching/narm.py:55-57, gru4rec.py:60) and its autograd. */
+int rh_gru_max_hidden(void);
+int rh_gru_fwd(const float* xw, const float* w_hh, const float* b_hh, int B, int T, int H, float* h_all, float* hu,
+               void* stream);
+int rh_gru_bwd(const float* xw, const float* w_hh, const float* h_all, const float* hu, const float* g, int B, int T, int H,
+               float* d_xw, float* d_s, void* stream);
+/* Additive attention pooling: s_l = sum_h w0_h sigmoid(P_lh + r_h), e_l = exp(s_l) mask_l, a_l = e_l / den with
+ * den = sum_l e_l (floor = 0) or max(sum_l e_l, 1e-12) (floor = 1), out (B, Dx) = sum_l a_l X_l (+ add).  P (B, L, H),
+ * r (B, H), w0 (H,), mask (B, L) float 0 / 1, X (B, L, Dx), add (B, Dx) or null.  1 <= L <= 1024, 1 <= H, Dx <= 4096.
+ * rh_attn_pool_fwd: e (B, L), sums (B, 2) = (sum, den) for the backward.
+ * rh_attn_pool_bwd: g (B, Dx) -> dP (B, L, H), dr (B, H), dw0 (H,) (per-sample partials dw0_part (B, H) summed in a
+ *   fixed order), dX (B, L, Dx) the pooling term only.
+ * replaces: NARM's q / alpha / c_l (models/matching/narm.py:60-63), STAMP's a / m_a (stamp.py:66-67), and autograd. */
+int rh_attn_pool_fwd(const float* P, const float* r, const float* w0, const float* mask, const float* X, const float* add,
+                     int B, int L, int H, int Dx, int floor_, float* out, float* e, float* sums, void* stream);
+int rh_attn_pool_bwd(const float* P, const float* r, const float* w0, const float* X, const float* e, const float* sums,
+                     const float* g, int B, int L, int H, int Dx, int floor_, float* dP, float* dr, float* dw0_part,
+                     float* dw0, float* dX, void* stream);
+/* Dropout (n elements, 0 < p < 1) with the counter hash of the fused MLP dropout: rng (device int64 [seed, counter, ..]);
+ * the forward records the counter it used in saved_ctr and advances rng's; the backward recomputes the mask from it. */
+/* counts (B,) int64 = the number of non-zero ids of each row of seq (B, L) int64; a row without any ORs
+ * RH_FLAG_SESSION_EMPTY into *err, and with check_full a batch whose longest row is shorter than L ORs RH_FLAG_SESSION_SHORT.
+ * replaces: value_mask.sum(1).to("cpu") and the errors of pack_padded_sequence / NARM's broadcast (narm.py:50-61),
+ *           STAMP's gather at count - 1 (stamp.py:60). */
+int rh_session_lengths(const int64_t* seq, int B, int L, int check_full, int64_t* counts, int32_t* err, void* stream);
+int rh_session_dropout_fwd(const float* x, int64_t n, float p, int64_t* rng, int64_t* saved_ctr, float* y, void* stream);
+int rh_session_dropout_bwd(const float* g, int64_t n, float p, const int64_t* rng, const int64_t* saved_ctr, float* dx,
+                           void* stream);
 
 /* ---- row-sharded tables (one shard per rank) -----------------------------------------------------------------------
  * Global row g of a table lives on rank g % world as local row g / world.  rh_shard_localize rewrites an index matrix

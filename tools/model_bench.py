@@ -17,6 +17,12 @@
                 reference defaults (d 512, H 8, dqk = dv = 64, 4 layers, L 256) at B 64, V 100 k.  Times the HIP step
                 (fused attention and next-token loss), a plain-PyTorch eager restatement of the reference's op chain
                 (dense (B, H, L, L) attention, (B, L, V) logits, clone, CrossEntropyLoss) and the kernels' device times.
+  narm / stamp : the session-based example's shape (examples/matching/run_sbr.py: B 512, L <= 19, D 100, NARM hidden 50,
+                NARM's dropouts 0.25 / 0.5) with
+                a synthetic 50 000-item catalogue; narm_large / stamp_large: B 4096 against 10^6 items.  MatchTrainer(mode=2)
+                through the fused catalogue loss, against a plain-PyTorch eager restatement of the reference's step
+                (pack_padded_sequence + nn.GRU, the (B, V) scores, CrossEntropyLoss, torch.optim.Adam).
+  gru4rec     : run_ml_gru4rec.py's shape (D 16, L 50, K 3 negatives, two bias-free GRU layers) at B 4096.
     python tools/model_bench.py --models dcn,dcnv2,din,dssm --steps 30
 """
 import argparse
@@ -392,6 +398,146 @@ def hstu_bench(name, dev, steps):
     ops.check_errors()
 
 
+SESSION = {"narm": dict(B=512, L=19, V=50000), "stamp": dict(B=512, L=19, V=50000),
+           "narm_large": dict(B=4096, L=19, V=1000000), "stamp_large": dict(B=4096, L=19, V=1000000),
+           "gru4rec": dict(B=4096, L=50, V=100000)}
+
+
+def session_bench(name, dev, steps):
+    """ms/step of MatchTrainer on NARM / STAMP / GRU4Rec and of a plain-PyTorch eager restatement of the reference's step."""
+    import re
+
+    import torch.nn.functional as F
+    import torch.nn.utils.rnn as rnn_utils
+
+    from torch_rechub_amd.basic.features import SequenceFeature, SparseFeature
+    from torch_rechub_amd.models.matching import NARM, STAMP, GRU4Rec
+    from torch_rechub_amd.trainers import MatchTrainer
+    c = SESSION[name]
+    B, L, V = c["B"], c["L"], c["V"]
+    kind = name.split("_")[0]
+    g = torch.Generator().manual_seed(0)
+    seq = torch.randint(1, V, (B, L), generator=g)
+    lens = torch.randint(1, L + 1, (B,), generator=g)
+    lens[0] = L
+    if kind != "gru4rec":
+        seq[torch.arange(L)[None] >= lens[:, None]] = 0
+    torch.manual_seed(0)
+    if kind == "gru4rec":
+        D = 16
+        hist = SequenceFeature("hist_item_id", V, D, pooling="concat", shared_with="item_id")
+        user = [SparseFeature("user_id", 6040, D), SparseFeature("gender", 3, D), SparseFeature("age", 8, D)]
+        item = [SparseFeature("item_id", V, D)]
+        neg = [SequenceFeature("neg_items", V, D, pooling="concat", shared_with="item_id")]
+        model = GRU4Rec(user, [hist], item, neg, user_params={"dims": [64, D]}).to(dev)
+        x = {"user_id": torch.randint(0, 6040, (B,), generator=g), "gender": torch.randint(0, 3, (B,), generator=g),
+             "age": torch.randint(0, 8, (B,), generator=g), "hist_item_id": seq,
+             "item_id": torch.randint(1, V, (B,), generator=g), "neg_items": torch.randint(1, V, (B, 3), generator=g)}
+        y = torch.zeros(B, dtype=torch.long)
+    else:
+        D = 100
+        f = SequenceFeature("hist_item_id", V, D, pooling="concat")
+        model = (NARM(f, 50, 0.25, 0.5) if kind == "narm" else STAMP(f, 0.05, 0.002)).to(dev)  # (run_sbr.py defaults)
+        x = {"hist_item_id": seq}
+        y = torch.randint(0, V, (B,), generator=g)
+    x, y = {k: v.to(dev) for k, v in x.items()}, y.to(dev)
+    trainer = MatchTrainer(model, mode=2, device=str(dev), show_progress=False)
+
+    def timed(fn):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / steps * 1e3
+
+    torch.cuda.reset_peak_memory_stats()
+    hip = timed(lambda: trainer.train_step(x, y))
+    mem_hip = torch.cuda.max_memory_allocated() / 2**30
+    kernels = {}
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            trainer.train_step(x, y)
+            torch.cuda.synchronize()
+        for ev in prof.key_averages():
+            if ev.device_time_total > 0:
+                m = re.search(r"\b(\w+_kernel)\b", ev.key)
+                key = m.group(1) if m else ev.key[:40]
+                us, n = kernels.get(key, (0.0, 0))
+                kernels[key] = (us + ev.device_time_total, n + ev.count)
+    except Exception as e:  # noqa: BLE001
+        print(f"  [{name}] profiler unavailable: {type(e).__name__}: {e}")
+
+    # plain PyTorch: the reference's op chain on the same parameters, torch.optim.Adam
+    params = [p for p in model.parameters()]
+    opt = torch.optim.Adam(params, lr=1e-3, weight_decay=1e-5)
+    if kind == "narm":
+        def eager_loss():
+            mask = seq_d != 0
+            counts = mask.sum(1).cpu()
+            embs = rnn_utils.pack_padded_sequence(F.dropout(F.embedding(seq_d, model.item_emb.weight, 0), 0.25), counts, batch_first=True,
+                                                  enforce_sorted=False)
+            h, h_t = torch.nn.GRU.forward(model.gru, embs)
+            h_t = h_t.permute(1, 0, 2)
+            h, _ = rnn_utils.pad_packed_sequence(h, batch_first=True)
+            q = torch.sigmoid(h_t @ model.a_1.T + h @ model.a_2.T) @ model.v
+            alpha = torch.exp(q) * mask.unsqueeze(-1)
+            alpha = alpha / alpha.sum(dim=1, keepdim=True)
+            cvec = F.dropout(torch.hstack((h_t.squeeze(1), (alpha * h).sum(1))), 0.5)
+            return F.cross_entropy(cvec @ model.b.T @ model.item_emb.weight.T, y)
+    elif kind == "stamp":
+        def eager_loss():
+            m = model
+            vm = (seq_d != 0).unsqueeze(-1)
+            vc = vm.sum(dim=1, keepdim=True).squeeze(-1)
+            e = F.embedding(seq_d, m.item_emb.weight, 0) * vm
+            x_t = F.embedding(torch.gather(seq_d, 1, vc - 1), m.item_emb.weight, 0)
+            m_s = (e.sum(1) / vc).unsqueeze(1)
+            a = F.normalize(torch.exp(torch.sigmoid(e @ m.w_1_t + x_t @ m.w_2_t + m_s @ m.w_3_t + m.b_a) @ m.w_0) * vm,
+                            p=1, dim=1)
+            m_a = (a * e).sum(1) + m_s.squeeze(1)
+            u = m.f_s(m_a) * m.f_t(x_t).squeeze(1)
+            return F.cross_entropy(u @ m.item_emb.weight.T, y)
+    else:
+        tabs = model.embedding.embed_dict
+
+        def emb(k, ids):
+            t = tabs["item_id" if k in ("hist_item_id", "neg_items") else k]
+            return F.embedding(ids, t.weight)[..., :D]
+
+        def eager_loss():
+            u_in = torch.cat([emb(k, x[k]) for k in ("user_id", "gender", "age")], 1)
+            _, h = torch.nn.GRU.forward(model.gru, emb("hist_item_id", x["hist_item_id"]))
+            u = F.normalize(model.user_mlp.mlp(torch.cat([u_in, h[-1]], 1)), dim=-1).unsqueeze(1)
+            items = F.normalize(torch.cat([emb("item_id", x["item_id"]).unsqueeze(1), emb("neg_items", x["neg_items"])], 1),
+                                dim=-1)
+            return F.cross_entropy((u * items).sum(1), y)
+    seq_d = x["hist_item_id"]
+
+    def eager_step():
+        loss = eager_loss()
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+
+    torch.cuda.reset_peak_memory_stats()
+    try:
+        eager = timed(eager_step)
+    except torch.cuda.OutOfMemoryError:
+        eager = float("nan")
+        print(f"  [{name}] eager restatement does not fit")
+    mem_eager = torch.cuda.max_memory_allocated() / 2**30
+    print(f"{name:12s} B={B} L={L} V={V}  HIP {hip:8.3f} ms/step (peak {mem_hip:.1f} GiB)   plain PyTorch eager "
+          f"{eager:8.3f} ms/step (peak {mem_eager:.1f} GiB)   speedup {eager / hip:.2f}x", flush=True)
+    for k, (us, n) in sorted(kernels.items(), key=lambda kv: -kv[1][0])[:12]:
+        print(f"    {k:40s} {us:10.1f} us per step ({n} launches)", flush=True)
+    from torch_rechub_amd import ops
+    ops.check_errors()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", default="dcn,dcnv2,din,dssm")
@@ -402,6 +548,10 @@ def main():
     dev = torch.device("cuda:0")
     for name in a.models.split(","):
         torch.cuda.empty_cache()
+        if name in SESSION:
+            session_bench(name, dev, a.steps)
+            torch.cuda.reset_peak_memory_stats()
+            continue
         if name in HSTU:
             hstu_bench(name, dev, a.steps)
             torch.cuda.reset_peak_memory_stats()

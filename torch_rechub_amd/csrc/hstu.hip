@@ -489,6 +489,10 @@ struct HeadArgs {
   float* g_bias;         // (V,) or null
   int M, D, V, nsplit, nce, R;
   float t1, t2;
+  int c_lo;              // first column that counts: 1 (HSTU: column 0 excluded) or 0 (catalogue: every column)
+  int all_rows;          // 1: every row counts (catalogue); 0: rows labelled 0 are ignored (HSTU)
+  int Sv;                // dh: V ranges per row tile; > 1 writes per-range partials to part_h
+  float* part_h;         // (Sv, M, D) dh partials or null
 };
 
 // z tile (64 rows r0.. x 64 columns c0..) of the wavefront's quadrant; hs / ws are (64 x 64 + pad) LDS staging
@@ -533,7 +537,7 @@ __global__ __launch_bounds__(RH_BLOCK) void head_fwd_kernel(const HeadArgs a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int c = c0 + wn * 32 + li;
-      hs[(wm * 32 + acc_row(r, kk)) * kLd + wn * 32 + li] = (c >= 1 && c < a.V) ? head_z(a, acc[r], c) : -INFINITY;
+      hs[(wm * 32 + acc_row(r, kk)) * kLd + wn * 32 + li] = (c >= a.c_lo && c < a.V) ? head_z(a, acc[r], c) : -INFINITY;
     }
     __syncthreads();
     float m = -INFINITY;
@@ -549,7 +553,7 @@ __global__ __launch_bounds__(RH_BLOCK) void head_fwd_kernel(const HeadArgs a) {
       rs = rs * expf(rm - nm) + s * expf(m - nm);
       rm = nm;
     }
-    if (lab >= c0 + part * 16 && lab < c0 + part * 16 + 16 && lab >= 1 && lab < a.V && grow < a.M)
+    if (lab >= c0 + part * 16 && lab < c0 + part * 16 + 16 && lab >= a.c_lo && lab < a.V && grow < a.M)
       a.zlab[grow] = hs[row * kLd + (int)(lab - c0)];
   }
   if (part == 0 && grow < a.M) {
@@ -577,7 +581,7 @@ __global__ __launch_bounds__(RH_BLOCK) void head_combine_kernel(const HeadArgs a
     const float l = m + logf(sum);
     a.lse[r] = l;
     const int64_t lab = a.labels[r];
-    if (lab != 0) {
+    if (a.all_rows || lab != 0) {
       sl += l - a.zlab[r];
       ++n;
     }
@@ -599,7 +603,7 @@ __global__ __launch_bounds__(RH_BLOCK) void head_combine_kernel(const HeadArgs a
   // nn.CrossEntropyLoss: 0 / 0 = NaN with every row ignored; NCELoss: then the mean over every row
   const bool all_rows = cnt == 0 && a.nce;
   for (int r = tid; r < a.M; r += RH_BLOCK)
-    a.wrow[r] = all_rows ? 1.f / (float)a.M : (a.labels[r] != 0 ? 1.f / (float)cnt : 0.f);
+    a.wrow[r] = all_rows ? 1.f / (float)a.M : ((a.all_rows || a.labels[r] != 0) ? 1.f / (float)cnt : 0.f);
   if (tid == 0) a.loss[0] = all_rows ? red_a[0] / (float)a.M : red_l[0] / (float)cnt;
 }
 
@@ -611,7 +615,7 @@ __device__ __forceinline__ void head_dz(const HeadArgs& a, const v16f& acc, int 
     const int64_t row = (int64_t)r0 + wm * 32 + acc_row(r, kk);
     const int c = c0 + wn * 32 + li;
     float d = 0.f;
-    if (row < a.M && c >= 1 && c < a.V) {
+    if (row < a.M && c >= a.c_lo && c < a.V) {
       const float p = expf(head_z(a, acc[r], c) - a.lse[row]);
       const float y = a.labels[row] == c ? 1.f : 0.f;
       d = ((g * a.wrow[row] * (p - y)) / a.t2) / a.t1;
@@ -631,7 +635,10 @@ __global__ __launch_bounds__(RH_BLOCK) void head_dh_kernel(const HeadArgs a) {
 #pragma unroll
   for (int q = 0; q < 4; ++q) acc[q] = zero16();
   const int nvt = (a.V + kT - 1) / kT;
-  for (int t = 0; t < nvt; ++t) {
+  const int vs = blockIdx.z;
+  const int t_lo = a.Sv > 1 ? (int)((int64_t)nvt * vs / a.Sv) : 0;
+  const int t_hi = a.Sv > 1 ? (int)((int64_t)nvt * (vs + 1) / a.Sv) : nvt;
+  for (int t = t_lo; t < t_hi; ++t) {
     const int c0 = t * kT;
     v16f z = head_logits(a, r0, c0, hs, ws, tid, li, kk, wm, wn);
     float d[16];
@@ -659,7 +666,10 @@ __global__ __launch_bounds__(RH_BLOCK) void head_dh_kernel(const HeadArgs a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int64_t row = (int64_t)r0 + wm * 32 + acc_row(r, kk);
-      if (row < a.M) a.g_h[row * a.D + c] = acc[j][r];
+      if (row < a.M) {
+        if (a.Sv > 1) a.part_h[((int64_t)vs * a.M + row) * a.D + c] = acc[j][r];
+        else a.g_h[row * a.D + c] = acc[j][r];
+      }
     }
   }
 }
@@ -734,6 +744,16 @@ __global__ __launch_bounds__(RH_BLOCK) void head_dw_reduce_kernel(const HeadArgs
   }
 }
 
+// dh = sum of the Sv per-range partials in range order
+__global__ __launch_bounds__(RH_BLOCK) void head_dh_reduce_kernel(const HeadArgs a) {
+  const int64_t n = (int64_t)a.M * a.D;
+  for (int64_t e = (int64_t)blockIdx.x * RH_BLOCK + threadIdx.x; e < n; e += (int64_t)gridDim.x * RH_BLOCK) {
+    float s = 0.f;
+    for (int v = 0; v < a.Sv; ++v) s += a.part_h[(int64_t)v * n + e];
+    a.g_h[e] = s;
+  }
+}
+
 int head_check(const char* name, const HeadArgs& a) {
   RH_REQUIRE(a.h && a.W && a.labels, RH_E_BADARG, "%s: null pointer", name);
   RH_REQUIRE(a.M >= 1 && a.D >= 1 && a.V >= 2 && a.t1 > 0.f && a.t2 > 0.f, RH_E_BADARG,
@@ -778,6 +798,7 @@ extern "C" int rh_hstu_head_fwd(const float* h, const float* W, const float* bia
   a.t1 = t1;
   a.t2 = t2;
   a.nce = nce;
+  a.c_lo = 1;
   a.nsplit = rh_hstu_head_nsplit(M, V);
   if (int rc = head_check("rh_hstu_head_fwd", a)) return rc;
   RH_REQUIRE(part && zlab && lse && wrow && loss, RH_E_BADARG, "rh_hstu_head_fwd: null output");
@@ -809,6 +830,8 @@ extern "C" int rh_hstu_head_bwd(const float* h, const float* W, const float* bia
   a.t1 = t1;
   a.t2 = t2;
   a.R = rh_hstu_head_rsplit(M, D, V);
+  a.c_lo = 1;
+  a.Sv = 1;
   if (int rc = head_check("rh_hstu_head_bwd", a)) return rc;
   RH_REQUIRE(lse && wrow && g_loss && part && g_h && g_W, RH_E_BADARG, "rh_hstu_head_bwd: null pointer");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -822,5 +845,95 @@ extern "C" int rh_hstu_head_bwd(const float* h, const float* W, const float* bia
     hipLaunchKernelGGL(head_dw_reduce_kernel, dim3(grid), dim3(RH_BLOCK), 0, st, a);
   }
   RH_LAUNCH_CHECK("rh_hstu_head_bwd");
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Full-catalogue cross entropy (NARM / STAMP with MatchTrainer(mode=2): nn.CrossEntropyLoss over u E^T, reference
+// examples/matching/run_sbr.py): the same streaming head with every column and every row counted, no bias, no
+// temperature.  The backward splits the item range of each row tile over Sv workgroups (B is small next to V here) and
+// sums their dh partials in range order.
+
+extern "C" int rh_catalogue_ce_vsplit(int B, int D, int V) {
+  const int nrt = (B + kT - 1) / kT, nvt = (V + kT - 1) / kT, ndc = (D + kHeadDc - 1) / kHeadDc;
+  int s = 1;
+  while (nrt * ndc * s < 1024 && s * 2 <= nvt && s < 256) s *= 2;
+  return s;
+}
+
+extern "C" int rh_catalogue_ce_fwd(const float* u, const float* E, const int64_t* labels, int B, int D, int V, float* part,
+                                   float* zlab, float* lse, float* wrow, float* loss, int32_t* err, void* stream) {
+  HeadArgs a{};
+  a.h = u;
+  a.W = E;
+  a.labels = labels;
+  a.part = part;
+  a.zlab = zlab;
+  a.lse = lse;
+  a.wrow = wrow;
+  a.loss = loss;
+  a.err = err;
+  a.M = B;
+  a.D = D;
+  a.V = V;
+  a.t1 = 1.f;
+  a.t2 = 1.f;
+  a.c_lo = 0;
+  a.all_rows = 1;
+  a.nsplit = rh_hstu_head_nsplit(B, V);
+  RH_REQUIRE(V >= 1 && V <= (1 << 30), RH_E_UNSUPPORTED, "rh_catalogue_ce_fwd: V=%d unsupported (1 <= V <= 2^30)", V);
+  if (int rc = head_check("rh_catalogue_ce_fwd", a)) return rc;
+  RH_REQUIRE(part && zlab && lse && wrow && loss, RH_E_BADARG, "rh_catalogue_ce_fwd: null output");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(head_fwd_kernel, dim3((B + kT - 1) / kT, a.nsplit), dim3(RH_BLOCK), 0, st, a);
+  hipLaunchKernelGGL(head_combine_kernel, dim3(1), dim3(RH_BLOCK), 0, st, a);
+  RH_LAUNCH_CHECK("rh_catalogue_ce_fwd");
+  return 0;
+}
+
+extern "C" int rh_catalogue_ce_bwd(const float* u, const float* E, const int64_t* labels, const float* lse, const float* wrow,
+                                   const float* g_loss, int B, int D, int V, float* part, float* part_h, float* g_u, float* g_E,
+                                   void* stream) {
+  HeadArgs a{};
+  a.h = u;
+  a.W = E;
+  a.labels = labels;
+  a.lse = const_cast<float*>(lse);
+  a.wrow = const_cast<float*>(wrow);
+  a.g_loss = g_loss;
+  a.part = part;
+  a.part_h = part_h;
+  a.g_h = g_u;
+  a.g_W = g_E;
+  a.M = B;
+  a.D = D;
+  a.V = V;
+  a.t1 = 1.f;
+  a.t2 = 1.f;
+  a.c_lo = 0;
+  a.all_rows = 1;
+  a.R = rh_hstu_head_rsplit(B, D, V);
+  a.Sv = rh_catalogue_ce_vsplit(B, D, V);
+  RH_REQUIRE(V >= 1 && V <= (1 << 30), RH_E_UNSUPPORTED, "rh_catalogue_ce_bwd: V=%d unsupported (1 <= V <= 2^30)", V);
+  if (int rc = head_check("rh_catalogue_ce_bwd", a)) return rc;
+  RH_REQUIRE(lse && wrow && g_loss && part && g_u && g_E && (a.Sv == 1 || part_h), RH_E_BADARG,
+             "rh_catalogue_ce_bwd: null pointer");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int nrt = (B + kT - 1) / kT, nvt = (V + kT - 1) / kT, ndc = (D + kHeadDc - 1) / kHeadDc;
+  hipLaunchKernelGGL(head_dh_kernel, dim3(nrt, ndc, a.Sv), dim3(RH_BLOCK), 0, st, a);
+  if (a.Sv > 1) {
+    const int64_t n = (int64_t)B * D;
+    int grid = (int)((n + RH_BLOCK - 1) / RH_BLOCK);
+    if (grid > 4096) grid = 4096;
+    hipLaunchKernelGGL(head_dh_reduce_kernel, dim3(grid), dim3(RH_BLOCK), 0, st, a);
+  }
+  hipLaunchKernelGGL(head_dw_kernel, dim3(nvt, ndc, a.R), dim3(RH_BLOCK), 0, st, a);
+  if (a.R > 1) {
+    const int64_t n = (int64_t)V * (D + 1);
+    int grid = (int)((n + RH_BLOCK - 1) / RH_BLOCK);
+    if (grid > 4096) grid = 4096;
+    hipLaunchKernelGGL(head_dw_reduce_kernel, dim3(grid), dim3(RH_BLOCK), 0, st, a);
+  }
+  RH_LAUNCH_CHECK("rh_catalogue_ce_bwd");
   return 0;
 }

@@ -141,6 +141,11 @@ def check_errors(device=None):
                 raise IndexError("torch_rechub_amd: an embedding index was out of range (index < 0 or >= vocab_size)")
             if v & 2:  # RH_FLAG_TARGET_OOB
                 raise IndexError("torch_rechub_amd: a target label was out of range (label < 0 or >= the number of classes)")
+            if v & 128:  # RH_FLAG_SESSION_EMPTY
+                raise RuntimeError("torch_rechub_amd: Length of all samples has to be greater than 0 (a session holds no item)")
+            if v & 256:  # RH_FLAG_SESSION_SHORT
+                raise RuntimeError("torch_rechub_amd: the longest session of the batch is shorter than its padded length L "
+                                   "(the reference NARM fails to broadcast its states against the mask)")
             if v & 64:  # RH_ERR_GATE_TIMEOUT
                 raise RuntimeError("torch_rechub_amd: a deferred table sweep waited 2 s for a training step that never started "
                                    "(rh_adam_sweep_gate); the tables may be inconsistent")
@@ -3011,3 +3016,227 @@ def next_token_loss(h, weight, bias, labels, temperature=1.0, nce_temperature=No
     nce = nce_temperature is not None
     return _NextTokenLossFn.apply(h, weight, bias, labels.to(torch.int64).contiguous(), float(temperature),
                                   float(nce_temperature) if nce else 1.0, nce)
+
+
+# --------------------------------------------------------------------------------------------
+# Session-based retrieval: general GRU, additive attention pooling, full-catalogue cross entropy
+# (csrc/session.hip, csrc/hstu.hip)
+# --------------------------------------------------------------------------------------------
+class _GruLayerFn(torch.autograd.Function):
+    """h_all (B, T, H) of one nn.GRU layer from the zero state; xw (B, T, 3H) = x W_ih^T (+ b_ih), rows r | z | n."""
+
+    @staticmethod
+    def forward(ctx, xw, w_hh, b_hh):
+        B, T, H3 = (int(v) for v in xw.shape)
+        H = H3 // 3
+        xw, w_hh = xw.contiguous(), w_hh.contiguous()
+        b_hh = None if b_hh is None else b_hh.contiguous()
+        h_all = torch.empty((B, T, H), dtype=torch.float32, device=xw.device)
+        hu = torch.empty((B, T, H3), dtype=torch.float32, device=xw.device)
+        _lib.call("rh_gru_fwd", _p(xw), _p(w_hh), _p(b_hh), B, T, H, _p(h_all), _p(hu), _stream())
+        ctx.has_bias = b_hh is not None
+        ctx.save_for_backward(xw, w_hh, h_all, hu)
+        return h_all
+
+    @staticmethod
+    def backward(ctx, g):
+        xw, w_hh, h_all, hu = ctx.saved_tensors
+        B, T, H3 = (int(v) for v in xw.shape)
+        H = H3 // 3
+        g = g.contiguous()
+        d_xw = torch.empty_like(xw)
+        d_s = torch.empty_like(xw)
+        _lib.call("rh_gru_bwd", _p(xw), _p(w_hh), _p(h_all), _p(hu), _p(g), B, T, H, _p(d_xw), _p(d_s), _stream())
+        d_w = d_b = None
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            # dW_hh = d_s^T h_prev over the B T rows (split-batch MFMA kernel), d b_hh its column sums
+            h_prev = torch.cat([h_all.new_zeros(B, 1, H), h_all[:, :-1]], dim=1).reshape(B * T, H)
+            d_w, d_b = linear_wgrad(d_s.view(B * T, H3), h_prev, want_bias=ctx.has_bias)
+        return d_xw, d_w, d_b
+
+
+def gru_layers_ok(gru_mod, x, batch_first=None):
+    bf = gru_mod.batch_first if batch_first is None else batch_first
+    return (isinstance(gru_mod, torch.nn.GRU) and not gru_mod.bidirectional and x.dim() == 3 and x.is_cuda and
+            x.dtype == torch.float32 and gru_mod.input_size == x.shape[-1] and gru_mod.proj_size == 0 and
+            1 <= gru_mod.hidden_size <= _lib.call("rh_gru_max_hidden") and x.shape[1 if bf else 0] >= 1)
+
+
+def gru_layers(gru_mod, x, batch_first=None):
+    """(output, h_n) of a multi-layer ``nn.GRU`` from the zero state, as the module returns them (``batch_first`` either way,
+    with or without bias; ``batch_first`` given: the layout of ``x`` and of the output instead of the module's): per layer the input halves of all steps are one ops.linear product and the recurrence one launch
+    each way (csrc/session.hip).  1 <= hidden_size <= 128; inter-layer dropout is not supported in training."""
+    require_hip(x)
+    bf = gru_mod.batch_first if batch_first is None else batch_first
+    if not gru_layers_ok(gru_mod, x, bf):
+        raise RuntimeError(f"torch_rechub_amd: nn.GRU(input {gru_mod.input_size}, hidden {gru_mod.hidden_size}, "
+                           f"bidirectional={gru_mod.bidirectional}) on {tuple(x.shape)} has no HIP kernel "
+                           f"(float32, unidirectional, 1 <= hidden_size <= {_lib.call('rh_gru_max_hidden')})")
+    if gru_mod.dropout > 0 and gru_mod.training and gru_mod.num_layers > 1:
+        raise RuntimeError("torch_rechub_amd: nn.GRU inter-layer dropout has no HIP kernel")
+    h = x if bf else x.transpose(0, 1)
+    B, T, _ = (int(v) for v in h.shape)
+    H = gru_mod.hidden_size
+    last = []
+    for k in range(gru_mod.num_layers):
+        w_ih, w_hh = getattr(gru_mod, f"weight_ih_l{k}"), getattr(gru_mod, f"weight_hh_l{k}")
+        b_ih = getattr(gru_mod, f"bias_ih_l{k}") if gru_mod.bias else None
+        b_hh = getattr(gru_mod, f"bias_hh_l{k}") if gru_mod.bias else None
+        xw = linear(h.reshape(B * T, -1), w_ih, b_ih).view(B, T, 3 * H)
+        h = _GruLayerFn.apply(xw, w_hh, b_hh)
+        last.append(h[:, -1])
+    h_n = torch.stack(last, 0)
+    return (h if bf else h.transpose(0, 1)), h_n
+
+
+class _AttnPoolFn(torch.autograd.Function):
+    """out (B, Dx) = sum_l a_l X_l (+ add), a = exp(w0 . sigmoid(P + r)) mask / den (csrc/session.hip)."""
+
+    @staticmethod
+    def forward(ctx, P, r, w0, mask, X, add, floor_):
+        B, L, H = (int(v) for v in P.shape)
+        Dx = int(X.shape[2])
+        dev = P.device
+        out = torch.empty((B, Dx), dtype=torch.float32, device=dev)
+        e = torch.empty((B, L), dtype=torch.float32, device=dev)
+        sums = torch.empty((B, 2), dtype=torch.float32, device=dev)
+        _lib.call("rh_attn_pool_fwd", _p(P), _p(r), _p(w0), _p(mask), _p(X), _p(add), B, L, H, Dx, int(floor_), _p(out), _p(e),
+                  _p(sums), _stream())
+        ctx.floor_ = int(floor_)
+        ctx.has_add = add is not None
+        ctx.save_for_backward(P, r, w0, X, e, sums)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        P, r, w0, X, e, sums = ctx.saved_tensors
+        B, L, H = (int(v) for v in P.shape)
+        Dx = int(X.shape[2])
+        dev = P.device
+        g = g.contiguous()
+        dP = torch.empty_like(P)
+        dr = torch.empty((B, H), dtype=torch.float32, device=dev)
+        dw0_part = torch.empty((B, H), dtype=torch.float32, device=dev)
+        dw0 = torch.empty((H,), dtype=torch.float32, device=dev)
+        dX = torch.empty_like(X)
+        _lib.call("rh_attn_pool_bwd", _p(P), _p(r), _p(w0), _p(X), _p(e), _p(sums), _p(g), B, L, H, Dx, ctx.floor_, _p(dP),
+                  _p(dr), _p(dw0_part), _p(dw0), _p(dX), _stream())
+        return dP, dr, dw0.view(w0.shape), None, dX, (g if ctx.has_add else None), None
+
+
+def additive_attention_pool(P, r, w0, mask, X, add=None, floor=False):
+    """Additive attention pooling of NARM / STAMP: s_l = sum_h w0_h sigmoid(P_lh + r_h), a_l = exp(s_l) mask_l / den,
+    out (B, Dx) = sum_l a_l X_l (+ add).  den = sum_l exp(s_l) mask_l, or max(that, 1e-12) with ``floor`` (F.normalize(p=1)).
+    P (B, L, H), r (B, H), w0 (H,) or (H, 1), mask (B, L) (bool / 0-1), X (B, L, Dx), add (B, Dx) or None."""
+    require_hip(P, r, w0, mask, X, add)
+    if P.dim() != 3 or X.dim() != 3 or P.shape[:2] != X.shape[:2] or r.shape != (P.shape[0], P.shape[2]) or \
+            w0.numel() != P.shape[2] or mask.shape != P.shape[:2] or (add is not None and add.shape != (X.shape[0], X.shape[2])):
+        raise RuntimeError(f"torch_rechub_amd: attention pooling shapes P {tuple(P.shape)}, r {tuple(r.shape)}, "
+                           f"w0 {tuple(w0.shape)}, mask {tuple(mask.shape)}, X {tuple(X.shape)} do not agree")
+    if not (1 <= P.shape[1] <= 1024 and 1 <= P.shape[2] <= 4096 and 1 <= X.shape[2] <= 4096):
+        raise RuntimeError(f"torch_rechub_amd: attention pooling with L={P.shape[1]}, H={P.shape[2]}, Dx={X.shape[2]} has "
+                           "no HIP kernel (1 <= L <= 1024, 1 <= H, Dx <= 4096)")
+    if any(t.dtype != torch.float32 for t in (P, r, w0, X) + (() if add is None else (add,))):
+        raise RuntimeError("torch_rechub_amd: attention pooling runs in float32 only")
+    m = mask.to(torch.float32).contiguous()
+    return _AttnPoolFn.apply(P.contiguous(), r.contiguous(), w0.contiguous(), m, X.contiguous(),
+                             None if add is None else add.contiguous(), bool(floor))
+
+
+class _CatalogueCEFn(torch.autograd.Function):
+    """Mean nn.CrossEntropyLoss of u E^T against labels without the (B, V) logits."""
+
+    @staticmethod
+    def forward(ctx, u, E, labels):
+        u, E = u.contiguous(), E.contiguous()
+        B, D = (int(v) for v in u.shape)
+        V = int(E.shape[0])
+        dev = u.device
+        nsplit = _lib.call("rh_hstu_head_nsplit", B, V)
+        part = torch.empty((B, nsplit, 2), dtype=torch.float32, device=dev)
+        zlab = torch.empty((B,), dtype=torch.float32, device=dev)
+        lse = torch.empty((B,), dtype=torch.float32, device=dev)
+        wrow = torch.empty((B,), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        _lib.call("rh_catalogue_ce_fwd", _p(u), _p(E), _p(labels), B, D, V, _p(part), _p(zlab), _p(lse), _p(wrow), _p(loss),
+                  _p(err_flag(dev)), _stream())
+        ctx.save_for_backward(u, E, labels, lse, wrow)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        u, E, labels, lse, wrow = ctx.saved_tensors
+        B, D = (int(v) for v in u.shape)
+        V = int(E.shape[0])
+        dev = u.device
+        R = _lib.call("rh_hstu_head_rsplit", B, D, V)
+        Sv = _lib.call("rh_catalogue_ce_vsplit", B, D, V)
+        part = torch.empty((R, V, D + 1) if R > 1 else (1,), dtype=torch.float32, device=dev)
+        part_h = torch.empty((Sv, B, D) if Sv > 1 else (1,), dtype=torch.float32, device=dev)
+        g_u = torch.empty_like(u)
+        g_E = torch.empty_like(E)
+        _lib.call("rh_catalogue_ce_bwd", _p(u), _p(E), _p(labels), _p(lse), _p(wrow), _p(g.reshape(1).contiguous()), B, D, V,
+                  _p(part), _p(part_h), _p(g_u), _p(g_E), _stream())
+        return g_u, g_E, None
+
+
+def catalogue_cross_entropy(u, weight, labels):
+    """torch.nn.CrossEntropyLoss()(u @ weight.T, labels) (mean over every row, every column a class) without forming the
+    (B, V) logits.  u (B, D), weight (V, D), labels (B,) integer in [0, V) (out of range: the device error word is set,
+    ops.check_errors raises).  The backward returns du and the dense d weight."""
+    require_hip(u, weight, labels)
+    if u.dim() != 2 or weight.dim() != 2 or u.shape[1] != weight.shape[1] or u.shape[0] < 1 or \
+            not (2 <= weight.shape[0] <= 1 << 30) or labels.shape != (u.shape[0],):
+        raise RuntimeError(f"torch_rechub_amd: catalogue cross entropy of u {tuple(u.shape)}, weight {tuple(weight.shape)}, "
+                           f"labels {tuple(labels.shape)} unsupported (u (B, D), weight (V, D), labels (B,), B >= 1, "
+                           "2 <= V <= 2^30)")
+    if u.dtype != torch.float32 or weight.dtype != torch.float32:
+        raise RuntimeError("torch_rechub_amd: the catalogue cross entropy runs in float32 only")
+    return _CatalogueCEFn.apply(u, weight, labels.to(torch.int64).contiguous())
+
+
+class _DropoutFn(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, x, p):
+        x = x.contiguous()
+        y = torch.empty_like(x)
+        rng = _dropout_rng(x.device)
+        ctr = torch.empty(1, dtype=torch.int64, device=x.device)
+        _lib.call("rh_session_dropout_fwd", _p(x), x.numel(), float(p), _p(rng), _p(ctr), _p(y), _stream())
+        ctx.p = float(p)
+        ctx.save_for_backward(rng, ctr)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        rng, ctr = ctx.saved_tensors
+        g = g.contiguous()
+        dx = torch.empty_like(g)
+        _lib.call("rh_session_dropout_bwd", _p(g), g.numel(), ctx.p, _p(rng), _p(ctr), _p(dx), _stream())
+        return dx, None
+
+
+def dropout(x, p, training=True):
+    """nn.Dropout(p) with the project's counter-hash mask (the fused MLP dropout's stream): identity at p = 0 or in eval;
+    the mask is recomputed in the backward, never stored."""
+    if not training or p == 0:
+        return x
+    require_hip(x)
+    if not (0 < p < 1) or x.dtype != torch.float32:
+        raise RuntimeError(f"torch_rechub_amd: dropout p={p} on {x.dtype} has no HIP kernel (0 <= p < 1, float32)")
+    return _DropoutFn.apply(x, p)
+
+
+def session_lengths(seq, check_full=False):
+    """(B,) int64 number of non-zero ids per row of a (B, L) id matrix, one launch.  A row without items (and, with
+    ``check_full``, a batch whose longest row is shorter than L) sets the device error word: outside a hipGraph capture this
+    checks it at once and raises RuntimeError, inside one the replayed step leaves it for the trainer's error check."""
+    require_hip(seq)
+    seq = seq.to(torch.int64).contiguous()
+    B, L = (int(v) for v in seq.shape)
+    counts = torch.empty((B,), dtype=torch.int64, device=seq.device)
+    _lib.call("rh_session_lengths", _p(seq), B, L, int(bool(check_full)), _p(counts), _p(err_flag(seq.device)), _stream())
+    if not torch.cuda.is_current_stream_capturing():
+        check_errors(seq.device)
+    return counts

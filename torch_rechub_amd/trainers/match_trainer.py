@@ -122,6 +122,11 @@ class MatchTrainer(CTRTrainer):
         elif self.mode == 1:
             pos_score, neg_score = self.model(x_dict)
             loss = self.criterion(pos_score, neg_score)
+        elif self.mode == 2 and self._catalogue_loss_ok() and (head := self.model.catalogue_head(x_dict)) is not None:
+            # full-catalogue softmax of NARM / STAMP (run_sbr.py: CrossEntropyLoss over the (B, V) scores): the fused
+            # streaming loss over the item table, which never forms the scores
+            u, table = head
+            loss = ops.catalogue_cross_entropy(u, table, y if y.dtype == torch.long else y.long())
         else:
             pred = self.model(x_dict)
             if self.mode == 2 and y.dtype != torch.long:  # (a DeviceDataLoader's label column is float32)
@@ -132,6 +137,11 @@ class MatchTrainer(CTRTrainer):
             else:
                 loss = self.criterion(pred, y)
         return self._add_reg(loss)
+
+    def _catalogue_loss_ok(self):
+        c = self.criterion
+        return (hasattr(self.model, "catalogue_head") and type(c) is torch.nn.CrossEntropyLoss and c.reduction == "mean" and
+                c.weight is None and c.label_smoothing == 0.0 and c.ignore_index == -100)
 
     def evaluate(self, model, data_loader):
         self.flush()
