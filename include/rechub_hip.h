@@ -854,7 +854,8 @@ int rh_hstu_attn_bwd(const float* proj, int64_t ld, int B, int L, int H, int dqk
  *   outside [0, V) ORs RH_FLAG_TARGET_OOB into *err (when not null) and its row's loss is undefined.
  * rh_hstu_head_bwd: g_loss (1,) device scalar -> g_h (M, D), g_W (V, D), g_bias (V,) (null: not wanted); part
  *   (rh_hstu_head_rsplit(M, D, V), V, D + 1) workspace, unused when that count is 1.  Logits recomputed tile by tile;
- *   no atomics.  M >= 1, V >= 2, any D.
+ *   no atomics.  M >= 1, V >= 2, any D.  g_W null (a frozen table: then g_bias must be null too): only g_h is
+ *   computed, no dW kernel runs and part is not read (may be null).
  * replaces: HSTUModel.forward's F.linear / temperature (models/generative/hstu.py:266-271), SeqTrainer's logits.clone()
  *           and CrossEntropyLoss / NCELoss (trainers/seq_trainer.py:177-194, basic/loss_func.py:141-175), and autograd. */
 int rh_hstu_head_nsplit(int M, int V);
@@ -865,6 +866,31 @@ int rh_hstu_head_fwd(const float* h, const float* W, const float* bias, const in
 int rh_hstu_head_bwd(const float* h, const float* W, const float* bias, const int64_t* labels, const float* lse,
                      const float* wrow, const float* g_loss, int M, int D, int V, float t1, float t2, float* part, float* g_h,
                      float* g_W, float* g_bias, void* stream);
+
+/* ---- HLLM: causal softmax multi-head attention with a bucketed relative-position bias and dropout -------------------
+ * q, k, v: (B, L, H, dh) views sharing the row stride ld >= H dh (three separate (B L, H dh) projections with ld = H dh,
+ * or three column blocks of one (B L, 3 H dh) product with ld = 3 H dh).  bias (nb, H) contiguous or null;
+ * bucket(i, j) = min(|i - j|, N) * (nb - 1) / N in integers (N = max_seq_len), formed in the kernel.  Causal (j <= i),
+ * no padding mask.  p_drop in [0, 1): dropout on the weights with the counter hash over element ((b H + h) L + i) L + j;
+ * rng = the device (seed, counter) pair, saved_ctr (1,) receives the counter this call used; p_drop = 0: both may be
+ * null and no hash is computed.
+ * rh_softmax_attn_fwd: out (B, L, H dh) = dropout(softmax_j(scale q_i . k_j + bias)) v; lse (B, H, L) the rows'
+ *   log-sum-exp for the backward.  The forward advances the counter on the device.
+ * rh_softmax_attn_bwd: g_out (B, L, H dh) -> g_q, g_k, g_v ((B, L, H, dh) views, row stride ldg), g_bias (nb, H) when
+ *   bias is given, through part (rh_softmax_attn_nparts(B, L, H), L) per-workgroup partials summed in a fixed order;
+ *   delta (B, H, L) workspace.  Weights recomputed tile by tile; nothing of size L x L is written.  No atomics.
+ * 1 <= L <= min(N, 1024), 1 <= dh <= 128, H >= 1, nb >= 1 or no bias, else RH_E_UNSUPPORTED; B = 0 returns at once.
+ * replaces: HLLMTransformerBlock.forward torch_rechub/models/generative/hllm.py:69-88 (view / transpose, matmul, tril,
+ *           masked_fill, bias add, softmax, dropout, matmul, transpose / contiguous) with RelPosBias.forward
+ *           utils/hstu_utils.py:54-68, and their autograd. */
+int rh_softmax_attn_nparts(int B, int L, int H);
+int rh_softmax_attn_fwd(const float* q, const float* k, const float* v, int64_t ld, int B, int L, int H, int dh,
+                        const float* bias, int N, int nb, float scale, float p_drop, int64_t* rng, int64_t* saved_ctr,
+                        float* out, float* lse, void* stream);
+int rh_softmax_attn_bwd(const float* q, const float* k, const float* v, int64_t ld, int B, int L, int H, int dh,
+                        const float* bias, int N, int nb, float scale, float p_drop, const int64_t* rng,
+                        const int64_t* saved_ctr, const float* out, const float* lse, const float* g_out, float* delta,
+                        float* g_q, float* g_k, float* g_v, int64_t ldg, float* part, float* g_bias, void* stream);
 
 /* Full-catalogue cross entropy (the same streaming head, every column and every row counted, no bias / temperature):
  * u (B, D), E (V, D), labels (B,) int64 in [0, V).  loss (1,) = mean over rows of lse(u E^T) - (u E^T)[label].

@@ -17,6 +17,11 @@
                 reference defaults (d 512, H 8, dqk = dv = 64, 4 layers, L 256) at B 64, V 100 k.  Times the HIP step
                 (fused attention and next-token loss), a plain-PyTorch eager restatement of the reference's op chain
                 (dense (B, H, L, L) attention, (B, L, V) logits, clone, CrossEntropyLoss) and the kernels' device times.
+  hllm / hllm_large : HLLMModel + SeqTrainer(loss_type='nce', temperature 1.0) on synthetic sequences: the MovieLens
+                example's shape with a small embedding (B 64, L 200, d 512, H 8, 2 layers, V 3707, dropout 0.1) and
+                d 2048, H 16, V 100 k.  Times the HIP step (fused causal softmax attention, frozen-table next-token
+                loss), a plain-PyTorch eager restatement of the reference's op chain (dense (B, H, L, L) softmax
+                attention with nn.Dropout, (B, L, V) logits, clone, NCELoss) and the kernels' device times.
   narm / stamp : the session-based example's shape (examples/matching/run_sbr.py: B 512, L <= 19, D 100, NARM hidden 50,
                 NARM's dropouts 0.25 / 0.5) with
                 a synthetic 50 000-item catalogue; narm_large / stamp_large: B 4096 against 10^6 items.  MatchTrainer(mode=2)
@@ -538,6 +543,107 @@ def session_bench(name, dev, steps):
     ops.check_errors()
 
 
+HLLM = {"hllm": dict(B=64, L=200, V=3707, d_model=512, n_heads=8, n_layers=2),
+        "hllm_large": dict(B=64, L=200, V=100000, d_model=2048, n_heads=16, n_layers=2)}
+
+
+def hllm_bench(name, dev, steps):
+    """ms/step of the HIP SeqTrainer step of HLLMModel and of a plain-PyTorch eager restatement of the reference's step."""
+    import re
+
+    import torch.nn.functional as F
+    from torch.profiler import ProfilerActivity, profile
+
+    from torch_rechub_amd.models.generative import HLLMModel
+    from torch_rechub_amd.trainers import SeqTrainer
+    cfg = dict(HLLM[name])
+    B, L, V = cfg.pop("B"), cfg.pop("L"), cfg.pop("V")
+    torch.manual_seed(0)
+    g = torch.Generator().manual_seed(0)
+    model = HLLMModel(torch.randn(V, cfg["d_model"], generator=g), V, max_seq_len=L, dropout=0.1, **cfg)
+    trainer = SeqTrainer(model, device=str(dev), loss_type="nce", loss_params={"temperature": 1.0, "ignore_index": 0})
+    model.train()
+    lens = torch.randint(L // 4, L + 1, (B,), generator=g)
+    tok = torch.randint(1, V, (B, L), generator=g) * (torch.arange(L)[None, :] >= L - lens[:, None])  # left padded
+    td = torch.sort(torch.randint(0, 10**8, (B, L), generator=g), 1, descending=True).values
+    tok, td, tg = tok.to(dev), td.to(dev), torch.randint(1, V, (B,), generator=g).to(dev)
+
+    def timed(fn):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / steps * 1e3
+
+    torch.cuda.reset_peak_memory_stats()
+    hip = timed(lambda: trainer.train_step(tok, td, tg))
+    mem_hip = torch.cuda.max_memory_allocated() / 2**30
+    kernels = {}
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        trainer.train_step(tok, td, tg)
+        torch.cuda.synchronize()
+    evs = [ev for ev in prof.key_averages() if ev.device_time_total > 0]
+    hip_total = sum(ev.device_time_total for ev in evs)
+    for ev in evs:
+        m = re.search(r"\b(softmax_attn_\w+_kernel|head_\w+_kernel|dropout\w*_kernel|drop_advance_kernel)", ev.key)
+        if m:
+            us, n = kernels.get(m.group(1), (0.0, 0))
+            kernels[m.group(1)] = (us + ev.device_time_total, n + ev.count)
+    torch.cuda.reset_peak_memory_stats()
+
+    def eager_loss():
+        x = model.item_embeddings[tok] + model.position_embedding(torch.arange(L, device=dev))[None]
+        x = x + model.time_embedding(model._time_diff_to_bucket(td))
+        x = F.dropout(x, 0.1)
+        bias = model.rel_pos_bias(L)
+        causal = torch.tril(torch.ones(L, L, device=dev, dtype=torch.bool))[None, None]
+        for blk in model.transformer_blocks:
+            H, dh = blk.n_heads, blk.head_dim
+            h = blk.norm1(x)
+            q, k, v = (w(h).view(B, L, H, dh).transpose(1, 2) for w in (blk.W_Q, blk.W_K, blk.W_V))
+            s = (torch.matmul(q, k.transpose(-2, -1)) * blk.scale).masked_fill(~causal, float("-inf")) + bias
+            a = F.dropout(F.softmax(s, dim=-1), 0.1)
+            o = torch.matmul(a, v).transpose(1, 2).contiguous().view(B, L, H * dh)
+            x = x + F.dropout(blk.W_O(o), 0.1)
+            h = F.dropout(F.relu(blk.ffn[0](blk.norm2(x))), 0.1)
+            x = x + F.dropout(blk.ffn[3](h), 0.1)
+        logits = torch.matmul(F.normalize(x, dim=-1, eps=1e-8), model.item_embeddings.t()) / model.temperature
+        return trainer._compute_next_token_loss(logits, tok, tg)
+
+    def eager_step():
+        loss = eager_loss()
+        model.zero_grad()
+        loss.backward()
+        trainer.optimizer.step()
+
+    eager_top = []
+    try:
+        eager = timed(eager_step)
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            eager_step()
+            torch.cuda.synchronize()
+        evs = [ev for ev in prof.key_averages() if ev.device_time_total > 0]
+        total = sum(ev.device_time_total for ev in evs)
+        eager_top = [(ev.key[:70], ev.device_time_total, ev.count) for ev in
+                     sorted(evs, key=lambda ev: -ev.device_time_total)[:8]] + [("(all device work)", total, 0)]
+    except torch.cuda.OutOfMemoryError:
+        eager = float("nan")
+        print(f"  [{name}] eager restatement does not fit")
+    mem_eager = torch.cuda.max_memory_allocated() / 2**30
+    print(f"{name:10s} B={B} L={L} V={V}  HIP {hip:8.3f} ms/step (peak {mem_hip:.2f} GiB)   plain PyTorch eager "
+          f"{eager:8.3f} ms/step (peak {mem_eager:.2f} GiB)   speedup {eager / hip:.2f}x", flush=True)
+    for k, (us, n) in sorted(kernels.items(), key=lambda kv: -kv[1][0]):
+        print(f"    {k:32s} {us:10.1f} us per step ({n} launches)", flush=True)
+    print(f"    {'(all device work of the HIP step)':32s} {hip_total:10.1f} us per step", flush=True)
+    for k, us, n in eager_top:
+        print(f"    eager: {k:70s} {us:12.1f} us per step ({n} launches)", flush=True)
+    from torch_rechub_amd import ops
+    ops.check_errors()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", default="dcn,dcnv2,din,dssm")
@@ -554,6 +660,10 @@ def main():
             continue
         if name in HSTU:
             hstu_bench(name, dev, a.steps)
+            torch.cuda.reset_peak_memory_stats()
+            continue
+        if name in HLLM:
+            hllm_bench(name, dev, a.steps)
             torch.cuda.reset_peak_memory_stats()
             continue
         trainer, x, y = build(name, dev, a.batch, a.scale)

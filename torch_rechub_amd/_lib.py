@@ -201,6 +201,11 @@ SIGNATURES = {
                          c_int, c_f32, c_f32, c_ptr, c_ptr],
     "rh_hstu_attn_bwd": [c_ptr, c_i64, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int,
                          c_int, c_f32, c_f32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr],
+    "rh_softmax_attn_nparts": [c_int, c_int, c_int],
+    "rh_softmax_attn_fwd": [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_ptr, c_int, c_int, c_f32, c_f32, c_ptr,
+                            c_ptr, c_ptr, c_ptr, c_ptr],
+    "rh_softmax_attn_bwd": [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_ptr, c_int, c_int, c_f32, c_f32, c_ptr,
+                            c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr],
     "rh_hstu_head_nsplit": [c_int, c_int],
     "rh_hstu_head_rsplit": [c_int, c_int, c_int],
     "rh_hstu_head_fwd": [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_f32, c_f32, c_int, c_ptr, c_ptr, c_ptr, c_ptr,
@@ -230,7 +235,7 @@ _VALUE_RETURNING = {"rh_abi_version", "rh_embed_bwd_nchunks", "rh_cross_bwd_nblo
                     "rh_bn_act_nchunks", "rh_dice_nblocks", "rh_linear_wgrad_workspace", "rh_linear_wgrad_tiles", "rh_linear_wgrad_splits",
                     "rh_head_nblocks", "rh_ce_nblocks", "rh_bn_prelu_nblocks", "rh_head_loss_nblocks", "rh_cross_mix_nblocks", "rh_cross_moe_kp", "rh_cross_moe_supported", "rh_cross_moe_mid_blocks", "rh_din_att_l1_supported", "rh_din_att_l1_chunk_rows", "rh_prelu_nblocks", "rh_gemm_stats_rows", "rh_gemm_chain_stats_rows", "rh_bn_dice_stats_blocks", "rh_augru_max_dim", "rh_cen_nchunks",
                     "rh_capsule_supported", "rh_capsule_wgrad_nchunks", "rh_sa_supported",
-                    "rh_hstu_attn_nparts", "rh_hstu_head_nsplit", "rh_hstu_head_rsplit",
+                    "rh_hstu_attn_nparts", "rh_softmax_attn_nparts", "rh_hstu_head_nsplit", "rh_hstu_head_rsplit",
                     "rh_catalogue_ce_vsplit", "rh_gru_max_hidden"}
 
 ABI_VERSION = 1

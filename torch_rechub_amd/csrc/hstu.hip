@@ -833,12 +833,14 @@ extern "C" int rh_hstu_head_bwd(const float* h, const float* W, const float* bia
   a.c_lo = 1;
   a.Sv = 1;
   if (int rc = head_check("rh_hstu_head_bwd", a)) return rc;
-  RH_REQUIRE(lse && wrow && g_loss && part && g_h && g_W, RH_E_BADARG, "rh_hstu_head_bwd: null pointer");
+  // g_W null: a frozen item table (HLLM) -- no dW kernel runs and no workspace is read
+  RH_REQUIRE(lse && wrow && g_loss && g_h && (g_W ? part != nullptr : g_bias == nullptr), RH_E_BADARG,
+             "rh_hstu_head_bwd: null pointer");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int nrt = (M + kT - 1) / kT, nvt = (V + kT - 1) / kT, ndc = (D + kHeadDc - 1) / kHeadDc;
   hipLaunchKernelGGL(head_dh_kernel, dim3(nrt, ndc), dim3(RH_BLOCK), 0, st, a);
-  hipLaunchKernelGGL(head_dw_kernel, dim3(nvt, ndc, a.R), dim3(RH_BLOCK), 0, st, a);
-  if (a.R > 1) {
+  if (g_W) hipLaunchKernelGGL(head_dw_kernel, dim3(nvt, ndc, a.R), dim3(RH_BLOCK), 0, st, a);
+  if (g_W && a.R > 1) {
     const int64_t n = (int64_t)V * (D + 1);
     int grid = (int)((n + RH_BLOCK - 1) / RH_BLOCK);
     if (grid > 4096) grid = 4096;

@@ -27,7 +27,9 @@ _MODELS = {"ranking": ("DeepFM", "WideDeep", "DCN", "DCNv2", "DIN", "DIEN", "BST
                        "DeepFFM", "FatDeepFFM"),
            "matching": ("DSSM", "YoutubeDNN", "MIND", "ComirecSA", "ComirecDR", "GRU4Rec", "NARM", "STAMP"),
            "multi_task": ("SharedBottom", "ESMM", "MMOE", "PLE", "AITM"),
-           "generative": ("HSTUModel",)}
+           "generative": ("HSTUModel", "HLLMModel")}
+# classes a reference module defines beside its model and does not re-export from the sub-package
+_MODEL_PARTS = {"generative.hllm": ("HLLMTransformerBlock",)}
 _TRAINERS = ("CTRTrainer", "MatchTrainer", "MTLTrainer", "SeqTrainer")
 
 _undo = []  # (module, attribute, original object)
@@ -79,6 +81,9 @@ def enable(layers=True, models=True, trainers=True, package="torch_rechub"):
         done += _swap(package, f"{package}.basic.layers", amd_layers, _LAYERS)
     if models:
         for sub, names in _MODELS.items():
+            amd_sub = importlib.import_module(f"{__package__}.models.{sub}")
+            done += _swap(package, f"{package}.models.{sub}", amd_sub, names)
+        for sub, names in _MODEL_PARTS.items():
             amd_sub = importlib.import_module(f"{__package__}.models.{sub}")
             done += _swap(package, f"{package}.models.{sub}", amd_sub, names)
     if trainers:

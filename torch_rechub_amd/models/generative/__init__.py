@@ -1,1 +1,2 @@
 from .hstu import HSTUModel  # noqa: F401
+from .hllm import HLLMModel, HLLMTransformerBlock  # noqa: F401

@@ -1,4 +1,4 @@
-"""SeqTrainer (reference torch_rechub/trainers/seq_trainer.py): next-item training of generative models (HSTUModel).
+"""SeqTrainer (reference torch_rechub/trainers/seq_trainer.py): next-item training of generative models (HSTUModel, HLLMModel).
 
 A model that exposes ``hidden_and_head`` trains through the fused next-token loss (ops.next_token_loss, csrc/hstu.hip):
 the (B, L, V) logits, their clone and the same-sized softmax gradient of the reference never exist.  ``evaluate`` scores
