@@ -826,7 +826,7 @@ int rh_listwise_bwd(const float* u, const float* pos, int64_t ldp, const float* 
                     const float* g, int B, int I, int D, int K, float temperature, float* g_u, float* g_pos, float* g_neg,
                     void* stream);
 
-/* ---- HSTU generative model: pointwise relative-bias attention and the next-token head --------------------------------
+/* ---- HSTU generative model: pointwise relative-bias attention (csrc/hstu.hip) and the next-token head ---------------
  * Attention of one HSTULayer on proj (B, L, ld) = silu(proj1(LN(x))) (row stride ld >= 2 H (dqk + dv)): per head h,
  * q at columns h dqk, k at H dqk + h dqk, v at 2 H dqk + H dv + h dv.  td (B, L) int64 seconds or null (position-only
  * bias), kmask (B, L) int32 nonzero = kept key or null.  pos_w (2 N - 1, H), ts_w (nb + 1, H) contiguous; N = max_seq_len,
@@ -847,9 +847,10 @@ int rh_hstu_attn_bwd(const float* proj, int64_t ld, int B, int L, int H, int dqk
                      const int32_t* kmask, const float* pos_w, const float* ts_w, int N, int nb, int fn_log, int minutes,
                      float divisor, float alpha, const float* g_out, float* g_proj, float* pos_part, float* ts_part,
                      float* g_pos_w, float* g_ts_w, void* stream);
-/* Next-token cross entropy over the item table: h (M, D), W (V, D), bias (V,) or null, labels (M,) int64 (0 = ignored,
- * else in [1, V)).  z = ((h W^T + bias) / t1) / t2, column 0 excluded from the normaliser; loss (1,) = mean over rows with
- * a label of lse - z[label] (NaN when there is none; nce = 1: then the mean over every row of lse + 1e9 / t2).
+/* Next-token cross entropy over the item table (csrc/stream_ce.hip): h (M, D), W (V, D), bias (V,) or null, labels
+ * (M,) int64 (0 = ignored, else in [1, V)).  z = ((h W^T + bias) / t1) / t2, column 0 excluded from the normaliser;
+ * loss (1,) = mean over rows with a label of lse - z[label] (NaN when there is none; nce = 1: then the mean over every
+ * row of lse + 1e9 / t2).
  * rh_hstu_head_fwd: part (M, rh_hstu_head_nsplit(M, V), 2) workspace; zlab, lse, wrow (M,) for the backward; a label
  *   outside [0, V) ORs RH_FLAG_TARGET_OOB into *err (when not null) and its row's loss is undefined.
  * rh_hstu_head_bwd: g_loss (1,) device scalar -> g_h (M, D), g_W (V, D), g_bias (V,) (null: not wanted); part
@@ -892,7 +893,7 @@ int rh_softmax_attn_bwd(const float* q, const float* k, const float* v, int64_t 
                         const int64_t* saved_ctr, const float* out, const float* lse, const float* g_out, float* delta,
                         float* g_q, float* g_k, float* g_v, int64_t ldg, float* part, float* g_bias, void* stream);
 
-/* Full-catalogue cross entropy (the same streaming head, every column and every row counted, no bias / temperature):
+/* Full-catalogue cross entropy (csrc/stream_ce.hip: the same head, every column and row counted, no bias / temperature):
  * u (B, D), E (V, D), labels (B,) int64 in [0, V).  loss (1,) = mean over rows of lse(u E^T) - (u E^T)[label].
  * rh_catalogue_ce_fwd: part (B, rh_hstu_head_nsplit(B, V), 2) workspace; zlab, lse, wrow (B,) for the backward; a label
  *   outside [0, V) ORs RH_FLAG_TARGET_OOB into *err (when not null) and its row's loss is undefined.

@@ -1,6 +1,6 @@
-"""HSTU on the MI355X: the attention and next-token head kernels of csrc/hstu.hip against float64 numpy at full size, the
-kernel's time buckets against torch CPU, bitwise repeatable backwards, the model step against a float64 restatement, and
-the memory bound of the fused step."""
+"""HSTU on the MI355X: the attention kernels of csrc/hstu.hip and the next-token head of csrc/stream_ce.hip against
+float64 numpy at full size, the kernel's time buckets against torch CPU, bitwise repeatable backwards, the model step
+against a float64 restatement, and the memory bound of the fused step."""
 import numpy as np
 import pytest
 import torch

@@ -1,4 +1,4 @@
-"""NARM / STAMP / GRU4Rec on the MI355X: the kernels of csrc/session.hip and the full-catalogue head against float64 at
+"""NARM / STAMP / GRU4Rec on the MI355X: the kernels of csrc/session.hip and the full-catalogue head (csrc/stream_ce.hip) against float64 at
 full size and at their edges, repeatable backwards, the models and three MatchTrainer steps against the reference's
 fixtures (tools/gen_golden_session.py), the errors for inputs the reference rejects, batches of different L, the memory
 bound of a large-catalogue NARM step and the captured step against eager."""

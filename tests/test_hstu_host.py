@@ -264,8 +264,8 @@ def test_seq_trainer_rejects_unsupported_loss_params_at_construction():
 
 
 def test_hstu_entry_points_reject_unsupported_shapes():
-    """Argument validation of csrc/hstu.hip at the first shape past each limit: nothing is launched (the pointers are
-    never dereferenced)."""
+    """Argument validation of csrc/hstu.hip and csrc/stream_ce.hip at the first shape past each limit: nothing is
+    launched (the pointers are never dereferenced)."""
     import ctypes
 
     from torch_rechub_amd import _lib

@@ -1,6 +1,6 @@
 """NARM / STAMP / GRU4Rec without a GPU: the public names, the reference's state_dict layout and seeded initial tensors,
 float64 numpy restatements of the GRU recurrence, the additive attention pooling and the full-catalogue cross entropy
-(forward and backward, the math csrc/session.hip and the catalogue head implement) checked against torch autograd, and
+(forward and backward, the math csrc/session.hip and csrc/stream_ce.hip implement) checked against torch autograd, and
 the shape limits of the C entry points."""
 import ctypes
 import json

@@ -6,7 +6,7 @@ Inputs are drawn on the CPU from a fixed seed and stored with the outputs: loss,
 rh_hstu_head_bwd (g_loss = 1) for three configurations that cover the forward's V split, the backward's row split,
 NCE and the bias.  tests/test_gpu_session.py replays them through ops.next_token_loss and requires the same bits, so a
 change to the shared streaming head cannot move HSTU's results.  The archive was recorded from the library of the
-commit before the full-catalogue mode was added to csrc/hstu.hip.
+commit before the full-catalogue mode was added to the head (now csrc/stream_ce.hip).
 """
 import argparse
 import ctypes

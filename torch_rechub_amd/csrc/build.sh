@@ -7,10 +7,15 @@ INC=../../include
 FLAGS="--offload-arch=gfx950 -mcode-object-version=5 -munsafe-fp-atomics -O3 -std=c++17 -fPIC -I$INC -I. -Wall -Wno-unused-function"
 mkdir -p _build
 pids=()
-for src in api.cpp embed.hip cross.hip optim.hip data.hip match.hip fm.hip seqpool.hip mlp.hip din.hip dinmlp.hip crossmix.hip moe.hip linear.hip gemm.hip shard.hip augru.hip ffm.hip interest.hip hstu.hip session.hip hllm.hip; do
+for src in api.cpp embed.hip cross.hip optim.hip data.hip match.hip fm.hip seqpool.hip mlp.hip din.hip dinmlp.hip crossmix.hip moe.hip linear.hip gemm.hip shard.hip augru.hip ffm.hip interest.hip hstu.hip stream_ce.hip session.hip hllm.hip; do
   [ -f "$src" ] || continue
   obj="_build/${src%.*}.o"
-  if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ common.h -nt "$obj" ] || [ wgrad_body.h -nt "$obj" ] || [ $INC/rechub_hip.h -nt "$obj" ]; then
+  stale=0
+  [ -f "$obj" ] || stale=1
+  for dep in "$src" *.h $INC/rechub_hip.h; do
+    if [ "$dep" -nt "$obj" ]; then stale=1; fi
+  done
+  if [ $stale = 1 ]; then
     ( $HIPCC $FLAGS -x hip -c "$src" -o "$obj" ) &
     pids+=($!)
   fi

@@ -22,40 +22,16 @@
 // counter the forward reads from the device-resident (seed, counter) and then advances; the backward re-derives the mask
 // from the saved counter.  p = 0 takes a path with no hash.
 //
-// Products on v_mfma_f32_32x32x2_f32 (exact f32, k-ordered accumulation); lane maps as in hstu.hip.
+// The products run on the 64 x 64 MFMA tile of mfma_tile.h.
 #include <math.h>
 
-#include "common.h"
+#include "mfma_tile.h"
 
 namespace {
 
-typedef float v16f __attribute__((ext_vector_type(16)));
-
-constexpr int kT = 64;        // tile edge (queries, keys) and LDS column chunk
-constexpr int kLd = kT + 1;   // padded LDS row stride
 constexpr int kMaxDh = 128;
 constexpr int kNC = kMaxDh / kT;  // column chunks of a head
 constexpr int kMaxL = 1024;
-
-__device__ __forceinline__ int acc_row(int r, int kk) { return 4 * kk + (r & 3) + 8 * (r >> 2); }
-
-__device__ __forceinline__ v16f zero16() {
-  v16f z;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) z[r] = 0.f;
-  return z;
-}
-
-// acc += A (32 x K) B (K x 32) with A[i][k] = a[i * ai + k * ak], B[k][j] = b[k * bk + j * bj] (LDS), K even
-__device__ __forceinline__ v16f mma_lds(v16f acc, const float* a, int ai, int ak, const float* b, int bk, int bj, int K,
-                                        int li, int kk) {
-  for (int k = 0; k < K; k += 2) {
-    const float av = a[li * ai + (k + kk) * ak];
-    const float bv = b[(k + kk) * bk + li * bj];
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
-  }
-  return acc;
-}
 
 struct SArgs {
   const float* q;        // (B, L, H, dh) views, row stride ld
@@ -84,18 +60,6 @@ __device__ __forceinline__ float bias_of(const SArgs& a, int i, int j, int h) {
   d = d < a.N ? d : a.N;
   const int bucket = (int)((int64_t)d * (a.nb - 1) / a.N);
   return a.bias[(int64_t)bucket * a.H + h];
-}
-
-// rows [r0, r0 + 64) x columns [c0, c0 + 64) of one head (column offset col) into s[64][kLd]; zero outside L / dh
-__device__ __forceinline__ void load_chunk(float* s, const float* base, int64_t ld, int col, int c0, int r0, int L, int d,
-                                           int b, int tid) {
-  for (int e = tid; e < kT * kT; e += RH_BLOCK) {
-    const int r = e / kT, c = e % kT;
-    const int row = r0 + r;
-    float val = 0.f;
-    if (row < L && c0 + c < d) val = base[((int64_t)b * L + row) * ld + col + c0 + c];
-    s[r * kLd + c] = val;
-  }
 }
 
 // the row's fragment for the A / B operand of a product over the head's columns: element s = column 2 s + kk
@@ -158,8 +122,8 @@ __global__ __launch_bounds__(RH_BLOCK) void softmax_attn_fwd_kernel(const SArgs 
     for (int c = 0; c < kNC; ++c) {
       if (c >= nc) continue;
       __syncthreads();
-      load_chunk(ks, a.k, a.ld, col, c * kT, j0, L, dh, b, tid);
-      if (c == 0) load_chunk(vs, a.v, a.ld, col, 0, j0, L, dh, b, tid);
+      load_tile(ks, a.k, a.ld, col, c * kT, j0, L, dh, b, tid);
+      if (c == 0) load_tile(vs, a.v, a.ld, col, 0, j0, L, dh, b, tid);
       __syncthreads();
 #pragma unroll
       for (int k = 0; k < kT; k += 2)
@@ -215,7 +179,7 @@ __global__ __launch_bounds__(RH_BLOCK) void softmax_attn_fwd_kernel(const SArgs 
       if (c >= nc) continue;
       if (c > 0) {
         __syncthreads();
-        load_chunk(vs, a.v, a.ld, col, c * kT, j0, L, dh, b, tid);
+        load_tile(vs, a.v, a.ld, col, c * kT, j0, L, dh, b, tid);
         __syncthreads();
       }
       // O quadrant: rows wm * 32, columns c * 64 + wn * 32;  O += P (64 x 64 keys) V (64 keys x 64 columns)
@@ -286,8 +250,8 @@ __global__ __launch_bounds__(RH_BLOCK) void softmax_attn_dkv_kernel(const SArgs 
     for (int c = 0; c < kNC; ++c) {
       if (c >= nc) continue;
       __syncthreads();
-      load_chunk(qs, a.q, a.ld, col, c * kT, i0, L, dh, b, tid);
-      load_chunk(gs, a.g_out, ldo, col, c * kT, i0, L, dh, b, tid);
+      load_tile(qs, a.q, a.ld, col, c * kT, i0, L, dh, b, tid);
+      load_tile(gs, a.g_out, ldo, col, c * kT, i0, L, dh, b, tid);
       if (c == 0 && tid < kT) {
         const int i = i0 + tid;
         lses[tid] = i < L ? a.lse[(int64_t)bh * L + i] : 0.f;
@@ -326,7 +290,7 @@ __global__ __launch_bounds__(RH_BLOCK) void softmax_attn_dkv_kernel(const SArgs 
       if (c >= nc) continue;
       if (c != nc - 1) {
         __syncthreads();
-        load_chunk(gs, a.g_out, ldo, col, c * kT, i0, L, dh, b, tid);
+        load_tile(gs, a.g_out, ldo, col, c * kT, i0, L, dh, b, tid);
       }
       __syncthreads();
       // dV quadrant: keys wm * 32, columns c * 64 + wn * 32;  dV += P^T dO  (A[key][i] = xs[i][key])
@@ -341,7 +305,7 @@ __global__ __launch_bounds__(RH_BLOCK) void softmax_attn_dkv_kernel(const SArgs 
       if (c >= nc) continue;
       if (c != nc - 1) {
         __syncthreads();
-        load_chunk(qs, a.q, a.ld, col, c * kT, i0, L, dh, b, tid);
+        load_tile(qs, a.q, a.ld, col, c * kT, i0, L, dh, b, tid);
       }
       __syncthreads();
       // dK quadrant: keys wm * 32, columns c * 64 + wn * 32;  dK += dS^T Q
@@ -397,8 +361,8 @@ __global__ __launch_bounds__(RH_BLOCK) void softmax_attn_dq_kernel(const SArgs a
     for (int c = 0; c < kNC; ++c) {
       if (c >= nc) continue;
       __syncthreads();
-      load_chunk(ks, a.k, a.ld, col, c * kT, j0, L, dh, b, tid);
-      load_chunk(vs, a.v, a.ld, col, c * kT, j0, L, dh, b, tid);
+      load_tile(ks, a.k, a.ld, col, c * kT, j0, L, dh, b, tid);
+      load_tile(vs, a.v, a.ld, col, c * kT, j0, L, dh, b, tid);
       __syncthreads();
 #pragma unroll
       for (int k = 0; k < kT; k += 2) {
@@ -426,7 +390,7 @@ __global__ __launch_bounds__(RH_BLOCK) void softmax_attn_dq_kernel(const SArgs a
       if (c >= nc) continue;
       if (c != nc - 1) {
         __syncthreads();
-        load_chunk(ks, a.k, a.ld, col, c * kT, j0, L, dh, b, tid);
+        load_tile(ks, a.k, a.ld, col, c * kT, j0, L, dh, b, tid);
       }
       __syncthreads();
       // dQ quadrant: queries wm * 32, columns c * 64 + wn * 32;  dQ += dS K
@@ -503,13 +467,9 @@ int sattn_check(const char* name, const SArgs& a) {
   return 0;
 }
 
-}  // namespace
-
-extern "C" int rh_softmax_attn_nparts(int B, int L, int H) { return B * H * ((L + kT - 1) / kT) + H; }
-
-extern "C" int rh_softmax_attn_fwd(const float* q, const float* k, const float* v, int64_t ld, int B, int L, int H, int dh,
-                                   const float* bias, int N, int nb, float scale, float p_drop, int64_t* rng,
-                                   int64_t* saved_ctr, float* out, float* lse, void* stream) {
+SArgs sattn_args(const float* q, const float* k, const float* v, int64_t ld, int B, int L, int H, int dh, const float* bias,
+                 int N, int nb, float scale, float p_drop, const int64_t* rng, const int64_t* saved_ctr, const float* out,
+                 const float* lse) {
   SArgs a{};
   a.q = q;
   a.k = k;
@@ -517,18 +477,29 @@ extern "C" int rh_softmax_attn_fwd(const float* q, const float* k, const float* 
   a.ld = ld;
   a.bias = bias;
   a.rng = rng;
-  a.saved_ctr = saved_ctr;
-  a.out = out;
-  a.lse = lse;
+  a.saved_ctr = const_cast<int64_t*>(saved_ctr);
+  a.out = const_cast<float*>(out);
+  a.lse = const_cast<float*>(lse);
   a.B = B;
   a.L = L;
   a.H = H;
   a.dh = dh;
   a.N = N;
   a.nb = nb;
-  a.fwd = 1;
   a.scale = scale;
   a.p_drop = p_drop;
+  return a;
+}
+
+}  // namespace
+
+extern "C" int rh_softmax_attn_nparts(int B, int L, int H) { return B * H * ((L + kT - 1) / kT) + H; }
+
+extern "C" int rh_softmax_attn_fwd(const float* q, const float* k, const float* v, int64_t ld, int B, int L, int H, int dh,
+                                   const float* bias, int N, int nb, float scale, float p_drop, int64_t* rng,
+                                   int64_t* saved_ctr, float* out, float* lse, void* stream) {
+  SArgs a = sattn_args(q, k, v, ld, B, L, H, dh, bias, N, nb, scale, p_drop, rng, saved_ctr, out, lse);
+  a.fwd = 1;
   if (int rc = sattn_check("rh_softmax_attn_fwd", a)) return rc;
   RH_REQUIRE(out && lse, RH_E_BADARG, "rh_softmax_attn_fwd: null output");
   if (B == 0) return 0;
@@ -545,16 +516,7 @@ extern "C" int rh_softmax_attn_bwd(const float* q, const float* k, const float* 
                                    const int64_t* saved_ctr, const float* out, const float* lse, const float* g_out,
                                    float* delta, float* g_q, float* g_k, float* g_v, int64_t ldg, float* part,
                                    float* g_bias, void* stream) {
-  SArgs a{};
-  a.q = q;
-  a.k = k;
-  a.v = v;
-  a.ld = ld;
-  a.bias = bias;
-  a.rng = rng;
-  a.saved_ctr = const_cast<int64_t*>(saved_ctr);
-  a.out = const_cast<float*>(out);
-  a.lse = const_cast<float*>(lse);
+  SArgs a = sattn_args(q, k, v, ld, B, L, H, dh, bias, N, nb, scale, p_drop, rng, saved_ctr, out, lse);
   a.g_out = g_out;
   a.delta = delta;
   a.g_q = g_q;
@@ -563,14 +525,6 @@ extern "C" int rh_softmax_attn_bwd(const float* q, const float* k, const float* 
   a.ldg = ldg;
   a.part = part;
   a.g_bias = g_bias;
-  a.B = B;
-  a.L = L;
-  a.H = H;
-  a.dh = dh;
-  a.N = N;
-  a.nb = nb;
-  a.scale = scale;
-  a.p_drop = p_drop;
   if (int rc = sattn_check("rh_softmax_attn_bwd", a)) return rc;
   RH_REQUIRE(out && lse && g_out && delta && g_q && g_k && g_v && (!bias || (part && g_bias)), RH_E_BADARG,
              "rh_softmax_attn_bwd: null pointer");

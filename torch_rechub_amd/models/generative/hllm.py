@@ -8,8 +8,8 @@ nn.Dropout applications of the reference (on the attention weights and on the pr
 the project's counter hash, so a captured train step draws a new mask on every replay.
 
 ``forward`` returns the (B, L, V) logits as the reference does.  ``hidden_and_head`` returns the normalised hidden
-states and the frozen item table without forming the logits: SeqTrainer feeds them to the fused next-token loss, whose
-backward then computes no (V, D) gradient at all.
+states and the frozen item table without forming the logits: SeqTrainer feeds them to the fused next-token loss
+(csrc/stream_ce.hip), whose backward then computes no (V, D) gradient at all.
 """
 import torch
 import torch.nn as nn

@@ -2901,7 +2901,7 @@ def listwise_logits(u, pos, neg, temperature=1.0):
 
 
 # --------------------------------------------------------------------------------------------
-# HSTU: pointwise relative-bias attention and the next-token head (csrc/hstu.hip)
+# HSTU: pointwise relative-bias attention (csrc/hstu.hip) and the next-token head (csrc/stream_ce.hip)
 # --------------------------------------------------------------------------------------------
 class _HstuAttnFn(torch.autograd.Function):
     """(B, L, H dv) = (silu(alpha q k^T + rab) / N, causal and key-padding masked) v, q / k / v read from proj."""
@@ -2963,6 +2963,20 @@ def hstu_attention(proj, pos_w, ts_w, n_heads, dqk, dv, max_seq_len, time_diffs=
     return _HstuAttnFn.apply(proj, pos_w.contiguous(), ts_w.contiguous(), td, km, cfg)
 
 
+def _head_fwd_workspaces(M, V, dev):
+    """part, zlab, lse, wrow, loss of the streaming cross entropy's forward over M rows and V items."""
+    nsplit = _lib.call("rh_hstu_head_nsplit", M, V)
+    return (torch.empty((M, nsplit, 2), dtype=torch.float32, device=dev), torch.empty((M,), dtype=torch.float32, device=dev),
+            torch.empty((M,), dtype=torch.float32, device=dev), torch.empty((M,), dtype=torch.float32, device=dev),
+            torch.empty((), dtype=torch.float32, device=dev))
+
+
+def _head_dw_slab(M, D, V, dev):
+    """The (R, V, D + 1) dW / d_bias partials of the streaming cross entropy's backward; unused when R is 1."""
+    R = _lib.call("rh_hstu_head_rsplit", M, D, V)
+    return torch.empty((R, V, D + 1) if R > 1 else (1,), dtype=torch.float32, device=dev)
+
+
 class _NextTokenLossFn(torch.autograd.Function):
     """Mean next-token cross entropy over the item table without the (M, V) logits."""
 
@@ -2971,15 +2985,9 @@ class _NextTokenLossFn(torch.autograd.Function):
         h, w = h.contiguous(), w.contiguous()
         M, D = (int(v) for v in h.shape)
         V = int(w.shape[0])
-        dev = h.device
-        nsplit = _lib.call("rh_hstu_head_nsplit", M, V)
-        part = torch.empty((M, nsplit, 2), dtype=torch.float32, device=dev)
-        zlab = torch.empty((M,), dtype=torch.float32, device=dev)
-        lse = torch.empty((M,), dtype=torch.float32, device=dev)
-        wrow = torch.empty((M,), dtype=torch.float32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
+        part, zlab, lse, wrow, loss = _head_fwd_workspaces(M, V, h.device)
         _lib.call("rh_hstu_head_fwd", _p(h), _p(w), _p(bias), _p(labels), M, D, V, t1, t2, int(nce), _p(part), _p(zlab),
-                  _p(lse), _p(wrow), _p(loss), _p(err_flag(dev)), _stream())
+                  _p(lse), _p(wrow), _p(loss), _p(err_flag(h.device)), _stream())
         ctx.t = (t1, t2)
         ctx.has_bias = bias is not None
         ctx.save_for_backward(h, w, bias, labels, lse, wrow)
@@ -2998,8 +3006,7 @@ class _NextTokenLossFn(torch.autograd.Function):
             _lib.call("rh_hstu_head_bwd", _p(h), _p(w), _p(bias), _p(labels), _p(lse), _p(wrow),
                       _p(g.reshape(1).contiguous()), M, D, V, t1, t2, _NULL, _p(g_h), _NULL, _NULL, _stream())
             return g_h, None, None, None, None, None, None
-        R = _lib.call("rh_hstu_head_rsplit", M, D, V)
-        part = torch.empty((R, V, D + 1) if R > 1 else (1,), dtype=torch.float32, device=dev)
+        part = _head_dw_slab(M, D, V, dev)
         g_w = torch.empty_like(w)
         g_b = torch.empty((V,), dtype=torch.float32, device=dev) if ctx.has_bias else None
         _lib.call("rh_hstu_head_bwd", _p(h), _p(w), _p(bias), _p(labels), _p(lse), _p(wrow), _p(g.reshape(1).contiguous()),
@@ -3104,7 +3111,7 @@ def softmax_attention(q, k, v, n_heads, max_seq_len, bias_table=None, dropout_p=
 
 # --------------------------------------------------------------------------------------------
 # Session-based retrieval: general GRU, additive attention pooling, full-catalogue cross entropy
-# (csrc/session.hip, csrc/hstu.hip)
+# (csrc/session.hip, csrc/stream_ce.hip)
 # --------------------------------------------------------------------------------------------
 class _GruLayerFn(torch.autograd.Function):
     """h_all (B, T, H) of one nn.GRU layer from the zero state; xw (B, T, 3H) = x W_ih^T (+ b_ih), rows r | z | n."""
@@ -3235,15 +3242,9 @@ class _CatalogueCEFn(torch.autograd.Function):
         u, E = u.contiguous(), E.contiguous()
         B, D = (int(v) for v in u.shape)
         V = int(E.shape[0])
-        dev = u.device
-        nsplit = _lib.call("rh_hstu_head_nsplit", B, V)
-        part = torch.empty((B, nsplit, 2), dtype=torch.float32, device=dev)
-        zlab = torch.empty((B,), dtype=torch.float32, device=dev)
-        lse = torch.empty((B,), dtype=torch.float32, device=dev)
-        wrow = torch.empty((B,), dtype=torch.float32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
+        part, zlab, lse, wrow, loss = _head_fwd_workspaces(B, V, u.device)
         _lib.call("rh_catalogue_ce_fwd", _p(u), _p(E), _p(labels), B, D, V, _p(part), _p(zlab), _p(lse), _p(wrow), _p(loss),
-                  _p(err_flag(dev)), _stream())
+                  _p(err_flag(u.device)), _stream())
         ctx.save_for_backward(u, E, labels, lse, wrow)
         return loss
 
@@ -3253,9 +3254,8 @@ class _CatalogueCEFn(torch.autograd.Function):
         B, D = (int(v) for v in u.shape)
         V = int(E.shape[0])
         dev = u.device
-        R = _lib.call("rh_hstu_head_rsplit", B, D, V)
         Sv = _lib.call("rh_catalogue_ce_vsplit", B, D, V)
-        part = torch.empty((R, V, D + 1) if R > 1 else (1,), dtype=torch.float32, device=dev)
+        part = _head_dw_slab(B, D, V, dev)
         part_h = torch.empty((Sv, B, D) if Sv > 1 else (1,), dtype=torch.float32, device=dev)
         g_u = torch.empty_like(u)
         g_E = torch.empty_like(E)

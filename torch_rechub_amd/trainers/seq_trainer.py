@@ -1,6 +1,6 @@
 """SeqTrainer (reference torch_rechub/trainers/seq_trainer.py): next-item training of generative models (HSTUModel, HLLMModel).
 
-A model that exposes ``hidden_and_head`` trains through the fused next-token loss (ops.next_token_loss, csrc/hstu.hip):
+A model that exposes ``hidden_and_head`` trains through the fused next-token loss (ops.next_token_loss, csrc/stream_ce.hip):
 the (B, L, V) logits, their clone and the same-sized softmax gradient of the reference never exist.  ``evaluate`` scores
 only the last position's (B, V) logits for the top-1 hit.  ``_compute_next_token_loss`` keeps the reference's semantics
 on given logits.  Single device only.
