@@ -28,6 +28,9 @@
  *                                 [slot*D, slot*D + D) of out / g_out / emb (slot = f unless sequence
  *                                 features are interleaved with sparse ones, basic/layers.py:80-99)
  * Two fields may name the same table (SparseFeature.shared_with, basic/layers.py:85,99).
+ *
+ * Keep this file plain C: torch_rechub_amd/_header.py parses it for the ctypes signatures and refuses what it cannot map
+ * (scalars other than int / int64_t / float by value, structs by value, function pointers, non-integer RH_* macros).
  */
 #ifndef RECHUB_HIP_H
 #define RECHUB_HIP_H

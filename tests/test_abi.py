@@ -55,3 +55,87 @@ def test_missing_library_fails_loudly(monkeypatch):
     monkeypatch.setattr(_lib, "LIB_PATH", "/nonexistent/librechub_hip.so")
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         _lib.load()
+
+
+def test_every_declaration_has_a_derived_signature():
+    """The ctypes signatures come from the header: the parser may not skip a declaration the regex above finds."""
+    from torch_rechub_amd import _lib
+    syms = declared_symbols()
+    assert not [name for name in syms if name not in _lib.SIGNATURES]
+    assert len(_lib.SIGNATURES) == len(syms) == len(_lib._RESTYPES)
+
+
+def test_loaded_functions_carry_the_derived_types():
+    from torch_rechub_amd import _lib
+    lib = _lib.load()
+    for name in declared_symbols():
+        fn = getattr(lib, name)
+        assert list(fn.argtypes) == _lib.SIGNATURES[name], name
+        assert fn.restype is _lib._RESTYPES[name], name
+    assert lib.rh_embed_fwd.argtypes[9:11] == [ctypes.c_void_p, ctypes.c_int64]  # float* out, int64_t out_stride
+    assert lib.rh_last_error.restype is ctypes.c_char_p and lib.rh_linear_wgrad_workspace.restype is ctypes.c_int64
+    assert lib.rh_cross_max_layers.restype is ctypes.c_int and lib.rh_dice_fwd.argtypes[2] is ctypes.c_float
+
+
+MINI_HEADER = """
+#define RH_ABI_VERSION 1
+#define RH_E_BADARG (-1)  /* an argument error */
+typedef struct RhPackItem {
+  uint64_t src; /* device pointer */
+  int64_t numel;
+} RhPackItem;
+int rh_a(const float* x, int64_t n, float eps, void** out);  // a comment
+const char* rh_b(void);
+"""
+
+
+def test_parser_maps_plain_c_and_raises_on_the_rest():
+    from torch_rechub_amd import _header
+    functions, fields, macros = _header.parse(MINI_HEADER)
+    assert functions == {"rh_a": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p]),
+                         "rh_b": (ctypes.c_char_p, [])}
+    assert fields == [("src", ctypes.c_uint64), ("numel", ctypes.c_int64)]
+    assert macros == {"RH_ABI_VERSION": 1, "RH_E_BADARG": -1}
+    for bad, message in (("int rh_c(const float* x, size_t n);", "cannot map `size_t n`"),
+                         ("int rh_c(double scale, void* stream);", "cannot map `double scale`"),
+                         ("int rh_c(RhPackItem item);", "cannot map `RhPackItem item`"),
+                         ("int rh_c(void (*done)(int), void* stream);", "cannot map"),
+                         ("double rh_c(int n);", "return type `double`"),
+                         ("#define RH_SCALE 0.5", "not an integer constant"),
+                         ("int rh_c(int n, void* stream", "cut off before `;`")):
+        with pytest.raises(ValueError, match=re.escape(message)):
+            _header.parse(MINI_HEADER + bad + "\n")
+
+
+def test_pack_item_layout_is_the_headers():
+    from torch_rechub_amd import _lib
+    assert ctypes.sizeof(_lib.PackItem) == 48
+    text = open(os.path.join(ROOT, "include", "rechub_hip.h")).read()
+    body = re.search(r"typedef struct RhPackItem \{(.*?)\} RhPackItem;", text, flags=re.S).group(1)
+    names = re.findall(r"(\w+);", body)
+    assert [f for f, _ in _lib.PackItem._fields_] == names == ["src", "add", "nparts", "stride", "numel", "dst_offset"]
+
+
+def test_header_macros_are_exposed():
+    from torch_rechub_amd import _lib
+    assert len(vars(_lib.H)) == 28
+    assert (_lib.H.RH_E_BADARG, _lib.H.RH_E_UNSUPPORTED) == (-1, -2)
+    assert (_lib.H.RH_FLAG_INDEX_OOB, _lib.H.RH_FLAG_TARGET_OOB, _lib.H.RH_ERR_GATE_TIMEOUT, _lib.H.RH_FLAG_SESSION_EMPTY,
+            _lib.H.RH_FLAG_SESSION_SHORT) == (1, 2, 64, 128, 256)
+    assert (_lib.H.RH_TUNE_DEFERRED_GRID, _lib.H.RH_TUNE_SWEEP_GATE_NS, _lib.H.RH_GATE_WORDS) == (8, 13, 16)
+
+
+def test_status_and_value_returns_are_told_apart():
+    """A function without a pointer parameter returns a value; rh_set_tuning is the exception and returns a status."""
+    from torch_rechub_amd import _lib
+    assert len(_lib._VALUE_RETURNING) == 34 and "rh_set_tuning" not in _lib._VALUE_RETURNING
+    assert "rh_last_error" not in _lib._VALUE_RETURNING and "rh_linear_wgrad_workspace" in _lib._VALUE_RETURNING
+    with pytest.raises(RuntimeError, match="rh_set_tuning failed"):
+        _lib.call("rh_set_tuning", 3, 0)  # key 3 was removed: the header says it fails
+    assert _lib.call("rh_cross_max_layers", 4096) == 0  # a value of 0, not a status
+
+
+def test_a_missing_argument_is_a_type_error():
+    from torch_rechub_amd import _lib
+    with pytest.raises(TypeError):
+        _lib.call("rh_cross_max_layers")

@@ -137,16 +137,16 @@ def check_errors(device=None):
         v = int(f.item())
         if v:
             f.zero_()
-            if v & 1:
+            if v & _lib.H.RH_FLAG_INDEX_OOB:
                 raise IndexError("torch_rechub_amd: an embedding index was out of range (index < 0 or >= vocab_size)")
-            if v & 2:  # RH_FLAG_TARGET_OOB
+            if v & _lib.H.RH_FLAG_TARGET_OOB:
                 raise IndexError("torch_rechub_amd: a target label was out of range (label < 0 or >= the number of classes)")
-            if v & 128:  # RH_FLAG_SESSION_EMPTY
+            if v & _lib.H.RH_FLAG_SESSION_EMPTY:
                 raise RuntimeError("torch_rechub_amd: Length of all samples has to be greater than 0 (a session holds no item)")
-            if v & 256:  # RH_FLAG_SESSION_SHORT
+            if v & _lib.H.RH_FLAG_SESSION_SHORT:
                 raise RuntimeError("torch_rechub_amd: the longest session of the batch is shorter than its padded length L "
                                    "(the reference NARM fails to broadcast its states against the mask)")
-            if v & 64:  # RH_ERR_GATE_TIMEOUT
+            if v & _lib.H.RH_ERR_GATE_TIMEOUT:
                 raise RuntimeError("torch_rechub_amd: a deferred table sweep waited 2 s for a training step that never started "
                                    "(rh_adam_sweep_gate); the tables may be inconsistent")
             raise RuntimeError(f"torch_rechub_amd: kernel error flag {v}")

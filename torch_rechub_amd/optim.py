@@ -20,7 +20,9 @@ import torch
 from . import _lib, graphs, ops
 
 
-SWEEP_WINDOW, SWEEP_FLUSH, SWEEP_LAZY_TABLES, SWEEP_DENSE_TABLES = 0, 1, 2, 3  # rh_adam_lazy_sweep modes
+# rh_adam_lazy_sweep modes
+SWEEP_WINDOW, SWEEP_FLUSH = _lib.H.RH_SWEEP_WINDOW, _lib.H.RH_SWEEP_FLUSH
+SWEEP_LAZY_TABLES, SWEEP_DENSE_TABLES = _lib.H.RH_SWEEP_LAZY_TABLES, _lib.H.RH_SWEEP_DENSE_TABLES
 EAGER_HEAD = _lib.ab("eagerhead")  # False (RECHUB_AB=eagerhead=0): the one-kernel head stays a captured graph segment
 ASSEMBLE_WITH_REFRESH = _lib.ab("assemble")  # False (RECHUB_AB=assemble=0): rh_batch_gather and the refresh as two launches
 RELAXED_JOIN = _lib.ab("lookahead")  # False (RECHUB_AB=lookahead=0): the eager head on the sweep's queue, strict join (below)
@@ -146,7 +148,7 @@ class TableAdam(torch.optim.Adam):
                 self._rider = None          # ... and the weight-gradient group that launch carries (_ride_wgrad)
                 # step-ahead form: the sweep's release is a device word the LAST launch of the step's graph counts up
                 # (rh_adam_sweep_gate_open): [openings, wall clock of the last one]
-                self._gate = torch.zeros(16, dtype=torch.int64, device=dev)  # RH_GATE_WORDS (include/rechub_hip.h)
+                self._gate = torch.zeros(_lib.H.RH_GATE_WORDS, dtype=torch.int64, device=dev)
                 self._gate_seen = 0  # openings issued so far (one per replay of a step-ahead graph)
                 self._gate_by_pack = False
                 self.gate_by_chain = False  # the captured step-ahead graph holds a chain-start count (rh_linear_fwd_gate)

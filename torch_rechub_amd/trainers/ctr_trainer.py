@@ -389,16 +389,16 @@ class CTRTrainer(object):
                                  "'branch' were removed)")
             grid = os.environ.get("RECHUB_SWEEP_GRID", "")
             if grid:
-                _lib.call("rh_set_tuning", 8, int(grid))
+                _lib.call("rh_set_tuning", _lib.H.RH_TUNE_DEFERRED_GRID, int(grid))
             # (round 5 measured larger residency caps for the sweep-bound configs[4] step -- 1024 / 2048 workgroups: 0.98 / 1.04 ms
             # against 0.834 at 512 and 0.833 at 256 -- the chain loses more than the sweep gains there too; not candidates)
             cands = [c for c in self.TUNE_CANDIDATES if (not form or c[0] == form) and
                      (not grid or c[0] == "inline" or c[1] == int(grid))]
             if form and (grid or not cands):  # fully pinned (also forms / grids that are not tuning candidates)
                 cands = [(form, int(grid or 512) if form != "inline" else 0, 0)]
-            # a user who pinned the deferred sweep's grid / hold-back through RECHUB_TUNE (keys 8 / 13, exact match) keeps them
+            # a user who pinned the deferred sweep's grid / hold-back through RECHUB_TUNE (exact match of the key) keeps them
             pinned = {kv.split("=")[0].strip() for kv in os.environ.get("RECHUB_TUNE", "").split(",") if "=" in kv}
-            if "13" in pinned or form and (grid or len(cands) == 1):
+            if str(_lib.H.RH_TUNE_SWEEP_GATE_NS) in pinned or form and (grid or len(cands) == 1):
                 seen, kept = set(), []
                 for c in cands:  # one candidate per (form, grid): the hold-back stays what the user / the library set
                     if c[:2] not in seen:
@@ -414,7 +414,7 @@ class CTRTrainer(object):
                         seen.add(c[:2])
                         kept.append((c[0], c[1], 0))
                 cands = kept
-            active = lazy and self.dp is None and len(cands) > 1 and "8" not in pinned
+            active = lazy and self.dp is None and len(cands) > 1 and str(_lib.H.RH_TUNE_DEFERRED_GRID) not in pinned
             st = self._tune = {"active": bool(active), "wait": (opt.lazy_k + 8) if lazy else 0, "i": 0, "n": 0, "ev": [],
                                "cands": cands}
             if lazy and self.dp is None and form and form != self._form and len(cands) == 1:
@@ -452,9 +452,9 @@ class CTRTrainer(object):
         from .. import _lib
         form, grid, hold = cand
         if form != "inline":
-            _lib.call("rh_set_tuning", 8, int(grid))
+            _lib.call("rh_set_tuning", _lib.H.RH_TUNE_DEFERRED_GRID, int(grid))
             if hold:
-                _lib.call("rh_set_tuning", 13, int(hold))
+                _lib.call("rh_set_tuning", _lib.H.RH_TUNE_SWEEP_GATE_NS, int(hold))
         if self._form != form:
             self._switch_form(form, loader)
 
