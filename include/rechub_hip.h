@@ -929,7 +929,7 @@ int rh_gru_bwd(const float* xw, const float* w_hh, const float* h_all, const flo
  * r (B, H), w0 (H,), mask (B, L) float 0 / 1, X (B, L, Dx), add (B, Dx) or null.  1 <= L <= 1024, 1 <= H, Dx <= 4096.
  * rh_attn_pool_fwd: e (B, L), sums (B, 2) = (sum, den) for the backward.
  * rh_attn_pool_bwd: g (B, Dx) -> dP (B, L, H), dr (B, H), dw0 (H,) (per-sample partials dw0_part (B, H) summed in a
- *   fixed order), dX (B, L, Dx) the pooling term only.
+ *   fixed order; zero at B = 0), dX (B, L, Dx) the pooling term only.
  * replaces: NARM's q / alpha / c_l (models/matching/narm.py:60-63), STAMP's a / m_a (stamp.py:66-67), and autograd. */
 int rh_attn_pool_fwd(const float* P, const float* r, const float* w0, const float* mask, const float* X, const float* add,
                      int B, int L, int H, int Dx, int floor_, float* out, float* e, float* sums, void* stream);

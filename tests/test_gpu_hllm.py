@@ -1,7 +1,8 @@
 """HLLM on the MI355X: the causal softmax attention kernels of csrc/hllm.hip against the float64 numpy restatement over
 the supported head widths and lengths, bitwise repeatable backwards, the block and the model against the reference's
 fixtures (outputs, loss, gradients, the three-step SeqTrainer trajectory), dropout on the weights, the captured step, and
-the memory bounds of the attention and of the frozen head."""
+the memory bounds of the attention and of the frozen head.  Tile and chunk edges, many-partial bias-table sums, the guard
+and the backward under dropout against float64 are in test_gpu_session_hllm_shapes.py."""
 import json
 
 import numpy as np

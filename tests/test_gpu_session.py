@@ -1,7 +1,9 @@
 """NARM / STAMP / GRU4Rec on the MI355X: the kernels of csrc/session.hip and the full-catalogue head (csrc/stream_ce.hip) against float64 at
 full size and at their edges, repeatable backwards, the models and three MatchTrainer steps against the reference's
 fixtures (tools/gen_golden_session.py), the errors for inputs the reference rejects, batches of different L, the memory
-bound of a large-catalogue NARM step and the captured step against eager."""
+bound of a large-catalogue NARM step and the captured step against eager.  The rest of the kernels' shape range (partly
+filled GRU workgroups, second trips of the strided loops, the guards' largest shapes, every split path of the catalogue
+head, the empty batch) is in test_gpu_session_hllm_shapes.py."""
 import numpy as np
 import pytest
 import torch

@@ -438,7 +438,6 @@ extern "C" int rh_attn_pool_bwd(const float* P, const float* r, const float* w0,
                                 const float* sums, const float* g, int B, int L, int H, int Dx, int floor_, float* dP, float* dr,
                                 float* dw0_part, float* dw0, float* dX, void* stream) {
   if (int rc = pool_check("rh_attn_pool_bwd", B, L, H, Dx)) return rc;
-  if (B == 0) return 0;
   RH_REQUIRE(P && r && w0 && X && e && sums && g && dP && dr && dw0_part && dw0 && dX, RH_E_BADARG,
              "rh_attn_pool_bwd: null pointer");
   PoolArgs a{};
@@ -446,7 +445,8 @@ extern "C" int rh_attn_pool_bwd(const float* P, const float* r, const float* w0,
   a.dP = dP, a.dr = dr, a.dw0_part = dw0_part, a.dw0 = dw0, a.dX = dX;
   a.B = B, a.L = L, a.H = H, a.Dx = Dx, a.floor_ = floor_ != 0;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(pool_bwd_kernel, dim3(B), dim3(RH_BLOCK), 0, st, a);
+  // d w0 (H,) does not depend on B: an empty batch still writes it (the sum over no sample, zero)
+  if (B > 0) hipLaunchKernelGGL(pool_bwd_kernel, dim3(B), dim3(RH_BLOCK), 0, st, a);
   hipLaunchKernelGGL(pool_dw0_kernel, dim3(H), dim3(RH_BLOCK), 0, st, a);
   RH_LAUNCH_CHECK("rh_attn_pool_bwd");
   return 0;

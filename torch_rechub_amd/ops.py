@@ -3173,7 +3173,7 @@ def gru_layers(gru_mod, x, batch_first=None):
         w_ih, w_hh = getattr(gru_mod, f"weight_ih_l{k}"), getattr(gru_mod, f"weight_hh_l{k}")
         b_ih = getattr(gru_mod, f"bias_ih_l{k}") if gru_mod.bias else None
         b_hh = getattr(gru_mod, f"bias_hh_l{k}") if gru_mod.bias else None
-        xw = linear(h.reshape(B * T, -1), w_ih, b_ih).view(B, T, 3 * H)
+        xw = linear(h.reshape(B * T, h.shape[-1]), w_ih, b_ih).view(B, T, 3 * H)  # (B = 0: -1 would be ambiguous)
         h = _GruLayerFn.apply(xw, w_hh, b_hh)
         last.append(h[:, -1])
     h_n = torch.stack(last, 0)
