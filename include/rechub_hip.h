@@ -56,32 +56,17 @@ extern "C" {
 int rh_abi_version(void);
 const char* rh_last_error(void);
 
-/* tuning knobs (process-wide; defaults are the measured winners) */
-#define RH_TUNE_WIDE_ATOMICS 1 /* 1: table-gradient atomics carry whole rows per request (default), 0: 16 B pieces */
+/* tuning knobs (process-wide; defaults are the measured winners).  Keys 1, 3, 4, 5, 6, 10, 11, 14, 15 and 16 selected experiments
+ * that were measured and rejected (DESIGN.md keeps the numbers); they are removed with the variants behind them, and
+ * rh_set_tuning fails for them as for any unknown key. */
 #define RH_TUNE_SWEEP_GRID 2   /* workgroups of rh_adam_lazy_sweep (0 = default 8192) */
-/* key 3 (an LDS-padding residency cap of the deferred sweep) was measured in round 3 and removed: rh_set_tuning(3, .) fails */
 #define RH_TUNE_DEFERRED_GRID 8 /* persistent workgroups of a DEFERRED sweep (default 512 = 2 per CU; 0 = as RH_TUNE_SWEEP_GRID):
                                   the residency cap that lets the step's chain keep its wave slots and issue cycles */
 #define RH_TUNE_SWEEP_STAGGER_NS 12 /* rh_adam_sweep_stagger: hold-back in nanoseconds (default 15000; 0 = no launch) */
 #define RH_TUNE_SWEEP_GATE_NS 13 /* rh_adam_sweep_gate(fallback_ns = 0): hold-back behind the opening, ns (default 32000) */
-#define RH_TUNE_SWEEP_WIDE 14 /* deferred window sweep of the lazy tables: float4 per lane at embed_dim >= 8 (2 = default: two
-                                 independent float4 chains per lane, round 5; 1 = one float4 per lane, the round-4 kernel) */
-#define RH_TUNE_WGRAD_RIDER_ORDER 15 /* rh_adam_lazy_step_ahead_wgrad: weight-gradient workgroups 2 = behind the optimizer's parts
-                                      * (default), 0 = in front of them, 1 = dealt alternately with them */
 #define RH_TUNE_WGRAD_BLOCKS 9 /* workgroups rh_linear_wgrad aims for when the reduction is >= 32768 rows (default 1024) */
-#define RH_TUNE_WGRAD_ROWS_FORM 16 /* rh_linear_wgrad, reductions >= 32768 rows whose output is 2 .. 8 tiles of 64 x 64: value > 0 = ONE
-                                      workgroup per row split computes the whole (N, K) slab, `value` workgroups aimed for (default 512), two
-                                      tiles per wavefront where the tile counts pair up; value < 0 = -value workgroups, one tile per
-                                      wavefront; 0 = one workgroup per tile and split (rounds 1-5) */
-#define RH_TUNE_WGRAD_SHORT_FORM 11 /* rh_linear_wgrad at B < 32768: 0 = 206-register build, 1 = the 128-register build (default) */
-#define RH_TUNE_DICE_VEC 10    /* bit mask of lanes-per-row (16 | 32 | 64) for which the Dice passes use the rows-per-wavefront
-                                  kernel (C = 64 / 128 / 256); default 16 | 32 */
-#define RH_TUNE_BWD_SPLIT 4     /* retired (accepted, ignored) */
-#define RH_TUNE_BWD_SLABS 5     /* retired (accepted, ignored) */
-#define RH_TUNE_FWD_PATH 7      /* rh_embed_fwd: 0 auto (by batch size), 1 lane-split kernel only, 2 field-uniform kernel only */
-#define RH_TUNE_BWD_PATH 6      /* rh_embed_bwd experiments: 0 auto, 1 global atomics for every table, 3 no sink, 4 chunk-fastest
-                                 * block order; TIMING ONLY (wrong sums on colliding rows, tools/bwd_ceiling_probe.py): 5 the
-                                 * row-wide requests as plain stores, 6 one plain 16-byte store per lane */
+#define RH_TUNE_FWD_PATH 7      /* rh_embed_fwd: 0 auto (by batch size), 1 lane-split kernel only, 2 field-uniform kernel only;
+                                   any other value fails */
 int rh_set_tuning(int key, int value);
 
 /* ---------------------------------------------------------------------------------------------

@@ -118,7 +118,7 @@ def test_pack_item_layout_is_the_headers():
 
 def test_header_macros_are_exposed():
     from torch_rechub_amd import _lib
-    assert len(vars(_lib.H)) == 28
+    assert len(vars(_lib.H)) == 19
     assert (_lib.H.RH_E_BADARG, _lib.H.RH_E_UNSUPPORTED) == (-1, -2)
     assert (_lib.H.RH_FLAG_INDEX_OOB, _lib.H.RH_FLAG_TARGET_OOB, _lib.H.RH_ERR_GATE_TIMEOUT, _lib.H.RH_FLAG_SESSION_EMPTY,
             _lib.H.RH_FLAG_SESSION_SHORT) == (1, 2, 64, 128, 256)
@@ -133,6 +133,26 @@ def test_status_and_value_returns_are_told_apart():
     with pytest.raises(RuntimeError, match="rh_set_tuning failed"):
         _lib.call("rh_set_tuning", 3, 0)  # key 3 was removed: the header says it fails
     assert _lib.call("rh_cross_max_layers", 4096) == 0  # a value of 0, not a status
+
+
+@pytest.mark.parametrize("key", [1, 4, 5, 6, 10, 11, 14, 15, 16])
+def test_removed_tuning_keys_are_rejected(key):
+    """The keys of the measured-and-rejected experiments went with their variants (the two that were accepted and ignored
+    included): rh_set_tuning fails for them as it does for key 3, whatever the value, and the header defines no macro for them."""
+    from torch_rechub_amd import _lib
+    for value in (0, 1):
+        with pytest.raises(RuntimeError, match="rh_set_tuning failed"):
+            _lib.call("rh_set_tuning", key, value)
+    assert key not in {v for k, v in vars(_lib.H).items() if k.startswith("RH_TUNE_")}
+
+
+def test_forward_path_key_takes_its_three_values_only():
+    from torch_rechub_amd import _lib
+    for value in (3, 4, -1):
+        with pytest.raises(RuntimeError, match="rh_set_tuning failed"):
+            _lib.call("rh_set_tuning", _lib.H.RH_TUNE_FWD_PATH, value)
+    for value in (1, 2, 0):
+        assert _lib.call("rh_set_tuning", _lib.H.RH_TUNE_FWD_PATH, value) == 0
 
 
 def test_a_missing_argument_is_a_type_error():

@@ -18,7 +18,6 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--batches", default="4096,65536")
-    ap.add_argument("--slabs", default="0", help="RH_TUNE_BWD_PATH values to sweep for the backward (0 auto, 4 = chunk-fastest block order)")
     ap.add_argument("--dtypes", default="i64")
     args = ap.parse_args()
     from torch_rechub_amd import _lib, ops
@@ -69,17 +68,12 @@ def main():
                               ops._p(lr_w), ops._p(partial), 1.0, 0, ops._p(None), SPB, ops._p(ops.err_flag(dev)),
                               ops._stream())
 
-                us_b = []
-                for sl in [int(x) for x in args.slabs.split(",")]:
-                    _lib.call("rh_set_tuning", 6, sl)
-                    us_b.append(timeit(bwd, args.iters))
-                us_all, us_b = us_b, us_b[0]
+                us_b = timeit(bwd, args.iters)
                 ib = 8 if i64 else 4
                 fb = F * (ib + 128) + 8 + 8 * nd
                 bb = F * (ib + 192) + 4
                 print(f"B={B:6d} {name:9s} F={F:2d} idx={'i64' if i64 else 'i32'}  fwd {us_f:8.2f} us {fb * B / us_f / 1e3:6.0f} GB/s | "
-                      f"bwd {us_b:8.2f} us {bb * B / us_b / 1e3:6.0f} GB/s  paths {args.slabs}: " +
-                      " ".join(f"{u:.1f}" for u in us_all), flush=True)
+                      f"bwd {us_b:8.2f} us {bb * B / us_b / 1e3:6.0f} GB/s", flush=True)
         for w in all_tables:
             ops.grad_buffer(w).zero_()
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """rh_embed_fwd kernels (RH_TUNE_FWD_PATH) on the DeepFM / Criteo call (26 tables, D = 16, 13 dense columns, FM + LR), with the index set
 CYCLED between launches (6 sets) so that the 256 MiB Infinity Cache cannot keep the rows of the previous launch:
-    python tools/fwd_probe.py [--batches 4096,65536] [--vars 0,1,2,3] [--splits 0]
+    python tools/fwd_probe.py [--batches 4096,65536] [--vars 0,1,2] [--splits 0]
 Prints us per launch and the fraction of the 8 TB/s HBM peak on the algorithmic bytes (bench.py's figure)."""
 import argparse
 import os
@@ -17,7 +17,7 @@ from bench import CRITEO_VOCABS  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", default="4096,8192,16384,32768,65536")
-    ap.add_argument("--vars", default="1,2,3,4", help="RH_TUNE_FWD_PATH values: 1 lane-split kernel, 2 / 3 / 4 field-uniform kernel, 4 / 2 / 1 wavefronts per sample group")
+    ap.add_argument("--vars", default="1,2", help="RH_TUNE_FWD_PATH values: 0 auto, 1 lane-split kernel, 2 field-uniform kernel")
     ap.add_argument("--splits", default="0")
     ap.add_argument("--sets", type=int, default=6)
     ap.add_argument("--rounds", type=int, default=30)

@@ -76,8 +76,7 @@ def main():
             g_out = torch.randn(B, F * D + 13, device=dev)
             g_y = torch.randn(B, device=dev)
             fdesc, idesc = call.fdesc(True), call.idesc()
-            for wide, spb in [(w, s) for w in (0, 1) for s in (128, 256, 512, 1024)]:
-                _lib.call("rh_set_tuning", 1, wide)
+            for spb in (128, 256, 512, 1024):
                 nch = _lib.call("rh_embed_bwd_nchunks", B, spb)
                 partial = torch.empty(nch, F * D, device=dev)
 
@@ -86,7 +85,7 @@ def main():
                               ops._p(out), out.stride(0), ops._p(ssum), ops._p(g_y), ops._p(g_y), ops._p(lr_w),
                               ops._p(partial), 1.0, 0, ops._p(None), spb, ops._p(ops.err_flag(dev)), ops._stream())
                 us = timeit(raw, args.iters)
-                print(f"bwd* B={B:6d} wide={wide} spb={spb:4d} {us:8.2f} us  "
+                print(f"bwd* B={B:6d} spb={spb:4d} {us:8.2f} us  "
                       f"{BWD_BYTES_PER_SAMPLE * B / us / 1e3:7.0f} GB/s (alg)", flush=True)
             for w in tables:
                 ops.grad_buffer(w).zero_()

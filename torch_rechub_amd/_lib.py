@@ -33,7 +33,7 @@ _lib = None
 
 
 def ab(name, default=True):
-    """Same-box A/B switches of benchmarks, ONE environment variable: RECHUB_AB="chain=0,headside=0,assemble=0" turns the named
+    """Same-box A/B switches of benchmarks, ONE environment variable: RECHUB_AB="chain=0,ahead=0,lookahead=0" turns the named
     round-4 paths off (each has a bit- or tolerance-pinned twin; the tests flip the module attributes instead)."""
     for item in filter(None, os.environ.get("RECHUB_AB", "").split(",")):
         k, _, v = item.partition("=")

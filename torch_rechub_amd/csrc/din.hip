@@ -227,7 +227,7 @@ __global__ __launch_bounds__(RH_BLOCK) void dice_kernel(const DiceArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// The same four passes for C = 64 / 128 / 256 with LPR = C / 4 lanes per row and 64 / LPR rows per wavefront pass: one
+// The same four passes for C = 64 / 128 with LPR = C / 4 lanes per row and 64 / LPR rows per wavefront pass: one
 // 16-byte load per lane and row, and the per-row reductions (2 forward, 4-5 backward) run for all rows of the pass in the
 // same instructions.  dice_kernel above spends one wavefront per row whatever C is: at C = 128 its fixed per-row work
 // (reductions, loop, addressing) bounded it at 1.8 - 2.9 TB/s of its streams.  Rows r = (wavefront pass) * RPW + lane / LPR;
@@ -247,7 +247,6 @@ static __device__ __forceinline__ float group_sum(float v) {
   const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16));
   const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32));
   const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48));
-  if (LPR == 64) return (r0 + r1) + (r2 + r3);
   return (threadIdx.x & 32) ? r2 + r3 : r0 + r1;
 }
 
@@ -440,8 +439,6 @@ __global__ __launch_bounds__(RH_BLOCK) void dice_vec_kernel(const DiceArgs a) {
   }
 }
 
-int g_dice_vec = 16 | 32;  // tuning knob RH_TUNE_DICE_VEC: bit mask of the LPR values dice_vec_kernel serves (C = 4 * LPR)
-
 int dice_epl(int C) {
   int e = 1;
   while (e * RH_WAVE < C) e *= 2;
@@ -477,12 +474,11 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 
 template <int MODE, bool HEAD = false>
 int dice_dispatch(const DiceArgs& a, hipStream_t s) {
-  if ((a.C == 64 || a.C == 128 || a.C == 256) && (g_dice_vec & (a.C / 4)) && aligned16(a.x) && aligned16(a.out) &&
+  if ((a.C == 64 || a.C == 128) && aligned16(a.x) && aligned16(a.out) &&
       (HEAD || aligned16(a.g)) && aligned16(a.scale) && aligned16(a.shift) && aligned16(a.stat) && aligned16(a.gamma) &&
       aligned16(a.head_w)) {
     if (a.C == 64) dice_vec_launch<16, MODE, HEAD>(a, s);
-    else if (a.C == 128) dice_vec_launch<32, MODE, HEAD>(a, s);
-    else dice_vec_launch<64, MODE, HEAD>(a, s);
+    else dice_vec_launch<32, MODE, HEAD>(a, s);
     return 0;
   }
   const unsigned grid = MODE == 2 ? dice_grid(a.N, kStatsBlocks) : dice_grid(a.N);
@@ -697,14 +693,6 @@ extern "C" int rh_prelu_bwd(const float* x, const float* g, const float* slope, 
                      slope, n / 4, n, gx, partial);
   RH_LAUNCH_CHECK("rh_prelu_bwd");
   return 0;
-}
-
-extern "C" int rh_din_set_tuning(int key, int value) {
-  if (key == RH_TUNE_DICE_VEC) {
-    g_dice_vec = value;
-    return 0;
-  }
-  return RH_E_BADARG;
 }
 
 extern "C" int rh_dice_nblocks(int64_t N) { return (int)dice_grid(N); }

@@ -387,8 +387,6 @@ struct EmbedBwdArgs {
   float* rows_out;
   const float* rows_in;
   int spb;
-  int wide_atomics;
-  int path;  // experiment knob: 0 auto, 1 global atomics for every table, 3 no sink, 4 chunk-fastest block order
   int nchunks8;  // sample chunks rounded up to a multiple of 8
   int* err;
 };
@@ -401,7 +399,7 @@ constexpr int kSweeps = 2;  // phase-B sweeps of the small-table path: covers kS
 // batch size, 21.9 / 47.0 / 159 us against 11.9 / 30.2 / 103 us: removed, DESIGN 3.2 keeps the numbers.)
 //
 // Small tables (Criteo has vocab 3, 4, 10, 15, 18, 24, 27, 105): every lookup of the batch lands on a few rows, and what
-// is expensive on MI355X is contention, measured at B = 65536 (tools/bwd_field_probe.py):
+// is expensive on MI355X is contention, measured at B = 65536 (round 2):
 //   * device-scope atomics on ONE cache line serialise at ~11 ns per request (a 3-row table: 1 ms; 105 rows: +9 us);
 //   * LDS float atomics (ds_add_f32) retire at ~5 cycles per LANE, conflict-free or not (the 9 tables of <= 512 rows
 //     LDS-aggregated: 126 us; with 16 private copies: 84 us);
@@ -431,18 +429,13 @@ __global__ __launch_bounds__(RH_BLOCK) void embed_bwd_kernel(const EmbedBwdArgs 
   // Block -> (sample chunk, field).  The blocks that read the SAME rows of g_out / emb / s_sum (one chunk, all fields:
   // adjacent 64-byte pieces of the same 1.7 KB rows) are made neighbours on ONE XCD (block id % 8 = XCD, measured
   // placement): they run at the same time and share the XCD's L2 lines, instead of each fetching a piece of every
-  // line on its own.  a.path == 4 keeps the plain chunk-fastest order for comparison.
+  // line on its own.
   int f, chunk;
   {
     const int L = blockIdx.x, F_ = a.F;
-    if (a.path == 4) {
-      chunk = L % a.nchunks8;
-      f = L / a.nchunks8;
-    } else {
-      const int xcd = L & 7, within = L >> 3;
-      f = within % F_;
-      chunk = (within / F_) * 8 + xcd;
-    }
+    const int xcd = L & 7, within = L >> 3;
+    f = within % F_;
+    chunk = (within / F_) * 8 + xcd;
   }
   if ((int64_t)chunk * a.spb >= (int64_t)a.B) return;  // padding block (chunk count rounded up to the 8 XCDs)
   const int tid = threadIdx.x;
@@ -460,7 +453,7 @@ __global__ __launch_bounds__(RH_BLOCK) void embed_bwd_kernel(const EmbedBwdArgs 
   constexpr int RG = kSmallOk ? RH_WAVE / (4 * LPR) : 1;  // row groups of phase B
   constexpr int NL = LPP * U;                            // lookups per pass
   constexpr int RPS = (RH_BLOCK / RH_WAVE) * RG;         // rows per phase-B sweep
-  const bool small = kSmallOk && has_tab && a.path != 1 && vocab <= (int64_t)kSweeps * RPS;  // block-uniform
+  const bool small = kSmallOk && has_tab && vocab <= (int64_t)kSweeps * RPS;  // block-uniform
   float* park = lds;                                                 // [NL][D] gradient rows of the pass
   int* park_row = reinterpret_cast<int*>(lds + NL * 4 * LPR);       // [NL] row id, -1 = dead lookup
   float acc[kSweeps];
@@ -517,18 +510,12 @@ __global__ __launch_bounds__(RH_BLOCK) void embed_bwd_kernel(const EmbedBwdArgs 
       } else {
         const bool oob = (uint64_t)row[u] >= (uint64_t)vocab;
         oob_any |= (oob && ok[u]);
-        const bool live = ok[u] && has_tab && !oob && row[u] != pad && a.path != 3;
+        const bool live = ok[u] && has_tab && !oob && row[u] != pad;
         if (kSmallOk && small) {
           const int j = u * LPP + slot;
           *reinterpret_cast<float4*>(park + j * (4 * LPR) + q * 4) = gr;
           if (q == 0) park_row[j] = live ? (int)row[u] : -1;
-        } else if (a.path == 6) {
-          // TIMING ONLY (tools/bwd_ceiling_probe.py; wrong sums when two lookups meet on a row): the cheapest scatter there
-          // is -- one plain 16-byte store per lane, a whole 64-byte row per LPR lanes, no re-layout, no read-modify-write.
-          // The ceiling of ANY scheme that writes each lookup's row once (sorted / segmented reductions included: with
-          // uniform indices over 10 M-row tables a batch holds next to no duplicate to merge).
-          if (live) gstore<float4>(gtab + row[u] * D + q * 4, gr);
-        } else if (a.wide_atomics) {
+        } else {
           // Re-lay the wavefront's 256 gradient floats (64/LPR rows x 4*LPR dwords) so that one atomic
           // instruction carries WHOLE rows: 4 requests of 64 contiguous dwords instead of 4 requests that each
           // touch a quarter of every row.  Device-scope float atomics are memory-side RMWs on MI355X: their cost
@@ -547,15 +534,15 @@ __global__ __launch_bounds__(RH_BLOCK) void embed_bwd_kernel(const EmbedBwdArgs 
             const int c = dw & 3;
             const float val = c == 0 ? vx : (c == 1 ? vy : (c == 2 ? vz : vw));
             const int head = rsl * LPR;
-            const int64_t r = ((int64_t)__shfl(row_hi, head, RH_WAVE) << 32) | (uint32_t)__shfl(row_lo, head, RH_WAVE);
-            const int flag = __shfl((int)live, head, RH_WAVE);
-            if (flag) {
-              if (a.path == 5) gstore<float>(gtab + r * DD + dw, val);  // TIMING ONLY: the same requests as plain stores
-              else gatomic_add_f32(gtab + r * DD + dw, val);
-            }
+            // the row's head lane: with rows of >= 64 dwords it is the same for the whole wavefront (a scalar read)
+            auto from_head = [&](int x) {
+              if constexpr (DD >= RH_WAVE) return __builtin_amdgcn_readlane(x, head);
+              else return __shfl(x, head, RH_WAVE);
+            };
+            const int64_t r = ((int64_t)from_head(row_hi) << 32) | (uint32_t)from_head(row_lo);
+            const int flag = from_head((int)live);
+            if (flag) gatomic_add_f32(gtab + r * DD + dw, val);
           }
-        } else if (live) {
-          gatomic_add_f4(gtab + row[u] * D + q * 4, gr);
         }
       }
     }
@@ -603,17 +590,9 @@ __global__ __launch_bounds__(RH_BLOCK) void embed_bwd_kernel(const EmbedBwdArgs 
   if (oob_any && a.err != nullptr) atomicOr(a.err, RH_FLAG_INDEX_OOB);
 }
 
-int g_bwd_path = 0;        // tuning knob RH_TUNE_BWD_PATH (experiments)
-
-int g_wide_atomics = 1;  // tuning knob RH_TUNE_WIDE_ATOMICS (rh_set_tuning / RECHUB_TUNE=1=0), default on
-
-int wide_atomics_default() { return g_wide_atomics; }
-
 template <int LPR, typename IdxT, int SRC, int SINK>
 int launch_bwd(EmbedBwdArgs a, hipStream_t s) {
   const unsigned gx = (unsigned)((a.B + a.spb - 1) / a.spb);
-  a.wide_atomics = wide_atomics_default();
-  a.path = g_bwd_path;
   // parked gradient rows of one pass (16 KiB) + their row ids
   const size_t shmem = (SINK != 1) ? (size_t)(RH_BLOCK * 4 * 4 + (RH_BLOCK / LPR) * 4) * sizeof(float) : 0;
   a.nchunks8 = (int)((gx + 7) / 8 * 8);
@@ -705,7 +684,7 @@ extern "C" int rh_embed_bwd(const int64_t* fdesc, const int64_t* idesc, int idx_
              "rh_embed_bwd: lr_wgrad needs emb and g_lr");
   if (B == 0) return 0;
   EmbedBwdArgs a{fdesc, idesc, B, F, D, g_out, g_stride, emb, emb_stride, s_sum, g_fm, g_lr, lr_w,
-                 lr_wgrad, scale, rows_out, nullptr, pick_spb(samples_per_block), 0, 0, 0, err_flag};
+                 lr_wgrad, scale, rows_out, nullptr, pick_spb(samples_per_block), 0, err_flag};
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   int rc;
   if (sink == 0)
@@ -718,22 +697,13 @@ extern "C" int rh_embed_bwd(const int64_t* fdesc, const int64_t* idesc, int idx_
 }
 
 extern "C" int rh_set_tuning(int key, int value) {
-  if (key == RH_TUNE_WIDE_ATOMICS) {
-    g_wide_atomics = value != 0;
-    return 0;
-  }
-  if (key == RH_TUNE_BWD_PATH) {
-    g_bwd_path = value;
-    return 0;
-  }
   if (key == RH_TUNE_FWD_PATH) {
+    RH_REQUIRE(value >= 0 && value <= 2, RH_E_BADARG, "rh_set_tuning: RH_TUNE_FWD_PATH takes 0, 1 or 2, not %d", value);
     g_fwd_path = value;
     return 0;
   }
-  if (key == RH_TUNE_BWD_SPLIT || key == RH_TUNE_BWD_SLABS) return 0;  // retired knobs (kept so old probes still run)
   if (rh_optim_set_tuning(key, value) == 0) return 0;
   if (rh_linear_set_tuning(key, value) == 0) return 0;
-  if (rh_din_set_tuning(key, value) == 0) return 0;
   rh_set_error("rh_set_tuning: unknown key %d", key);
   return RH_E_BADARG;
 }
@@ -750,7 +720,7 @@ extern "C" int rh_embed_scatter_rows(const int64_t* fdesc, const int64_t* idesc,
   RH_REQUIRE(rows != nullptr, RH_E_BADARG, "rh_embed_scatter_rows: rows is null");
   if (B == 0) return 0;
   EmbedBwdArgs a{fdesc, idesc, B, F, D, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
-                 nullptr, scale, nullptr, rows, pick_spb(samples_per_block), 0, 0, 0, err_flag};
+                 nullptr, scale, nullptr, rows, pick_spb(samples_per_block), 0, err_flag};
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   int rc = idx_is_i64 ? dispatch_bwd<int64_t, 1, 0>(a, s) : dispatch_bwd<int32_t, 1, 0>(a, s);
   if (rc != 0) return rc;

@@ -31,18 +31,13 @@ __global__ __launch_bounds__(RH_BLOCK) void linear_wgrad_kernel(const WgradArgs 
   linear_wgrad_body<false>(a, red, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
-__global__ __launch_bounds__(RH_BLOCK) void linear_wgrad_group_kernel(const WgradGroupArgs ga) {
-  extern __shared__ float red[];
-  linear_wgrad_group_body<false>(ga, red, (int)blockIdx.x);
-}
-
 __global__ __launch_bounds__(RH_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))) void linear_wgrad_long_kernel(
     const WgradArgs a) {
   extern __shared__ float red[];  // kPartStride floats: the block's tile + its db slice
   linear_wgrad_body<true>(a, red, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
-// (the grouped launch in the 128-register build: RH_TUNE_WGRAD_SHORT_FORM = 1, the default)
+// (the grouped launch, batch-sized reductions: the 128-register build only -- see wgrad_impl)
 __global__ __launch_bounds__(RH_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))) void linear_wgrad_group_long_kernel(
     const WgradGroupArgs ga) {
   extern __shared__ float red[];
@@ -191,21 +186,18 @@ __global__ __launch_bounds__(RH_BLOCK) void wgrad_reduce_kernel(const WgradArgs 
 // wavefronts to cover the latency of the operand loads (tuning knob RH_TUNE_WGRAD_BLOCKS).
 int g_long_blocks = 1024;   // negative: -value workgroups with the default build of the kernel (A/B)
 constexpr int kLongRows = 32768;
-// RH_TUNE_WGRAD_SHORT_FORM: build used for batch-sized reductions (B < 32768).  0: the round-1 form (78 VGPRs + 128 AGPRs,
-// four LDS tiles); 1: the 128-register, one-LDS-tile build of the long reductions.  Beside the optimizer's resident sweep
-// (2 wavefronts of 112 registers per SIMD) only ONE wavefront of the 206-register build fits on a SIMD where the launch's
-// ~500 workgroups want two: measured 28.5 us alone, 39.5 us beside the sweep (round 4).  Default 1 since the relaxed join
-// (optim.py) took the sweep off the step's critical cycle: 0.2622 -> 0.2580 ms per step (same box, two rounds); while the
-// sweep's path was the longer one the two builds tied.
-int g_short_form = 1;
-// RH_TUNE_WGRAD_ROWS_FORM: long reductions of at most kRowsMaxTiles tiles as ONE workgroup per row split (linear_wgrad_rows_kernel);
-// value = the workgroups aimed for (default 512: two 512-thread workgroups per CU), 0 = the tile-per-workgroup form.
-int g_rows_form = 512;
-int g_rows_pair = 1;  // (RH_TUNE_WGRAD_ROWS_FORM given negative: -value workgroups, one tile per wavefront)
+// Batch-sized reductions (B < 32768) take the 128-register, one-LDS-tile build of the long reductions, not the round-1 form
+// (78 VGPRs + 128 AGPRs, four LDS tiles).  Beside the optimizer's resident sweep (2 wavefronts of 112 registers per SIMD) only
+// ONE wavefront of the 206-register build fits on a SIMD where the launch's ~500 workgroups want two: measured 28.5 us alone,
+// 39.5 us beside the sweep (round 4); 0.2622 -> 0.2580 ms per step since the relaxed join (optim.py) took the sweep off the
+// step's critical cycle (same box, two rounds); while the sweep's path was the longer one the two builds tied.
+// Long reductions of at most kRowsMaxTiles tiles run as ONE workgroup per row split (linear_wgrad_rows_kernel).
+// kRowsForm is the number of workgroups that form aims for: 512, two 512-thread workgroups per CU.
+constexpr int kRowsForm = 512;
 
 static bool wgrad_rows_form(int B, int N, int K) {
   const int tiles = ((N + kTile - 1) / kTile) * ((K + kTile - 1) / kTile);
-  return g_rows_form > 0 && g_long_blocks > 0 && B >= kLongRows && tiles >= 2 && tiles <= kRowsMaxTiles;
+  return g_long_blocks > 0 && B >= kLongRows && tiles >= 2 && tiles <= kRowsMaxTiles;
 }
 
 void wgrad_plan(int B, int N, int K, int* tiles_n, int* tiles_k, int* S, int* rps) {
@@ -213,13 +205,13 @@ void wgrad_plan(int B, int N, int K, int* tiles_n, int* tiles_k, int* S, int* rp
   *tiles_k = (K + kTile - 1) / kTile;
   const int tiles = *tiles_n * *tiles_k;
   if (wgrad_rows_form(B, N, K)) {
-    // g_rows_form workgroups of 8 wavefronts = 4 x g_rows_form wavefronts (8 per CU at the default, two per SIMD: what the
+    // kRowsForm workgroups of 8 wavefronts = 4 x kRowsForm wavefronts (8 per CU, two per SIMD: what the
     // paired-tile builds' ~220 registers allow); a slab of fewer wavefronts is split further to keep that many in flight
     // ((256, 64) as two wavefronts of 128 x 64: 1024 splits -- with 512 its launch took 228 us alone for 160)
-    const bool pair = g_rows_pair && (*tiles_k % 2 == 0 || *tiles_n % 2 == 0);
+    const bool pair = *tiles_k % 2 == 0 || *tiles_n % 2 == 0;
     const int waves = pair ? tiles / 2 : tiles;
-    int s = g_rows_form * kRowsMaxTiles / (2 * waves);
-    if (s < g_rows_form) s = g_rows_form;
+    int s = kRowsForm * kRowsMaxTiles / (2 * waves);
+    if (s < kRowsForm) s = kRowsForm;
     const int max_s = (B + 255) / 256;
     if (s > max_s) s = max_s;
     int r = (B + s - 1) / s;
@@ -813,7 +805,7 @@ static int wgrad_impl(const float* g, int64_t ldg, const float* x, int64_t ldx, 
   int tn, tk;
   wgrad_plan(B, N, K, &tn, &tk, &a.S, &a.rows_per_split);
   a.direct = (reduce && a.S == 1) ? 1 : 0;
-  const bool long_form = (B >= kLongRows && g_long_blocks > 0) || (B < kLongRows && g_short_form == 1);
+  const bool long_form = B < kLongRows || g_long_blocks > 0;
   const size_t lds = (size_t)(long_form ? 1 : kWaves) * kPartStride * sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
@@ -824,10 +816,10 @@ static int wgrad_impl(const float* g, int64_t ldg, const float* x, int64_t ldx, 
   }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (wgrad_rows_form(B, N, K)) {
-    // two tiles per wavefront along K when the K tiles pair up, else along N (RH_TUNE_WGRAD_ROWS_FORM < 0: one per wavefront)
-    if (g_rows_pair && tk % 2 == 0)
+    // two tiles per wavefront along K when the K tiles pair up, else along N
+    if (tk % 2 == 0)
       hipLaunchKernelGGL((linear_wgrad_rows_kernel<1, 2>), dim3(a.S), dim3(RH_WAVE * tn * (tk / 2)), 0, st, a, tk / 2);
-    else if (g_rows_pair && tn % 2 == 0)
+    else if (tn % 2 == 0)
       hipLaunchKernelGGL((linear_wgrad_rows_kernel<2, 1>), dim3(a.S), dim3(RH_WAVE * (tn / 2) * tk), 0, st, a, tk);
     else
       hipLaunchKernelGGL((linear_wgrad_rows_kernel<1, 1>), dim3(a.S), dim3(RH_WAVE * tn * tk), 0, st, a, tk);
@@ -876,19 +868,8 @@ extern "C" int rh_linear_wgrad_partial_group(int n, const float* const* g, const
   WgradGroupArgs ga;
   const int rc = rh_wgrad_group_fill(n, g, ldg, x, ldx, B, N, K, partial, &ga, "rh_linear_wgrad_partial_group");
   if (rc != 0) return rc;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(linear_wgrad_group_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kWaves * kPartStride * sizeof(float)));
-    RH_REQUIRE(e == hipSuccess, (int)e, "rh_linear_wgrad_partial_group: cannot reserve LDS: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
-  if (g_short_form == 1)
-    hipLaunchKernelGGL(linear_wgrad_group_long_kernel, dim3((unsigned)ga.prefix[n]), dim3(RH_BLOCK),
-                       (size_t)kPartStride * sizeof(float), reinterpret_cast<hipStream_t>(stream), ga);
-  else
-    hipLaunchKernelGGL(linear_wgrad_group_kernel, dim3((unsigned)ga.prefix[n]), dim3(RH_BLOCK),
-                       (size_t)kWaves * kPartStride * sizeof(float), reinterpret_cast<hipStream_t>(stream), ga);
+  hipLaunchKernelGGL(linear_wgrad_group_long_kernel, dim3((unsigned)ga.prefix[n]), dim3(RH_BLOCK),
+                     (size_t)kPartStride * sizeof(float), reinterpret_cast<hipStream_t>(stream), ga);
   RH_LAUNCH_CHECK("rh_linear_wgrad_partial_group");
   return 0;
 }
@@ -896,15 +877,6 @@ extern "C" int rh_linear_wgrad_partial_group(int n, const float* const* g, const
 extern "C" int rh_linear_set_tuning(int key, int value) {
   if (key == RH_TUNE_WGRAD_BLOCKS) {
     g_long_blocks = value;
-    return 0;
-  }
-  if (key == RH_TUNE_WGRAD_SHORT_FORM) {
-    g_short_form = value;
-    return 0;
-  }
-  if (key == RH_TUNE_WGRAD_ROWS_FORM) {
-    g_rows_form = value < 0 ? -value : value;
-    g_rows_pair = value < 0 ? 0 : 1;
     return 0;
   }
   return RH_E_BADARG;

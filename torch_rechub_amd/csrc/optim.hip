@@ -843,7 +843,6 @@ struct StepAheadParts {
   int spbA;
   int nC, chunksC;  // part C: chunksC x F workgroups of `look` samples
   int nD;           // part D
-  int w_order;      // adam_lazy_step_ahead_wgrad_kernel: how part W is dealt among the others (RH_TUNE_WGRAD_RIDER_ORDER)
   // rh_adam_lazy_step_ahead_touched (round 6, data parallel): part A walks BA rows of another index matrix -- the GATHERED
   // lookups of every rank's batch, columns idescA -- instead of the batch at dataset positions pos - B .. (BA = 0)
   const int64_t* idescA;
@@ -924,38 +923,17 @@ __global__ __launch_bounds__(RH_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))
   const int nW = ga.prefix[rh_wgrad::kWgradGroup];
   const int nrest = (int)gridDim.x - nW;
   // Workgroup order (beside the optimizer's resident sweep a SIMD has room for two wavefronts of this launch).  Measured, same
-  // box, ms per step (profiles/r06_ab_wgrad_rider.txt): no rider 0.2418; W in front of the other parts (w_order 0) 0.2315; dealt
-  // alternately with them (1: pair p = (W[p], rest[p]), the order inside a pair flipping every 256 workgroups) 0.2378; W
-  // BEHIND them (2, the default) 0.2268 -- the refresh part's workgroups run longest (a replay of up to lazy_k steps per row)
+  // box, ms per step (profiles/r06_ab_wgrad_rider.txt): no rider 0.2418; W in front of the other parts 0.2315; dealt
+  // alternately with them (pair p = (W[p], rest[p]), the order inside a pair flipping every 256 workgroups) 0.2378; W
+  // BEHIND them (what is built) 0.2268 -- the refresh part's workgroups run longest (a replay of up to lazy_k steps per row)
   // and want to be placed first; the short MFMA workgroups then fill the launch's tail.
-  int bx = (int)blockIdx.x;
-  bool is_w;
-  int idx;
-  if (parts.w_order == 1) {
-    const int m = nW < nrest ? nW : nrest;
-    if (bx < 2 * m) {
-      is_w = (((bx & 1) ^ ((bx >> 8) & 1)) == 0);
-      idx = bx >> 1;
-    } else {
-      is_w = nW > nrest;
-      idx = bx - m;
-    }
-  } else if (parts.w_order == 2) {
-    is_w = bx >= nrest;
-    idx = is_w ? bx - nrest : bx;
-  } else {
-    is_w = bx < nW;
-    idx = is_w ? bx : bx - nW;
-  }
-  if (is_w) {
-    rh_wgrad::linear_wgrad_group_body<true>(ga, wred, idx);
+  const int bx = (int)blockIdx.x;
+  if (bx >= nrest) {
+    rh_wgrad::linear_wgrad_group_body<true>(ga, wred, bx - nrest);
     return;
   }
-  step_ahead_body<LPR>(a, parts, idx, nrest);
+  step_ahead_body<LPR>(a, parts, bx, nrest);
 }
-
-int g_rider_order = 2;  // RH_TUNE_WGRAD_RIDER_ORDER: workgroup order of adam_lazy_step_ahead_wgrad_kernel (see there)
-int g_sweep_wide = 2;  // RH_TUNE_SWEEP_WIDE: float4 per lane of the deferred lazy-table sweep at embed_dim >= 8 (2 = default; 1 = round-4 kernel)
 
 // the deferred window sweep of the lazy tables, VPL float4 per lane (lazy_sweep_wide_body)
 template <int LPR, int VPL>
@@ -986,7 +964,7 @@ int launch_sweep(LazySweepArgs& a, int mode, const int64_t* h_rows, const int64_
   // (four float4 per lane, measured in round 5: 148 registers -- two such wavefronts leave a SIMD no room for the chain's
   // 235-register GEMM prologue -- 0.2696 ms per step against 0.2408; not built)
   if constexpr (LPR >= 2) {
-    if (mode == RH_SWEEP_LAZY_TABLES && a.t_value >= 0 && touch == nullptr && g_sweep_wide >= 2)
+    if (mode == RH_SWEEP_LAZY_TABLES && a.t_value >= 0 && touch == nullptr)
       return launch_sweep_wide<LPR / 2, 2>(a, h_rows, h_window, s);
   }
   a.vb_prefix[0] = 0;
@@ -1272,14 +1250,6 @@ extern "C" int rh_optim_set_tuning(int key, int value) {
   }
   if (key == RH_TUNE_SWEEP_GATE_NS) {
     g_gate_ns = value;
-    return 0;
-  }
-  if (key == RH_TUNE_SWEEP_WIDE) {
-    g_sweep_wide = value;
-    return 0;
-  }
-  if (key == RH_TUNE_WGRAD_RIDER_ORDER) {
-    g_rider_order = value;
     return 0;
   }
   return RH_E_BADARG;
@@ -1708,7 +1678,6 @@ static int step_ahead_impl(const int64_t* ldesc, int T, const int64_t* h_rows, c
   parts.chunksC = (look_depth * B + look - 1) / look;
   parts.nC = parts.chunksC * F;
   parts.nD = parts.chunksB;
-  parts.w_order = g_rider_order;
   int64_t sweep_grid = a.total_vblocks;
   const int64_t cap = g_sweep_grid > 0 ? g_sweep_grid : 256 * 32;
   if (sweep_grid > cap) sweep_grid = cap;

@@ -23,19 +23,12 @@ from . import _lib, graphs, ops
 # rh_adam_lazy_sweep modes
 SWEEP_WINDOW, SWEEP_FLUSH = _lib.H.RH_SWEEP_WINDOW, _lib.H.RH_SWEEP_FLUSH
 SWEEP_LAZY_TABLES, SWEEP_DENSE_TABLES = _lib.H.RH_SWEEP_LAZY_TABLES, _lib.H.RH_SWEEP_DENSE_TABLES
-EAGER_HEAD = _lib.ab("eagerhead")  # False (RECHUB_AB=eagerhead=0): the one-kernel head stays a captured graph segment
-ASSEMBLE_WITH_REFRESH = _lib.ab("assemble")  # False (RECHUB_AB=assemble=0): rh_batch_gather and the refresh as two launches
 RELAXED_JOIN = _lib.ab("lookahead")  # False (RECHUB_AB=lookahead=0): the eager head on the sweep's queue, strict join (below)
-TOUCH_GROUP = _lib.ab("touchgroup")  # False (RECHUB_AB=touchgroup=0): one touched-rows launch per gather of a step with several
-MERGE_I32 = _lib.ab("mergei32")  # False (RECHUB_AB=mergei32=0): int32 index batches keep the touched pass and the dense tables' step apart
 DP_MERGED_TAIL = _lib.ab("dptail")  # False (RECHUB_AB=dptail=0): head_behind's touched pass and next refresh as two launches
 GATED_FORK = _lib.ab("gatedfork")  # False (RECHUB_AB=gatedfork=0): a head on the chain's queue forks its sweep at a segment boundary
 DP_HEAD_BEHIND = _lib.ab("dpbehind")  # False (RECHUB_AB=dpbehind=0): the data-parallel strict head stays an eager launch in front of the graph
 STEP_AHEAD = _lib.ab("ahead")  # False (RECHUB_AB=ahead=0): the head stays an eager launch in front of every replay
-CHAIN_GATE = _lib.ab("chaingate")  # False (RECHUB_AB=chaingate=0): the sweep is released RH_TUNE_SWEEP_GATE_NS behind the opening (round 4)
-HOST_DONE = _lib.ab("hostdone")  # False (RECHUB_AB=hostdone=0): an event record behind every deferred sweep instead of the gates' host-mapped count
 WGRAD_RIDER = _lib.ab("wgradrider")  # False (RECHUB_AB=wgradrider=0): the chain's grouped weight gradients stay a launch of the backward
-LATE_PACK = _lib.ab("latepack")  # False (RECHUB_AB=latepack=0): the gate is opened by a one-lane launch of its own
 GATE_FALLBACK_NS = 50000  # step-ahead form with a chain-start count in the graph: release of a sweep no chain start follows (ns)
 LOOK_DEPTH = 2  # step-ahead form: batches beyond the next one whose lookups in the coming sweep's window are refreshed early
 
@@ -140,7 +133,7 @@ class TableAdam(torch.optim.Adam):
                 # branch of the step's graph: 0.312 ms), external-event nodes (1.66 ms), CU-masked streams (0.350 ms), the
                 # row-list table gradient (backward 159 vs 103 us at B = 65536).
                 self.overlap_sweep = os.environ.get("RECHUB_STEP_FORM", "deferred") != "inline"
-                self.head_on_side = _lib.ab("headside")
+                self.head_on_side = True  # (the trainers put the head back on the chain's queue where the step joins its sweep inside)
                 self._head_event = None
                 self._sweep_events = None   # relaxed join: the ends of the sweeps launched by the last two heads
                 self._look_token = None     # relaxed join: (graph, loader generation, step) the last head looked ahead for
@@ -284,7 +277,7 @@ class TableAdam(torch.optim.Adam):
         """``_touch`` for several gathers of one step: ONE launch (rh_adam_lazy_touched_group) when they all belong to the same
         table group, one launch each otherwise."""
         recs = list(recs)
-        if TOUCH_GROUP and 2 <= len(recs) <= 4 and len(groups) >= 1:
+        if 2 <= len(recs) <= 4 and len(groups) >= 1:
             owner = []
             for rec in recs:
                 mine = [g for g in groups if g["D"] == rec["D"] and any(id(w) in g["local"] for w in rec["weights"])]
@@ -390,7 +383,7 @@ class TableAdam(torch.optim.Adam):
         ``strict``: only the strict eager head (round 6, replicated tables under data parallelism: the sweep is joined in front
         of the touched pass over the gathered rows in every step, so neither the relaxed join's preview nor the step-ahead
         launch -- both protect the LOCAL batch's rows only -- has anything to win or the right to run)."""
-        if self.lazy_k <= 1 or not self._tables or not ASSEMBLE_WITH_REFRESH or not self._k_decided:
+        if self.lazy_k <= 1 or not self._tables or not self._k_decided:
             return False
         if ops.chain_gate is self._gate:
             ops.chain_gate = None  # (a capture that was abandoned between its head and its last launch)
@@ -424,7 +417,7 @@ class TableAdam(torch.optim.Adam):
                  ops._p(self._t_hyper), ops._p(self._t_ring), self.RING, 64, ops._p(ops.err_flag(self._tables[0].device)),
                  ops._p(a["perm"]), ops._p(a["pos"]), a["N"], ops._p(a["sparse"]), a["F"], ops._p(a["dense"]), a["ND"],
                  ops._p(a["label"]), ops._p(a["sparse_out"]), ops._p(a["dense_out"]), ops._p(a["label_out"]))
-        if capturing and seg is not None and self.overlap_sweep and self.head_on_side and EAGER_HEAD and \
+        if capturing and seg is not None and self.overlap_sweep and self.head_on_side and \
                 len(seg.segments) == 1 and self._join_seg is not seg:
             # The head of the step is now ONE kernel: it is not captured at all.  Every replay launches it eagerly on the
             # sweep's queue -- [wait for the previous chain] head -> event -> sweep -- in front of the ONE graph that holds
@@ -561,7 +554,7 @@ class TableAdam(torch.optim.Adam):
                 seg.after(tail_behind)
                 self._advance_seg = seg  # (step_tables: tail_behind counts the replayed steps)
                 self._dp_tail_head = dict(seg=seg, cargs=cargs, keep=keep, rec=rec, grp=grp, ft=ft, a=a)
-                ops.chain_gate = self._gate if CHAIN_GATE else None  # (the first own GEMM captured into this graph counts the chain start)
+                ops.chain_gate = self._gate  # (the first own GEMM captured into this graph counts the chain start)
                 del ops.chain_gate_used[:]
             elif strict:
                 seg.at_start(head)
@@ -572,7 +565,7 @@ class TableAdam(torch.optim.Adam):
                 self._step_ahead = dict(seg=seg, rec=rec, grp=grp, ft=ft, a=a)
                 # the first own GEMM captured into this graph counts the chain start that releases the sweep (round 5: a
                 # dependency instead of round 4's wall-clock hold-back behind the opening; ops._MlpChainFn, csrc/gemm.hip)
-                ops.chain_gate = self._gate if CHAIN_GATE else None
+                ops.chain_gate = self._gate
                 del ops.chain_gate_used[:]
                 # ... and the chain's grouped weight gradients ride in this graph's last table launch (round 6)
                 ops.wgrad_rider = self._ride_wgrad if WGRAD_RIDER else None
@@ -660,7 +653,6 @@ class TableAdam(torch.optim.Adam):
     # sweep's own stream: batch assembly -> refresh -> sweep are consecutive kernels of one queue (no event in between; the
     # previous sweep is in front of them on that queue, which IS the join), and it is the chain on the main stream that waits
     # for the event recorded behind the refresh.  The cross-queue latency moves from the longer path to the shorter one.
-    # (A/B: RECHUB_AB=headside=0.)
     def _head_begin(self):
         """at_start of a segmented replay: the head segment (on the side stream) follows the previous step's chain."""
         if self._side is None:
@@ -695,7 +687,7 @@ class TableAdam(torch.optim.Adam):
                 # nobody opens gives up after its timeout).  Same order on the device: refresh -> sweep -> (join in front
                 # of the next replay).
                 _lib.call("rh_adam_sweep_gate_open", ops._p(self._gate), ops._stream())
-                ops.chain_gate = self._gate if CHAIN_GATE else None
+                ops.chain_gate = self._gate
                 del ops.chain_gate_used[:]
                 self._gated_fork_seg = seg
                 if self._fork_sweep_gated not in seg.after_fns:
@@ -764,14 +756,14 @@ class TableAdam(torch.optim.Adam):
         rec, grp = self._touch_log[0], groups[0]
         # (int32 index columns -- the row-sharded step's localised indices -- take the merged launch too since round 6,
         # rh_adam_lazy_step_mode_idx; the step-ahead launches read int64 indices from the dataset and check for themselves)
-        return not (grp["D"] != rec["D"] or not (rec["idx_is_i64"] or MERGE_I32) or rec["B"] < 1 or
+        return not (grp["D"] != rec["D"] or rec["B"] < 1 or
                     not any(id(w) in grp["local"] for w in rec["weights"]))
 
     def gate_for_late_pack(self):
         """Called by the trainer where it would launch the dense gradients' packing + Adam: while the step-ahead graph is
         being captured, returns the gate the packing launch shall open -- the trainer then launches it BEHIND step() -- else None."""
         ah = getattr(self, "_step_ahead", None)
-        if ah is None or graphs.active() is not ah["seg"] or not torch.cuda.is_current_stream_capturing() or not LATE_PACK:
+        if ah is None or graphs.active() is not ah["seg"] or not torch.cuda.is_current_stream_capturing():
             return None
         self._gate_by_pack = True
         return self._gate
@@ -782,14 +774,13 @@ class TableAdam(torch.optim.Adam):
         """The host-mapped word in which the sweep gates of the step-ahead form count the finished sweeps, or None."""
         if self._sweep_done is None:
             self._sweep_done = False
-            if HOST_DONE:
-                try:
-                    host = torch.zeros(1, dtype=torch.int64).pin_memory()
-                    dev = ctypes.c_void_p()
-                    _lib.call("rh_host_device_pointer", ctypes.c_void_p(host.data_ptr()), ctypes.byref(dev))
-                    self._sweep_done = (host, dev)
-                except RuntimeError:
-                    self._sweep_done = False
+            try:
+                host = torch.zeros(1, dtype=torch.int64).pin_memory()
+                dev = ctypes.c_void_p()
+                _lib.call("rh_host_device_pointer", ctypes.c_void_p(host.data_ptr()), ctypes.byref(dev))
+                self._sweep_done = (host, dev)
+            except RuntimeError:
+                self._sweep_done = False
         return self._sweep_done or None
 
     @staticmethod
@@ -895,7 +886,7 @@ class TableAdam(torch.optim.Adam):
     # per step.  Below ~200 M lazy elements the deferred sweep no longer pays for its segment boundary and cross-queue edge --
     # the window sweep goes back in line (the merged end-of-step launch) and an automatic lazy_k drops to 64 (a shorter
     # replay per refreshed row; the short sweep's traffic does not matter).  Measured per-rank step of the DeepFM headline on a
-    # one-rank group with every table at 1/2, 1/4, 1/8 of its rows (tools/r05_session{3,4}.sh, profiles/r05_dp_shard_form.txt):
+    # one-rank group with every table at 1/2, 1/4, 1/8 of its rows (round 5, profiles/r05_dp_shard_form.txt):
     #   1/2 (270 M elements): deferred K = 128 / 64 0.326 / 0.322 ms, in line K = 128 / 64 0.332 / 0.324  -> left deferred
     #   1/4 (135 M):          deferred 0.325 / 0.315,                 in line 0.300 / 0.289
     #   1/8 ( 68 M):          deferred 0.313,                          in line 0.282 / 0.269 (K = 32: 0.267, K = 16: 0.272)
