@@ -673,10 +673,13 @@ def test_adam_lazy_rows_lag_at_most_k_steps():
     assert int(lag.min()) >= 0 and int(lag.max()) < 8
 
 
-@pytest.mark.parametrize("B,C,p", [(4096, 256, 0.0), (4096, 128, 0.0), (37, 32, 0.0), (1000, 200, 0.0), (513, 16, 0.0),
-                                   (8192, 64, 0.0), (2, 8, 0.0), (20000, 64, 0.0), (1000, 30, 0.0)])
-def test_bn_relu_dropout_vs_torch_modules(B, C, p):
-    """Fused epilogue == nn.BatchNorm1d -> ReLU -> Dropout(p=0) (outputs, running stats, all gradients) and eval mode."""
+_BN_RELU_SHAPES = [(4096, 256), (4096, 128), (37, 32), (1000, 200), (513, 16), (8192, 64), (2, 8), (20000, 64), (1000, 30)]
+
+
+@pytest.mark.parametrize("B,C", _BN_RELU_SHAPES, ids=[f"{B}-{C}-0.0" for B, C in _BN_RELU_SHAPES])  # (the ids it always had)
+def test_bn_relu_dropout_vs_torch_modules(B, C):
+    """Fused epilogue == nn.BatchNorm1d -> ReLU -> Dropout(p=0) (outputs, running stats, all gradients) and eval mode.
+    p > 0 against a float64 reference with a host-side mask: tests/test_gpu_mlp_dropout_oracle.py."""
     from torch_rechub_amd import ops
     torch.manual_seed(B + C)
     h0 = (torch.randn(B, C) * 2 + torch.randn(C) * 3).to(dev())
@@ -691,7 +694,7 @@ def test_bn_relu_dropout_vs_torch_modules(B, C, p):
     ya = torch.relu(bn_ref(ha))
     ya.backward(gy)
     hb = h0.clone().requires_grad_(True)
-    yb = ops.bn_relu_dropout(hb, bn_mine, p)
+    yb = ops.bn_relu_dropout(hb, bn_mine, 0.0)
     yb.backward(gy)
     close(yb, ya.detach().cpu().numpy(), rtol=2e-5, atol_scale=2e-6, what="bn out")
     close(hb.grad, ha.grad.cpu().numpy(), rtol=1e-4, atol_scale=1e-5, what="bn dx")

@@ -1277,6 +1277,24 @@ def _col(t, B):
     return t.reshape(B).contiguous()
 
 
+def _leaf_extra(*extras):
+    """Is one of the head's extra terms a leaf that wants a gradient?  (see _extra_grads)"""
+    return any(e is not None and e.requires_grad and e.grad_fn is None for e in extras)
+
+
+def _extra_grads(g_z, s0, s1, leaf):
+    """The gradients of the head's extra terms e0 / e1: both are g_z.  Handed on as two views of ONE buffer they are safe for
+    graph-interior terms (the wide / FM outputs: autograd adds a second gradient into a buffer in place only when it owns its
+    storage alone), but a LEAF keeps the very tensor it is handed as its .grad and adds every later backward into it in
+    place -- with two leaves on one buffer each accumulation landed in both (e.grad = g(1) + 2 g(2) after two backwards).
+    ``leaf``: e1 then gets a buffer of its own."""
+    g0 = None if s0 is None else g_z.view(s0)
+    g1 = None if s1 is None else g_z.view(s1)
+    if leaf and g0 is not None and g1 is not None:
+        g1 = g1.clone()
+    return g0, g1
+
+
 class DeferredGrads(object):
     """Parameter gradients that exist only as per-block / per-split partial slabs until the step's ONE packing launch
     (rh_pack_grads) sums them straight into the flat gradient bucket.
@@ -1444,6 +1462,7 @@ class _HeadFn(torch.autograd.Function):
             _lib.call("rh_head_fwd", _p(h), h.stride(0), _p(weight), _p(bias), _p(c0), _p(c1), B, K, _p(y), _stream())
         ctx.save_for_backward(h, weight, y)
         ctx.shapes = (None if e0 is None else e0.shape, None if e1 is None else e1.shape, bias is not None)
+        ctx.leaf_extra = _leaf_extra(e0, e1)
         ctx.params = (weight, bias)
         # h straight out of a BatchNorm1d + ReLU + Dropout layer (the MLP's last hidden layer): the backward below then
         # also forms that layer's BatchNorm-backward column sums (one statistics launch less per step)
@@ -1501,7 +1520,7 @@ class _HeadFn(torch.autograd.Function):
             if has_bias:
                 g_b = deferred.offer(bp, partial.data_ptr() + 4 * K, nblk, K + 1, 1, lambda: partial[:, K].sum().view(1),
                                      partial)
-        return (g_h, g_w, g_b, None if s0 is None else g_z.view(s0), None if s1 is None else g_z.view(s1))
+        return (g_h, g_w, g_b) + _extra_grads(g_z, s0, s1, ctx.leaf_extra)
 
 
 # Fused MLP chain (round 4): [Linear -> BatchNorm1d -> ReLU -> Dropout] x L -> Linear(., 1) (+ wide / FM terms)
@@ -1622,6 +1641,7 @@ class _MlpChainFn(torch.autograd.Function):
         ctx.L, ctx.ps = L, [float(v) for v in ps]
         ctx.params = params  # the parameter objects themselves (ops.deferred keys gradients by identity)
         ctx.shapes = (None if e0 is None else e0.shape, None if e1 is None else e1.shape)
+        ctx.leaf_extra = _leaf_extra(e0, e1)
         ctx.save_for_backward(x, y, *hs, *acts, *stat, *ctrs)
         return y
 
@@ -1734,7 +1754,7 @@ class _MlpChainFn(torch.autograd.Function):
             for (l, g_h, inp, W, b), rec in zip(problems, recs):
                 grads[4 * l], grads[4 * l + 1] = _offer_wgrad_slabs(W, b, rec[6], B)
         s0, s1 = ctx.shapes
-        return (g_x, None if s0 is None else g_z.view(s0), None if s1 is None else g_z.view(s1), None) + tuple(grads)
+        return (g_x,) + _extra_grads(g_z, s0, s1, ctx.leaf_extra) + (None,) + tuple(grads)
 
 
 def mlp_chain_ok(x, blocks, head, extras):
