@@ -814,6 +814,48 @@ int rh_listwise_bwd(const float* u, const float* pos, int64_t ldp, const float* 
                     const float* g, int B, int I, int D, int K, float temperature, float* g_u, float* g_pos, float* g_neg,
                     void* stream);
 
+/* ---- SINE sparse-interest retrieval (csrc/sine.hip) ------------------------------------------------------------------
+ * B samples, S = seq_max_len positions, width E, T concept prototypes, K intentions, one attention head.
+ * 1 <= S <= 64, 1 <= E <= 128, 1 <= T <= 64, 1 <= K <= min(T, 8), else RH_E_UNSUPPORTED; B = 0 returns at once.
+ * rh_sine_supported and rh_sine_nchunks answer through a HOST int (*supported = 0 / 1, *nchunks = the chunk count of a batch
+ * of B) and return a status like every entry point that takes a pointer.  mask (B, S) int32, 1 = kept, any pattern; every softmax over S is of a + -1e9 (1 - mask) formed in
+ * fp32 as the reference forms it (a fully padded row comes out uniform).  No atomics: two runs give the same bits.
+ *
+ * rh_sine_interest_fwd: X (B, S, E) = x_u, Y (B, S, E) = X w_3, a1 (B, S) = tanh(X w_1) w_2, a2 (B, S, K) =
+ *   tanh(X w_k1) w_k2, C (T, E) the concept table.  Per sample: P1 = softmax_S(a1); z_u = P1^T X; s_u = z_u C^T; idx (B, K)
+ *   = the K largest of s_u in descending order, ties to the lower index (torch.topk); c_u[k] = sigmoid(s_u[idx[k]])
+ *   C[idx[k]]; PU[:, s] = softmax_k(normalize(Y[s]) . normalize(c_u[k])) (F.normalize, eps 1e-12); P2[k] =
+ *   softmax_S(a2[:, k]); phi (B, K, E)[k] = sum_s PU[k, s] P2[k, s] X[s]; xhat (B, S, E)[s] = sum_k PU[k, s] c_u[k].
+ *   Saves P1 (B, S), P2 (B, K, S) and PU (B, K, S) for the backward, which recomputes the rest.
+ * rh_sine_interest_bwd: g_phi (B, K, E), g_xhat (B, S, E) -> g_X, g_Y (B, S, E), g_a1 (B, S), g_a2 (B, S, K).  The top-k
+ *   passes gradient to the chosen scores only (through the gate and through s_u = z_u . C[idx] to z_u and C).  g_crow
+ *   (B, K, E) is a workspace (the per-sample rows of the table's gradient); c_partial (rh_sine_nchunks(B), T*E) the
+ *   per-chunk sums of those rows over consecutive samples in a fixed order (g_C = rh_colsum of it).
+ * replaces: SINE.user_tower torch_rechub/models/matching/sine.py:94-118 (the softmaxes, einsums, topk, sigmoid gate,
+ *           concept gather and F.normalize calls between the w_1 / w_k1 / w_3 products and h_3) and their autograd.
+ *
+ * rh_sine_aggregate_fwd: xhat (B, S, E), a3 (B, S) = tanh(xhat w_4) w_5, phi (B, K, E).  P3 = softmax_S(a3); m (B, E) =
+ *   P3^T xhat; c_apt = m / max(|m|_p, 1e-12) with p = -1, |m|_p = 1 / sum_e 1 / |m_e| (sine.py:122 passes -1 as the ORDER
+ *   of F.normalize, not as its axis); e (B, K) = softmax_k(c_apt . phi[k] * inv_temperature); v (B, E) = sum_k e[k] phi[k].
+ *   |m|_p is about the smallest |m_e| and ill-conditioned in fp32: both kernels compute in fp64 inside and round their
+ *   outputs once; the backward recomputes the chain from the inputs, nothing is saved.
+ * rh_sine_aggregate_bwd: g_v (B, E) -> g_xhat (B, S, E), g_a3 (B, S), g_phi (B, K, E) (through e and directly).
+ * replaces: sine.py:122-128 after h_3 w_5 (softmax, mask term, einsum, F.normalize, softmax over k, einsum) and their
+ *           autograd. */
+int rh_sine_supported(int S, int E, int T, int K, int* supported);
+int rh_sine_nchunks(int B, int* nchunks);
+int rh_sine_interest_fwd(const float* X, const float* Y, const float* a1, const float* a2, const int32_t* mask,
+                         const float* C, int B, int S, int E, int T, int K, int32_t* idx, float* phi, float* xhat, float* P1,
+                         float* P2, float* PU, void* stream);
+int rh_sine_interest_bwd(const float* X, const float* Y, const float* C, const int32_t* idx, const float* P1, const float* P2,
+                         const float* PU, const float* g_phi, const float* g_xhat, int B, int S, int E, int T, int K,
+                         float* g_X, float* g_Y, float* g_a1, float* g_a2, float* g_crow, float* c_partial, void* stream);
+int rh_sine_aggregate_fwd(const float* xhat, const float* a3, const int32_t* mask, const float* phi, float inv_temperature,
+                          int B, int S, int E, int K, float* v, void* stream);
+int rh_sine_aggregate_bwd(const float* xhat, const float* a3, const int32_t* mask, const float* phi, const float* g_v,
+                          float inv_temperature, int B, int S, int E, int K, float* g_xhat, float* g_a3, float* g_phi,
+                          void* stream);
+
 /* ---- HSTU generative model: pointwise relative-bias attention (csrc/hstu.hip) and the next-token head ---------------
  * Attention of one HSTULayer on proj (B, L, ld) = silu(proj1(LN(x))) (row stride ld >= 2 H (dqk + dv)): per head h,
  * q at columns h dqk, k at H dqk + h dqk, v at 2 H dqk + H dv + h dv.  td (B, L) int64 seconds or null (position-only

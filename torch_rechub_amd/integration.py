@@ -25,7 +25,7 @@ _FEATURES = ("DenseFeature", "SparseFeature", "SequenceFeature")
 _ACTIVATIONS = ("Dice", "activation_layer")
 _MODELS = {"ranking": ("DeepFM", "WideDeep", "DCN", "DCNv2", "DIN", "DIEN", "BST", "AFM", "AutoInt", "EDCN", "FiBiNet",
                        "DeepFFM", "FatDeepFFM"),
-           "matching": ("DSSM", "YoutubeDNN", "MIND", "ComirecSA", "ComirecDR", "GRU4Rec", "NARM", "STAMP"),
+           "matching": ("DSSM", "YoutubeDNN", "MIND", "ComirecSA", "ComirecDR", "GRU4Rec", "NARM", "STAMP", "SINE"),
            "multi_task": ("SharedBottom", "ESMM", "MMOE", "PLE", "AITM"),
            "generative": ("HSTUModel", "HLLMModel")}
 # classes a reference module defines beside its model and does not re-export from the sub-package
