@@ -856,6 +856,37 @@ int rh_sine_aggregate_bwd(const float* xhat, const float* a3, const int32_t* mas
                           float inv_temperature, int B, int S, int E, int K, float* g_xhat, float* g_a3, float* g_phi,
                           void* stream);
 
+/* ---- RQ-VAE residual quantizer (csrc/rq.hip) -----------------------------------------------------------------------------
+ * Rows (N, E) fp32, L codebooks C_l (n_e[l], E).  C: HOST array of L device pointers, n_e: HOST array of L sizes (as
+ * rh_cross_moe_pack takes its arrays).  1 <= E <= 128, 1 <= n_e[l] <= 1024, 1 <= L <= 8, else RH_E_UNSUPPORTED; N = 0
+ * returns at once.  rh_rq_supported and rh_rq_nchunks answer through HOST ints (*supported = 0 / 1; *fwd_blocks = the rows
+ * of sse_partial, *bwd_chunks = the rows of c_partial for N rows) and return a status like every entry point that takes a
+ * pointer.  No atomics: two runs give the same bits.
+ *
+ * rh_rq_fwd: the levels [l0, l1) on r_in (N, E), the residual entering level l0 (x when l0 = 0).  Per level l:
+ *   idx[:, l] = argmin_k sum_e (r - C_l[k])^2 (direct form; an exact tie goes to the lower index, as torch.argmin), unless
+ *   bit l of `given` is set: then idx[:, l] is read, not searched (clamped into [0, n_e[l])); r <- r - C_l[idx[:, l]];
+ *   sse[l] = sum over rows and columns of (C_l[idx] - r_l)^2, through sse_partial (fwd_blocks, l1 - l0) summed in a fixed
+ *   order.  idx (N, L) int32 (only the columns of the range are touched), r_out (N, E) the residual after level l1 - 1,
+ *   x_q (N, E) = r_in - r_out.  sse (L,): only the entries of the range are written.  No (N, n_e) array is formed.
+ *   The level's loss is (1 + beta) sse[l] / (N E) = codebook_loss + beta commitment_loss in value.
+ * rh_rq_bwd: all L levels, from x (N, E), idx (N, L), g_xq (N, E) and the DEVICE scalar g_loss (gradient of the mean over
+ *   levels of the level losses); s = g_loss 2 / (L N E):
+ *   g_x (N, E) = g_xq + s beta (x - C_0[idx_0])   (the commitment terms of the levels >= 1 cancel: d r_{l+1} / d r_l = I - I
+ *   through the straight-through estimator); g_C (sum_l n_e[l] E,) = the L tables' gradients one after the other,
+ *   g_C_l[k] = s sum over rows with idx_l = k of (C_l[k] - r_l), the residuals recomputed from x and idx; rows of a table
+ *   that no row chose get exactly 0.  c_partial (bwd_chunks, sum_l n_e[l] E): per-chunk sums over consecutive rows in row
+ *   order, every element written, added by rh_colsum's kernel.
+ * replaces: VectorQuantizer.forward torch_rechub/models/generative/rqvae.py:241-274 (distance matrix, argmin, embedding
+ *           gather, the two mse_loss calls, the straight-through sum) and ResidualVectorQuantizer.forward :382-398 (the
+ *           residual updates, the stacks and the mean), and their autograd. */
+int rh_rq_supported(int E, int L, const int* n_e, int* supported);
+int rh_rq_nchunks(int N, int* fwd_blocks, int* bwd_chunks);
+int rh_rq_fwd(const float* r_in, const float* const* C, const int* n_e, int N, int E, int L, int l0, int l1, int given,
+              int32_t* idx, float* r_out, float* x_q, float* sse_partial, float* sse, void* stream);
+int rh_rq_bwd(const float* x, const float* const* C, const int* n_e, const int32_t* idx, const float* g_xq,
+              const float* g_loss, float beta, int N, int E, int L, float* g_x, float* c_partial, float* g_C, void* stream);
+
 /* ---- HSTU generative model: pointwise relative-bias attention (csrc/hstu.hip) and the next-token head ---------------
  * Attention of one HSTULayer on proj (B, L, ld) = silu(proj1(LN(x))) (row stride ld >= 2 H (dqk + dv)): per head h,
  * q at columns h dqk, k at H dqk + h dqk, v at 2 H dqk + H dv + h dv.  td (B, L) int64 seconds or null (position-only

@@ -4,13 +4,14 @@
 The reference has no plugin layer: its models bind their layers BY NAME at import time
 (``from ...basic.layers import FM, LR, MLP, EmbeddingLayer``, torch_rechub/models/ranking/deepfm.py:10), so swapping
 the implementation means rebinding those names in ``torch_rechub.basic.layers`` AND in every already-imported
-``torch_rechub.*`` module that holds a reference to the original class.  ``enable()`` does exactly that, at three levels:
+``torch_rechub.*`` module that holds a reference to the original class.  ``enable()`` does exactly that, at these levels:
 
   layers    EmbeddingLayer, InputMask, the pooling layers, LR, MLP, FM, CrossNetwork, CrossNetV2, CrossNetMix, Dice and
             the Feature descriptors -> an UNMODIFIED reference model class (e.g. the source of
             torch_rechub/models/ranking/deepfm.py as it stands) then builds and runs on the HIP layers;
   models    DeepFM, WideDeep, DCN, DCNv2, DIN, ... -> the fused forwards (one gather launch emits the MLP input, FM and LR);
   trainers  CTRTrainer / MatchTrainer / MTLTrainer -> TableAdam, device-resident loader, hipGraph step, RCCL data parallel.
+  data      EmbDataset of ``utils.data`` (its own flag).
 
 Constructor signatures, attribute names and ``state_dict`` keys are the reference's at every level
 (tests/test_integration_patch.py).  ``disable()`` restores the original bindings.
@@ -27,10 +28,14 @@ _MODELS = {"ranking": ("DeepFM", "WideDeep", "DCN", "DCNv2", "DIN", "DIEN", "BST
                        "DeepFFM", "FatDeepFFM"),
            "matching": ("DSSM", "YoutubeDNN", "MIND", "ComirecSA", "ComirecDR", "GRU4Rec", "NARM", "STAMP", "SINE"),
            "multi_task": ("SharedBottom", "ESMM", "MMOE", "PLE", "AITM"),
-           "generative": ("HSTUModel", "HLLMModel")}
+           "generative": ("HSTUModel", "HLLMModel", "RQVAEModel")}
 # classes a reference module defines beside its model and does not re-export from the sub-package
-_MODEL_PARTS = {"generative.hllm": ("HLLMTransformerBlock",)}
+_MODEL_PARTS = {"generative.hllm": ("HLLMTransformerBlock",),
+                "generative.rqvae": ("VectorQuantizer", "ResidualVectorQuantizer")}
 _TRAINERS = ("CTRTrainer", "MatchTrainer", "MTLTrainer", "SeqTrainer")
+# classes the reference keeps in a module of their own, not re-exported from the sub-package: (module, names)
+_TRAINER_PARTS = {"trainers.rqvae_trainer": ("Trainer",)}
+_DATA = {"utils.data": ("EmbDataset",)}
 
 _undo = []  # (module, attribute, original object)
 
@@ -66,11 +71,12 @@ def _swap(root, ref_modname, amd_module, names):
     return done
 
 
-def enable(layers=True, models=True, trainers=True, package="torch_rechub"):
+def enable(layers=True, models=True, trainers=True, package="torch_rechub", data=True):
     """Rebind the reference package's hot-path classes to the HIP implementations.  Returns the list of patched names.
 
     Call it after ``import torch_rechub`` (and its ``models`` / ``trainers`` sub-packages, if the level is wanted) and
-    before models are built.  Idempotent."""
+    before models are built.  ``data`` is a level of its own: the data-set classes of ``utils.data`` that have a mirror here
+    (``EmbDataset``).  Idempotent."""
     from . import basic, trainers as amd_trainers
     from .basic import activation, features, layers as amd_layers
     importlib.import_module(package)
@@ -88,6 +94,11 @@ def enable(layers=True, models=True, trainers=True, package="torch_rechub"):
             done += _swap(package, f"{package}.models.{sub}", amd_sub, names)
     if trainers:
         done += _swap(package, f"{package}.trainers", amd_trainers, _TRAINERS)
+        for sub, names in _TRAINER_PARTS.items():
+            done += _swap(package, f"{package}.{sub}", importlib.import_module(f"{__package__}.{sub}"), names)
+    if data:
+        for sub, names in _DATA.items():
+            done += _swap(package, f"{package}.{sub}", importlib.import_module(f"{__package__}.{sub}"), names)
     del basic
     return done
 

@@ -1,2 +1,3 @@
 from .hstu import HSTUModel  # noqa: F401
 from .hllm import HLLMModel, HLLMTransformerBlock  # noqa: F401
+from .rqvae import RQVAEModel, ResidualVectorQuantizer, VectorQuantizer  # noqa: F401

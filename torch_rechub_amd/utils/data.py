@@ -11,6 +11,9 @@ Two loaders with the same batch contract ``(x_dict, y)`` as the reference:
   ``x_dict`` values are column views of the static (B,F) / (B,ND) buffers.
 """
 
+import os
+
+import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset, random_split
 
@@ -358,3 +361,28 @@ class SeqDataset(Dataset):
 
     def __len__(self):
         return len(self.targets)
+
+
+class EmbDataset(Dataset):
+    """Precomputed embeddings (num_samples, emb_dim) from a ``.npy`` array or a ``.pt`` tensor (reference
+    torch_rechub/utils/data.py EmbDataset): item ``i`` is row ``i`` as a float32 tensor; ``dim`` is the width."""
+
+    def __init__(self, data_path, device='cpu'):
+        self.data_path = data_path
+        suffix = os.path.splitext(data_path)[-1]
+        if suffix == ".npy":
+            self.embeddings = np.load(data_path)
+        elif suffix == ".pt":
+            tensor = torch.load(data_path, map_location=device)
+            if not isinstance(tensor, torch.Tensor):
+                raise TypeError(f"{data_path} does not contain a torch.Tensor")
+            self.embeddings = tensor.cpu().numpy()
+        else:
+            raise ValueError(f"Unsupported embedding format: {suffix}")
+        self.dim = self.embeddings.shape[-1]
+
+    def __getitem__(self, index):
+        return torch.FloatTensor(self.embeddings[index])
+
+    def __len__(self):
+        return len(self.embeddings)
