@@ -970,6 +970,30 @@ int rh_catalogue_ce_bwd(const float* u, const float* E, const int64_t* labels, c
                         const float* g_loss, int B, int D, int V, float* part, float* part_h, float* g_u, float* g_E,
                         void* stream);
 
+/* ---- exact top-K item retrieval (csrc/topk.hip) ---------------------------------------------------------------------
+ * score[i][j] = q_i . x_j (+ bias[j]) over the whole table, the K best per query, without the (M, V) score matrix.
+ * q (M, D) fp32 with row stride ldq, x (V, D) fp32 contiguous, bias (V,) or null.  exclude (M, S) int64 or null (S = 0):
+ * the ids of row i that may not be returned to query i; entries outside [0, V) are ignored (pad with -1; a 0-padded
+ * history also drops id 0).  invalid (n_inv,) int64 or null: ids dropped for every query.
+ * ids (M, K) int64 and scores (M, K) fp32, sorted by (score descending, id ascending): an exact tie goes to the lower id,
+ * as torch.topk.  Excluded and invalid ids never appear; with fewer than K candidates left the tail is id -1, score -inf
+ * (K > V is legal).  Inputs are assumed finite (NaN is not checked).  The products are exact f32 accumulated in k order
+ * from zero on the 64 x 64 MFMA tile, the bias is added last: one score depends on q_i, x_j and D only -- not on M, V,
+ * the position in a tile or the split.  nsplit ranges [V s / nsplit, V (s + 1) / nsplit) are scanned by separate
+ * workgroups and merged under the same total order: every nsplit in [1, min(V, 1024)] gives the same bits.  No atomics.
+ * 1 <= D <= 1024, 1 <= K <= 256, 0 <= S <= 1024, 1 <= V < 2^31, any M, else RH_E_UNSUPPORTED; M = 0 returns at once.
+ * rh_topk_supported and rh_topk_plan answer through HOST pointers (*supported = 0 / 1; *nsplit = the default split,
+ * *workspace_bytes = 8 M nsplit K for it -- a caller that passes another nsplit sizes the workspace by the same formula)
+ * and return a status like every entry point that takes a pointer.
+ * replaces: Annoy.fit / Annoy.query of examples/matching/movielens_utils.py:17-42, torch.topk over the (B, V) scores of
+ *           examples/matching/run_sbr.py:53 and the masked torch.topk of examples/generative/run_hstu_movielens.py:109-114,
+ *           the builders of torch_rechub/serving (annoy, faiss, milvus). */
+int rh_topk_supported(int D, int K, int S, int* supported);
+int rh_topk_plan(int M, int V, int K, int* nsplit, int64_t* workspace_bytes);
+int rh_topk_fwd(const float* q, int64_t ldq, const float* x, const float* bias, const int64_t* exclude, int S,
+                const int64_t* invalid, int n_inv, int M, int D, int V, int K, int nsplit, void* workspace, int64_t* ids,
+                float* scores, void* stream);
+
 /* ---- session-based retrieval (csrc/session.hip) ---------------------------------------------------------------------
  * GRU recurrence of nn.GRU (gate order r, z, n) from the zero state: xw (B, T, 3H) = x W_ih^T (+ b_ih) for every step,
  * w_hh (3H, H) = weight_hh, b_hh (3H,) or null.  1 <= H <= rh_gru_max_hidden() (128), else RH_E_UNSUPPORTED.

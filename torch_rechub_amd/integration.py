@@ -12,6 +12,8 @@ the implementation means rebinding those names in ``torch_rechub.basic.layers`` 
   models    DeepFM, WideDeep, DCN, DCNv2, DIN, ... -> the fused forwards (one gather launch emits the MLP input, FM and LR);
   trainers  CTRTrainer / MatchTrainer / MTLTrainer -> TableAdam, device-resident loader, hipGraph step, RCCL data parallel.
   data      EmbDataset of ``utils.data`` (its own flag).
+  serving   ``builder_factory`` of ``serving`` learns ``"hip"`` (when that package can be imported at all: it imports annoy,
+            faiss and pymilvus unconditionally), and ``utils.match`` gains ``ExactIndex`` (its own flag).
 
 Constructor signatures, attribute names and ``state_dict`` keys are the reference's at every level
 (tests/test_integration_patch.py).  ``disable()`` restores the original bindings.
@@ -37,7 +39,8 @@ _TRAINERS = ("CTRTrainer", "MatchTrainer", "MTLTrainer", "SeqTrainer")
 _TRAINER_PARTS = {"trainers.rqvae_trainer": ("Trainer",)}
 _DATA = {"utils.data": ("EmbDataset",)}
 
-_undo = []  # (module, attribute, original object)
+_undo = []  # (module, attribute, original object or _ABSENT)
+_ABSENT = object()  # the attribute did not exist before enable()
 
 
 def _rebind_everywhere(root, original, replacement):
@@ -71,12 +74,45 @@ def _swap(root, ref_modname, amd_module, names):
     return done
 
 
-def enable(layers=True, models=True, trainers=True, package="torch_rechub", data=True):
+def _enable_serving(package):
+    """``"hip"`` for the reference's ``builder_factory`` and ``ExactIndex`` beside its ``Annoy``."""
+    from . import serving as amd_serving
+    from .utils import match as amd_match
+    done = []
+    try:
+        ref_serving = importlib.import_module(f"{package}.serving")
+    except (ImportError, OSError):  # a backend library that is absent or does not load: nothing to teach
+        ref_serving = None
+    theirs = getattr(ref_serving, "builder_factory", None)
+    if theirs is not None and not getattr(theirs, "_rh_hip", False):
+
+        def builder_factory(model, **builder_config):
+            if model == "hip":
+                return amd_serving.HipBuilder(**builder_config)
+            return theirs(model, **builder_config)
+
+        builder_factory._rh_hip = True
+        builder_factory.__doc__ = theirs.__doc__
+        _rebind_everywhere(package, theirs, builder_factory)
+        done.append(f"{package}.serving.builder_factory")
+    try:
+        ref_match = importlib.import_module(f"{package}.utils.match")
+    except ImportError:
+        ref_match = None
+    if ref_match is not None and getattr(ref_match, "ExactIndex", None) is not amd_match.ExactIndex:
+        _undo.append((ref_match, "ExactIndex", getattr(ref_match, "ExactIndex", _ABSENT)))
+        ref_match.ExactIndex = amd_match.ExactIndex
+        done.append(f"{package}.utils.match.ExactIndex")
+    return done
+
+
+def enable(layers=True, models=True, trainers=True, package="torch_rechub", data=True, serving=True):
     """Rebind the reference package's hot-path classes to the HIP implementations.  Returns the list of patched names.
 
     Call it after ``import torch_rechub`` (and its ``models`` / ``trainers`` sub-packages, if the level is wanted) and
     before models are built.  ``data`` is a level of its own: the data-set classes of ``utils.data`` that have a mirror here
-    (``EmbDataset``).  Idempotent."""
+    (``EmbDataset``).  ``serving`` is another: the retrieval index (``builder_factory("hip")``, ``ExactIndex``); where
+    the reference's ``serving`` package cannot be imported, that half is skipped without an error.  Idempotent."""
     from . import basic, trainers as amd_trainers
     from .basic import activation, features, layers as amd_layers
     importlib.import_module(package)
@@ -99,6 +135,8 @@ def enable(layers=True, models=True, trainers=True, package="torch_rechub", data
     if data:
         for sub, names in _DATA.items():
             done += _swap(package, f"{package}.{sub}", importlib.import_module(f"{__package__}.{sub}"), names)
+    if serving:
+        done += _enable_serving(package)
     del basic
     return done
 
@@ -107,4 +145,7 @@ def disable():
     """Undo every rebinding made by ``enable`` (latest first)."""
     while _undo:
         mod, attr, original = _undo.pop()
-        setattr(mod, attr, original)
+        if original is _ABSENT:
+            delattr(mod, attr)
+        else:
+            setattr(mod, attr, original)

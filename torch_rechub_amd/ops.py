@@ -3612,3 +3612,77 @@ def session_lengths(seq, check_full=False):
     if not torch.cuda.is_current_stream_capturing():
         check_errors(seq.device)
     return counts
+
+
+# --------------------------------------------------------------------------------------------
+# Exact top-K item retrieval (csrc/topk.hip)
+# --------------------------------------------------------------------------------------------
+def topk_supported(D, K, S=0):
+    """Whether csrc/topk.hip takes width D, K results and S exclusions per query (D <= 1024, K <= 256, S <= 1024)."""
+    out = ctypes.c_int(0)
+    _lib.call("rh_topk_supported", int(D), int(K), int(S), ctypes.c_void_p(ctypes.addressof(out)))
+    return bool(out.value)
+
+
+def topk_plan(M, V, K):
+    """(nsplit, workspace_bytes): the default number of item ranges for M queries over V items and the size of the
+    partial lists for it (8 M nsplit K bytes)."""
+    nsplit, nbytes = ctypes.c_int(0), ctypes.c_int64(0)
+    _lib.call("rh_topk_plan", int(M), int(V), int(K), ctypes.c_void_p(ctypes.addressof(nsplit)),
+              ctypes.c_void_p(ctypes.addressof(nbytes)))
+    return nsplit.value, nbytes.value
+
+
+def topk_items(q, table, k, bias=None, exclude=None, invalid=None, nsplit=None):
+    """(ids (M, k) int64, scores (M, k) float32): the k best items of ``table`` (V, D) for every row of ``q`` (M, D) by
+    q_i . x_j (+ bias[j]), best first, exact ties to the lower id; the (M, V) scores are never formed.  ``exclude`` (M, S)
+    int64: ids that may not be returned to query i (entries outside [0, V) are ignored: pad with -1, or pass a 0-padded
+    history to drop id 0 with it); ``invalid``: ids dropped for every query.  With fewer than k candidates the tail is
+    id -1, score -inf.  ``nsplit`` forces the number of item ranges (the result does not depend on it).  No autograd;
+    runs on the current stream."""
+    if invalid is not None and not torch.is_tensor(invalid):
+        invalid = torch.as_tensor(list(invalid), dtype=torch.int64, device=q.device)
+    require_hip(q, table, bias, exclude, invalid)
+    if q.dim() != 2 or table.dim() != 2 or q.shape[1] != table.shape[1]:
+        raise ValueError("topk_items: q (M, D) and table (V, D) expected")
+    if q.dtype != torch.float32 or table.dtype != torch.float32 or (bias is not None and bias.dtype != torch.float32):
+        raise ValueError("torch_rechub_amd: topk_items takes float32 tensors")
+    if not table.is_contiguous():
+        raise ValueError("topk_items: the table must be contiguous")
+    M, D = (int(v) for v in q.shape)
+    V, k = int(table.shape[0]), int(k)
+    if exclude is not None and (exclude.dim() != 2 or exclude.shape[0] != M):
+        raise ValueError("topk_items: exclude (M, S) expected")
+    S = 0 if exclude is None else int(exclude.shape[1])
+    if bias is not None and tuple(bias.shape) != (V,):
+        raise ValueError("topk_items: bias (V,) expected")
+    if V < 1 or not topk_supported(D, k, S):
+        from .models.matching._listwise import no_kernel
+        raise no_kernel(f"top-k retrieval at D={D}, k={k}, {S} exclusions per query, V={V} "
+                        "(1 <= D <= 1024, 1 <= k <= 256, S <= 1024, V >= 1)")
+    q, table = q.detach(), table.detach()
+    if M > 0 and (q.stride(1) != 1 or q.stride(0) < D):
+        q = q.contiguous()
+    ldq = int(q.stride(0)) if M > 1 else D
+    if bias is not None:
+        bias = bias.detach().contiguous()
+    if S > 0:
+        exclude = exclude.to(torch.int64).contiguous()
+    n_inv = 0
+    if invalid is not None:
+        invalid = invalid.to(torch.int64).reshape(-1).contiguous()
+        n_inv = int(invalid.numel())
+    if nsplit is None:
+        nsplit, _ = topk_plan(M, V, k)
+    nsplit = int(nsplit)
+    if not 1 <= nsplit <= min(V, 1024):
+        raise ValueError(f"topk_items: nsplit={nsplit} outside [1, min(V, 1024)]")
+    dev = q.device
+    ids = torch.empty((M, k), dtype=torch.int64, device=dev)
+    scores = torch.empty((M, k), dtype=torch.float32, device=dev)
+    if M == 0:
+        return ids, scores
+    work = torch.empty((8 * M * nsplit * k,), dtype=torch.uint8, device=dev)
+    _lib.call("rh_topk_fwd", _p(q), ldq, _p(table), _p(bias), _p(exclude) if S > 0 else _NULL, S,
+              _p(invalid) if n_inv > 0 else _NULL, n_inv, M, D, V, k, nsplit, _p(work), _p(ids), _p(scores), _stream())
+    return ids, scores

@@ -98,3 +98,42 @@ def gather_inbatch_logits(scores, neg_indices, row_offset=0):
     positive_logits = torch.diagonal(scores, offset=row_offset).reshape(-1, 1)
     negative_logits = torch.gather(scores, 1, neg_indices)
     return torch.cat([positive_logits, negative_logits], dim=1)
+
+
+class ExactIndex(object):
+    """Exact nearest-neighbour search with the surface of the reference's ``Annoy`` engine (torch_rechub/utils/match.py:
+    252-296), on the streaming top-K kernel: ``ExactIndex().fit(item_embedding)`` then ``query(v, n)``, so that the
+    examples' ``match_evaluation`` runs with one name changed.  ``metric``: "angular" (Annoy's default), "L2" or "IP".
+    ``n_trees`` and ``search_k`` are accepted and ignored: there is no approximation to tune."""
+
+    def __init__(self, metric="angular", n_trees=None, search_k=None, device=None):
+        from ..serving.hip import _check_metric
+        self._metric = _check_metric({"euclidean": "L2", "l2": "L2", "dot": "IP", "ip": "IP"}.get(metric, metric))
+        self._device = device
+        self._indexer = None
+
+    def fit(self, X):
+        """Index the rows of ``X`` (n, d), a numpy array or a tensor."""
+        from ..serving.hip import HipIndexer
+        self._indexer = HipIndexer(torch.as_tensor(X), self._metric, self._device)
+        return self
+
+    def set_query_arguments(self, search_k=None):
+        pass
+
+    def query(self, v, n):
+        """1-D ``v``: (ids list, distances list) of the ``n`` nearest rows, as ``Annoy.query``.  2-D ``v`` (a batch
+        extension): the two (len(v), n) tensors of ``HipIndexer.query``."""
+        if self._indexer is None:
+            raise RuntimeError("ExactIndex.query before fit")
+        v = torch.as_tensor(v)
+        if v.dim() == 2:
+            return self._indexer.query(v, n)
+        if v.dim() != 1:
+            raise ValueError("query takes a 1-D vector or a 2-D batch")
+        ids, dist = self._indexer.query(v.reshape(1, -1), n)
+        keep = ids[0] >= 0  # Annoy returns fewer than n entries when the index holds fewer
+        return ids[0][keep].tolist(), dist[0][keep].tolist()
+
+    def __str__(self):
+        return f"ExactIndex(metric={self._metric})"
