@@ -253,8 +253,18 @@ struct LazySweepArgs {
   LazyTouchedArgs touch;
 };
 
-template <int LPR, typename IdxT, bool REFRESH, bool ASSEMBLE = false, bool LOOK = false, bool GRAD = !REFRESH>
+template <int LPR, typename IdxT, bool REFRESH, bool ASSEMBLE = false, bool LOOK = false, bool GRAD = !REFRESH,
+          int LOOKR = 1>
 static __device__ __forceinline__ void lazy_touched_body(const LazyTouchedArgs& a, int bx, int f);
+
+// The LDS copy of the per-step (A, E) ring of the replaying bodies below: ONE array per kernel, however many of them the kernel
+// combines.  A workgroup runs one body; as a __shared__ array inside each (template) body the end-of-step launch carried three
+// rings (refresh, lookahead, dense tables: 24 of its 28 KB of static LDS), and with the weight-gradient rider's 16.6 KB on top a
+// CU had room for three of its workgroups where registers allow four.
+static __device__ __forceinline__ float* ring_lds() {
+  __shared__ float ring_shared[2 * kMaxRing];
+  return ring_shared;
+}
 
 // (bx_, gdim_: this workgroup's index and the number of workgroups of the sweep / merged part -- blockIdx.x / gridDim.x unless
 // a launch carries more parts: round 4 measured the dense-gradient packing as such a part and dropped it)
@@ -289,7 +299,7 @@ static __device__ __forceinline__ void lazy_sweep_body(const LazySweepArgs& a, c
   const int slot = threadIdx.x / LPR;
   // The per-step (A, E) ring lives in LDS for the replay loop: a global load there would make every s_waitcnt vmcnt
   // also wait for the prefetched rows of the next unit (vmcnt retires in order) and serialise memory behind the ALU.
-  __shared__ float ring_s[2 * kMaxRing];
+  float* const ring_s = ring_lds();
   for (int i = threadIdx.x; i < 2 * (a.ring_mask + 1); i += RH_BLOCK) ring_s[i] = a.ring[i];
   __syncthreads();
 
@@ -589,7 +599,8 @@ __global__ void stream_gate_release_kernel(long long* gate) {
 // GRAD (default: !REFRESH): the rows may carry a gradient -- it is read, applied in the closing step and re-zeroed.  REFRESH
 // with GRAD is the refresh of the NEXT batch inside the end-of-step launch of THIS step (adam_lazy_step_ahead_kernel): a row
 // both batches look up is claimed by one of the two passes, and whichever it is applies the gradient.
-template <int LPR, typename IdxT, bool REFRESH, bool ASSEMBLE, bool LOOK, bool GRAD>
+// LOOKR (LOOK only): rounds of RH_BLOCK samples whose index loads a lookahead workgroup keeps in flight together (below).
+template <int LPR, typename IdxT, bool REFRESH, bool ASSEMBLE, bool LOOK, bool GRAD, int LOOKR>
 static __device__ __forceinline__ void lazy_touched_body(const LazyTouchedArgs& a, int bx, int f) {
   constexpr int LPP = RH_BLOCK / LPR;
   constexpr int D = 4 * LPR;
@@ -621,7 +632,7 @@ static __device__ __forceinline__ void lazy_touched_body(const LazyTouchedArgs& 
   // REFRESH replays up to K steps per row: the per-step (A, E) ring entries come from LDS, as in the sweep.  Read from
   // global memory inside the replay loop they were one dependent L2 round trip per replayed step (the compiler emits a
   // vector load + s_waitcnt vmcnt per iteration): the pass was bound by that latency, 26.8 us in the DeepFM step.
-  __shared__ float ring_t[REFRESH ? 2 * kMaxRing : 2];
+  float* const ring_t = REFRESH ? ring_lds() : nullptr;
   if (REFRESH) {
     for (int i = threadIdx.x; i < 2 * (a.ring_mask + 1); i += RH_BLOCK) ring_t[i] = a.ring[i];
     __syncthreads();
@@ -633,25 +644,49 @@ static __device__ __forceinline__ void lazy_touched_body(const LazyTouchedArgs& 
   // of the field whose only live lookup is that row.  (As a separate block of code with its own replay loop in front of
   // this loop it cost the pass 26 -> 48 us in the DeepFM step, where no field has a padding row at all.)
   const bool pad_pass = !LOOK && REFRESH && pad >= 0 && pad < rows && bx == 0;  // block-uniform
-  __shared__ int64_t s_look[LOOK ? RH_BLOCK : 1];
+  // LOOK keeps about one lookup in K: a pass over the hits of RH_BLOCK samples holds a handful of rows, and the wavefront they
+  // land in replays ~K steps with all its other lanes masked off.  So the hits of a workgroup's samples are COLLECTED, the index
+  // loads of kLookRounds x RH_BLOCK samples in flight together, and a pass is run when the samples are used up (or another
+  // round might not fit the list): its wavefronts are full of rows that are all ~K steps behind.
+  // The list holds what a flush may leave behind plus one round's worth: it is flushed as soon as it holds more than RH_BLOCK
+  // rows, so at most RH_BLOCK are carried into a round and at most kLookRounds * RH_BLOCK (one per sample) are added by it.
+  constexpr int kLookRounds = LOOKR;
+  constexpr int kLookCap = (kLookRounds + 1) * RH_BLOCK;
+  constexpr int kLookFlush = RH_BLOCK;  // flush threshold
+  static_assert(kLookFlush + kLookRounds * RH_BLOCK <= kLookCap, "s_look: carried rows + one round's rows must fit");
+  __shared__ int64_t s_look[LOOK ? kLookCap : 1];
   __shared__ int s_nlook;
   const int64_t look_b1 = b1;
-  for (int64_t sub = LOOK ? b0 : 0; sub < (LOOK ? look_b1 : 1); sub += RH_BLOCK) {
+  bool look_fresh = true;  // (block-uniform) the list is empty: the hits collected so far have had their pass
+  for (int64_t sub = LOOK ? b0 : 0; sub < (LOOK ? look_b1 : 1); sub += kLookRounds * RH_BLOCK) {
   if (LOOK) {
-    // the samples sub .. sub + 255 of the next batch, one per thread: keep the rows inside the coming sweep's window
+    // the samples sub .. sub + kLookRounds * 256 - 1 of the next batches, kLookRounds per thread: keep the rows inside the
+    // coming sweep's window
     const int64_t w = a.ldesc[7 * T + ti];
     const int64_t ws = ((int64_t)(t - 1) % K) * w;
-    if (threadIdx.x == 0) s_nlook = 0;
-    __syncthreads();  // (also: the previous round is done with s_look)
-    const int64_t b = sub + threadIdx.x;
-    if (b < look_b1) {
-      const int64_t p = (apos + a.off + (int64_t)a.B + b) % a.N;
-      const int64_t r = gload<int64_t>(a.src_sparse + gload<int64_t>(a.perm + p) * a.Fd + acol);
+    if (look_fresh && threadIdx.x == 0) s_nlook = 0;
+    __syncthreads();  // (also: the previous pass is done with s_look)
+    int64_t rl[kLookRounds];
+#pragma unroll
+    for (int u = 0; u < kLookRounds; ++u) {
+      const int64_t b = sub + (int64_t)u * RH_BLOCK + threadIdx.x;
+      rl[u] = -1;
+      if (b < look_b1) {
+        const int64_t p = (apos + a.off + (int64_t)a.B + b) % a.N;
+        rl[u] = gload<int64_t>(a.src_sparse + gload<int64_t>(a.perm + p) * a.Fd + acol);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kLookRounds; ++u) {
+      const int64_t r = rl[u];
       if (r >= ws && r < ws + w && r < rows && r != pad) s_look[atomicAdd(&s_nlook, 1)] = r;
     }
     __syncthreads();
+    const int n = s_nlook;  // <= kLookFlush carried over + kLookRounds * RH_BLOCK new ones <= kLookCap
+    look_fresh = sub + kLookRounds * RH_BLOCK >= look_b1 || n > kLookFlush;
+    if (!look_fresh) continue;
     b0 = 0;
-    b1 = s_nlook;
+    b1 = n;
   }
   const int64_t b_end = b1 + (pad_pass ? LPP : 0);
   for (int64_t base = b0; base < b_end; base += LPP) {  // uniform trip count: the claim is broadcast by shuffle
@@ -824,18 +859,25 @@ __global__ __launch_bounds__(RH_BLOCK) void adam_lazy_refresh_assemble_kernel(co
 
 // The END of step t and the HEAD of step t + 1 as ONE launch (round 4, relaxed join with the head folded into the previous
 // step's graph; reference: optimizer.step() of step t, trainers/ctr_trainer.py:99, then TorchDataset.__getitem__ +
-// default_collate of batch t + 1, utils/data.py:14-25,61-83).  Parts, in workgroup order:
+// default_collate of batch t + 1, utils/data.py:14-25,61-83).  Parts (workgroup order: C, B, A, D, E -- C's few workgroups run
+// longest, a full pass of rows that are all ~K steps behind, and go first):
 //   B  refresh of the lookups of batch t + 1 (dataset positions pos .. pos + B: the step's scalar launch has advanced pos),
 //      replay form WITH gradient: a row that batch t also looked up is claimed by one of the two passes (atomicMax on its
 //      last-step word, as in the merged touched + sweep launch) and the claimant applies the gradient;
 //   A  the touched-rows step of batch t, its indices read from the dataset too (positions pos - B ..): the static batch buffer
 //      they were gathered from is being overwritten by part D of this very launch;
 //   C  lookahead: the lookups of batches t + 2 .. t + 1 + depth that fall into the window of the sweep launched behind this
-//      step (LOOK above);
+//      step (LOOK above), kAheadLookSamples per workgroup;
 //   D  assembly of batch t + 1 into the static batch buffers;
 //   E  the dense (K = 1) tables' step, as rh_adam_lazy_step_mode(RH_SWEEP_DENSE_TABLES).
 // What the strict form ran as three dependent launches with two idle gaps between them (touched rows 22 us, gap, assembly +
 // refresh 30 us, gap) overlaps inside one launch; the step's graph then begins with the gather.
+// lookahead part of the end-of-step launch: index loads of kAheadLookRounds x RH_BLOCK samples in flight together, two such
+// rounds per workgroup -- ~ kAheadLookSamples / K of the samples' rows lie in the window, 16 at K = 128: one full wavefront of
+// D = 16 rows.  Measured with 1024 / 2048 / 4096 samples: 0.2171-0.2179 / 0.2172-0.2174 / 0.2173 ms per step.
+constexpr int kAheadLookRounds = 4;
+constexpr int kAheadLookSamples = 2 * kAheadLookRounds * RH_BLOCK;
+
 struct StepAheadParts {
   int nB, chunksB;  // part B: chunksB x F workgroups of spbB samples
   int spbB;
@@ -851,6 +893,13 @@ struct StepAheadParts {
 
 template <int LPR>
 __device__ __forceinline__ void step_ahead_body(const LazySweepArgs& a, const StepAheadParts& parts, int bx, const int nblocks) {
+  if (bx < parts.nC) {
+    LazyTouchedArgs ta = a.touch;
+    ta.off = 0;
+    lazy_touched_body<LPR, int64_t, true, true, true, true, kAheadLookRounds>(ta, bx % parts.chunksC, bx / parts.chunksC);
+    return;
+  }
+  bx -= parts.nC;
   if (bx < parts.nB) {
     LazyTouchedArgs ta = a.touch;
     ta.spb = parts.spbB;
@@ -874,13 +923,6 @@ __device__ __forceinline__ void step_ahead_body(const LazySweepArgs& a, const St
     return;
   }
   bx -= parts.nA;
-  if (bx < parts.nC) {
-    LazyTouchedArgs ta = a.touch;
-    ta.off = 0;
-    lazy_touched_body<LPR, int64_t, true, true, true, true>(ta, bx % parts.chunksC, bx / parts.chunksC);
-    return;
-  }
-  bx -= parts.nC;
   if (bx < parts.nD) {
     const LazyTouchedArgs& ta = a.touch;
     constexpr int G = 16;
@@ -1515,7 +1557,8 @@ extern "C" int rh_adam_lazy_refresh_assemble(const int64_t* ldesc, int T, const 
              "rh_adam_lazy_refresh_assemble: ring_size must be a power of two <= %d", kMaxRing);
   const int spb = samples_per_block <= 0 ? 64 : ((samples_per_block + 63) / 64) * 64;
   const int chunks = (B + spb - 1) / spb;
-  // lookahead workgroups walk R chunks each (one sample per thread and round), R fields share a grid row
+  // lookahead workgroups walk R chunks each (one sample per thread and round of RH_BLOCK; their hits are collected over the
+  // rounds, lazy_touched_body), R fields share a grid row
   int R = RH_BLOCK / spb >= 1 ? RH_BLOCK / spb : 1;
   if (chunks % R != 0) R = 1;
   LazyTouchedArgs a{ldesc, field_table, idesc, hyper, ring, ring_size - 1, T, B, F, spb, err_flag,
@@ -1662,7 +1705,7 @@ static int step_ahead_impl(const int64_t* ldesc, int T, const int64_t* h_rows, c
   a.total_vblocks = a.vb_prefix[T];
   a.touch_blocks = a.touch_chunks = 0;
   a.touch_period = 1;
-  const int look = RH_BLOCK;
+  const int look = kAheadLookSamples;
   a.touch = LazyTouchedArgs{ldesc, field_table, idesc, hyper, ring, ring_size - 1, T, B, F, 64, err_flag,
                             perm, pos, N, sparse, Fd, dense, ND, label, sparse_out, dense_out, label_out,
                             look, look_depth * B, 0};
