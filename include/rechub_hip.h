@@ -1029,6 +1029,72 @@ int rh_session_dropout_fwd(const float* x, int64_t n, float p, int64_t* rng, int
 int rh_session_dropout_bwd(const float* g, int64_t n, float p, const int64_t* rng, const int64_t* saved_ctr, float* dx,
                            void* stream);
 
+/* ---- SASRec: the transformer block around the causal attention, fused per row tile (csrc/sasrec.hip) -----------------
+ * fp32.  M = B L rows of width D, 1 <= D <= 128, any M >= 1, else RH_E_UNSUPPORTED before any launch; M = 0 returns at
+ * once.  seq (B, L) int64: the history ids, 0 = pad (m = seq != 0).  Every LayerNorm: mean, then the variance as the mean
+ * of (x - mean)^2 (two passes), rstd = 1 / sqrt(var + eps), out = (x - mean) rstd gamma + beta; stats (M, 2) = the rows'
+ * (mean, rstd).  An all-zero row gives exactly beta.  No atomics: every reduction over rows goes through one partial per
+ * workgroup (rh_sasrec_ntiles(M, D) of them: a HOST int, like rh_sine_nchunks) summed in a fixed order by rh_colsum; a
+ * backward run twice gives the same bits.  Dropout: rh_drop_hash over the device (seed, counter) pair rng, kept when
+ * hash >= p 2^32, scaled by 1 / (1 - p), recomputed in the backward; an entry point draws ONE counter value, returns it in
+ * saved_ctr (1,) and advances the device counter; p = 0 computes no hash and takes null rng / saved_ctr.  Element index
+ * ranges of one call:  rh_sasrec_input_fwd  [0, M D): (b L + l) D + d;
+ *                      rh_sasrec_ffn_fwd    dropout1 [0, M D): row D + c;  dropout2 [M D, 2 M D): M D + row D + c.
+ *
+ * rh_sasrec_input_fwd: e (B, L, D) with row (b, l) at e + b e_bstride + l e_rstride (a slice of the (B, 3, L, >= D) gather),
+ *   P (max_len, D), L <= max_len.  x0 (B, L, D) = m dropout(e scale + P[l]) (scale = sqrt(D) as the caller rounds it).
+ * rh_sasrec_input_bwd: g_x0 -> g_e (B, L, D) contiguous and g_P (max_len, D) = the sum over b in ascending order, rows
+ *   l >= L written as zero.  The one exception to "M = 0 returns at once": with B L = 0 it still launches, because the sum
+ *   over no samples is a result too -- g_P is written as all zero (g_e has no element).
+ * replaces: SASRec.seq_forward torch_rechub/models/matching/sasrec.py:75-84 (scale, position lookup and add, dropout, mask).
+ *
+ * rh_sasrec_attn_in_fwd: x (M, D) -> Q (M, D) = LN(x; gamma, beta), qkv (M, 3 D) = [Q Wq^T + bq | x Wk^T + bk | x Wv^T + bv]
+ *   with w (3 D, D) = in_proj_weight, b (3 D,) = in_proj_bias, stats (M, 2).
+ * rh_sasrec_attn_in_bwd: g_qkv (M, 3 D), g_Q (M, D) (the residual's) -> g_x (M, D) and part (ntiles, 2, D) = per-tile
+ *   (g_gamma, g_beta).  The weight and bias gradients are rh_linear_wgrad of (g_qkv[:, :D], Q) and (g_qkv[:, D:], x).
+ * replaces: sasrec.py:90-91 (LayerNorm, the in-projection of nn.MultiheadAttention with query != key) and their autograd.
+ *
+ * rh_sasrec_ffn_fwd: attn (M, D) (the heads' output before out_proj), Q (M, D) -> y = Q + attn Wo^T + bo; z = LN(y);
+ *   a = relu(dropout1(z W1^T + b1)); out = m (z + dropout2(a W2^T + b2)); ONE launch for the chain (the counter's advance
+ *   is a one-thread launch behind it, as in rh_softmax_attn_fwd).  Saves y, z, a (M, D) and stats (M, 2).
+ * rh_sasrec_ffn_bwd: g_out (M, D) -> g_attn, g_Q (M, D); g_f = g (a W2^T + b2) and g_h = g (z W1^T + b1) (M, D) are emitted
+ *   as the operands of the weight gradients, formed by rh_linear_wgrad: (g_f, a) for W2 / b2, (g_h, z) for W1 / b1,
+ *   (g_Q, attn) for Wo / bo (g_y = g_Q); part (ntiles, 2, D) = per-tile (g_gamma, g_beta).  ONE launch.
+ * replaces: sasrec.py:91-98 (out_proj, residual, LayerNorm, PointWiseFeedForward sasrec.py:173-177, mask) and their
+ *           autograd.
+ *
+ * rh_sasrec_head_fwd: s = LN(x) (M = B L rows); pos_logit, neg_logit (M,) = s . pos_e, s . neg_e with pos_e / neg_e
+ *   (B, L, D) slices of the gather (row (b, l) at b *_bstride + l e_rstride).  pos_e = neg_e = null: LayerNorm only (s written; the logits
+ *   may be null); s may be null when the logits are wanted.
+ * rh_sasrec_head_bwd: g_s (M, D) or null, g_pos, g_neg (M,) or null -> g_x (M, D), g_pos_e, g_neg_e (B, L, D) contiguous,
+ *   part (ceil(M / 64), 2, D) = per-workgroup (g_gamma, g_beta).
+ * replaces: sasrec.py:100 (last_layernorm) and 156-157 (the two masked products and sums), torch.nn.LayerNorm of the
+ *           selected rows in user_tower, and their autograd. */
+int rh_sasrec_ntiles(int M, int D, int* ntiles);
+int rh_sasrec_input_fwd(const int64_t* seq, const float* e, int64_t e_bstride, int64_t e_rstride, const float* P, int B, int L,
+                        int D, int max_len, float scale, float p_drop, int64_t* rng, int64_t* saved_ctr, float* x0, void* stream);
+int rh_sasrec_input_bwd(const int64_t* seq, const float* g_x0, int B, int L, int D, int max_len, float scale, float p_drop,
+                        const int64_t* rng, const int64_t* saved_ctr, float* g_e, float* g_P, void* stream);
+int rh_sasrec_attn_in_fwd(const float* x, const float* gamma, const float* beta, float eps, const float* w, const float* b,
+                          int M, int D, float* Q, float* qkv, float* stats, void* stream);
+int rh_sasrec_attn_in_bwd(const float* x, const float* gamma, const float* w, const float* stats, const float* g_qkv,
+                          const float* g_Q, int M, int D, float* g_x, float* part, void* stream);
+int rh_sasrec_ffn_fwd(const float* attn, const float* Q, const int64_t* seq, const float* wo, const float* bo,
+                      const float* gamma, const float* beta, float eps, const float* w1, const float* b1, const float* w2,
+                      const float* b2, int M, int D, float p_drop, int64_t* rng, int64_t* saved_ctr, float* y, float* z,
+                      float* a, float* stats, float* out, void* stream);
+int rh_sasrec_ffn_bwd(const int64_t* seq, const float* wo, const float* gamma, const float* w1, const float* w2,
+                      const float* y, const float* a, const float* stats, const float* g_out, int M, int D, float p_drop,
+                      const int64_t* rng, const int64_t* saved_ctr, float* g_f, float* g_h, float* g_Q, float* g_attn,
+                      float* part, void* stream);
+int rh_sasrec_head_fwd(const float* x, const float* gamma, const float* beta, float eps, const float* pos_e,
+                       int64_t pos_bstride, const float* neg_e, int64_t neg_bstride, int64_t e_rstride, int B, int L, int D,
+                       float* s, float* pos_logit, float* neg_logit, float* stats, void* stream);
+int rh_sasrec_head_bwd(const float* x, const float* gamma, const float* beta, const float* stats, const float* pos_e,
+                       int64_t pos_bstride, const float* neg_e, int64_t neg_bstride, int64_t e_rstride, const float* g_s,
+                       const float* g_pos, const float* g_neg, int B, int L, int D, float* g_x, float* g_pos_e, float* g_neg_e, float* part,
+                       void* stream);
+
 /* ---- row-sharded tables (one shard per rank) -----------------------------------------------------------------------
  * Global row g of a table lives on rank g % world as local row g / world.  rh_shard_localize rewrites an index matrix
  * idx (n_rows, F) (int64 / int32, contiguous: the all-gathered indices of the global batch) for this rank's shards:

@@ -1,0 +1,142 @@
+"""SASRec without a GPU: the float64 restatement of the four fused stages (tests/sasrec_oracle.py) reproduces the
+reference's intermediates and gradients (sasrec_layers.npz), and the mirror class has the reference's state_dict keys,
+shapes and initialisation statistics, is listed for integration.enable() and refuses bad arguments before any launch."""
+import json
+
+import numpy as np
+import pytest
+import torch
+
+import sasrec_oracle as O
+from conftest import load_golden
+
+EPS = 1e-8
+
+
+def close(got, want, what, scale=1e-5):
+    """To fp32 rounding of the fixture: the project's kernel convention (rtol 1e-4, atol 1e-5 max|want|)."""
+    want = np.asarray(want, np.float64)
+    np.testing.assert_allclose(got, want, rtol=1e-4, atol=scale * float(np.abs(want).max()) + 1e-12, err_msg=what)
+
+
+def block_chain(gold, k, H):
+    """One block + input stage + head in float64 from the fixture's ids and parameters -> (intermediates, gradients)."""
+    sd = {n[len(k + "sd."):]: gold[n].astype(np.float64) for n in gold.files if n.startswith(k + "sd.")}
+    seq, pos, neg = gold[k + "seq"], gold[k + "pos"], gold[k + "neg"]
+    table, P = sd["item_emb.embed_dict.seq.weight"], sd["position_emb.weight"]
+    pa, pm, pf, pw = "attention_layernorms.0.", "attention_layers.0.", "forward_layernorms.0.", "forward_layers.0."
+    x0 = O.input_fwd(seq, table[seq], P)
+    Q, qkv, c_in = O.attn_in_fwd(x0, sd[pa + "weight"], sd[pa + "bias"], sd[pm + "in_proj_weight"], sd[pm + "in_proj_bias"], EPS)
+    att, c_att = O.attention_fwd(qkv, H)
+    out, inter = O.ffn_fwd(att, Q, seq, sd[pm + "out_proj.weight"], sd[pm + "out_proj.bias"], sd[pf + "weight"],
+                           sd[pf + "bias"], sd[pw + "conv1.weight"], sd[pw + "conv1.bias"], sd[pw + "conv2.weight"],
+                           sd[pw + "conv2.bias"], EPS)
+    s, pl, nl, c_head = O.head_fwd(out, sd["last_layernorm.weight"], sd["last_layernorm.bias"], table[pos], table[neg], EPS)
+    fwd = dict(x0=x0, Q=Q, mha=att @ sd[pm + "out_proj.weight"].T + sd[pm + "out_proj.bias"], y=inter["y"], z=inter["z"],
+               block=out, s=s, pos_logits=pl, neg_logits=nl)
+    gh = O.head_bwd(gold[k + "g_pos_logits"], gold[k + "g_neg_logits"], sd["last_layernorm.weight"], c_head)
+    gf = O.ffn_bwd(gh["x"], sd[pf + "weight"], inter)
+    g_qkv = O.attention_bwd(gf["attn"], c_att)
+    gi = O.attn_in_bwd(sd[pa + "weight"], sd[pm + "in_proj_weight"], c_in, g_qkv, gf["Q"])
+    g_e, g_P = O.input_bwd(seq, gi["x"], P.shape[0])
+    g_table = np.zeros_like(table)
+    D = table.shape[1]
+    for ids, g in ((seq, g_e), (pos, gh["pos_e"]), (neg, gh["neg_e"])):
+        np.add.at(g_table, ids.reshape(-1), g.reshape(-1, D))
+    shape = sd[pw + "conv1.weight"].shape
+    grads = {"item_emb.embed_dict.seq.weight": g_table, "position_emb.weight": g_P, pa + "weight": gi["gamma"],
+             pa + "bias": gi["beta"], pm + "in_proj_weight": gi["W"], pm + "in_proj_bias": gi["b"],
+             pm + "out_proj.weight": gf["Wo"], pm + "out_proj.bias": gf["bo"], pf + "weight": gf["gamma"],
+             pf + "bias": gf["beta"], pw + "conv1.weight": gf["W1"].reshape(shape), pw + "conv1.bias": gf["b1"],
+             pw + "conv2.weight": gf["W2"].reshape(shape), pw + "conv2.bias": gf["b2"],
+             "last_layernorm.weight": gh["gamma"], "last_layernorm.bias": gh["beta"]}
+    g_inter = dict(g_block=gh["x"], g_y=gf["Q"], g_mha=gf["Q"], g_x0=gi["x"])
+    return fwd, grads, g_inter
+
+
+@pytest.mark.parametrize("cfg", ["b5l7d12h3", "b4l5d10h1"])
+def test_float64_oracle_reproduces_the_reference_block(cfg):
+    gold = load_golden("sasrec_layers.npz")
+    H = json.loads(str(gold["cfgs"]))[cfg][3]
+    k = cfg + "."
+    fwd, grads, g_inter = block_chain(gold, k, H)
+    for name, got in fwd.items():
+        close(got, gold[k + name], f"{cfg}: {name}")
+    for name, got in g_inter.items():
+        close(got, gold[k + name], f"{cfg}: {name}")
+    assert set(grads) == {n[len(k + "grad."):] for n in gold.files if n.startswith(k + "grad.")}
+    for name, got in grads.items():
+        close(got, gold[k + "grad." + name], f"{cfg}: grad {name}")
+
+
+def test_an_all_zero_row_through_the_oracle_layernorm_returns_beta():
+    rng = np.random.default_rng(0)
+    x = rng.standard_normal((3, 7))
+    x[1] = 0.0
+    gamma, beta = rng.standard_normal(7), rng.standard_normal(7)
+    out, (xh, rstd) = O.ln_fwd(x, gamma, beta, EPS)
+    assert np.array_equal(out[1], beta) and rstd[1, 0] == 1.0 / np.sqrt(EPS)
+    g_x, _, _ = O.ln_bwd(rng.standard_normal((3, 7)), gamma, (xh, rstd))
+    assert np.isfinite(g_x).all()
+
+
+def features(D, V=23):
+    from torch_rechub_amd.basic.features import SequenceFeature
+    return [SequenceFeature("seq", vocab_size=V, embed_dim=D, pooling="concat"),
+            SequenceFeature("pos", vocab_size=V, embed_dim=D, pooling="concat", shared_with="seq"),
+            SequenceFeature("neg", vocab_size=V, embed_dim=D, pooling="concat", shared_with="seq")]
+
+
+@pytest.mark.parametrize("cfg", ["d12h3b2", "d10h1b1"])
+def test_mirror_has_the_reference_keys_shapes_and_initialisation(cfg):
+    from torch_rechub_amd.models.matching import SASRec
+    gold = load_golden(f"model_sasrec_{cfg}.npz")
+    c = json.loads(str(gold["cfg"]))
+    torch.manual_seed(3)
+    model = SASRec(features(c["D"]), max_len=9, dropout_rate=0.0, num_blocks=c["blocks"], num_heads=c["H"])
+    sd = model.state_dict()
+    assert list(sd) == [str(n) for n in gold["sd_keys"]]
+    for n, t in sd.items():
+        want = gold["init." + n]
+        assert tuple(t.shape) == want.shape, n
+        got = t.numpy()
+        if "layernorm" in n or n.endswith("in_proj_bias") or n.endswith("out_proj.bias"):
+            assert np.array_equal(got, want), n  # ones / zeros
+        else:  # a drawn, zero-mean tensor of n samples: mean and spread within five standard errors of the fixture's
+            n_el, sigma = got.size, float(want.std())
+            assert abs(got.mean()) <= 5 * sigma / np.sqrt(n_el), n
+            assert abs(got.std() / sigma - 1) <= 5 / np.sqrt(2 * n_el), n
+            assert np.abs(got).max() <= 6 * sigma, n
+    model.load_state_dict({n[4:]: torch.from_numpy(gold[n]) for n in gold.files if n.startswith("sd0.")})
+
+
+def test_integration_lists_sasrec():
+    from torch_rechub_amd import integration
+    from torch_rechub_amd.models.matching import sasrec
+    assert "SASRec" in integration._MODELS["matching"]
+    assert integration._MODEL_PARTS["matching.sasrec"] == ("PointWiseFeedForward",)
+    assert hasattr(sasrec, "PointWiseFeedForward") and hasattr(sasrec, "SASRec")
+
+
+def test_argument_errors_are_raised_before_anything_runs():
+    """On CPU tensors: every refusal below comes before the first look at a device."""
+    from torch_rechub_amd.models.matching import SASRec
+    ids = torch.randint(1, 23, (2, 7))
+    x = {"seq": ids, "pos": ids, "neg": ids}
+    with pytest.raises(ValueError, match="not divisible"):
+        m = SASRec(features(12), max_len=9, num_heads=1)
+        m.attention_layers[0].num_heads = 5  # (nn.MultiheadAttention's own constructor asserts the same)
+        m(x)
+    with pytest.raises(AssertionError):
+        SASRec(features(12), max_len=9, num_heads=5)
+    with pytest.raises((ValueError, RuntimeError), match="128"):
+        SASRec(features(129), max_len=9)(x)
+    with pytest.raises(IndexError, match="index out of range in self"):
+        SASRec(features(12), max_len=6)(x)
+    with pytest.raises(IndexError, match="index out of range in self"):
+        SASRec(features(12), max_len=6).user_tower(x)
+    long_ids = torch.ones(1, 1025, dtype=torch.int64)  # within max_len, beyond the attention kernel's 1024 positions
+    with pytest.raises(RuntimeError, match="L <= 1024"):
+        SASRec(features(4, V=3), max_len=1100, num_blocks=1)({"seq": long_ids, "pos": long_ids, "neg": long_ids})
+    with pytest.raises(RuntimeError, match="HIP device"):  # and nothing falls back to the CPU
+        SASRec(features(12), max_len=9)(x)

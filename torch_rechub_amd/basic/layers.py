@@ -256,6 +256,41 @@ class EmbeddingLayer(nn.Module):
             return torch.cat([out] + self._dense_columns(x, dense_feas), dim=1)
         return out
 
+    def shared_rows(self, x, features, table=None):
+        """(B, sum of L_i, D) rows of features that all read ONE replicated table -- concat-pooled sequence features with
+        (B, L_i) ids, plain sparse features with (B,) ids (L_i = 1) -- as ONE gather launch, where ``forward`` takes one
+        launch per sequence feature and a concatenation (SASRec: history, positives and negatives of the shared item
+        table).  Several features: their ids land side by side in ONE buffer owned by this layer, as in ``_multi_lookup``
+        (its address, hence the gather's cached descriptor, stays fixed from the eager steps into a hipGraph capture).
+        ``table``: the embedding to read where the features do not name it themselves (SASRec's target item)."""
+        if table is None:
+            table = self.table_of(features[0])
+            if any(self.table_of(f) is not table for f in features):
+                raise ValueError("torch_rechub_amd: shared_rows needs features of one table")
+        if sharding.is_sharded(table):
+            raise RuntimeError("torch_rechub_amd: shared_rows on a row-sharded table is not supported")
+        if not _fusable_dim(int(table.weight.shape[1])):
+            raise RuntimeError(f"torch_rechub_amd: sequence embed_dim={features[0].embed_dim} has no HIP kernel (> 128)")
+        parts = [_as_index(x[f.name]) for f in features]
+        B = int(parts[0].shape[0])
+        if len(parts) == 1 and parts[0].dim() == 1:
+            # one plain sparse feature: the fused gather, which reads a strided id column (a DeviceDataLoader batch's) in place
+            out, _, _ = ops.fused_embedding(ops.EmbedCall([table.weight], [table.padding_idx], parts))
+            return out[:, :features[0].embed_dim].unsqueeze(1)
+        parts = [t.reshape(B, -1) for t in parts]
+        idx = parts[0]
+        if len(parts) > 1:
+            parts = [t if t.dtype == torch.int64 else t.long() for t in parts]
+            key = (B, tuple(int(t.shape[1]) for t in parts), str(parts[0].device))
+            idx = self.__dict__.setdefault("_shared_index", {}).get(key)
+            if idx is None:
+                if parts[0].is_cuda and torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("torch_rechub_amd: run the step eagerly once before capturing a hipGraph")
+                idx = self._shared_index[key] = torch.empty((B, sum(key[1])), dtype=torch.int64, device=parts[0].device)
+            torch.cat(parts, dim=1, out=idx)
+        rows = ops.seq_pool(table.weight, idx, "concat", table.padding_idx)
+        return rows[..., :features[0].embed_dim]  # (a PaddedEmbedding's zero padding columns are cut off as a view)
+
     def pieces(self, x, features):
         """The per-feature tensors of ``forward(x, features)`` as a list -- (B, D) per sparse feature, (B, L, D) per
         concat-pooled sequence feature -- for callers that take the (B, n, ...) result apart again feature by feature

@@ -28,11 +28,13 @@ _FEATURES = ("DenseFeature", "SparseFeature", "SequenceFeature")
 _ACTIVATIONS = ("Dice", "activation_layer")
 _MODELS = {"ranking": ("DeepFM", "WideDeep", "DCN", "DCNv2", "DIN", "DIEN", "BST", "AFM", "AutoInt", "EDCN", "FiBiNet",
                        "DeepFFM", "FatDeepFFM"),
-           "matching": ("DSSM", "YoutubeDNN", "MIND", "ComirecSA", "ComirecDR", "GRU4Rec", "NARM", "STAMP", "SINE"),
+           "matching": ("DSSM", "YoutubeDNN", "MIND", "ComirecSA", "ComirecDR", "GRU4Rec", "NARM", "STAMP", "SINE",
+                        "SASRec"),
            "multi_task": ("SharedBottom", "ESMM", "MMOE", "PLE", "AITM"),
            "generative": ("HSTUModel", "HLLMModel", "RQVAEModel")}
 # classes a reference module defines beside its model and does not re-export from the sub-package
-_MODEL_PARTS = {"generative.hllm": ("HLLMTransformerBlock",),
+_MODEL_PARTS = {"matching.sasrec": ("PointWiseFeedForward",),
+                "generative.hllm": ("HLLMTransformerBlock",),
                 "generative.rqvae": ("VectorQuantizer", "ResidualVectorQuantizer")}
 _TRAINERS = ("CTRTrainer", "MatchTrainer", "MTLTrainer", "SeqTrainer")
 # classes the reference keeps in a module of their own, not re-exported from the sub-package: (module, names)

@@ -1113,13 +1113,18 @@ def _offer_wgrad_slabs(weight, bias, partial, B):
     return dW, db
 
 
-def linear_wgrad(g, x, want_bias=True, weight=None, bias=None):
+def linear_wgrad(g, x, want_bias=True, weight=None, bias=None, out=None):
     """(dW (N, K), db (N,) | None) = (g^T x, colsum(g)) for g (B, N), x (B, K): split-batch f32 MFMA kernel.
 
     ``weight`` / ``bias``: the parameters these are the gradients of.  While the trainer's fast path has armed
     ``ops.deferred`` for them, the per-split slabs are NOT reduced here: they are registered and the function returns
-    None for that gradient (the step's packing launch sums them into the flat bucket)."""
+    None for that gradient (the step's packing launch sums them into the flat bucket).
+
+    ``out`` = (dW, db): contiguous buffers (slices of a larger gradient, say) the result is written into and returned as;
+    for gradients assembled from several products, which therefore cannot be deferred (``weight`` / ``bias`` are not taken)."""
     require_hip(g, x)
+    if out is not None and (weight is not None or bias is not None or not want_bias):
+        raise ValueError("linear_wgrad: out=(dW, db) goes without weight / bias and with want_bias")
     if g.stride(1) != 1:
         g = g.contiguous()
     if x.stride(1) != 1:
@@ -1127,7 +1132,13 @@ def linear_wgrad(g, x, want_bias=True, weight=None, bias=None):
     B, N = g.shape
     K = x.shape[1]
     dev = g.device
+    if out is not None:
+        dW, db = out
+        if tuple(dW.shape) != (N, K) or tuple(db.shape) != (N,) or not (dW.is_contiguous() and db.is_contiguous()):
+            raise ValueError(f"linear_wgrad: out must be contiguous ({N}, {K}) and ({N},) buffers")
     if B == 0:
+        if out is not None:
+            return dW.zero_(), db.zero_()
         return (torch.zeros((N, K), dtype=torch.float32, device=dev),
                 torch.zeros((N,), dtype=torch.float32, device=dev) if want_bias else None)
     partial = torch.empty(_lib.call("rh_linear_wgrad_workspace", B, N, K), dtype=torch.float32, device=dev)
@@ -1140,8 +1151,9 @@ def linear_wgrad(g, x, want_bias=True, weight=None, bias=None):
         if not (rider is not None and B < _WGRAD_GROUP_MAX_B and rider([(g, g.stride(0), x, x.stride(0), N, K, partial)], B)):
             _lib.call("rh_linear_wgrad_partial", _p(g), g.stride(0), _p(x), x.stride(0), B, N, K, _p(partial), _stream())
         return _offer_wgrad_slabs(weight, bias if want_bias else None, partial, B)
-    dW = torch.empty((N, K), dtype=torch.float32, device=dev)
-    db = torch.empty((N,), dtype=torch.float32, device=dev) if want_bias else None
+    if out is None:
+        dW = torch.empty((N, K), dtype=torch.float32, device=dev)
+        db = torch.empty((N,), dtype=torch.float32, device=dev) if want_bias else None
     _lib.call("rh_linear_wgrad", _p(g), g.stride(0), _p(x), x.stride(0), B, N, K, _p(dW), _p(db), _p(partial),
               _stream())
     return dW, db
@@ -3686,3 +3698,305 @@ def topk_items(q, table, k, bias=None, exclude=None, invalid=None, nsplit=None):
     _lib.call("rh_topk_fwd", _p(q), ldq, _p(table), _p(bias), _p(exclude) if S > 0 else _NULL, S,
               _p(invalid) if n_inv > 0 else _NULL, n_inv, M, D, V, k, nsplit, _p(work), _p(ids), _p(scores), _stream())
     return ids, scores
+
+
+# --------------------------------------------------------------------------------------------
+# SASRec: the transformer block around ops.softmax_attention, fused per row tile (csrc/sasrec.hip)
+# --------------------------------------------------------------------------------------------
+_SASREC_MAX_D = 128
+
+
+def _sasrec_check(what, D, *tensors):
+    """Before anything is allocated or launched: float32 tensors and a width the kernels take."""
+    if any(t is not None and t.dtype != torch.float32 for t in tensors):
+        raise ValueError(f"torch_rechub_amd: {what} takes float32 tensors")
+    if not 1 <= int(D) <= _SASREC_MAX_D:
+        from .models.matching._listwise import no_kernel
+        raise no_kernel(f"{what} at width {int(D)} (1 <= D <= {_SASREC_MAX_D})")
+
+
+def _sasrec_ntiles(M, D):
+    out = ctypes.c_int(0)
+    _lib.call("rh_sasrec_ntiles", int(M), int(D), ctypes.c_void_p(ctypes.addressof(out)))
+    return out.value
+
+
+def _ln_param_grads(part, D):
+    """(g_gamma, g_beta) (D,) from the per-workgroup partials (n, 2, D), summed in a fixed order."""
+    out = torch.empty((2 * D,), dtype=torch.float32, device=part.device)
+    _lib.call("rh_colsum", _p(part), int(part.shape[0]), 2 * D, _p(out), _NULL, 0, _NULL, _stream())
+    return out[:D], out[D:]
+
+
+def _sample_view(t, B, L, D):
+    """A (B, L, D) tensor as the kernels read it: unit column stride, rows and samples one stride apart each (a slice of
+    the (B, 3, L, >= D) gather, or a contiguous tensor) -> (tensor, sample stride, row stride)."""
+    if not (t.stride(2) == 1 and t.stride(1) >= D and t.stride(0) >= L * t.stride(1)):
+        t = t.contiguous()
+    return t, int(t.stride(0)), int(t.stride(1))
+
+
+class _SasrecInputFn(torch.autograd.Function):
+    """x0 (B, L, D) = m dropout(e sqrt(D) + P[l]), m = seq != 0."""
+
+    @staticmethod
+    def forward(ctx, seq, e, P, p):
+        B, L, D = (int(v) for v in e.shape)
+        dev = e.device
+        e, ebs, ers = _sample_view(e, B, L, D)
+        x0 = torch.empty((B, L, D), dtype=torch.float32, device=dev)
+        rng = _dropout_rng(dev) if p > 0 else None
+        ctr = torch.empty(1, dtype=torch.int64, device=dev) if p > 0 else None
+        scale = float(torch.tensor(float(D)**0.5, dtype=torch.float32))
+        _lib.call("rh_sasrec_input_fwd", _p(seq), _p(e), ebs, ers, _p(P), B, L, D, int(P.shape[0]), scale, p, _p(rng), _p(ctr),
+                  _p(x0), _stream())
+        ctx.cfg = (B, L, D, int(P.shape[0]), scale, p)
+        ctx.save_for_backward(seq, rng, ctr)
+        return x0
+
+    @staticmethod
+    def backward(ctx, g):
+        seq, rng, ctr = ctx.saved_tensors
+        B, L, D, max_len, scale, p = ctx.cfg
+        g = g.contiguous()
+        g_e = torch.empty((B, L, D), dtype=torch.float32, device=g.device)
+        g_P = torch.empty((max_len, D), dtype=torch.float32, device=g.device)
+        _lib.call("rh_sasrec_input_bwd", _p(seq), _p(g), B, L, D, max_len, scale, p, _p(rng), _p(ctr), _p(g_e), _p(g_P),
+                  _stream())
+        return None, g_e, g_P, None
+
+
+def _seq_ids(seq, B, L):
+    if seq.dim() != 2 or tuple(seq.shape) != (B, L):
+        raise ValueError(f"torch_rechub_amd: the history ids must be (B, L) = ({B}, {L}), got {tuple(seq.shape)}")
+    return seq.to(torch.int64).contiguous()
+
+
+def _drop_p(p, training):
+    p = float(p) if training else 0.0
+    if not 0.0 <= p < 1.0:
+        raise RuntimeError(f"torch_rechub_amd: dropout p={p} has no HIP kernel (0 <= p < 1)")
+    return p
+
+
+def sasrec_input(seq, e, P, dropout_p=0.0, training=True):
+    """SASRec's input stage x0 (B, L, D) = m dropout(e sqrt(D) + P[:L]) from the history ids seq (B, L) (0 = pad, m = seq
+    != 0), their gathered rows e (B, L, D) (a slice of the (B, 3, L, D) gather is read in place) and the position table P
+    (max_len, D), L <= max_len."""
+    require_hip(seq, e, P)
+    if e.dim() != 3 or P.dim() != 2 or P.shape[1] != e.shape[2]:
+        raise ValueError("sasrec_input: e (B, L, D) and P (max_len, D) expected")
+    B, L, D = (int(v) for v in e.shape)
+    _sasrec_check("SASRec's input stage", D, e, P)
+    if L > P.shape[0]:
+        raise IndexError("index out of range in self")  # the reference's position lookup fails with this error
+    return _SasrecInputFn.apply(_seq_ids(seq, B, L), e, P.contiguous(), _drop_p(dropout_p, training))
+
+
+class _SasrecAttnInFn(torch.autograd.Function):
+    """(Q (M, D), qkv (M, 3 D)) = (LN(x), [Q Wq^T + bq | x Wk^T + bk | x Wv^T + bv])."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, w, b, eps):
+        M, D = (int(v) for v in x.shape)
+        dev = x.device
+        Q = torch.empty((M, D), dtype=torch.float32, device=dev)
+        qkv = torch.empty((M, 3 * D), dtype=torch.float32, device=dev)
+        stats = torch.empty((M, 2), dtype=torch.float32, device=dev)
+        _lib.call("rh_sasrec_attn_in_fwd", _p(x), _p(gamma), _p(beta), eps, _p(w), _p(b), M, D, _p(Q), _p(qkv), _p(stats),
+                  _stream())
+        ctx.save_for_backward(x, gamma, w, Q, stats)
+        return Q, qkv
+
+    @staticmethod
+    def backward(ctx, g_Q, g_qkv):
+        x, gamma, w, Q, stats = ctx.saved_tensors
+        M, D = (int(v) for v in x.shape)
+        dev = x.device
+        g_Q, g_qkv = g_Q.contiguous(), g_qkv.contiguous()
+        g_x = torch.empty((M, D), dtype=torch.float32, device=dev)
+        g_w = torch.empty((3 * D, D), dtype=torch.float32, device=dev)
+        g_b = torch.empty((3 * D,), dtype=torch.float32, device=dev)
+        if M == 0:
+            z = torch.zeros((D,), dtype=torch.float32, device=dev)
+            return g_x, z, z.clone(), g_w.zero_(), g_b.zero_(), None
+        part = torch.empty((_sasrec_ntiles(M, D), 2, D), dtype=torch.float32, device=dev)
+        _lib.call("rh_sasrec_attn_in_bwd", _p(x), _p(gamma), _p(w), _p(stats), _p(g_qkv), _p(g_Q), M, D, _p(g_x), _p(part),
+                  _stream())
+        g_gamma, g_beta = _ln_param_grads(part, D)
+        linear_wgrad(g_qkv[:, :D], Q, out=(g_w[:D], g_b[:D]))
+        linear_wgrad(g_qkv[:, D:], x, out=(g_w[D:], g_b[D:]))
+        return g_x, g_gamma, g_beta, g_w, g_b, None
+
+
+def sasrec_attention_in(x, ln_weight, ln_bias, in_proj_weight, in_proj_bias, eps=1e-8):
+    """(Q, qkv) for one SASRec block from x (..., D): Q = LayerNorm(x) (the attention's query input and the block's
+    residual) and qkv (..., 3 D) = the in-projection of nn.MultiheadAttention with query Q and key = value = x.  The three
+    column blocks of qkv feed ops.softmax_attention without a copy."""
+    require_hip(x, ln_weight, ln_bias, in_proj_weight, in_proj_bias)
+    D = int(x.shape[-1])
+    _sasrec_check("SASRec's LayerNorm + in-projection", D, x, ln_weight, ln_bias, in_proj_weight, in_proj_bias)
+    if tuple(in_proj_weight.shape) != (3 * D, D) or tuple(in_proj_bias.shape) != (3 * D,) or \
+            tuple(ln_weight.shape) != (D,) or tuple(ln_bias.shape) != (D,):
+        raise ValueError("sasrec_attention_in: LayerNorm (D,), in_proj_weight (3 D, D), in_proj_bias (3 D,) expected")
+    lead = tuple(x.shape[:-1])
+    Q, qkv = _SasrecAttnInFn.apply(x.reshape(-1, D).contiguous(), ln_weight.contiguous(), ln_bias.contiguous(),
+                                   in_proj_weight.contiguous(), in_proj_bias.contiguous(), float(eps))
+    return Q.view(lead + (D,)), qkv.view(lead + (3 * D,))
+
+
+class _SasrecFfnFn(torch.autograd.Function):
+    """out = m (z + dropout2(W2 relu(dropout1(W1 z + b1)) + b2)), z = LN(Q + attn Wo^T + bo); one launch each way, the
+    D x D weight gradients by rh_linear_wgrad on the operands the backward emits."""
+
+    @staticmethod
+    def forward(ctx, attn, Q, seq, wo, bo, gamma, beta, w1, b1, w2, b2, eps, p):
+        M, D = (int(v) for v in attn.shape)
+        dev = attn.device
+        y, z, a, out = (torch.empty((M, D), dtype=torch.float32, device=dev) for _ in range(4))
+        stats = torch.empty((M, 2), dtype=torch.float32, device=dev)
+        rng = _dropout_rng(dev) if p > 0 else None
+        ctr = torch.empty(1, dtype=torch.int64, device=dev) if p > 0 else None
+        _lib.call("rh_sasrec_ffn_fwd", _p(attn), _p(Q), _p(seq), _p(wo), _p(bo), _p(gamma), _p(beta), eps, _p(w1), _p(b1),
+                  _p(w2), _p(b2), M, D, p, _p(rng), _p(ctr), _p(y), _p(z), _p(a), _p(stats), _p(out), _stream())
+        ctx.p = p
+        ctx.save_for_backward(attn, seq, wo, gamma, w1, w2, y, z, a, stats, rng, ctr)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        attn, seq, wo, gamma, w1, w2, y, z, a, stats, rng, ctr = ctx.saved_tensors
+        M, D = (int(v) for v in attn.shape)
+        dev = attn.device
+        g = g.contiguous()
+        g_f, g_h, g_Q, g_attn = (torch.empty((M, D), dtype=torch.float32, device=dev) for _ in range(4))
+        g_w = torch.empty((3, D, D), dtype=torch.float32, device=dev)  # Wo, W1, W2
+        g_b = torch.empty((3, D), dtype=torch.float32, device=dev)
+        if M == 0:
+            zero = torch.zeros((D,), dtype=torch.float32, device=dev)
+            g_w.zero_(), g_b.zero_()
+            return (g_attn, g_Q, None, g_w[0], g_b[0], zero, zero.clone(), g_w[1].view(w1.shape), g_b[1],
+                    g_w[2].view(w2.shape), g_b[2], None, None)
+        part = torch.empty((_sasrec_ntiles(M, D), 2, D), dtype=torch.float32, device=dev)
+        _lib.call("rh_sasrec_ffn_bwd", _p(seq), _p(wo), _p(gamma), _p(w1), _p(w2), _p(y), _p(a), _p(stats), _p(g), M, D, ctx.p,
+                  _p(rng), _p(ctr), _p(g_f), _p(g_h), _p(g_Q), _p(g_attn), _p(part), _stream())
+        g_gamma, g_beta = _ln_param_grads(part, D)
+        linear_wgrad(g_Q, attn, out=(g_w[0], g_b[0]))
+        linear_wgrad(g_h, z, out=(g_w[1], g_b[1]))
+        linear_wgrad(g_f, a, out=(g_w[2], g_b[2]))
+        return (g_attn, g_Q, None, g_w[0], g_b[0], g_gamma, g_beta, g_w[1].view(w1.shape), g_b[1], g_w[2].view(w2.shape),
+                g_b[2], None, None)
+
+
+def sasrec_ffn(attn, Q, seq, out_proj_weight, out_proj_bias, ln_weight, ln_bias, w1, b1, w2, b2, eps=1e-8, dropout_p=0.0,
+               training=True):
+    """The second half of a SASRec block, (B, L, D): y = Q + attn Wo^T + bo, z = LayerNorm(y), out = m (z + dropout(W2
+    relu(dropout(W1 z + b1)) + b2)) with m = seq != 0.  attn (B, L, D) is the heads' output (ops.softmax_attention), Q the
+    normalised query (ops.sasrec_attention_in); w1 / w2 are (D, D) or Conv1d's (D, D, 1)."""
+    require_hip(attn, Q, seq, out_proj_weight, out_proj_bias, ln_weight, ln_bias, w1, b1, w2, b2)
+    if attn.dim() != 3 or attn.shape != Q.shape:
+        raise ValueError("sasrec_ffn: attn and Q (B, L, D) expected")
+    B, L, D = (int(v) for v in attn.shape)
+    _sasrec_check("SASRec's out-projection + FFN", D, attn, Q, out_proj_weight, out_proj_bias, ln_weight, ln_bias, w1, b1, w2,
+                  b2)
+    if any(w.numel() != D * D for w in (out_proj_weight, w1, w2)) or any(
+            tuple(v.shape) != (D,) for v in (out_proj_bias, ln_weight, ln_bias, b1, b2)):
+        raise ValueError("sasrec_ffn: three (D, D) weights and five (D,) vectors expected")
+    out = _SasrecFfnFn.apply(attn.reshape(B * L, D).contiguous(), Q.reshape(B * L, D).contiguous(), _seq_ids(seq, B, L),
+                             out_proj_weight.contiguous(), out_proj_bias.contiguous(), ln_weight.contiguous(),
+                             ln_bias.contiguous(), w1.contiguous(), b1.contiguous(), w2.contiguous(), b2.contiguous(),
+                             float(eps), _drop_p(dropout_p, training))
+    return out.view(B, L, D)
+
+
+class _SasrecHeadFn(torch.autograd.Function):
+    """(pos_logits, neg_logits) (B, L) = LN(x) . pos_e, LN(x) . neg_e."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, pos_e, neg_e, eps):
+        B, L, D = (int(v) for v in x.shape)
+        dev = x.device
+        pos_e, pbs, prs = _sample_view(pos_e, B, L, D)
+        neg_e, nbs, nrs = _sample_view(neg_e, B, L, D)
+        if prs != nrs:
+            pos_e, pbs, prs = pos_e.contiguous(), L * D, D
+            neg_e, nbs, nrs = neg_e.contiguous(), L * D, D
+        pos = torch.empty((B, L), dtype=torch.float32, device=dev)
+        neg = torch.empty((B, L), dtype=torch.float32, device=dev)
+        stats = torch.empty((B * L, 2), dtype=torch.float32, device=dev)
+        _lib.call("rh_sasrec_head_fwd", _p(x), _p(gamma), _p(beta), eps, _p(pos_e), pbs, _p(neg_e), nbs, prs, B, L, D, _NULL,
+                  _p(pos), _p(neg), _p(stats), _stream())
+        ctx.strides = (pbs, nbs, prs)
+        ctx.save_for_backward(x, gamma, beta, pos_e, neg_e, stats)
+        return pos, neg
+
+    @staticmethod
+    def backward(ctx, g_pos, g_neg):
+        x, gamma, beta, pos_e, neg_e, stats = ctx.saved_tensors
+        B, L, D = (int(v) for v in x.shape)
+        dev = x.device
+        g_pos, g_neg = g_pos.contiguous(), g_neg.contiguous()
+        g_x, g_pe, g_ne = (torch.empty((B, L, D), dtype=torch.float32, device=dev) for _ in range(3))
+        if B * L == 0:
+            z = torch.zeros((D,), dtype=torch.float32, device=dev)
+            return g_x, z, z.clone(), g_pe, g_ne, None
+        part = torch.empty((-(-B * L // 64), 2, D), dtype=torch.float32, device=dev)
+        _lib.call("rh_sasrec_head_bwd", _p(x), _p(gamma), _p(beta), _p(stats), _p(pos_e), ctx.strides[0], _p(neg_e),
+                  ctx.strides[1], ctx.strides[2], _NULL, _p(g_pos), _p(g_neg), B, L, D, _p(g_x), _p(g_pe), _p(g_ne), _p(part), _stream())
+        g_gamma, g_beta = _ln_param_grads(part, D)
+        return g_x, g_gamma, g_beta, g_pe, g_ne, None
+
+
+class _LayerNormFn(torch.autograd.Function):
+    """LayerNorm over the last axis of (M, D) (the head kernels without their products)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps):
+        M, D = (int(v) for v in x.shape)
+        s = torch.empty((M, D), dtype=torch.float32, device=x.device)
+        stats = torch.empty((M, 2), dtype=torch.float32, device=x.device)
+        _lib.call("rh_sasrec_head_fwd", _p(x), _p(gamma), _p(beta), eps, _NULL, 0, _NULL, 0, 0, M, 1, D, _p(s), _NULL, _NULL,
+                  _p(stats), _stream())
+        ctx.save_for_backward(x, gamma, beta, stats)
+        return s
+
+    @staticmethod
+    def backward(ctx, g):
+        x, gamma, beta, stats = ctx.saved_tensors
+        M, D = (int(v) for v in x.shape)
+        dev = x.device
+        g = g.contiguous()
+        g_x = torch.empty((M, D), dtype=torch.float32, device=dev)
+        if M == 0:
+            z = torch.zeros((D,), dtype=torch.float32, device=dev)
+            return g_x, z, z.clone(), None
+        part = torch.empty((-(-M // 64), 2, D), dtype=torch.float32, device=dev)
+        _lib.call("rh_sasrec_head_bwd", _p(x), _p(gamma), _p(beta), _p(stats), _NULL, 0, _NULL, 0, 0, _p(g), _NULL, _NULL, M, 1,
+                  D, _p(g_x), _NULL, _NULL, _p(part), _stream())
+        g_gamma, g_beta = _ln_param_grads(part, D)
+        return g_x, g_gamma, g_beta, None
+
+
+def layer_norm(x, weight, bias, eps=1e-5):
+    """F.layer_norm(x, (D,), weight, bias, eps) over the last axis of a float32 (..., D) tensor, D <= 128: two-pass
+    variance, so an all-zero row gives exactly ``bias``; the weight and bias gradients are summed in a fixed order."""
+    require_hip(x, weight, bias)
+    D = int(x.shape[-1])
+    _sasrec_check("LayerNorm", D, x, weight, bias)
+    if tuple(weight.shape) != (D,) or tuple(bias.shape) != (D,):
+        raise ValueError("layer_norm: weight and bias (D,) expected")
+    out = _LayerNormFn.apply(x.reshape(-1, D).contiguous(), weight.contiguous(), bias.contiguous(), float(eps))
+    return out.view(x.shape)
+
+
+def sasrec_head(x, ln_weight, ln_bias, pos_e, neg_e, eps=1e-8):
+    """SASRec's training head: (pos_logits, neg_logits) (B, L) = sum_d LayerNorm(x) pos_e, sum_d LayerNorm(x) neg_e for x,
+    pos_e, neg_e (B, L, D); pos_e / neg_e may be slices of the (B, 3, L, D) gather (read in place)."""
+    require_hip(x, ln_weight, ln_bias, pos_e, neg_e)
+    if x.dim() != 3 or pos_e.shape != x.shape or neg_e.shape != x.shape:
+        raise ValueError("sasrec_head: x, pos_e, neg_e (B, L, D) expected")
+    D = int(x.shape[2])
+    _sasrec_check("SASRec's final LayerNorm + logits", D, x, ln_weight, ln_bias, pos_e, neg_e)
+    if tuple(ln_weight.shape) != (D,) or tuple(ln_bias.shape) != (D,):
+        raise ValueError("sasrec_head: LayerNorm weight and bias (D,) expected")
+    return _SasrecHeadFn.apply(x.contiguous(), ln_weight.contiguous(), ln_bias.contiguous(), pos_e, neg_e, float(eps))
