@@ -159,6 +159,26 @@ def test_given_indices_replace_the_search():
     np.testing.assert_allclose(c["r"][2], c["r"][1] - cbs[1].double().numpy()[given])
 
 
+def test_shape_cases_exclude_at_most_two_percent_of_their_rows():
+    """The cases of test_gpu_sine_rq_topk_shapes.py: the rows left out of the comparison (an arg-min gap below 1e-4) follow
+    from the inputs and the oracle alone, and the table reaches the tile, stride and chunk paths its comments name."""
+    from retrieval_shape_cases import MAX_EXCLUDED, MIN_GAP, RQ_CASES, rq_tile_codes
+    assert [rq_tile_codes(E) for E in (1, 47, 48, 63, 64, 127, 128)] == [256, 256, 192, 192, 128, 64, 64]
+    tiles = {rq_tile_codes(E) for _, E, sizes, _ in RQ_CASES if any(0 < n % rq_tile_codes(E) < n for n in sizes)}
+    assert tiles == {256, 192, 128, 64}  # a partial last tile behind a full one, at every tile size
+    assert any(0 < n % rq_tile_codes(E) < 64 < n for _, E, sizes, _ in RQ_CASES for n in sizes)
+    assert any(N > 2048 * 16 and N * E > 4096 * 256 for N, E, _, _ in RQ_CASES)      # the forward's and g_x's second trips
+    assert any(N > 1024 and 63 * -(-N // 64) >= N for N, _, _, _ in RQ_CASES)         # a chunk that starts past N
+    assert any(E == 128 and sizes == [1024] * 8 for _, E, sizes, _ in RQ_CASES)
+    for N, E, sizes, seed in RQ_CASES:
+        x, cbs = draw_inputs(N, E, sizes, seed)
+        x_q, loss, idx, c = np_rq_forward(x.numpy(), [t.numpy() for t in cbs], BETA)
+        excluded = int((c["gap"] < MIN_GAP).sum())
+        print(f"({N}, {E}, {sizes}, {seed}): {excluded} of {N} rows excluded")
+        assert np.isfinite(x_q).all() and np.isfinite(loss)
+        assert excluded <= MAX_EXCLUDED * N, (N, E, sizes, seed, excluded)
+
+
 def test_host_sinkhorn_reproduces_the_fixture(layers):
     Q = np_sinkhorn(layers["sk_dc"], float(layers["sk_epsilon"]), int(layers["sk_iters"]))
     np.testing.assert_allclose(Q, layers["sk_Q"], rtol=1e-9, atol=1e-300)

@@ -259,6 +259,27 @@ def test_top_k_takes_the_lower_index_on_ties_like_torch():
     assert idx.tolist() == [[1, 2, 0]]
 
 
+def test_shape_cases_exclude_at_most_two_percent_of_their_rows():
+    """The cases of test_gpu_sine_rq_topk_shapes.py: the rows left out of the comparison (a top-k gap below 1e-4) follow
+    from the inputs and the oracle alone, and every value of the oracle is finite at these limits."""
+    from retrieval_shape_cases import (MAX_EXCLUDED, MIN_GAP, SINE_AGG_ONLY_CASE, SINE_CASES, SINE_TEMPERATURE,
+                                       SINE_WARM_TEMPERATURE)
+    assert any(S * E % 4 for _, S, E, _, _, _, _ in SINE_CASES) and any(K == T > 1 for _, _, _, T, K, _, _ in SINE_CASES)
+    assert {1, 64, 65} <= {E for _, _, E, _, _, _, _ in SINE_CASES} and SINE_AGG_ONLY_CASE[0] > 16384 * 4
+    for B, S, E, T, K, seed, holes in SINE_CASES + [SINE_AGG_ONLY_CASE]:
+        inp = draw_inputs(B, S, E, T, K, seed, holes)
+        assert not inp["mask"][0].any()
+        s_u = oracle(inp, SINE_TEMPERATURE)["s_u"]
+        keep = top_k_gap(s_u, K) >= MIN_GAP
+        excluded = int((~keep).sum())
+        print(f"({B}, {S}, {E}, {T}, {K}, {seed}, {holes}): {excluded} of {B} rows excluded")
+        assert excluded <= MAX_EXCLUDED * B, (B, S, E, T, K, seed, excluded)
+        for temperature in (SINE_TEMPERATURE, SINE_WARM_TEMPERATURE):
+            o = oracle(inp, temperature, keep_rows=keep)
+            for name, v in o.items():
+                assert name == "cache" or np.isfinite(v).all(), (B, S, E, T, K, seed, temperature, name)
+
+
 # ---- the model ------------------------------------------------------------------------------------------------------------
 def test_sine_is_exported_with_the_reference_layout():
     from torch_rechub_amd.models import matching
