@@ -1112,6 +1112,45 @@ int rh_shard_localize(const void* idx, int idx_is_i64, int64_t n_rows, int F, co
  * beyond int32 stay out of range, below -1 -> -1); written into the caller's slice of the gather buffer (in-place collective). */
 int rh_shard_narrow(const int64_t* idx, int64_t ld, int64_t n_rows, int F, int32_t* out, void* stream);
 
+/* ---- two-tower score tails and the SENET field gate (csrc/twotower.hip) ---------------------------------------------
+ * fp32, one wavefront per row, no atomics: every backward run twice gives the same bits.  A refusal (RH_E_*) returns
+ * before any launch and touches nothing.  rh_twotower_nblocks answers through a HOST int, like rh_sine_nchunks: *nblocks = the
+ * workgroups a launch over B rows uses (the rows of rh_senet_bwd's w_partial).
+ * rh_band_logits_fwd: logits (B, K1)[i, k] = (u_i . v_j / (max(||u_i||, eps) max(||v_j||, eps)) - log w_j) / temperature,
+ *   j = (i + k) mod B; nu (B,) = ||u_i||, nv (B,) = ||v_j|| saved.  u, v (B, D) with row strides ldu, ldv; w (B,).
+ * rh_band_logits_bwd: g (B, K1) -> g_u (B, D), g_v (B, D), both contiguous and fully written by the wavefront of their row:
+ *   g_u[r] over the item rows (r + k) mod B, g_v[r] over the user rows (r - k) mod B, ascending k.  As in ATen, the clamp
+ *   takes no part in the gradient: dc/du = (v^ - c u / ||u||) / max(||u||, eps), and v^ / eps for a zero row.  w gets no
+ *   gradient.
+ *   1 <= D <= 1024, 1 <= K1 <= B, else RH_E_UNSUPPORTED.
+ * replaces: torch.cosine_similarity(u.unsqueeze(1), v, dim=2), the broadcast log-weight subtraction, the [index0, index1]
+ *           gather and the division of YoutubeSBC.forward torch_rechub/models/matching/youtube_sbc.py:61-80, whose
+ *           intermediates are (B, B) and (B, B, D).
+ * rh_pair_cosine_fwd: pos (B,) = n(hu) . n(hp), neg (B,) = n(hu) . n(hn), n(x) = x / max(||x||, eps) row-wise; nrm (3, B) =
+ *   the three norms saved.  rh_pair_cosine_bwd: g_pos, g_neg (B,) -> g_hu, g_hp, g_hn (B, D) contiguous.  1 <= D <= 1024.
+ * replaces: the three F.normalize calls and two multiply-sum reductions of FaceBookDSSM
+ *           torch_rechub/models/matching/dssm_facebook.py:52-53,64,75-76.
+ * rh_senet_fwd: x (B, F, D) with sample stride ldx (a sample's F D values contiguous), w1 (R, F), w2 (F, R) ->
+ *   z (B, F) = mean_d x, h (B, R) = relu(w1 z), a (B, F) = relu(w2 h), y (B, F D) contiguous = x a[..., None].
+ * rh_senet_bwd: g (B, F, D) with sample stride ldg -> g_x (B, F D) contiguous; w_partial (*nblocks of rh_twotower_nblocks, 2 R F) =
+ *   per-workgroup sums [g_w1 (R, F) | g_w2 (F, R)] over the workgroup's samples in ascending order (g_w = rh_colsum of it).
+ *   ReLU's derivative at 0 is 0.  1 <= R <= F <= 64, 1 <= D <= 256, else RH_E_UNSUPPORTED.
+ * replaces: SENETLayer.forward torch_rechub/basic/layers.py:525-529 and its autograd. */
+int rh_twotower_nblocks(int B, int* nblocks);
+int rh_band_logits_fwd(const float* u, int64_t ldu, const float* v, int64_t ldv, const float* w, int B, int D, int K1,
+                       float temperature, float eps, float* logits, float* nu, float* nv, void* stream);
+int rh_band_logits_bwd(const float* u, int64_t ldu, const float* v, int64_t ldv, const float* nu, const float* nv, const float* g,
+                       int B, int D, int K1, float temperature, float eps, float* g_u, float* g_v, void* stream);
+int rh_pair_cosine_fwd(const float* hu, int64_t ldu, const float* hp, int64_t ldp, const float* hn, int64_t ldn, int B, int D,
+                       float eps, float* pos, float* neg, float* nrm, void* stream);
+int rh_pair_cosine_bwd(const float* hu, int64_t ldu, const float* hp, int64_t ldp, const float* hn, int64_t ldn, const float* nrm,
+                       const float* g_pos, const float* g_neg, int B, int D, float eps, float* g_hu, float* g_hp, float* g_hn,
+                       void* stream);
+int rh_senet_fwd(const float* x, int64_t ldx, const float* w1, const float* w2, int B, int F, int R, int D, float* y, float* z,
+                 float* h, float* a, void* stream);
+int rh_senet_bwd(const float* x, int64_t ldx, const float* w1, const float* w2, const float* z, const float* h, const float* a,
+                 const float* g, int64_t ldg, int B, int F, int R, int D, float* g_x, float* w_partial, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -638,15 +638,21 @@ class CrossNetMix(nn.Module):
 
 
 class SENETLayer(nn.Module):
-    """SENET field gating: a = relu(W2 relu(W1 mean_d(x))), out = x * a[..., None] (reference layers.py:509-529)."""
+    """SENET field gating: a = relu(W2 relu(W1 mean_d(x))), out = x * a[..., None] (reference layers.py:509-529).
+
+    ``fused`` (off unless the owner sets it: the SENet DSSM does, FiBiNET does not) runs the whole layer as one HIP launch
+    each way (csrc/twotower.hip) for a HIP float32 (B, F, D) block with F <= 64, D <= 256."""
 
     def __init__(self, num_fields, reduction_ratio=3):
         super().__init__()
         hidden = max(1, int(num_fields / reduction_ratio))
         self.mlp = nn.Sequential(nn.Linear(num_fields, hidden, bias=False), nn.ReLU(), nn.Linear(hidden, num_fields, bias=False),
                                  nn.ReLU())
+        self.fused = False
 
     def forward(self, x):
+        if self.fused and ops.senet_ok(x, self.mlp[0].weight, self.mlp[2].weight):
+            return ops.senet(x, self.mlp[0].weight, self.mlp[2].weight)
         return x * self.mlp(x.mean(dim=-1)).unsqueeze(-1)
 
 

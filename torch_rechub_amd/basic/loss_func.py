@@ -76,6 +76,27 @@ class BPRLoss(nn.Module):
         return -diff.sigmoid().log().mean()
 
 
+class HingeLoss(nn.Module):
+    """max(max(neg, dim=-1) - pos + margin, 0).mean() (API mirror of torch_rechub/basic/loss_func.py:71-92): the pair-wise
+    loss FaceBookDSSM's docstring names.  As in the reference the maximum runs over the LAST axis of ``neg_score``, so a 1-D
+    ``neg_score`` (one negative per row) is reduced to its largest element over the batch.  With ``num_items`` the loss is
+    weighted by log(rank + 1), rank = the share of negatives inside the margin times ``num_items``."""
+
+    def __init__(self, margin=2, num_items=None):
+        super().__init__()
+        self.margin = margin
+        self.n_items = num_items
+
+    def forward(self, pos_score, neg_score, in_batch_neg=False):
+        pos_score = pos_score.view(-1)
+        loss = torch.clamp_min(neg_score.max(dim=-1).values - pos_score + self.margin, 0)
+        if self.n_items is None:
+            return loss.mean()
+        impostors = neg_score - pos_score.view(-1, 1) + self.margin > 0
+        rank = impostors.float().mean(-1) * self.n_items
+        return (loss * torch.log(rank + 1)).mean()
+
+
 class NCELoss(nn.Module):
     """Temperature-scaled softmax cross entropy with an ignored target id (reference basic/loss_func.py:110-175): the
     mean / sum over rows whose target is not ``ignore_index``, or over every row when there is none."""

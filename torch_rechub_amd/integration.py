@@ -29,11 +29,12 @@ _ACTIVATIONS = ("Dice", "activation_layer")
 _MODELS = {"ranking": ("DeepFM", "WideDeep", "DCN", "DCNv2", "DIN", "DIEN", "BST", "AFM", "AutoInt", "EDCN", "FiBiNet",
                        "DeepFFM", "FatDeepFFM"),
            "matching": ("DSSM", "YoutubeDNN", "MIND", "ComirecSA", "ComirecDR", "GRU4Rec", "NARM", "STAMP", "SINE",
-                        "SASRec"),
+                        "SASRec", "FaceBookDSSM", "YoutubeSBC"),
            "multi_task": ("SharedBottom", "ESMM", "MMOE", "PLE", "AITM"),
            "generative": ("HSTUModel", "HLLMModel", "RQVAEModel")}
 # classes a reference module defines beside its model and does not re-export from the sub-package
 _MODEL_PARTS = {"matching.sasrec": ("PointWiseFeedForward",),
+                "matching.dssm_senet": ("DSSM",),  # its own class of that name; models.matching exports ours as DSSMSENet
                 "generative.hllm": ("HLLMTransformerBlock",),
                 "generative.rqvae": ("VectorQuantizer", "ResidualVectorQuantizer")}
 _TRAINERS = ("CTRTrainer", "MatchTrainer", "MTLTrainer", "SeqTrainer")
