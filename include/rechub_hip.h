@@ -1151,6 +1151,47 @@ int rh_senet_fwd(const float* x, int64_t ldx, const float* w1, const float* w2, 
 int rh_senet_bwd(const float* x, int64_t ldx, const float* w1, const float* w2, const float* z, const float* h, const float* a,
                  const float* g, int64_t ldg, int B, int F, int R, int D, float* g_x, float* w_partial, void* stream);
 
+/* ---- TIGER / T5: masked, biased, rectangular softmax attention and the residual RMS norm (csrc/t5attn.hip) ----------
+ * q: (B, Lq, H, dh) view with row stride ldq; k, v: (B, Lk, H, dh) views sharing the row stride ldkv (separate projections,
+ * or column blocks of one fused QKV / KV product).  No scale on q . k.  key_mask (B, Lk) uint8 or null: a key with 0 is
+ * excluded; causal = 1 excludes j > i and needs Lq == Lk.  An excluded score is the most negative finite float, as the
+ * reference's additive mask makes it: a row with no key left (under a mask and causal = 1 also a row whose keys j <= i are
+ * all masked) gets weight 1 / Lk on every one of the Lk keys.  bias (nb, H) or null,
+ * bucket (Lq + Lk - 1,) int32 built by the host: the score (i, j, h) gets bias[bucket[(j - i) + (Lq - 1)], h].  p_drop in
+ * [0, 1): dropout on the weights with the counter hash over element ((b H + h) Lq + i) Lk + j; rng, saved_ctr as in
+ * rh_softmax_attn_*.
+ * rh_t5_attn_fwd: out (B, Lq, H dh); lse (B, H, Lq) the rows' log-sum-exp, +inf marking a row with no key left.
+ * rh_t5_attn_bwd: g_out (B, Lq, H dh) -> g_q ((B, Lq, H, dh) view, row stride ldgq), g_k, g_v ((B, Lk, H, dh) views, row
+ *   stride ldgkv), g_bias (nb, H) when bias is given, through part (*nparts of rh_t5_attn_nparts(B, Lq, H), Lq + Lk - 1) per-workgroup
+ *   sums by diagonal, added in a fixed order; delta (B, H, Lq) workspace.  Weights recomputed tile by tile from lse; nothing
+ *   of size Lq x Lk is written; no atomics.
+ * The two nparts functions answer through a HOST int, like rh_twotower_nblocks.
+ * Lq <= 8 (the decoder side) runs one wavefront per (sample, head), four to a workgroup; longer queries the 64 x 64 MFMA tile.
+ * 1 <= Lq, Lk <= 1024, 1 <= dh <= 128, H >= 1, nb >= 1 or no bias, else RH_E_UNSUPPORTED before any launch; B = 0
+ * returns at once.
+ * replaces: T5Attention.forward (projection reshapes, matmul, compute_bias, the additive mask, softmax, dropout, matmul)
+ *           of the T5 stack under torch_rechub/models/generative/tiger.py, and its autograd.
+ * rh_add_rms_norm_fwd: h_new (M, D) = h + delta (delta null: h_new = h, and h_new may be null), y = h_new *
+ *   rsqrt(mean(h_new^2) + eps) * w, rstd (M,) saved.  rh_add_rms_norm_bwd: g_y (M, D), g_res (M, D) or null (the gradient
+ *   that reached h_new directly) -> g_h (M, D) (= g_delta); part (*nparts of rh_add_rms_norm_nparts(M), D) per-workgroup sums of g_w
+ *   over rows in a fixed order (g_w = rh_colsum of it).  One wavefront per row, one pass.  1 <= D <= 1024, else
+ *   RH_E_UNSUPPORTED; M = 0 returns at once.
+ * replaces: the residual add and T5LayerNorm.forward of every T5 sub-layer, and their autograd. */
+int rh_t5_attn_nparts(int B, int Lq, int H, int* nparts);
+int rh_t5_attn_fwd(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv, int B, int Lq, int Lk, int H,
+                   int dh, const uint8_t* key_mask, int causal, const float* bias, const int32_t* bucket, int nb, float p_drop,
+                   int64_t* rng, int64_t* saved_ctr, float* out, float* lse, void* stream);
+int rh_t5_attn_bwd(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv, int B, int Lq, int Lk, int H,
+                   int dh, const uint8_t* key_mask, int causal, const float* bias, const int32_t* bucket, int nb, float p_drop,
+                   const int64_t* rng, const int64_t* saved_ctr, const float* out, const float* lse, const float* g_out,
+                   float* delta, float* g_q, int64_t ldgq, float* g_k, float* g_v, int64_t ldgkv, float* part, float* g_bias,
+                   void* stream);
+int rh_add_rms_norm_nparts(int M, int* nparts);
+int rh_add_rms_norm_fwd(const float* h, const float* delta, const float* w, float eps, int M, int D, float* h_new, float* y,
+                        float* rstd, void* stream);
+int rh_add_rms_norm_bwd(const float* h_new, const float* w, const float* rstd, const float* g_y, const float* g_res, int M,
+                        int D, float* g_h, float* part, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

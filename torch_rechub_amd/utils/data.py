@@ -386,3 +386,166 @@ class EmbDataset(Dataset):
 
     def __len__(self):
         return len(self.embeddings)
+
+
+class TigerSeqDataset(Dataset):
+    """Next-item samples of TIGER over semantic IDs (API of the reference's ``TigerSeqDataset``, utils/data.py:599-795).
+
+    ``inters_json`` maps a user to the item ids of the history in order, ``indices_json`` an item id (as a string) to the
+    tokens of its semantic ID.  A sample is ``{"input_ids": the joined tokens of the history, "labels": those of the
+    target}`` as text for a tokenizer.  ``train`` leaves the last two items of every user out and takes every proper prefix
+    of the rest as a history, ``valid`` predicts the item before the last from all before it, ``test`` the last one;
+    ``max_his_len`` > 0 keeps that many most recent items; ``sample_num`` > 0 draws that many test samples."""
+
+    def __init__(self, inters_json, indices_json, max_his_len, mode="train", sample_num=0):
+        super().__init__()
+        if mode not in ("train", "valid", "test"):
+            raise NotImplementedError(f"TigerSeqDataset: mode {mode!r} (train, valid or test)")
+        self.max_his_len = max_his_len
+        self.sample_num = sample_num
+        self.mode = mode
+        self.inters = inters_json
+        self.indices = indices_json
+        self.remapped_inters = {uid: ["".join(indices_json[str(i)]) for i in items] for uid, items in inters_json.items()}
+        self.new_tokens = None
+        self.all_items = None
+        self.allowed_tokens = None
+        self.inter_data = self._samples()
+
+    def _recent(self, history):
+        return history[-self.max_his_len:] if self.max_his_len > 0 else history
+
+    def _samples(self):
+        out = []
+        for items in self.remapped_inters.values():
+            if self.mode == "train":
+                seen = items[:-2]
+                out.extend({"item": seen[i], "inters": "".join(self._recent(seen[:i]))} for i in range(1, len(seen)))
+            else:
+                cut = -2 if self.mode == "valid" else -1
+                out.append({"item": items[cut], "inters": "".join(self._recent(items[:cut]))})
+        if self.mode == "test" and self.sample_num > 0:
+            pick = np.random.choice(np.arange(len(out)), self.sample_num, replace=False)
+            out = [out[int(i)] for i in pick]
+        return out
+
+    def get_new_tokens(self):
+        """Every token of every semantic ID, sorted, once each (the tokens to add to a tokenizer)."""
+        if self.new_tokens is None:
+            self.new_tokens = sorted({tok for index in self.indices.values() for tok in index})
+        return self.new_tokens
+
+    def get_all_items(self, as_list=False):
+        """The joined semantic IDs of all items: a set, or a list in the order of ``indices_json``."""
+        if self.all_items is None:
+            items = ["".join(index) for index in self.indices.values()]
+            self.all_items = items if as_list else set(items)
+        return self.all_items
+
+    def get_prefix_allowed_tokens_fn(self, tokenizer):
+        """Per-level constraint: after the start token 0, position i may hold any token some item has at level i, and
+        the position after the last level the EOS token."""
+        if self.allowed_tokens is None:
+            allowed = {}
+            for index in self.indices.values():
+                for level, tok in enumerate(index):
+                    allowed.setdefault(level, set()).add(tokenizer(tok)["input_ids"][0])
+            allowed[len(allowed)] = {tokenizer.eos_token_id}
+            self.allowed_tokens = allowed
+
+        def prefix_allowed_tokens_fn(batch_id, sentence):
+            sentence = sentence.tolist()
+            for back, tok in enumerate(reversed(sentence)):
+                if tok == 0:
+                    return list(self.allowed_tokens[back])
+
+        return prefix_allowed_tokens_fn
+
+    def __len__(self):
+        return len(self.inter_data)
+
+    def __getitem__(self, index):
+        d = self.inter_data[index % len(self.inter_data)]
+        return {"input_ids": d["inters"], "labels": d["item"]}
+
+    def get_collate_fn(self, tokenizer):
+        """Tokenizes a list of samples to padded ``input_ids`` / ``attention_mask`` / ``labels``; padded label slots are
+        -100 (the loss ignores them)."""
+        if tokenizer.pad_token_id is None:
+            tokenizer.pad_token_id = 0
+
+        def collate_fn(batch):
+            kw = dict(return_tensors="pt", padding="longest", max_length=tokenizer.model_max_length, truncation=True,
+                      return_attention_mask=True)
+            inputs = tokenizer([d["input_ids"] for d in batch], **kw)
+            labels = tokenizer([d["labels"] for d in batch], **kw)["input_ids"]
+            labels[labels == tokenizer.pad_token_id] = -100
+            inputs["labels"] = labels
+            return inputs
+
+        return collate_fn
+
+
+class Trie(object):
+    """Prefix tree over token-id sequences for constrained decoding (API of the reference's ``Trie``, utils/data.py:798-886):
+    ``get(prefix)`` lists the tokens that continue ``prefix`` towards some stored sequence, ``len`` counts the sequences
+    added."""
+
+    def __init__(self, sequences=()):
+        self.trie_dict = {}
+        self.len = 0
+        self.append_trie = None
+        self.bos_token_id = None
+        for seq in sequences or ():
+            self.add(seq)
+
+    def add(self, sequence):
+        node = self.trie_dict
+        for tok in sequence:
+            node = node.setdefault(tok, {})
+        self.len += 1
+
+    def append(self, trie, bos_token_id):
+        """A second trie entered at ``bos_token_id`` (and consulted for a prefix this one does not hold)."""
+        self.append_trie = trie
+        self.bos_token_id = bos_token_id
+
+    def get(self, prefix_sequence):
+        node = self.trie_dict
+        for pos, tok in enumerate(prefix_sequence):
+            if tok not in node:
+                return self.append_trie.get(list(prefix_sequence[pos:])) if self.append_trie else []
+            node = node[tok]
+        out = list(node.keys())
+        if self.append_trie and self.bos_token_id in out:
+            out.remove(self.bos_token_id)
+            out += list(self.append_trie.trie_dict.keys())
+        return out
+
+    def def_prefix_allowed_tokens_fn(self, candidate_trie):
+        def prefix_allowed_tokens(batch_id, sentence):
+            return candidate_trie.get(sentence.tolist())
+
+        return prefix_allowed_tokens
+
+    @staticmethod
+    def load_from_dict(trie_dict):
+        trie = Trie()
+        trie.trie_dict = trie_dict
+        trie.len = sum(1 for _ in trie)
+        return trie
+
+    def __iter__(self):
+        def walk(prefix, node):
+            if not node:
+                yield prefix
+            for tok, child in node.items():
+                yield from walk(prefix + [tok], child)
+
+        return walk([], self.trie_dict)
+
+    def __len__(self):
+        return self.len
+
+    def __getitem__(self, value):
+        return self.get(value)
