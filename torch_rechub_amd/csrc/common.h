@@ -222,3 +222,32 @@ static __device__ __forceinline__ uint32_t rh_drop_hash(uint64_t seed, uint64_t 
   h ^= h >> 16;
   return h;
 }
+
+// One call's dropout key for the kernels that hash per element: the forward reads the counter from the device-resident
+// (seed, counter) state and saves it, the backward reads the saved one.  The element index is the caller's.
+struct DropKey {
+  uint64_t seed, ctr;
+  uint32_t thr;
+  float keep;
+};
+
+static __device__ __forceinline__ DropKey drop_key(float p, const int64_t* rng, const int64_t* saved_ctr, int fwd) {
+  DropKey d{};
+  d.keep = 1.f;
+  if (p > 0.f) {
+    d.seed = (uint64_t)rng[0];
+    d.ctr = fwd ? (uint64_t)rng[1] : (uint64_t)saved_ctr[0];
+    d.thr = (uint32_t)(p * 4294967296.0);
+    d.keep = 1.f / (1.f - p);
+  }
+  return d;
+}
+
+// 1 / (1 - p) for a kept element, 0 for a dropped one; p = 0 takes a path with no hash
+static __device__ __forceinline__ float drop_mul(float p, const DropKey& d, uint64_t idx) {
+  if (p <= 0.f) return 1.f;
+  return rh_drop_hash(d.seed, d.ctr, idx) >= d.thr ? d.keep : 0.f;
+}
+
+// follows, on the same stream, the forward that drew the call's mask
+static __global__ void drop_advance_kernel(int64_t* rng) { rng[1] += 1; }

@@ -21,32 +21,6 @@ constexpr int kMaxD = 128;
 constexpr int kKC = 32;    // reduction steps of a weight matrix held in LDS at a time
 constexpr int kHR = 64;    // rows per workgroup of the head's backward
 
-struct Drop {
-  uint64_t seed, ctr;
-  uint32_t thr;
-  float keep;
-};
-
-__device__ __forceinline__ Drop drop_key(float p, const int64_t* rng, const int64_t* saved_ctr, int fwd) {
-  Drop d{};
-  d.keep = 1.f;
-  if (p > 0.f) {
-    d.seed = (uint64_t)rng[0];
-    d.ctr = fwd ? (uint64_t)rng[1] : (uint64_t)saved_ctr[0];
-    d.thr = (uint32_t)(p * 4294967296.0);
-    d.keep = 1.f / (1.f - p);
-  }
-  return d;
-}
-
-// 1 / (1 - p) for a kept element, 0 for a dropped one
-__device__ __forceinline__ float drop_mul(float p, const Drop& d, uint64_t idx) {
-  if (p <= 0.f) return 1.f;
-  return rh_drop_hash(d.seed, d.ctr, idx) >= d.thr ? d.keep : 0.f;
-}
-
-__global__ void sasrec_advance_kernel(int64_t* rng) { rng[1] += 1; }
-
 // ---------------------------------------------------------------------------------------------------------------------
 // input stage
 struct InArgs {
@@ -65,7 +39,7 @@ struct InArgs {
 };
 
 __global__ __launch_bounds__(RH_BLOCK) void input_fwd_kernel(const InArgs a) {
-  const Drop dk = drop_key(a.p, a.rng, a.saved_ctr, 1);
+  const DropKey dk = drop_key(a.p, a.rng, a.saved_ctr, 1);
   if (a.p > 0.f && blockIdx.x == 0 && threadIdx.x == 0) a.saved_ctr[0] = (int64_t)dk.ctr;
   const int64_t n = (int64_t)a.B * a.L * a.D;
   for (int64_t i = (int64_t)blockIdx.x * RH_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * RH_BLOCK) {
@@ -80,7 +54,7 @@ __global__ __launch_bounds__(RH_BLOCK) void input_fwd_kernel(const InArgs a) {
 
 // one thread per (l, d) of the position table walks the samples in ascending order
 __global__ __launch_bounds__(RH_BLOCK) void input_bwd_kernel(const InArgs a) {
-  const Drop dk = drop_key(a.p, a.rng, a.saved_ctr, 0);
+  const DropKey dk = drop_key(a.p, a.rng, a.saved_ctr, 0);
   const int n = a.max_len * a.D;
   for (int i = blockIdx.x * RH_BLOCK + threadIdx.x; i < n; i += gridDim.x * RH_BLOCK) {
     const int l = i / a.D, d = i % a.D;
@@ -360,7 +334,7 @@ __global__ __launch_bounds__(RH_BLOCK) void ffn_fwd_kernel(const FfnArgs a) {
   const Lane t = lane_of<DP>();
   const int r0 = blockIdx.x * TR, M = a.M, D = a.D;
   const int64_t MD = (int64_t)M * D;
-  const Drop dk = drop_key(a.p, a.rng, a.saved_ctr, 1);
+  const DropKey dk = drop_key(a.p, a.rng, a.saved_ctr, 1);
   if (a.p > 0.f && blockIdx.x == 0 && t.tid == 0) a.saved_ctr[0] = (int64_t)dk.ctr;
   load_rows<DP>(s0, a.attn, D, r0, M, D, t.tid);
   v16f acc = tile_gemm<DP, true>(zero16(), s0, a.wo, D, D, D, wl, t);
@@ -398,7 +372,7 @@ __global__ __launch_bounds__(RH_BLOCK) void ffn_bwd_kernel(const FfnArgs a) {
   const Lane t = lane_of<DP>();
   const int r0 = blockIdx.x * TR, M = a.M, D = a.D;
   const int64_t MD = (int64_t)M * D;
-  const Drop dk = drop_key(a.p, a.rng, a.saved_ctr, 0);
+  const DropKey dk = drop_key(a.p, a.rng, a.saved_ctr, 0);
   load_stats<TR>(sm, sr, a.stats, r0, M, t.tid);
   // g_f = the gradient of a W2^T + b2: mask, dropout2
   for (int e = t.tid; e < TR * DP; e += RH_BLOCK) {
@@ -620,7 +594,7 @@ extern "C" int rh_sasrec_input_fwd(const int64_t* seq, const float* e, int64_t e
   int64_t grid = (n + RH_BLOCK - 1) / RH_BLOCK;
   if (grid > 8192) grid = 8192;
   hipLaunchKernelGGL(input_fwd_kernel, dim3((unsigned)grid), dim3(RH_BLOCK), 0, st, a);
-  if (p_drop > 0.f) hipLaunchKernelGGL(sasrec_advance_kernel, dim3(1), dim3(1), 0, st, rng);
+  if (p_drop > 0.f) hipLaunchKernelGGL(drop_advance_kernel, dim3(1), dim3(1), 0, st, rng);
   RH_LAUNCH_CHECK("rh_sasrec_input_fwd");
   return 0;
 }
@@ -734,7 +708,7 @@ extern "C" int rh_sasrec_ffn_fwd(const float* attn, const float* Q, const int64_
   a.p = p_drop;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   RH_SASREC_LAUNCH(ffn_fwd_kernel, D, tiles_of(M, D), st, a);
-  if (p_drop > 0.f) hipLaunchKernelGGL(sasrec_advance_kernel, dim3(1), dim3(1), 0, st, rng);
+  if (p_drop > 0.f) hipLaunchKernelGGL(drop_advance_kernel, dim3(1), dim3(1), 0, st, rng);
   RH_LAUNCH_CHECK("rh_sasrec_ffn_fwd");
   return 0;
 }
