@@ -1192,6 +1192,31 @@ int rh_add_rms_norm_fwd(const float* h, const float* delta, const float* w, floa
 int rh_add_rms_norm_bwd(const float* h_new, const float* w, const float* rstd, const float* g_y, const float* g_res, int M,
                         int D, float* g_h, float* part, void* stream);
 
+/* Compressed Interaction Network, one layer (csrc/cin.hip): a GEMM over rows m = (b, d) and channels c = f Hp + h whose A
+ * operand x0[b, f, d] h[b, h, d] is formed in registers from two LDS tiles; the (B, F Hp, D) product never exists in HBM.
+ * fp32, the 64 x 64 tile on v_mfma_f32_32x32x2_f32, K = F Hp walked in chunks of 64 (an odd K ends in a zero-filled step).
+ * x0 (B, F, D): sample stride x0_sample_stride, field stride x0_field_stride >= D, d contiguous (a view of the fused
+ * gather's output is read in place).  h (B, Hp, D): sample stride h_sample_stride, a sample's Hp D values contiguous (the
+ * second half of the previous layer's y is read in place).  w (Ho, F Hp) = conv.weight[:, :, 0], bias (Ho,).
+ * rh_cin_fwd:   y (B, Ho, D) contiguous = relu(bias[o] + sum_c w[o, c] x0[b, f, d] h[b, h, d]).
+ * rh_cin_bwd:   y, g_y (B, Ho, D) contiguous; gp = g_y where y > 0, else 0 -> g_x0 (B, F, D) and g_h (B, Hp, D), both
+ *   contiguous, either may be null (not computed).  A workgroup owns 64 rows for all of K: no atomics, a fixed order,
+ *   every element written exactly once.
+ * rh_cin_wgrad: partial (*nchunks of rh_cin_wgrad_chunks, Ho F Hp + Ho) = per-chunk sums [g_w (Ho, F Hp) | g_bias (Ho,)]
+ *   over consecutive rows in a fixed order ([g_w | g_bias] = rh_colsum of it: bitwise reproducible).  *nchunks <= 16,
+ *   a HOST int, like rh_sine_nchunks.
+ * B >= 0, 1 <= D <= 128, 1 <= F <= 64, 1 <= Hp <= 256, 1 <= Ho <= 512, else RH_E_UNSUPPORTED before any launch; B = 0
+ * returns at once.  LDS: forward and bwd 4 (64 (F|1 + Hp|1) + 8320) bytes each (115712 at the limits), wgrad 33280.
+ * replaces: CIN.forward torch_rechub/basic/layers.py:359-362 (broadcast product, view, Conv1d, relu) and its autograd. */
+int rh_cin_wgrad_chunks(int B, int D, int F, int Hp, int Ho, int* nchunks);
+int rh_cin_fwd(const float* x0, int64_t x0_sample_stride, int64_t x0_field_stride, const float* h, int64_t h_sample_stride,
+               const float* w, const float* bias, int B, int D, int F, int Hp, int Ho, float* y, void* stream);
+int rh_cin_bwd(const float* x0, int64_t x0_sample_stride, int64_t x0_field_stride, const float* h, int64_t h_sample_stride,
+               const float* w, const float* y, const float* g_y, int B, int D, int F, int Hp, int Ho, float* g_x0, float* g_h,
+               void* stream);
+int rh_cin_wgrad(const float* x0, int64_t x0_sample_stride, int64_t x0_field_stride, const float* h, int64_t h_sample_stride,
+                 const float* y, const float* g_y, int B, int D, int F, int Hp, int Ho, float* partial, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

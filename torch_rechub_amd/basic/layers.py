@@ -9,7 +9,8 @@
 | LR               | :164-189                    | nn.Linear (library GEMV); DeepFM fuses it into the gather kernel |
 | MLP              | :254-292                    | nn.Linear / BatchNorm1d / activation / Dropout (hipBLASLt: true dense contraction) |
 | FM               | :295-319                    | ops.fm kernel; DeepFM fuses it into the gather kernel |
-| CrossNetwork     | :390-420                    | ops.cross_network: one wavefront per sample, all layers in registers |
+| CIN              | :322-368                    | ops.cin_layer: one MFMA GEMM launch per layer each way, the (B, F*Hp, D) product formed in registers |
+| CrossNetwork     | :390-420                   | ops.cross_network: one wavefront per sample, all layers in registers |
 | CrossNetV2       | :423-444                    | library GEMM + ONE fused Hadamard/bias/residual kernel (ops.cross_v2_epilogue) |
 | CrossNetMix      | :447-506                    | experts batched into 3 GEMMs per layer (was 150 mm per step) + ONE fused bias/Hadamard/gate-mix/residual kernel |
 | FFM              | :736-746                    | ops.ffm: one pass each way over the (B, F, F, D) input (DeepFFM fuses it into the lookup) |
@@ -550,6 +551,52 @@ class CEN(nn.Module):
         d = ops.cen_descriptor(em, self.u)
         s = self.mlp_att(d)
         return ops.cen_rescale(em, s)
+
+
+class CIN(nn.Module):
+    """Compressed Interaction Network of xDeepFM (reference layers.py:322-368): per layer relu(Conv1d(x0 (x) h)) over the
+    F * Hp products of the input fields and the previous layer's channels, the first half of the channels kept and the
+    second fed on under ``split_half``, then ``fc`` over the sum across the embedding axis.  ``conv_layers.{i}`` and ``fc`` are
+    the reference's modules, built in its order.  Each layer is one MFMA GEMM launch each way (ops.cin_layer) that never
+    forms the (B, F * Hp, D) product; a non-HIP input or a shape outside the kernel's ranges runs the reference's
+    formulation on torch ops."""
+
+    def __init__(self, input_dim, cin_size, split_half=True):
+        super().__init__()
+        self.num_layers = len(cin_size)
+        self.split_half = split_half
+        if split_half:
+            odd = [int(s) for s in cin_size[:-1] if int(s) % 2]
+            if odd:
+                raise ValueError(f"CIN: with split_half every cin_size entry but the last must be even, got {list(cin_size)}: "
+                                 f"the reference's forward fails on an odd one (torch.split(x, {odd[0]} // 2, dim=1) gives "
+                                 "three pieces, unpacked into two names)")
+        self.conv_layers = torch.nn.ModuleList()
+        prev_dim, fc_input_dim = input_dim, 0
+        for i in range(self.num_layers):
+            cross_layer_size = cin_size[i]
+            self.conv_layers.append(torch.nn.Conv1d(input_dim * prev_dim, cross_layer_size, 1, stride=1, dilation=1, bias=True))
+            if self.split_half and i != self.num_layers - 1:
+                cross_layer_size //= 2
+            prev_dim = cross_layer_size
+            fc_input_dim += prev_dim
+        self.fc = torch.nn.Linear(fc_input_dim, 1)
+
+    def forward(self, x):
+        xs = []
+        x0, h = x, x
+        for i, conv in enumerate(self.conv_layers):
+            if ops.cin_layer_ok(x0, h, conv.weight, conv.bias):
+                y = ops.cin_layer(x0, h, conv.weight, conv.bias)
+            else:
+                z = x0.unsqueeze(2) * h.unsqueeze(1)
+                y = torch.relu(conv(z.reshape(z.shape[0], z.shape[1] * z.shape[2], z.shape[3])))
+            if self.split_half and i != self.num_layers - 1:
+                y, h = torch.split(y, y.shape[1] // 2, dim=1)
+            else:
+                h = y
+            xs.append(y)
+        return self.fc(torch.sum(torch.cat(xs, dim=1), 2))
 
 
 class CrossNetwork(nn.Module):

@@ -23,7 +23,7 @@ import sys
 
 _LAYERS = ("EmbeddingLayer", "InputMask", "SumPooling", "AveragePooling", "ConcatPooling", "LR", "MLP", "FM",
            "CrossNetwork", "CrossNetV2", "CrossNetMix", "SENETLayer", "BiLinearInteractionLayer", "InteractingLayer",
-           "CrossLayer", "FFM", "CEN", "MultiInterestSA", "CapsuleNetwork", "HSTULayer", "HSTUBlock")
+           "CrossLayer", "FFM", "CEN", "CIN", "MultiInterestSA", "CapsuleNetwork", "HSTULayer", "HSTUBlock")
 _FEATURES = ("DenseFeature", "SparseFeature", "SequenceFeature")
 _ACTIVATIONS = ("Dice", "activation_layer")
 _MODELS = {"ranking": ("DeepFM", "WideDeep", "DCN", "DCNv2", "DIN", "DIEN", "BST", "AFM", "AutoInt", "EDCN", "FiBiNet",

@@ -15,6 +15,7 @@ _EXPORTS = {
     "edcn": ("EDCN",),
     "fibinet": ("FiBiNet",),
     "widedeep": ("WideDeep",),
+    "xdeepfm": ("xDeepFM",),
 }
 __all__ = []
 for _module, _names in _EXPORTS.items():
