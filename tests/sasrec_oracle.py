@@ -1,6 +1,7 @@
 """numpy float64 restatement of SASRec's four fused stages (csrc/sasrec.hip), forward and backward, plus the causal
-attention between them (for chaining a whole block).  Dropout enters as explicit boolean keep-masks, so a test can build
-them from the kernels' counter hash.  Not a test module; imported by test_sasrec_host.py and test_gpu_sasrec.py."""
+attention between them (for chaining a whole block) and the whole model with its BPR loss.  Dropout enters as explicit
+boolean keep-masks (a multiplier on the attention weights), so a test can build them from the kernels' counter hash.  Not a
+test module; imported by test_sasrec_host.py, test_gpu_sasrec.py and the dropout-oracle modules."""
 import numpy as np
 
 F64 = np.float64
@@ -85,8 +86,9 @@ def attn_in_bwd(gamma, W, cache, g_qkv, g_Q):
     return dict(x=g_x, gamma=g_gamma, beta=g_beta, W=g_W, b=g_qkv.reshape(-1, 3 * D).sum(0))
 
 
-# ---- causal multi-head attention (no dropout, no padding mask) ---------------------------------------------------------
-def attention_fwd(qkv, H):
+# ---- causal multi-head attention (no padding mask) -----------------------------------------------------------------------
+def attention_fwd(qkv, H, mult=None):
+    """mult: None, or the (B, H, L, L) dropout multiplier on the weights (keep flags times keep_scale(p))."""
     qkv = f64(qkv)
     B, L, D3 = qkv.shape
     D = D3 // 3
@@ -96,16 +98,20 @@ def attention_fwd(qkv, H):
     s = np.where(np.tril(np.ones((L, L), bool)), s, -np.inf)
     w = np.exp(s - s.max(-1, keepdims=True))
     w = w / w.sum(-1, keepdims=True)
-    out = (w @ v).transpose(0, 2, 1, 3).reshape(B, L, D)
-    return out, (q, k, v, w)
+    m = None if mult is None else f64(mult).reshape(B, H, L, L)
+    out = ((w if m is None else w * m) @ v).transpose(0, 2, 1, 3).reshape(B, L, D)
+    return out, (q, k, v, w) if m is None else (q, k, v, w, m)
 
 
 def attention_bwd(g_out, cache):
-    q, k, v, w = cache
+    q, k, v, w = cache[:4]
+    m = cache[4] if len(cache) > 4 else None
     B, H, L, dh = q.shape
     g = f64(g_out).reshape(B, L, H, dh).transpose(0, 2, 1, 3)
-    g_v = w.transpose(0, 1, 3, 2) @ g
+    g_v = (w if m is None else w * m).transpose(0, 1, 3, 2) @ g
     g_w = g @ v.transpose(0, 1, 3, 2)
+    if m is not None:
+        g_w = g_w * m
     g_s = w * (g_w - (g_w * w).sum(-1, keepdims=True)) * dh**-0.5
     g_q, g_k = g_s @ k, g_s.transpose(0, 1, 3, 2) @ q
     back = lambda a: a.transpose(0, 2, 1, 3).reshape(B, L, H * dh)  # noqa: E731
@@ -156,3 +162,63 @@ def head_bwd(g_pos, g_neg, gamma, cache, g_s=None):
     g = gp * pos_e + gn * neg_e + (0.0 if g_s is None else f64(g_s))
     g_x, g_gamma, g_beta = ln_bwd(g, gamma, ln)
     return dict(x=g_x, pos_e=gp * s, neg_e=gn * s, gamma=g_gamma, beta=g_beta)
+
+
+# ---- the whole model: input stage, blocks, head, BPR loss ------------------------------------------------------------------
+def model_fwd_bwd(sd, seq, pos, neg, H, eps, p=0.0, draw=None):
+    """SASRec.forward + BPRLoss (-log sigmoid(pos - neg), mean over all B L positions) and its backward from the
+    state_dict ``sd`` (numpy arrays under the model's names; the item table's logical columns).
+
+    draw: None, or a callable draw(n) -> n boolean keep flags, called once per dropout COUNTER in the model's program
+    order: the input stage (n = B L D, flat over (B, L, D)); per block the attention weights (n = B H L L, flat over
+    (B, H, L, L)) and the FFN (n = 2 M D of ONE counter: dropout1 is [0, M D), dropout2 [M D, 2 M D), M = B L).
+
+    -> dict(pos, neg, loss, grads {name: array}, kink): kink = the smallest |conv1 output| over the units dropout1 keeps,
+    over all blocks (the ReLU follows dropout1)."""
+    sd = {n: f64(a) for n, a in sd.items()}
+    seq, pos, neg = np.asarray(seq), np.asarray(pos), np.asarray(neg)
+    B, L = seq.shape
+    table, P = sd["item_emb.embed_dict.seq.weight"], sd["position_emb.weight"]
+    D = table.shape[1]
+    n_blocks = sum(1 for n in sd if n.startswith("attention_layernorms.") and n.endswith(".weight"))
+    keep0 = None if draw is None else np.asarray(draw(B * L * D)).reshape(B, L, D)
+    x = input_fwd(seq, table[seq], P, keep0, p)
+    caches, kink = [], float("inf")
+    for b in range(n_blocks):
+        pa, pm, pf, pw = (f"{s}.{b}." for s in ("attention_layernorms", "attention_layers", "forward_layernorms", "forward_layers"))
+        Q, qkv, c_in = attn_in_fwd(x, sd[pa + "weight"], sd[pa + "bias"], sd[pm + "in_proj_weight"], sd[pm + "in_proj_bias"], eps)
+        mult = None if draw is None else _mult(np.asarray(draw(B * H * L * L)), p, (B, H, L, L))
+        att, c_att = attention_fwd(qkv, H, mult)
+        k1 = k2 = None
+        if draw is not None:
+            both = np.asarray(draw(2 * B * L * D))
+            k1, k2 = both[:B * L * D].reshape(B, L, D), both[B * L * D:].reshape(B, L, D)
+        x, inter = ffn_fwd(att, Q, seq, sd[pm + "out_proj.weight"], sd[pm + "out_proj.bias"], sd[pf + "weight"], sd[pf + "bias"],
+                           sd[pw + "conv1.weight"], sd[pw + "conv1.bias"], sd[pw + "conv2.weight"], sd[pw + "conv2.bias"], eps,
+                           k1, k2, p)
+        h1 = np.abs(inter["z"] @ sd[pw + "conv1.weight"].reshape(D, D).T + sd[pw + "conv1.bias"])
+        kink = min(kink, float((h1 if k1 is None else h1[k1]).min()))
+        caches.append((pa, pm, pf, pw, c_in, c_att, inter))
+    s, pl, nl, c_head = head_fwd(x, sd["last_layernorm.weight"], sd["last_layernorm.bias"], table[pos], table[neg], eps)
+    diff = pl - nl
+    loss = float(np.mean(np.logaddexp(0.0, -diff)))
+    g_diff = -1.0 / (1.0 + np.exp(diff)) / diff.size
+    gh = head_bwd(g_diff, -g_diff, sd["last_layernorm.weight"], c_head)
+    grads = {"last_layernorm.weight": gh["gamma"], "last_layernorm.bias": gh["beta"]}
+    g_x = gh["x"]
+    for pa, pm, pf, pw, c_in, c_att, inter in reversed(caches):
+        gf = ffn_bwd(g_x, sd[pf + "weight"], inter)
+        gi = attn_in_bwd(sd[pa + "weight"], sd[pm + "in_proj_weight"], c_in, attention_bwd(gf["attn"], c_att), gf["Q"])
+        g_x = gi["x"]
+        shape = sd[pw + "conv1.weight"].shape
+        grads.update({pa + "weight": gi["gamma"], pa + "bias": gi["beta"], pm + "in_proj_weight": gi["W"],
+                      pm + "in_proj_bias": gi["b"], pm + "out_proj.weight": gf["Wo"], pm + "out_proj.bias": gf["bo"],
+                      pf + "weight": gf["gamma"], pf + "bias": gf["beta"], pw + "conv1.weight": gf["W1"].reshape(shape),
+                      pw + "conv1.bias": gf["b1"], pw + "conv2.weight": gf["W2"].reshape(shape), pw + "conv2.bias": gf["b2"]})
+    g_e, g_P = input_bwd(seq, g_x, P.shape[0], keep0, p)
+    g_table = np.zeros_like(table)
+    for ids, g in ((seq, g_e), (pos, gh["pos_e"]), (neg, gh["neg_e"])):
+        np.add.at(g_table, ids.reshape(-1), g.reshape(-1, D))
+    grads["item_emb.embed_dict.seq.weight"] = g_table
+    grads["position_emb.weight"] = g_P
+    return dict(pos=pl, neg=nl, loss=loss, grads=grads, kink=kink)

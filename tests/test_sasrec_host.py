@@ -140,3 +140,72 @@ def test_argument_errors_are_raised_before_anything_runs():
         SASRec(features(4, V=3), max_len=1100, num_blocks=1)({"seq": long_ids, "pos": long_ids, "neg": long_ids})
     with pytest.raises(RuntimeError, match="HIP device"):  # and nothing falls back to the CPU
         SASRec(features(12), max_len=9)(x)
+
+
+# ---- the oracle under dropout (tests/test_gpu_seq_models_dropout_oracle.py runs the model against it) ---------------------
+def _qkv_case(B=3, L=7, D=12, seed=0):
+    rng = np.random.default_rng(seed)
+    return rng.standard_normal((B, L, 3 * D)), rng.standard_normal((B, L, D))
+
+
+def test_attention_with_an_all_ones_multiplier_is_the_undropped_attention_exactly():
+    qkv, g = _qkv_case()
+    out0, c0 = O.attention_fwd(qkv, 3)
+    out1, c1 = O.attention_fwd(qkv, 3, np.ones((3, 3, 7, 7)))
+    assert np.array_equal(out0, out1) and np.array_equal(O.attention_bwd(g, c0), O.attention_bwd(g, c1))
+
+
+@pytest.mark.parametrize("p", [0.0, 0.5])
+def test_attention_backward_under_a_multiplier_equals_float64_autograd(p):
+    """The numpy backward against torch's autograd of the same forward (float64), to 1e-12 of the largest gradient."""
+    B, L, D, H = 3, 7, 12, 3
+    qkv, g = _qkv_case(B, L, D, 1)
+    keep = np.random.default_rng(2).random((B, H, L, L)) >= p
+    mult = keep * O.keep_scale(p)
+    out, cache = O.attention_fwd(qkv, H, mult)
+    got = O.attention_bwd(g, cache)
+    t = torch.tensor(qkv, requires_grad=True)
+    q, k, v = (t[..., i * D:(i + 1) * D].reshape(B, L, H, D // H).permute(0, 2, 1, 3) for i in range(3))
+    s = (q @ k.transpose(2, 3)) * (D // H)**-0.5
+    s = s.masked_fill(~torch.tril(torch.ones(L, L, dtype=torch.bool)), float("-inf"))
+    ref = ((torch.softmax(s, -1) * torch.tensor(mult)) @ v).permute(0, 2, 1, 3).reshape(B, L, D)
+    ref.backward(torch.tensor(g))
+    assert np.abs(out - ref.detach().numpy()).max() <= 1e-12 * np.abs(out).max()
+    assert np.abs(got - t.grad.numpy()).max() <= 1e-12 * np.abs(got).max()
+    assert (keep.mean() < 0.6) == (p > 0)
+
+
+def _model_state(cfg):
+    gold = load_golden(f"model_sasrec_{cfg}.npz")
+    c = json.loads(str(gold["cfg"]))
+    sd = {n[4:]: gold[n] for n in gold.files if n.startswith("sd0.")}
+    sd["item_emb.embed_dict.seq.weight"] = sd["item_emb.embed_dict.seq.weight"][:, :c["D"]]
+    return gold, c, sd
+
+
+@pytest.mark.parametrize("cfg", ["d12h3b2", "d10h1b1"])
+def test_whole_model_oracle_reproduces_the_recorded_loss_and_gradients(cfg):
+    gold, c, sd = _model_state(cfg)
+    res = O.model_fwd_bwd(sd, gold["b0.seq"], gold["b0.pos"], gold["b0.neg"], c["H"], EPS)
+    close(res["loss"], gold["loss"], "loss")
+    assert set(res["grads"]) == {str(n) for n in gold["sd_keys"]}
+    for n, g in res["grads"].items():
+        want = gold["grad." + n]
+        close(g, want[:, :g.shape[1]] if n.startswith("item_emb") else want, "grad " + n,
+              1e-4 if want.ndim >= 2 and "emb" not in n else 1e-5)
+
+
+def test_whole_model_oracle_with_all_kept_masks_is_the_undropped_oracle_exactly():
+    gold, c, sd = _model_state("d12h3b2")
+    args = (sd, gold["b0.seq"], gold["b0.pos"], gold["b0.neg"], c["H"], EPS)
+    sizes = []
+
+    def draw(n):
+        sizes.append(n)
+        return np.ones(n, bool)
+
+    a, b = O.model_fwd_bwd(*args), O.model_fwd_bwd(*args, p=0.0, draw=draw)
+    B, L, D, H = 5, 7, 12, 3
+    assert sizes == [B * L * D] + [B * H * L * L, 2 * B * L * D] * 2  # one counter per stage; the FFN's two ranges share one
+    assert a["loss"] == b["loss"] and np.array_equal(a["pos"], b["pos"]) and np.array_equal(a["neg"], b["neg"])
+    assert all(np.array_equal(a["grads"][n], b["grads"][n]) for n in a["grads"])

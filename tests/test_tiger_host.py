@@ -315,3 +315,35 @@ def test_integration_does_not_rebind_tiger():
     from torch_rechub_amd.models import generative
     assert "TIGERModel" not in integration._MODELS["generative"]
     assert hasattr(generative, "TIGERModel") and hasattr(generative, "TIGERConfig") and hasattr(generative.TIGERModel, "from_t5")
+
+
+# ---- the oracle's dropout sites (tests/test_gpu_seq_models_dropout_oracle.py runs the model against it) ------------------
+def test_an_all_ones_drop_reproduces_the_undropped_oracle_exactly_and_visits_the_sites_in_program_order(model_case):
+    z, cfg, P = model_case
+    ids, mask, labels = z["input_ids"], z["attention_mask"], z["labels"]
+    B, L, T = ids.shape[0], ids.shape[1], labels.shape[1]
+    H, D, F = cfg["num_heads"], cfg["d_model"], cfg["d_ff"]
+    shapes, kink = [], []
+
+    def drop(shape):
+        shapes.append(tuple(shape))
+        return torch.ones(shape, dtype=torch.float64)
+
+    for t in {id(t): t for t in P.values()}.values():
+        t.grad = None
+    logits0, loss0 = O.forward(P, cfg, ids, mask, labels, 0.7)
+    loss0.backward()
+    grads0 = {n: t.grad.clone() for n, t in P.items()}
+    for t in {id(t): t for t in P.values()}.values():
+        t.grad = None
+    logits1, loss1 = O.forward(P, cfg, ids, mask, labels, 0.7, drop=drop, kink=kink)
+    loss1.backward()
+    assert torch.equal(logits0, logits1) and torch.equal(loss0, loss1)
+    assert all(torch.equal(grads0[n], P[n].grad) for n in P)
+    enc = [(B, L, D)] + [(B, H, L, L), (B, L, D), (B, L, F), (B, L, D)] * cfg["num_layers"] + [(B, L, D)]
+    dec = [(B, T, D)] + [(B, H, T, T), (B, T, D), (B, H, T, L), (B, T, D), (B, T, F), (B, T, D)] * cfg["num_decoder_layers"] \
+        + [(B, T, D)]
+    assert shapes == enc + dec
+    assert len(kink) == cfg["num_layers"] + cfg["num_decoder_layers"] and all(0 < m < 1 for m in kink)
+    for t in {id(t): t for t in P.values()}.values():
+        t.grad = None

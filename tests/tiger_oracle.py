@@ -80,32 +80,48 @@ def rms_norm(h, w, eps, vdt=None):
     return w * (h * torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + eps))
 
 
-def _attn_layer(P, pre, y, kv, H, key_mask, causal, table, bidirectional, maxd):
+def _attn_layer(P, pre, y, kv, H, key_mask, causal, table, bidirectional, maxd, drop=None):
     q = y @ P[pre + ".q.weight"].T
     k = kv @ P[pre + ".k.weight"].T
     v = kv @ P[pre + ".v.weight"].T
-    a = attention(q, k, v, H, key_mask, causal, table, bidirectional, maxd)
+    w = None if drop is None else drop((y.shape[0], H, y.shape[1], kv.shape[1]))
+    a = attention(q, k, v, H, key_mask, causal, table, bidirectional, maxd, w)
     return a @ P[pre + ".o.weight"].T
 
 
-def stack(P, cfg, name, ids, key_mask=None, enc=None, enc_mask=None, vdt=None):
+def _dropped(x, drop):
+    return x if drop is None else x * drop(tuple(x.shape))
+
+
+def stack(P, cfg, name, ids, key_mask=None, enc=None, enc_mask=None, vdt=None, drop=None, kink=None):
+    """drop: None, or a callable that is called once per dropout site in the model's program order (T5Stack.forward: the
+    token dropout; per block the self-attention weights, the attention delta, (decoder: the cross-attention weights and
+    their delta,) relu(wi) and wo; the final dropout) with the site's logical shape -- (B, H, Lq, Lk) for attention
+    weights, the tensor's own shape elsewhere -- and returns the multiplier.  kink: a list that receives, per ReLU, the
+    smallest |pre-activation| over the units its dropout keeps."""
     dec = name == "decoder"
     n = cfg["num_decoder_layers"] if dec else cfg["num_layers"]
     H, eps, maxd = cfg["num_heads"], cfg["layer_norm_epsilon"], cfg["relative_attention_max_distance"]
-    h = P["shared.weight"][torch.as_tensor(ids)]
+    h = _dropped(P["shared.weight"][torch.as_tensor(ids)], drop)
     table = P[f"{name}.block.0.layer.0.SelfAttention.relative_attention_bias.weight"]
     for b in range(n):
         pre = f"{name}.block.{b}.layer."
         y = rms_norm(h, P[pre + "0.layer_norm.weight"], eps, vdt)
-        h = h + _attn_layer(P, pre + "0.SelfAttention", y, y, H, key_mask, dec, table, not dec, maxd)
+        h = h + _dropped(_attn_layer(P, pre + "0.SelfAttention", y, y, H, key_mask, dec, table, not dec, maxd, drop), drop)
         f = 1
         if dec:
             y = rms_norm(h, P[pre + "1.layer_norm.weight"], eps, vdt)
-            h = h + _attn_layer(P, pre + "1.EncDecAttention", y, enc, H, enc_mask, False, None, True, maxd)
+            h = h + _dropped(_attn_layer(P, pre + "1.EncDecAttention", y, enc, H, enc_mask, False, None, True, maxd, drop), drop)
             f = 2
         y = rms_norm(h, P[pre + f"{f}.layer_norm.weight"], eps, vdt)
-        h = h + torch.relu(y @ P[pre + f"{f}.DenseReluDense.wi.weight"].T) @ P[pre + f"{f}.DenseReluDense.wo.weight"].T
-    return rms_norm(h, P[f"{name}.final_layer_norm.weight"], eps, vdt)
+        pre_act = y @ P[pre + f"{f}.DenseReluDense.wi.weight"].T
+        w = None if drop is None else drop(tuple(pre_act.shape))
+        if kink is not None:
+            live = pre_act.detach().abs() if w is None else pre_act.detach().abs()[torch.as_tensor(w) != 0]
+            kink.append(float(live.min()) if live.numel() else float("inf"))
+        mid = torch.relu(pre_act) if w is None else torch.relu(pre_act) * w
+        h = h + _dropped(mid @ P[pre + f"{f}.DenseReluDense.wo.weight"].T, drop)
+    return _dropped(rms_norm(h, P[f"{name}.final_layer_norm.weight"], eps, vdt), drop)
 
 
 def shift_right(labels, cfg):
@@ -117,17 +133,17 @@ def shift_right(labels, cfg):
     return out
 
 
-def decode(P, cfg, dec_ids, enc, mask, vdt=None):
-    out = stack(P, cfg, "decoder", dec_ids, None, enc, mask, vdt)
+def decode(P, cfg, dec_ids, enc, mask, vdt=None, drop=None, kink=None):
+    out = stack(P, cfg, "decoder", dec_ids, None, enc, mask, vdt, drop, kink)
     if cfg["tie_word_embeddings"]:
         out = out * cfg["d_model"]**-0.5
     return out @ P["lm_head.weight"].T
 
 
-def forward(P, cfg, ids, mask, labels, temperature=1.0, vdt=None):
-    """-> (logits (B, T, V), loss)"""
-    enc = stack(P, cfg, "encoder", ids, mask, vdt=vdt)
-    logits = decode(P, cfg, shift_right(labels, cfg), enc, mask, vdt)
+def forward(P, cfg, ids, mask, labels, temperature=1.0, vdt=None, drop=None, kink=None):
+    """-> (logits (B, T, V), loss); drop, kink: see ``stack`` (the encoder's sites come first)."""
+    enc = stack(P, cfg, "encoder", ids, mask, vdt=vdt, drop=drop, kink=kink)
+    logits = decode(P, cfg, shift_right(labels, cfg), enc, mask, vdt, drop, kink)
     lab = torch.as_tensor(np.asarray(labels)).reshape(-1)
     loss = torch.nn.functional.cross_entropy((logits / temperature).reshape(-1, logits.shape[-1]), lab, ignore_index=-100)
     return logits, loss
