@@ -313,7 +313,9 @@ int rh_inbatch_logits_bwd(const float* u, int64_t ldu, const float* v, int64_t l
  * rh_ce_fwd/bwd: torch.nn.CrossEntropyLoss() (mean) over the (B, C) in-batch logits (trainers/match_trainer.py:60,136;
  *   target int64 (B,), null = class 0 for every row as the trainer's zero targets): lse (B,) = logsumexp per row, loss_partial
  *   (rh_ce_nblocks(B),) per-block sums of lse - x[target] (the caller sums them and divides by B: rh_colsum);
- *   g_logits = g_loss[0] / B * (softmax - onehot).  C <= 1024; an out-of-range target sets RH_FLAG_INDEX_OOB. */
+ *   g_logits = g_loss[0] / B * (softmax - onehot), the softmax taken from the logits again as exp((x - max) - log sum): the
+ *   backward requires lse but does not read it (its rounding would be the error of p - 1 at the target).  C <= 1024; an
+ *   out-of-range target sets RH_FLAG_INDEX_OOB. */
 int rh_l2norm_fwd(const float* x, int64_t ldx, int B, int d, float eps, float* y, float* nrm, void* stream);
 int rh_l2norm_bwd(const float* y, const float* nrm, const float* g, int64_t ldg, int B, int d, float eps, float* gx, void* stream);
 int rh_ce_nblocks(int B);

@@ -183,7 +183,8 @@ __global__ __launch_bounds__(RH_BLOCK) void l2norm_bwd_kernel(const float* __res
   }
 }
 
-// one lane per row (C <= 64 classes: the in-batch logits have 1 + K columns): loss terms lse - x[target] summed per block
+// one lane per row, 1 <= C <= 1024 classes by the guard below (the in-batch logits have 1 + K columns; the trainer also
+// sends any list-wise (B, C <= 1024) prediction here): loss terms lse - x[target] summed per block
 __global__ __launch_bounds__(RH_BLOCK) void ce_fwd_kernel(const float* __restrict__ x, const int64_t* __restrict__ target, int B,
                                                           int C, float* __restrict__ lse, float* __restrict__ partial, int* err) {
   RH_CHAIN_PRIO();
@@ -216,17 +217,33 @@ __global__ __launch_bounds__(RH_BLOCK) void ce_fwd_kernel(const float* __restric
   }
 }
 
+// G lanes per row (a power of two, 4 <= G <= 64), a lane takes every G-th class.  The row's maximum and sum are taken again
+// here and the forward's lse is not read: lse = fl(m + log s) carries half an ulp of a number the size of the largest logit
+// (2e-6 at 60), exp(x - lse) turns that into the relative error of every probability, and at the target, where the result is
+// p - 1, into an absolute one -- twenty times the 1e-7 of the row's largest gradient the reference's fp32 keeps there.
+// exp((x - m) - log s) subtracts numbers no larger than log 1024.
 __global__ __launch_bounds__(RH_BLOCK) void ce_bwd_kernel(const float* __restrict__ x, const int64_t* __restrict__ target,
-                                                          const float* __restrict__ lse, const float* __restrict__ g_loss, int B,
-                                                          int C, float* __restrict__ gx) {
+                                                          const float* __restrict__ g_loss, int B, int C, int G,
+                                                          float* __restrict__ gx) {
   RH_CHAIN_PRIO();
   const float scale = g_loss[0] / (float)B;
-  for (int64_t i = (int64_t)blockIdx.x * RH_BLOCK + threadIdx.x; i < (int64_t)B * C; i += (int64_t)gridDim.x * RH_BLOCK) {
-    const int64_t r = i / C;
-    const int c = (int)(i - r * C);
+  const int lig = threadIdx.x % G, per = RH_BLOCK / G;
+  for (int64_t r0 = (int64_t)blockIdx.x * per; r0 < B; r0 += (int64_t)gridDim.x * per) {  // workgroup-uniform
+    int64_t r = r0 + threadIdx.x / G;
+    const bool live = r < B;
+    if (!live) r = B - 1;  // the dead groups of the last trip read a valid row and take part in the shuffles
+    const float* row = x + r * (int64_t)C;
+    float m = -INFINITY;
+    for (int c = lig; c < C; c += G) m = fmaxf(m, row[c]);
+    for (int k = 1; k < G; k <<= 1) m = fmaxf(m, __shfl_xor(m, k, RH_WAVE));
+    float s = 0.f;
+    for (int c = lig; c < C; c += G) s += expf(row[c] - m);
+    for (int k = 1; k < G; k <<= 1) s += __shfl_xor(s, k, RH_WAVE);
+    const float ls = logf(s);
     int64_t t = target ? target[r] : 0;
     if ((uint64_t)t >= (uint64_t)C) t = 0;
-    gx[i] = scale * (expf(x[i] - lse[r]) - (c == t ? 1.f : 0.f));
+    if (live)
+      for (int c = lig; c < C; c += G) gx[r * (int64_t)C + c] = scale * (expf((row[c] - m) - ls) - (c == t ? 1.f : 0.f));
   }
 }
 
@@ -277,10 +294,13 @@ extern "C" int rh_ce_bwd(const float* logits, const int64_t* target, const float
                          float* g_logits, void* stream) {
   RH_REQUIRE(logits && lse && g_loss && g_logits, RH_E_BADARG, "rh_ce_bwd: null pointer");
   RH_REQUIRE(B >= 1 && C >= 1 && C <= 1024, RH_E_UNSUPPORTED, "rh_ce_bwd: B=%d C=%d unsupported", B, C);
-  int64_t grid = ((int64_t)B * C + RH_BLOCK - 1) / RH_BLOCK;
+  int G = 4;
+  while (G < C && G < RH_WAVE) G *= 2;
+  const int per = RH_BLOCK / G;
+  int64_t grid = ((int64_t)B + per - 1) / per;
   if (grid > 4096) grid = 4096;
   hipLaunchKernelGGL(ce_bwd_kernel, dim3((unsigned)grid), dim3(RH_BLOCK), 0, reinterpret_cast<hipStream_t>(stream), logits, target,
-                     lse, g_loss, B, C, g_logits);
+                     g_loss, B, C, G, g_logits);
   RH_LAUNCH_CHECK("rh_ce_bwd");
   return 0;
 }

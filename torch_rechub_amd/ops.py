@@ -2003,6 +2003,8 @@ class _CrossEntropyFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, target):
         require_hip(logits)
+        if target is not None and (target.dtype != torch.int64 or target.shape != (logits.shape[0],) or not target.is_cuda):
+            raise ValueError("cross-entropy targets must be an int64 (B,) tensor on the device of the logits")
         logits = logits.contiguous()
         B, C = logits.shape
         dev = logits.device
@@ -2700,6 +2702,11 @@ class _InbatchLogitsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, u, v, neg, row0):
         require_hip(u, v, neg)
+        if u.dim() != 2 or v.dim() != 2 or u.shape[1] != v.shape[1]:
+            raise ValueError("in-batch logits expect (B, D) user and (C, D) item embeddings of one width")
+        if neg.dtype != torch.int64 or neg.dim() != 2 or neg.shape[0] != u.shape[0]:
+            # (the kernel reads int64 words: a narrower index tensor would be read past its end)
+            raise ValueError("in-batch negatives must be an int64 (B, K) tensor")
         if u.stride(1) != 1:
             u = u.contiguous()
         if v.stride(1) != 1:
