@@ -1219,6 +1219,58 @@ int rh_cin_bwd(const float* x0, int64_t x0_sample_stride, int64_t x0_field_strid
 int rh_cin_wgrad(const float* x0, int64_t x0_sample_stride, int64_t x0_field_stride, const float* h, int64_t h_sample_stride,
                  const float* y, const float* g_y, int B, int D, int F, int Hp, int Ho, float* partial, void* stream);
 
+/* ---- evaluation metrics (csrc/metric.hip) ---------------------------------------------------------------------------
+ * Exact AUC / GAUC.  pred: n float32 values with element stride pred_stride; label: n contiguous values of label_dtype
+ * (0 float32, 1 float64, 2 int64, 3 uint8 / bool), 1 = positive, 0 = negative; g: n dense group ids in [0, G) or null
+ * (G = 1).  Two predictions are tied when their VALUES are equal: -0.0 == +0.0, every other bit pattern -- distinct
+ * denormals included -- is its own value, whatever the FP denormal mode (bit patterns are compared).  1 <= n < 2^31.
+ * rh_auc_keys: keys (n,) int64 = the group in the high word, below it the prediction's bit pattern made monotone; any
+ *   ascending sort of the keys (torch.sort: plumbing, there is no hand-written sort here) gives the permutation `order`
+ *   under which (g, pred) ascends.
+ * rh_auc_groups: out (3, G) int64 = P_g (positives), N_g (negatives), U2_g = sum over the positives i of g of
+ *   2 #{negatives of g with pred < pred_i} + #{negatives of g with pred == pred_i}   (AUC_g = U2_g / (2 P_g N_g)).
+ *   Integer arithmetic throughout; tie runs and groups may span any number of workgroups (per-chunk aggregates, a scan by
+ *   one workgroup, a second pass; 64-bit integer atomics into the group slots): two runs give the same bits.  bad (2,)
+ *   int64 = the count of non-finite predictions and the count of labels that are neither 0 nor 1 (an `order` entry
+ *   outside [0, n) or a group id outside [0, G) is counted with the latter and written nowhere); with either non-zero,
+ *   out is undefined.  out and bad are zeroed by the call.  workspace: *workspace_bytes of rh_auc_plan.
+ * rh_auc_plan answers through HOST pointers: *chunk = the sorted elements one workgroup takes per trip, *max_grid = the
+ *   grid cap (more chunks than that: further trips).
+ * rh_gauc_reduce: stats = out of rh_auc_groups; weights (G,) double or null (the group size P_g + N_g).  result (2,)
+ *   double = sum_g w_g U2_g / (2 P_g N_g), sum_g w_g over the groups holding both classes; *single_class = the number of
+ *   groups holding one class (left out of both sums).  partial: 3072 doubles of workspace.  Per-workgroup partials over a
+ *   grid that depends on G alone, added in index order: bit-reproducible.
+ * rh_log_loss: result (1,) double = -mean(y log p + (1 - y) log(1 - p)), p widened to double first; partial: 1024
+ *   doubles; the same fixed order.  Non-finite terms propagate (p = 0 with y = 0 gives nan through 0 * -inf).
+ * replaces: roc_auc_score behind auc_score torch_rechub/basic/metric.py:20-22, get_user_pred and the per-user loop of
+ *           gauc_score metric.py:25-74, log_loss metric.py:198-200, and the per-batch .cpu() of the trainers' evaluate
+ *           (trainers/ctr_trainer.py:157-172, match_trainer.py:225-236, mtl_trainer.py:238-252).
+ *
+ * List metrics.  pred (M, K) int64 with row stride ld >= K, 1 <= K <= 256; truth as CSR: truth_off (M + 1,) and truth_ids
+ * (n_truth,) int64 (offsets are clamped into [0, n_truth]).  cutoffs: a HOST array of n_k <= 8 ints in [1, K].  gain (K,)
+ * double = 1 / log2(j + 2) and ideal (K + 1,) double = its sequential prefix sums, ideal[0] = 0, both built by the caller.
+ * Membership is equality of ids; duplicates on either side count as the reference counts them.  Per user with a
+ * non-empty list and cut-off k: hit = #{j < k: pred[j] in truth}, mrr = 1 / (1 + first hit), recall = hit / len,
+ * precision = hit / k, ndcg = dcg / ideal[min(len, k)], dcg = the gains of the hit positions added in ascending j -- the
+ * float64 reference's own operations in its own order, hence its bits.  A user with an empty list adds nothing.
+ * hits (n_k,) int64, gts (1,) int64 = sum of len (both exact, zeroed by the call), sums (n_k, 4) double = mrr, recall,
+ * precision, ndcg summed over users (per-workgroup partials added in index order), per_user (M, n_k, 5) double = hit, mrr,
+ * recall, precision, ndcg, or null.  partial: *partial_doubles of rh_rank_metrics_plan, which also reports (HOST
+ * pointers) *stage = the truth ids staged through LDS at a time, the users per workgroup and the grid cap.
+ * replaces: the loops of topk_metrics torch_rechub/basic/metric.py:142-176. */
+int rh_auc_plan(int64_t n, int* chunk, int* max_grid, int64_t* workspace_bytes);
+int rh_auc_keys(const float* pred, int64_t pred_stride, const int64_t* g, int64_t n, int64_t* keys, void* stream);
+int rh_auc_groups(const float* pred, int64_t pred_stride, const void* label, int label_dtype, const int64_t* g,
+                  const int64_t* order, int64_t n, int64_t G, void* workspace, int64_t* out, int64_t* bad, void* stream);
+int rh_gauc_reduce(const int64_t* stats, const double* weights, int64_t G, double* partial, double* result,
+                   int64_t* single_class, void* stream);
+int rh_log_loss(const float* pred, int64_t pred_stride, const void* label, int label_dtype, int64_t n, double* partial,
+                double* result, void* stream);
+int rh_rank_metrics_plan(int M, int* stage, int* users_per_workgroup, int* max_grid, int64_t* partial_doubles);
+int rh_rank_metrics(const int64_t* pred, int64_t ld, int M, int K, const int64_t* truth_off, const int64_t* truth_ids,
+                    int64_t n_truth, const int* cutoffs, int n_k, const double* gain, const double* ideal, double* partial,
+                    int64_t* hits, int64_t* gts, double* sums, double* per_user, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

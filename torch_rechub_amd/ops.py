@@ -4437,3 +4437,210 @@ def cin_layer(x0, h, weight, bias):
                            f"{tuple(weight.shape)}, bias {tuple(bias.shape)}: need x0 (B, F, D), h (B, Hp, D), weight "
                            "(Ho, F * Hp, 1), bias (Ho,)")
     return _CinLayerFn.apply(x0, h, weight, bias)
+
+
+# --------------------------------------------------------------------------------------------
+# Evaluation metrics (csrc/metric.hip): exact AUC / GAUC, log loss, top-K list metrics
+# --------------------------------------------------------------------------------------------
+_LABEL_DTYPES = {torch.float32: 0, torch.float64: 1, torch.int64: 2, torch.uint8: 3, torch.bool: 3}
+_RANK_MAX_K, _RANK_MAX_CUTOFFS = 256, 8
+_rank_tables = {}
+
+
+def auc_plan(n):
+    """(chunk, max_grid, workspace_bytes) of rh_auc_groups over n samples: the sorted elements a workgroup takes per trip,
+    the grid cap (more chunks than that are further trips) and the scratch size."""
+    chunk, grid, nbytes = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
+    _lib.call("rh_auc_plan", int(n), ctypes.c_void_p(ctypes.addressof(chunk)), ctypes.c_void_p(ctypes.addressof(grid)),
+              ctypes.c_void_p(ctypes.addressof(nbytes)))
+    return chunk.value, grid.value, nbytes.value
+
+
+def _metric_inputs(what, pred, label, *more):
+    """The guards of the pointwise metrics, before anything is allocated or launched.  -> (pred 1-D, possibly strided;
+    label 1-D contiguous; n)."""
+    require_hip(pred, label, *more)
+    if pred.dtype != torch.float32:
+        raise ValueError(f"torch_rechub_amd: {what} takes float32 predictions, got {pred.dtype}")
+    if label.dtype not in _LABEL_DTYPES:
+        raise ValueError(f"torch_rechub_amd: {what} takes float32, float64, int64, uint8 or bool labels, got {label.dtype}")
+    if pred.numel() != label.numel() or any(t.numel() != pred.numel() for t in more):
+        raise ValueError(f"torch_rechub_amd: {what}: {[tuple(t.shape) for t in (pred, label) + more]} do not agree")
+    n = int(pred.numel())
+    if n == 0:
+        raise ValueError(f"torch_rechub_amd: {what} of an empty input")
+    if n >= 2 ** 31:
+        raise ValueError(f"torch_rechub_amd: {what} takes fewer than 2**31 samples, got {n}")
+    pred = pred.detach()
+    if pred.dim() != 1:
+        pred = pred.reshape(-1)
+    return pred, label.detach().reshape(-1).contiguous(), n
+
+
+def _auc_groups(pred, label, g, G, n):
+    dev = pred.device
+    ps = int(pred.stride(0)) if n > 1 else 1
+    keys = torch.empty((n,), dtype=torch.int64, device=dev)
+    _lib.call("rh_auc_keys", _p(pred), ps, _p(g), n, _p(keys), _stream())
+    order = torch.sort(keys).indices  # the permutation is plumbing: the counting below is the metric
+    del keys
+    work = torch.empty((auc_plan(n)[2],), dtype=torch.uint8, device=dev)
+    out = torch.empty((3, G), dtype=torch.int64, device=dev)
+    bad = torch.empty((2,), dtype=torch.int64, device=dev)
+    _lib.call("rh_auc_groups", _p(pred), ps, _p(label), _LABEL_DTYPES[label.dtype], _p(g), _p(order), n, G, _p(work), _p(out),
+              _p(bad), _stream())
+    nonfinite, badlabel = bad.tolist()
+    if nonfinite:
+        raise ValueError(f"torch_rechub_amd: {nonfinite} predictions are NaN or infinite")
+    if badlabel:
+        raise ValueError(f"torch_rechub_amd: {badlabel} labels are neither 0 nor 1")
+    return out
+
+
+def auc_groups(pred, label, group=None):
+    """(P, N, U2), int64 tensors of length G: per group the positives, the negatives and the rank statistic
+    U2 = sum over positives of 2 #{negatives below} + #{negatives tied}, so that AUC_g = U2 / (2 P N) exactly.  ``group``:
+    dense int64 ids in [0, G) with G = max + 1, or None for one group.  Ties are equal VALUES (-0.0 == +0.0, distinct
+    denormals distinct).  NaN / infinite predictions and labels other than 0 / 1 raise ValueError.  No autograd; current
+    stream."""
+    more = () if group is None else (group,)
+    pred, label, n = _metric_inputs("auc_groups", pred, label, *more)
+    G, g = 1, None
+    if group is not None:
+        if group.dtype != torch.int64:
+            raise ValueError(f"torch_rechub_amd: auc_groups takes int64 group ids, got {group.dtype}")
+        g = group.detach().reshape(-1).contiguous()
+        lo, hi = int(g.min()), int(g.max())
+        if lo < 0 or hi >= 2 ** 31 - 1:
+            raise ValueError(f"torch_rechub_amd: auc_groups takes dense group ids in [0, G), G < 2**31; got [{lo}, {hi}]")
+        G = hi + 1
+    out = _auc_groups(pred, label, g, G, n)
+    return out[0], out[1], out[2]
+
+
+def auc(pred, label):
+    """roc_auc_score(label, pred) as a Python float: the exact rational U2 / (2 P N), correctly rounded."""
+    P, N, U2 = (int(t) for t in auc_groups(pred, label))
+    if P == 0 or N == 0:
+        raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
+    return U2 / (2 * P * N)
+
+
+def gauc(pred, label, users, weights=None):
+    """sum_u w_u AUC_u / sum_u w_u over the distinct values u of ``users`` (any int64 tensor); w_u = the samples of u, or
+    ``weights[u]`` (a 1-D tensor indexed by user id).  nan when a user holds one class only."""
+    pred, label, n = _metric_inputs("gauc", pred, label, users)
+    if users.dtype != torch.int64:
+        raise ValueError(f"torch_rechub_amd: gauc takes int64 user ids, got {users.dtype}")
+    if weights is not None:
+        require_hip(weights)
+        if weights.dim() != 1:
+            raise ValueError("torch_rechub_amd: gauc takes a 1-D weight tensor indexed by user id")
+    uniq, g = torch.unique(users.detach().reshape(-1), return_inverse=True)
+    G = int(uniq.numel())
+    w = None
+    if weights is not None:
+        if int(uniq[0]) < 0 or int(uniq[-1]) >= weights.numel():
+            raise ValueError("torch_rechub_amd: gauc: a user id lies outside the weight tensor")
+        w = weights.detach()[uniq].to(torch.float64).contiguous()
+    stats = _auc_groups(pred, label, g.contiguous(), G, n)
+    dev = pred.device
+    partial = torch.empty((3072,), dtype=torch.float64, device=dev)
+    result = torch.empty((2,), dtype=torch.float64, device=dev)
+    single = torch.empty((1,), dtype=torch.int64, device=dev)
+    _lib.call("rh_gauc_reduce", _p(stats), _p(w), G, _p(partial), _p(result), _p(single), _stream())
+    if int(single):
+        return float("nan")
+    num, den = result.tolist()
+    return num / den
+
+
+def log_loss(pred, label):
+    """-mean(y log p + (1 - y) log(1 - p)) as a Python float; p is widened to double before the logarithms."""
+    pred, label, n = _metric_inputs("log_loss", pred, label)
+    dev = pred.device
+    partial = torch.empty((1024,), dtype=torch.float64, device=dev)
+    result = torch.empty((1,), dtype=torch.float64, device=dev)
+    _lib.call("rh_log_loss", _p(pred), int(pred.stride(0)) if n > 1 else 1, _p(label), _LABEL_DTYPES[label.dtype], n,
+              _p(partial), _p(result), _stream())
+    return float(result)
+
+
+def rank_metrics_plan(M):
+    """(stage, users_per_workgroup, max_grid, partial_doubles) of rh_rank_metrics over M users."""
+    vals = [ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)]
+    _lib.call("rh_rank_metrics_plan", int(M), *[ctypes.c_void_p(ctypes.addressof(v)) for v in vals])
+    return tuple(v.value for v in vals)
+
+
+def rank_gain_tables(K):
+    """(gain (K,), ideal (K + 1,)) as float64 numpy arrays: gain[j] = 1 / log2(j + 2) position by position, ideal its
+    sequential prefix sums from 0 -- the operands and the order of additions of the host loop."""
+    import numpy as np
+    gain = np.array([1. / np.log2(j + 2) for j in range(K)], dtype=np.float64)
+    ideal = np.zeros(K + 1, dtype=np.float64)
+    for j in range(K):
+        ideal[j + 1] = ideal[j] + gain[j]
+    return gain, ideal
+
+
+def pack_truth(truth, device):
+    """A list of id lists as the CSR pair (offsets (M + 1,), ids) of int64 tensors on ``device``: packed once, on the host."""
+    import numpy as np
+    lens = np.fromiter((len(t) for t in truth), dtype=np.int64, count=len(truth))
+    off = np.zeros(len(truth) + 1, dtype=np.int64)
+    np.cumsum(lens, out=off[1:])
+    ids = np.fromiter((i for t in truth for i in t), dtype=np.int64, count=int(off[-1]))
+    return torch.from_numpy(off).to(device), torch.from_numpy(ids).to(device)
+
+
+def rank_metrics(pred_ids, truth, cutoffs, per_user=False):
+    """The raw sums behind the top-K list metrics.  ``pred_ids`` (M, K) int64 (what ``topk_items`` returns; a strided
+    ``ids[:, :k]`` view is read in place), ``truth`` an (offsets, ids) pair of int64 device tensors or a row-aligned list of
+    id lists, ``cutoffs`` at most 8 ints in [1, K].  -> dict: ``hits`` (n_k,) int64, ``gts`` (1,) int64, ``sums`` (n_k, 4)
+    float64 = mrr, recall, precision, ndcg summed over users, ``per_user`` (M, n_k, 5) float64 = hit, mrr, recall,
+    precision, ndcg or None.  No autograd; current stream."""
+    require_hip(pred_ids)
+    if pred_ids.dim() != 2 or pred_ids.dtype != torch.int64:
+        raise ValueError("torch_rechub_amd: rank_metrics takes an (M, K) int64 id tensor")
+    M, K = (int(v) for v in pred_ids.shape)
+    if M == 0 or K == 0:
+        raise ValueError("torch_rechub_amd: rank_metrics of an empty input")
+    if K > _RANK_MAX_K:
+        from .models.matching._listwise import no_kernel
+        raise no_kernel(f"list metrics over K={K} recommendations (1 <= K <= {_RANK_MAX_K})")
+    cutoffs = [int(k) for k in cutoffs]
+    if not 1 <= len(cutoffs) <= _RANK_MAX_CUTOFFS or any(not 1 <= k <= K for k in cutoffs):
+        raise ValueError(f"torch_rechub_amd: rank_metrics takes 1 to {_RANK_MAX_CUTOFFS} cut-offs within [1, K={K}], got "
+                         f"{cutoffs}")
+    if isinstance(truth, (tuple, list)) and len(truth) == 2 and all(torch.is_tensor(t) for t in truth):
+        off, ids = truth
+        require_hip(off, ids)
+        if off.dtype != torch.int64 or ids.dtype != torch.int64 or off.dim() != 1 or ids.dim() != 1:
+            raise ValueError("torch_rechub_amd: rank_metrics takes int64 1-D truth offsets and ids")
+        off, ids = off.contiguous(), ids.contiguous()
+    else:
+        if len(truth) != M:
+            raise ValueError(f"torch_rechub_amd: rank_metrics: {len(truth)} truth lists for {M} users")
+        off, ids = pack_truth(truth, pred_ids.device)
+    if off.numel() != M + 1:
+        raise ValueError(f"torch_rechub_amd: rank_metrics: {off.numel()} truth offsets for {M} users (M + 1 expected)")
+    pred_ids = pred_ids.detach()
+    if pred_ids.stride(1) != 1 or (M > 1 and pred_ids.stride(0) < K):
+        pred_ids = pred_ids.contiguous()
+    ld = int(pred_ids.stride(0)) if M > 1 else K
+    dev = pred_ids.device
+    tables = _rank_tables.get((K, dev))
+    if tables is None:
+        tables = _rank_tables[(K, dev)] = tuple(torch.from_numpy(t).to(dev) for t in rank_gain_tables(K))
+    n_k = len(cutoffs)
+    cuts = (ctypes.c_int * n_k)(*cutoffs)
+    partial = torch.empty((rank_metrics_plan(M)[3],), dtype=torch.float64, device=dev)
+    hits = torch.empty((n_k,), dtype=torch.int64, device=dev)
+    gts = torch.empty((1,), dtype=torch.int64, device=dev)
+    sums = torch.empty((n_k, 4), dtype=torch.float64, device=dev)
+    users = torch.empty((M, n_k, 5), dtype=torch.float64, device=dev) if per_user else None
+    _lib.call("rh_rank_metrics", _p(pred_ids), ld, M, K, _p(off), _p(ids), int(ids.numel()),
+              ctypes.c_void_p(ctypes.addressof(cuts)), n_k, _p(tables[0]), _p(tables[1]), _p(partial), _p(hits), _p(gts),
+              _p(sums), _p(users), _stream())
+    return {"hits": hits, "gts": gts, "sums": sums, "per_user": users}

@@ -693,7 +693,18 @@ class CTRTrainer(object):
     def _to_device(self, x_dict):
         return {k: (v if v.is_cuda else v.to(self.device, non_blocking=True)) for k, v in x_dict.items()}
 
-    def evaluate(self, model, data_loader):
+    def _require_default_metric(self, fns, defaults):
+        """on_device=True scores with the device metrics, which stand in for the DEFAULT evaluate functions only."""
+        if any(fn is not default for fn, default in zip(fns, defaults)):
+            raise ValueError("evaluate(on_device=True) scores with basic.metric.auc_score on the device in place of the "
+                             "default roc_auc_score; this trainer's evaluate function was replaced, so evaluate on the host")
+
+    def evaluate(self, model, data_loader, on_device=False):
+        """``on_device=True``: predictions and targets stay on the device (no copy per batch), are concatenated once and
+        scored with ``basic.metric.auc_score``; only for the default ``roc_auc_score``."""
+        if on_device:
+            from sklearn.metrics import roc_auc_score
+            self._require_default_metric([self.evaluate_fn], [roc_auc_score])
         self.flush()
         if self.tables == "shard":
             self._check_equal_batches(data_loader, "evaluate (row-sharded tables: each batch is a collective)")
@@ -704,9 +715,16 @@ class CTRTrainer(object):
                            disable=not self.show_progress)
             for x_dict, y in it:
                 y_pred = model(self._to_device(x_dict)) if self.loss_mode else model(self._to_device(x_dict))[0]
-                targets.append(y.detach().float().reshape(-1).cpu())
-                predicts.append(y_pred.detach().float().reshape(-1).cpu())
+                if on_device:
+                    targets.append(y.detach().to(self.device, non_blocking=True).float().reshape(-1))
+                    predicts.append(y_pred.detach().float().reshape(-1))
+                else:
+                    targets.append(y.detach().float().reshape(-1).cpu())
+                    predicts.append(y_pred.detach().float().reshape(-1).cpu())
         ops.check_errors(self.device)
+        if on_device:
+            from ..basic import metric
+            return metric.auc_score(torch.cat(targets), torch.cat(predicts))
         return self.evaluate_fn(torch.cat(targets).numpy(), torch.cat(predicts).numpy())
 
     def predict(self, model, data_loader):

@@ -143,7 +143,11 @@ class MatchTrainer(CTRTrainer):
         return (hasattr(self.model, "catalogue_head") and type(c) is torch.nn.CrossEntropyLoss and c.reduction == "mean" and
                 c.weight is None and c.label_smoothing == 0.0 and c.ignore_index == -100)
 
-    def evaluate(self, model, data_loader):
+    def evaluate(self, model, data_loader, on_device=False):
+        """``on_device=True``: as ``CTRTrainer.evaluate`` -- no copy per batch, one ``basic.metric.auc_score`` on the device."""
+        if on_device:
+            from sklearn.metrics import roc_auc_score
+            self._require_default_metric([self.evaluate_fn], [roc_auc_score])
         self.flush()
         model.eval()
         targets, predicts = [], []
@@ -151,9 +155,16 @@ class MatchTrainer(CTRTrainer):
             for x_dict, y in tqdm.tqdm(data_loader, desc="validation", smoothing=0, mininterval=1.0,
                                        disable=not self.show_progress):
                 y_pred = model(self._to_device(x_dict))
-                targets.append(y.detach().float().reshape(-1).cpu())
-                predicts.append(y_pred.detach().float().reshape(-1).cpu())
+                if on_device:
+                    targets.append(y.detach().to(self.device, non_blocking=True).float().reshape(-1))
+                    predicts.append(y_pred.detach().float().reshape(-1))
+                else:
+                    targets.append(y.detach().float().reshape(-1).cpu())
+                    predicts.append(y_pred.detach().float().reshape(-1).cpu())
         ops.check_errors(self.device)
+        if on_device:
+            from ..basic import metric
+            return metric.auc_score(torch.cat(targets), torch.cat(predicts))
         return self.evaluate_fn(torch.cat(targets).numpy(), torch.cat(predicts).numpy())
 
     def inference_embedding(self, model, mode, data_loader, model_path):

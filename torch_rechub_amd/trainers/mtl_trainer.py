@@ -128,7 +128,12 @@ class MTLTrainer(CTRTrainer):
             logger.finish()
         return total_log
 
-    def evaluate(self, model, data_loader):
+    def evaluate(self, model, data_loader, on_device=False):
+        """``on_device=True``: predictions and targets stay on the device, are concatenated once, and every classification
+        task is scored with ``basic.metric.auc_score``, every regression task with torch's mean squared error in float64;
+        only for the defaults of ``get_metric_func``."""
+        if on_device:
+            self._require_default_metric(self.evaluate_fns, [get_metric_func(t) for t in self.task_types])
         self.flush()
         if self.tables == "shard":
             self._check_equal_batches(data_loader, "evaluate (row-sharded tables: each batch is a collective)")
@@ -138,9 +143,24 @@ class MTLTrainer(CTRTrainer):
             for x_dict, ys in tqdm.tqdm(data_loader, desc="validation", smoothing=0, mininterval=1.0,
                                         disable=not self.show_progress):
                 y_preds = model(self._to_device(x_dict))
-                targets.append(ys.detach().float().cpu())
-                predicts.append(y_preds.detach().float().cpu())
+                if on_device:
+                    targets.append(ys.detach().to(self.device, non_blocking=True).float())
+                    predicts.append(y_preds.detach().float())
+                else:
+                    targets.append(ys.detach().float().cpu())
+                    predicts.append(y_preds.detach().float().cpu())
         ops.check_errors(self.device)
+        if on_device:
+            from ..basic import metric
+            targets, predicts = torch.cat(targets), torch.cat(predicts)
+            scores = []
+            for i, task in enumerate(self.task_types):
+                if task == "classification":
+                    scores.append(metric.auc_score(targets[:, i], predicts[:, i]))
+                else:
+                    diff = predicts[:, i].double() - targets[:, i].double()
+                    scores.append(float((diff * diff).mean()))
+            return scores
         targets, predicts = torch.cat(targets).numpy(), torch.cat(predicts).numpy()
         return [self.evaluate_fns[i](targets[:, i], predicts[:, i]) for i in range(self.n_task)]
 
