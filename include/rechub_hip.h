@@ -996,6 +996,39 @@ int rh_topk_fwd(const float* q, int64_t ldq, const float* x, const float* bias, 
                 const int64_t* invalid, int n_inv, int M, int D, int V, int K, int nsplit, void* workspace, int64_t* ids,
                 float* scores, void* stream);
 
+/* ---- inverted-file index (csrc/ivf.hip) ------------------------------------------------------------------------------
+ * The top K of rh_topk_fwd's score over the UNION of the lists a query probes, without a host synchronisation.
+ * xs (V, D) fp32 contiguous: the table with its rows grouped by list; bias_s (V,) or null, grouped alike; row_id (V,)
+ * int32: the original id of every grouped row, ASCENDING inside each list; list_off (nlists + 1,) int32: list l is the rows
+ * [list_off[l], list_off[l + 1]).  q (M, D) fp32 with row stride ldq.  exclude (M, S) int64 or null (S = 0): ORIGINAL ids
+ * that may not be returned to query i (others are padding).
+ * The (query, slot) pairs of probe (M, nprobe) arrive grouped by list, computed by the caller on the device: group 0 =
+ * the pairs whose slot holds no list (-1), group l + 1 = the pairs that probe list l (the lists of one query are distinct);
+ * pair (M nprobe,) int32 = the pair indices i nprobe + slot in group order (a permutation), pair_off (nlists + 2,) int32 =
+ * the groups' offsets into it, tile_off (nlists + 2,) int32 = the prefix sum of ceil(group size / rows_per_tile).
+ * One workgroup takes rows_per_tile pairs of one group and walks the WHOLE list (an over-long list is not split); the grid
+ * is the fixed bound ceil(M nprobe / rows_per_tile) + nlists + 1, a workgroup past tile_off's end leaves.
+ * partials: 8 M nprobe K bytes, every element written.  ids (M, K) int64 = original ids and scores (M, K) fp32, sorted by
+ * (score descending, id ascending); with fewer than K candidates the tail is id -1, score -inf.  A score is computed
+ * exactly as rh_topk_fwd computes it (it depends on q_i, x_j and D only), so with every list probed the result equals
+ * rh_topk_fwd's on the un-grouped table bit for bit.  No atomics: two runs give the same bits.
+ * 1 <= D <= 1024, 1 <= K <= 256, 0 <= S <= 1024, 1 <= nprobe <= 256, 1 <= V < 2^31, else RH_E_UNSUPPORTED; M = 0 returns
+ * at once.  rh_ivf_supported and rh_ivf_plan answer through HOST pointers: *supported = 0 / 1; *rows_per_tile = 64 up to
+ * K = 128, 32 above; *grid = the bound above; *workspace_bytes = 8 M nprobe K (partials) + 4 M nprobe (pair) +
+ * 8 (nlists + 2) (pair_off, tile_off).
+ * rh_ivf_list_mean: the update step of k-means.  centroids (nlists, D)[l] = the mean of the rows of list l of xs (V, D),
+ * summed in a fixed order (bit-reproducible, no atomics) and divided once; an empty list keeps previous (nlists, D)[l].
+ * replaces: FaissBuilder of torch_rechub/serving/faiss.py with index_type="IVF" (faiss's `IVF{nlists},Flat` with its
+ *           k-means training, and `nprobe`). */
+int rh_ivf_supported(int D, int K, int S, int nprobe, int* supported);
+int rh_ivf_plan(int M, int nlists, int nprobe, int K, int* rows_per_tile, int64_t* grid, int64_t* workspace_bytes);
+int rh_ivf_scan(const float* q, int64_t ldq, const float* xs, const float* bias_s, const int32_t* row_id,
+                const int32_t* list_off, int nlists, const int32_t* pair, const int32_t* pair_off, const int32_t* tile_off,
+                const int64_t* exclude, int S, int M, int D, int V, int K, int nprobe, void* partials, int64_t* ids,
+                float* scores, void* stream);
+int rh_ivf_list_mean(const float* xs, const int32_t* list_off, const float* previous, int V, int D, int nlists,
+                     float* centroids, void* stream);
+
 /* ---- session-based retrieval (csrc/session.hip) ---------------------------------------------------------------------
  * GRU recurrence of nn.GRU (gate order r, z, n) from the zero state: xw (B, T, 3H) = x W_ih^T (+ b_ih) for every step,
  * w_hh (3H, H) = weight_hh, b_hh (3H,) or null.  1 <= H <= rh_gru_max_hidden() (128), else RH_E_UNSUPPORTED.

@@ -1,6 +1,6 @@
 // The 64 x 64 workgroup tile on v_mfma_f32_32x32x2_f32 (exact f32 products, k-ordered accumulation) shared by the
 // attention kernels (hstu.hip; softmax_attn_tile.h, the flash-style body of hllm.hip and t5attn.hip), the streaming cross
-// entropy (stream_ce.hip), the top-k scores (topk.hip) and SASRec's row-tile GEMM stages (sasrec.hip).  Helpers only: a
+// entropy (stream_ce.hip), the top-k scores (topk.hip, ivf.hip) and SASRec's row-tile GEMM stages (sasrec.hip).  Helpers only: a
 // kernel family that is more than the tile has its own header on top of this one, as softmax_attn_tile.h is.
 //
 // Lane map: four wavefronts per workgroup; wavefront w owns the 32 x 32 accumulator of quadrant (wm = w & 1, wn = w >> 1);

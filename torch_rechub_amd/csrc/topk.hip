@@ -13,14 +13,10 @@
 // Merge kernel: one wavefront per row merges the nsplit sorted lists under the same total order.  Every range's top K
 // under a total order holds the global top K's members of that range, so the result does not depend on nsplit.
 // No atomics; every element of the partials is written (unused tail: -inf, -1).
-#include <math.h>
-
-#include "mfma_tile.h"
+// The K-list (threshold, ballot, cooperative insert) and the merge of one row live in topk_list.h, shared with ivf.hip.
+#include "topk_list.h"
 
 namespace {
-
-constexpr int kTopkMaxD = 1024, kTopkMaxK = 256, kTopkMaxS = 1024, kTopkMaxSplit = 1024;
-constexpr int kTopkListBytes = 64 * 1024;  // LDS of the K-lists of one workgroup
 
 struct TopkArgs {
   const float* q;          // (M, D), row stride ldq
@@ -37,19 +33,6 @@ struct TopkArgs {
   int64_t* ids;            // (M, K)
   float* scores;           // (M, K)
 };
-
-__host__ __device__ inline int topk_rows(int K) { return K * 64 * 8 <= kTopkListBytes ? 64 : 32; }
-
-size_t topk_lds_bytes(int K) {
-  return (size_t)2 * kT * kLd * sizeof(float) + (size_t)topk_rows(K) * K * 8 + (size_t)2 * kT * 4;
-}
-
-// orders the LDS accesses of the lanes of one wavefront (the hardware runs them in program order)
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __global__ __launch_bounds__(RH_BLOCK) void topk_scan_kernel(const TopkArgs a) {
   extern __shared__ __align__(16) float lds[];
@@ -107,52 +90,11 @@ __global__ __launch_bounds__(RH_BLOCK) void topk_scan_kernel(const TopkArgs a) {
       const float s = ws[row * kLd + lane];
       int n = cnt[row];
       float t = thr[row];
-      uint64_t m = __ballot(c0 + lane < hi && (n < K || s > t));
+      const uint64_t m = __ballot(c0 + lane < hi && (n < K || s > t));
       if (m == 0) continue;
-      float* rs = ls + row * K;
-      int* ri = li + row * K;
       const int64_t* ex = a.S > 0 ? a.exclude + (r0 + row) * a.S : nullptr;
-      while (m != 0) {
-        const int j = __ffsll((unsigned long long)m) - 1;
-        m &= m - 1;
-        const float sj = __shfl(s, j, RH_WAVE);
-        if (n >= K && !(sj > t)) continue;
-        const int64_t id = c0 + j;
-        bool drop = false;
-        for (int e = lane; e < a.S; e += RH_WAVE) drop |= ex[e] == id;
-        for (int e = lane; e < a.n_inv; e += RH_WAVE) drop |= a.invalid[e] == id;
-        if (__ballot(drop) != 0) continue;
-        // p = entries that stay in front (score >= sj: every entry has a lower id); entries [p, n) move one place back
-        int p = 0;
-        for (int u = 0; u < nch; ++u) {
-          const int e = u * RH_WAVE + lane;
-          p += __popcll(__ballot(e < n && rs[e] >= sj));
-        }
-        float os[kTopkMaxK / RH_WAVE];
-        int oi[kTopkMaxK / RH_WAVE];
-#pragma unroll
-        for (int u = 0; u < kTopkMaxK / RH_WAVE; ++u) {
-          const int e = u * RH_WAVE + lane;
-          const bool mv = e > p && e <= n && e < K;
-          os[u] = mv ? rs[e - 1] : 0.f;
-          oi[u] = mv ? ri[e - 1] : 0;
-        }
-        wave_sync();
-#pragma unroll
-        for (int u = 0; u < kTopkMaxK / RH_WAVE; ++u) {
-          const int e = u * RH_WAVE + lane;
-          if (e == p) {
-            rs[e] = sj;
-            ri[e] = (int)id;
-          } else if (e > p && e <= n && e < K) {
-            rs[e] = os[u];
-            ri[e] = oi[u];
-          }
-        }
-        wave_sync();
-        if (n < K) ++n;
-        if (n == K) t = rs[K - 1];
-      }
+      topk_row_hits(m, s, ls + row * K, li + row * K, n, t, K, nch, ex, a.S, a.invalid, a.n_inv, lane,
+                    [&](int j) { return c0 + j; });
       if (lane == 0) {
         cnt[row] = n;
         thr[row] = t;
@@ -170,66 +112,12 @@ __global__ __launch_bounds__(RH_BLOCK) void topk_scan_kernel(const TopkArgs a) {
   }
 }
 
-// (s, id) ahead of (bs, bi) in (score descending, id ascending); id < 0 = no entry, behind everything
-__device__ __forceinline__ bool topk_ahead(float s, int id, float bs, int bi) {
-  return id >= 0 && (bi < 0 || s > bs || (s == bs && id < bi));
-}
-
-// one wavefront per row; lane l owns the lists l, l + 64, ... and keeps the best of their heads
+// one wavefront per row
 __global__ __launch_bounds__(RH_WAVE) void topk_merge_kernel(const TopkArgs a) {
-  __shared__ int hp[kTopkMaxSplit];  // head of each list; touched by its owner lane only
-  const int lane = threadIdx.x, K = a.K;
+  __shared__ int hp[kTopkMaxSplit];
   const int64_t row = blockIdx.x;
-  const float* ps = a.part_s + row * a.nsplit * K;
-  const int32_t* pi = a.part_i + row * a.nsplit * K;
-  for (int l = lane; l < a.nsplit; l += RH_WAVE) hp[l] = 0;
-  float bs;
-  int bi, bl;
-  auto rescan = [&]() {
-    bs = -INFINITY;
-    bi = -1;
-    bl = -1;
-    for (int l = lane; l < a.nsplit; l += RH_WAVE) {
-      const int h = hp[l];
-      if (h >= K) continue;
-      const float s = ps[(int64_t)l * K + h];
-      const int id = pi[(int64_t)l * K + h];
-      if (topk_ahead(s, id, bs, bi)) {
-        bs = s;
-        bi = id;
-        bl = l;
-      }
-    }
-  };
-  rescan();
-  int k = 0;
-  for (; k < K; ++k) {
-    float s = bs;
-    int id = bi, l = bl;
-#pragma unroll
-    for (int m = RH_WAVE / 2; m >= 1; m >>= 1) {
-      const float s2 = __shfl_xor(s, m, RH_WAVE);
-      const int id2 = __shfl_xor(id, m, RH_WAVE), l2 = __shfl_xor(l, m, RH_WAVE);
-      if (topk_ahead(s2, id2, s, id)) {
-        s = s2;
-        id = id2;
-        l = l2;
-      }
-    }
-    if (id < 0) break;  // every list is used up (wavefront-uniform: ids are distinct, every lane holds the same winner)
-    if (lane == 0) {
-      a.ids[row * K + k] = id;
-      a.scores[row * K + k] = s;
-    }
-    if (lane == (l & (RH_WAVE - 1))) {
-      hp[l] += 1;
-      rescan();
-    }
-  }
-  for (int e = k + lane; e < K; e += RH_WAVE) {
-    a.ids[row * K + e] = -1;
-    a.scores[row * K + e] = -INFINITY;
-  }
+  topk_merge_row(a.part_s + row * a.nsplit * a.K, a.part_i + row * a.nsplit * a.K, a.nsplit, a.K, a.ids + row * a.K,
+                 a.scores + row * a.K, hp, threadIdx.x);
 }
 
 bool topk_shape_ok(int D, int K, int S) {

@@ -3708,6 +3708,121 @@ def topk_items(q, table, k, bias=None, exclude=None, invalid=None, nsplit=None):
 
 
 # --------------------------------------------------------------------------------------------
+# Inverted-file index: the list scan and the k-means update (csrc/ivf.hip)
+# --------------------------------------------------------------------------------------------
+def ivf_supported(D, K, S=0, nprobe=1):
+    """Whether csrc/ivf.hip takes width D, K results, S exclusions per query and nprobe lists per query (D <= 1024,
+    K <= 256, S <= 1024, nprobe <= 256)."""
+    out = ctypes.c_int(0)
+    _lib.call("rh_ivf_supported", int(D), int(K), int(S), int(nprobe), ctypes.c_void_p(ctypes.addressof(out)))
+    return bool(out.value)
+
+
+def ivf_plan(M, nlists, nprobe, K):
+    """(rows_per_tile, grid, workspace_bytes) of ``ivf_scan``: the (query, slot) pairs one workgroup takes, the fixed grid
+    bound ceil(M nprobe / rows_per_tile) + nlists + 1, and 8 M nprobe K bytes of partial lists + 4 M nprobe of pair
+    indices + 8 (nlists + 2) of group and tile offsets."""
+    rb, grid, nbytes = ctypes.c_int(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.call("rh_ivf_plan", int(M), int(nlists), int(nprobe), int(K), ctypes.c_void_p(ctypes.addressof(rb)),
+              ctypes.c_void_p(ctypes.addressof(grid)), ctypes.c_void_p(ctypes.addressof(nbytes)))
+    return rb.value, grid.value, nbytes.value
+
+
+def ivf_scan(q, table_sorted, row_ids, list_offsets, probe, k, bias=None, exclude=None):
+    """(ids (M, k) int64, scores (M, k) float32): the k best rows for every row of ``q`` (M, D) by q_i . x_j (+ bias[j])
+    among the lists it probes, best first, exact ties to the lower id; ``topk_items`` restricted to a union of lists.
+    ``table_sorted`` (V, D) holds the table's rows grouped by list, ``bias`` (V,) alike, ``row_ids`` (V,) int32 the original
+    id of every grouped row (ascending inside each list: a stable sort by list gives that), ``list_offsets`` (nlists + 1,)
+    int32 the lists' offsets.  ``probe`` (M, nprobe) int32: the lists of each query, distinct per row; an entry outside
+    [0, nlists) (-1) is no list.  ``exclude`` (M, S) int64: original ids that may not be returned to query i (anything
+    else is padding).  The returned ids are original ids; with fewer than k candidates the tail is id -1, score -inf.
+    With every list probed the result is ``topk_items``' on the un-grouped table, bit for bit.  The pairs are grouped by
+    list with a stable ``torch.sort``; nothing synchronises with the host.  No autograd; runs on the current stream."""
+    require_hip(q, table_sorted, row_ids, list_offsets, probe, bias, exclude)
+    if q.dim() != 2 or table_sorted.dim() != 2 or q.shape[1] != table_sorted.shape[1]:
+        raise ValueError("ivf_scan: q (M, D) and table_sorted (V, D) expected")
+    if q.dtype != torch.float32 or table_sorted.dtype != torch.float32 or \
+            (bias is not None and bias.dtype != torch.float32):
+        raise ValueError("torch_rechub_amd: ivf_scan takes float32 tensors")
+    if row_ids.dtype != torch.int32 or list_offsets.dtype != torch.int32 or probe.dtype != torch.int32:
+        raise ValueError("ivf_scan: row_ids, list_offsets and probe are int32 tensors")
+    if not table_sorted.is_contiguous():
+        raise ValueError("ivf_scan: the table must be contiguous")
+    M, D = (int(v) for v in q.shape)
+    V, k = int(table_sorted.shape[0]), int(k)
+    if tuple(row_ids.shape) != (V,) or list_offsets.dim() != 1 or list_offsets.shape[0] < 2:
+        raise ValueError("ivf_scan: row_ids (V,) and list_offsets (nlists + 1,) expected")
+    nlists = int(list_offsets.shape[0]) - 1
+    if probe.dim() != 2 or probe.shape[0] != M:
+        raise ValueError("ivf_scan: probe (M, nprobe) expected")
+    nprobe = int(probe.shape[1])
+    if exclude is not None and (exclude.dim() != 2 or exclude.shape[0] != M):
+        raise ValueError("ivf_scan: exclude (M, S) expected")
+    S = 0 if exclude is None else int(exclude.shape[1])
+    if bias is not None and tuple(bias.shape) != (V,):
+        raise ValueError("ivf_scan: bias (V,) expected")
+    if V < 1 or M * nprobe >= 2 ** 31 - 64 * (nlists + 2) or not ivf_supported(D, k, S, nprobe):
+        from .models.matching._listwise import no_kernel
+        raise no_kernel(f"the inverted-file scan at D={D}, k={k}, {S} exclusions per query, nprobe={nprobe}, V={V} "
+                        "(1 <= D <= 1024, 1 <= k <= 256, S <= 1024, 1 <= nprobe <= 256, V >= 1, M nprobe < 2^31)")
+    q, table_sorted = q.detach(), table_sorted.detach()
+    if M > 0 and (q.stride(1) != 1 or q.stride(0) < D):
+        q = q.contiguous()
+    ldq = int(q.stride(0)) if M > 1 else D
+    row_ids, list_offsets = row_ids.contiguous(), list_offsets.contiguous()
+    if bias is not None:
+        bias = bias.detach().contiguous()
+    if S > 0:
+        exclude = exclude.to(torch.int64).contiguous()
+    dev = q.device
+    ids = torch.empty((M, k), dtype=torch.int64, device=dev)
+    scores = torch.empty((M, k), dtype=torch.float32, device=dev)
+    if M == 0:
+        return ids, scores
+    rb = ivf_plan(M, nlists, nprobe, k)[0]
+    # the pairs grouped by list: group 0 = no list, group l + 1 = list l (a stable sort: reproducible pair order)
+    key = torch.where((probe >= 0) & (probe < nlists), probe + 1, torch.zeros_like(probe)).reshape(-1)
+    key, order = torch.sort(key, stable=True)
+    pair = order.to(torch.int32)
+    del order
+    bounds = torch.arange(nlists + 2, dtype=torch.int32, device=dev)
+    pair_off = torch.searchsorted(key, bounds, out_int32=True)
+    del key, bounds
+    tile_off = torch.zeros_like(pair_off)
+    tile_off[1:] = torch.cumsum((pair_off[1:] - pair_off[:-1] + (rb - 1)) // rb, 0)
+    part = torch.empty((8 * M * nprobe * k,), dtype=torch.uint8, device=dev)
+    _lib.call("rh_ivf_scan", _p(q), ldq, _p(table_sorted), _p(bias), _p(row_ids), _p(list_offsets), nlists, _p(pair),
+              _p(pair_off), _p(tile_off), _p(exclude) if S > 0 else _NULL, S, M, D, V, k, nprobe, _p(part), _p(ids),
+              _p(scores), _stream())
+    return ids, scores
+
+
+def ivf_list_mean(x_sorted, list_offsets, previous):
+    """(nlists, D) float32: row l = the mean of the rows [list_offsets[l], list_offsets[l + 1]) of ``x_sorted`` (V, D),
+    summed in a fixed order (two runs give the same bits) and divided once; an empty list keeps ``previous[l]``.  The
+    update step of k-means over rows grouped by list.  No autograd; runs on the current stream."""
+    require_hip(x_sorted, list_offsets, previous)
+    if x_sorted.dim() != 2 or previous.dim() != 2 or previous.shape[1] != x_sorted.shape[1] or previous.shape[0] < 1 or \
+            x_sorted.shape[1] < 1:
+        raise ValueError("ivf_list_mean: x_sorted (V, D) and previous (nlists, D) expected")
+    if x_sorted.dtype != torch.float32 or previous.dtype != torch.float32:
+        raise ValueError("torch_rechub_amd: ivf_list_mean takes float32 tensors")
+    nlists = int(previous.shape[0])
+    if list_offsets.dtype != torch.int32 or tuple(list_offsets.shape) != (nlists + 1,):
+        raise ValueError("ivf_list_mean: list_offsets (nlists + 1,) int32 expected")
+    if not x_sorted.is_contiguous():
+        raise ValueError("ivf_list_mean: the rows must be contiguous")
+    V, D = (int(v) for v in x_sorted.shape)
+    if V >= 2 ** 31:
+        from .models.matching._listwise import no_kernel
+        raise no_kernel(f"the list mean over V={V} rows (V < 2^31)")
+    previous, list_offsets = previous.detach().contiguous(), list_offsets.contiguous()
+    out = torch.empty_like(previous)
+    _lib.call("rh_ivf_list_mean", _p(x_sorted.detach()), _p(list_offsets), _p(previous), V, D, nlists, _p(out), _stream())
+    return out
+
+
+# --------------------------------------------------------------------------------------------
 # SASRec: the transformer block around ops.softmax_attention, fused per row tile (csrc/sasrec.hip)
 # --------------------------------------------------------------------------------------------
 _SASREC_MAX_D = 128

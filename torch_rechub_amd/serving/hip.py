@@ -7,6 +7,10 @@ Every metric is an inner-product search with a per-item bias, so one kernel serv
   "angular"  value = sqrt(max(0, 2 - 2 cos)), ascending (Annoy's distance); the table rows are normalised once at build,
              the queries at query time; a zero vector has cos 0 with everything.
 A query with fewer than ``top_k`` candidates gets id -1 and value +inf (-inf for "IP") in the tail.
+
+``HipIvfIndexer`` is the inverted-file index over the same three metrics (``HipBuilder(index_type="IVF")``): k-means
+centroids trained on the device, every row in the list of its nearest centroid, a query scanning only its ``nprobe``
+nearest lists on ``ops.ivf_scan`` (csrc/ivf.hip) -- approximate only in which rows it looks at.
 """
 import contextlib
 
@@ -93,19 +97,185 @@ class HipIndexer(BaseIndexer):
         save_index(file_path, self.metric, self._table)
 
 
-class HipBuilder(BaseBuilder):
-    """Builder of ``HipIndexer``.  ``metric``: "L2" (the default, as the reference's FaissBuilder), "IP" or "angular";
-    ``device``: where the table lives (default: the current HIP device).  An index file carries its own metric."""
+INDEX_TYPES = ("Flat", "IVF")
 
-    def __init__(self, metric="L2", device=None):
+
+def _assign(x, centroids, ops):
+    """(n,) int64: the nearest centroid of every row under L2, ties to the lower list: argmax of 2 x . c - |c|^2."""
+    bias = -(centroids * centroids).sum(dim=1)
+    return ops.topk_items(x * 2.0, centroids, 1, bias=bias)[0][:, 0]
+
+
+def _group(assign, nlists):
+    """(order (n,) int64, list_off (nlists + 1,) int32): the rows in list order -- a stable sort, so ids ascend inside a
+    list -- and the lists' offsets."""
+    key, order = torch.sort(assign, stable=True)
+    bounds = torch.arange(nlists + 1, dtype=key.dtype, device=key.device)
+    return order, torch.searchsorted(key, bounds, out_int32=True)
+
+
+def train_centroids(x, centroids, niter, ops):
+    """``niter`` rounds of Lloyd's k-means on the device: assign every row to its nearest centroid, then every centroid
+    becomes the mean of its rows (``ops.ivf_list_mean``; a centroid that lost all its rows stays where it was)."""
+    for _ in range(niter):
+        order, list_off = _group(_assign(x, centroids, ops), centroids.shape[0])
+        centroids = ops.ivf_list_mean(x[order], list_off, centroids)
+    return centroids
+
+
+class HipIvfIndexer(BaseIndexer):
+    """``table`` (n, d) on the device behind an inverted file: every row belongs to the list of its nearest centroid
+    (L2; for "angular" between unit vectors), a query scans the ``nprobe`` lists whose centroids are nearest to it (for
+    "IP": whose centroids have the largest inner product with it) on ``ops.ivf_scan``.  Among the probed rows the answer
+    is exact and means what ``HipIndexer`` returns; with ``nprobe == nlists`` it is ``HipIndexer``'s answer bit for bit."""
+
+    def __init__(self, table, centroids, metric="L2", device=None, nprobe=1):
+        from .. import ops
+        self.metric = _check_metric(metric)
+        if table.dim() != 2 or centroids.dim() != 2 or centroids.shape[1] != table.shape[1]:
+            raise ValueError("an IVF index holds a 2D (n, d) table and (nlists, d) centroids")
+        device = torch.device("cuda" if device is None else device)
+        self._ops = ops
+        self._table = table.detach().to(device, torch.float32).contiguous()
+        ops.require_hip(self._table)
+        self.centroids = centroids.detach().to(device, torch.float32).contiguous()
+        self.nlists = int(self.centroids.shape[0])
+        if not 1 <= self.nlists <= len(self):
+            raise ValueError(f"nlists={self.nlists} must lie in [1, {len(self)}] (the number of rows)")
+        self.nprobe = self._clip(nprobe)
+        self._cbias = -(self.centroids * self.centroids).sum(dim=1)
+        search, bias = self._table, None
+        if metric == "L2":
+            bias = -(self._table * self._table).sum(dim=1)
+        elif metric == "angular":
+            search = _unit_rows(self._table)
+        order, self._list_off = _group(_assign(search, self.centroids, ops), self.nlists)
+        self._row_id = order.to(torch.int32)
+        self._search = search[order].contiguous()
+        self._bias = None if bias is None else bias[order].contiguous()
+
+    def _clip(self, nprobe):
+        nprobe = 1 if nprobe is None else int(nprobe)
+        if nprobe < 1:
+            raise ValueError(f"nprobe={nprobe} must be at least 1")
+        return min(nprobe, self.nlists)
+
+    def __len__(self):
+        return int(self._table.shape[0])
+
+    def list_sizes(self):
+        """(nlists,) int64: the rows of every list."""
+        return (self._list_off[1:] - self._list_off[:-1]).to(torch.int64)
+
+    def lists(self):
+        """(row_id (n,) int32 = the original ids in list order, list_off (nlists + 1,) int32)."""
+        return self._row_id, self._list_off
+
+    def query(self, embeddings, top_k, *, exclude=None, nprobe=None):
+        """As ``HipIndexer.query``, over the ``nprobe`` (default: the index's) nearest lists of every query."""
+        if embeddings.dim() != 2:
+            raise ValueError("query takes a 2D (n, d) tensor")
+        nprobe = self.nprobe if nprobe is None else self._clip(nprobe)
+        out_dev = embeddings.device
+        dev = self._table.device
+        q = embeddings.detach().to(dev, torch.float32)
+        if exclude is not None:
+            exclude = exclude.to(dev)
+        ops = self._ops
+        if self.metric == "angular":
+            q = _unit_rows(q)
+        if self.metric == "IP":
+            probe = ops.topk_items(q, self.centroids, nprobe)[0]
+        else:
+            probe = ops.topk_items(q * 2.0, self.centroids, nprobe, bias=self._cbias)[0]
+        probe = probe.to(torch.int32)
+        scan = (self._search, self._row_id, self._list_off, probe, top_k)
+        if self.metric == "L2":
+            qn = (q * q).sum(dim=1, keepdim=True)
+            ids, s = ops.ivf_scan(q * 2.0, *scan, bias=self._bias, exclude=exclude)
+            val = (qn - s).clamp_min(0.0)
+        elif self.metric == "angular":
+            ids, s = ops.ivf_scan(q, *scan, exclude=exclude)
+            val = (2.0 - 2.0 * s).clamp_min(0.0).sqrt()
+        else:
+            ids, val = ops.ivf_scan(q, *scan, exclude=exclude)
+        if self.metric != "IP":
+            val = torch.where(ids < 0, torch.full_like(val, float("inf")), val)
+        return ids.to(out_dev), val.to(out_dev)
+
+    def save(self, file_path):
+        """One ``torch.save`` dict: the metric, the table in its original row order, the centroids and ``nprobe``.
+        Loading assigns the rows to the stored centroids again, which gives the same lists."""
+        torch.save({"metric": self.metric, "table": self._table.cpu(), "index_type": "IVF",
+                    "centroids": self.centroids.cpu(), "nprobe": self.nprobe}, file_path)
+
+
+_IVF_KEYS = {"metric", "table", "index_type", "centroids", "nprobe"}
+
+
+class HipBuilder(BaseBuilder):
+    """Builder of ``HipIndexer`` (``index_type="Flat"``, exact) and ``HipIvfIndexer`` (``"IVF"``).  ``metric``: "L2" (the
+    default, as the reference's FaissBuilder), "IP" or "angular"; ``device``: where the table lives (default: the current
+    HIP device).  For "IVF", as the reference's FaissBuilder: ``nlists`` lists, of which a query scans ``nprobe`` (None:
+    1, as faiss; clipped to ``nlists``).  The centroids come from ``niter`` rounds of k-means on the device, started from
+    ``nlists`` distinct rows drawn by ``torch.Generator(seed)`` or from ``centroids`` (nlists, d); ``niter=0`` with
+    ``centroids`` uses them as they are.  k-means minimises L2 for every metric ("angular": between the unit rows).
+    An index file carries its own metric and its own type."""
+
+    def __init__(self, metric="L2", device=None, *, index_type="Flat", nlists=100, nprobe=None, niter=10, seed=2022,
+                 centroids=None):
         self.metric = _check_metric(metric)
         self.device = device
+        if index_type == "HNSW":
+            raise NotImplementedError('index_type "HNSW" (graph search) is not built here; use "Flat" or "IVF"')
+        if index_type not in INDEX_TYPES:
+            raise ValueError(f"index_type must be one of {INDEX_TYPES}, got {index_type!r}")
+        self.index_type = index_type
+        self.nlists = int(nlists)
+        self.nprobe = 1 if nprobe is None else int(nprobe)
+        self.niter = int(niter)
+        self.seed = int(seed)
+        self.centroids = centroids
+        if index_type == "IVF":
+            if self.nprobe < 1 or self.niter < 0:
+                raise ValueError(f"nprobe={nprobe} must be at least 1 and niter={niter} at least 0")
+            self.nprobe = min(self.nprobe, max(self.nlists, 1))
+            if centroids is not None and (centroids.dim() != 2 or centroids.shape[0] != self.nlists):
+                raise ValueError(f"centroids must be a (nlists={self.nlists}, d) tensor")
+
+    def _ivf(self, embeddings):
+        from .. import ops
+        if embeddings.dim() != 2:
+            raise ValueError("an index holds a 2D (n, d) table")
+        n = int(embeddings.shape[0])
+        if not 1 <= self.nlists <= n:
+            raise ValueError(f"nlists={self.nlists} must lie in [1, {n}] (the number of rows)")
+        device = torch.device("cuda" if self.device is None else self.device)
+        table = embeddings.detach().to(device, torch.float32).contiguous()
+        ops.require_hip(table)
+        x = _unit_rows(table) if self.metric == "angular" else table
+        if self.centroids is not None:
+            if self.centroids.shape[1] != table.shape[1]:
+                raise ValueError(f"centroids must be a (nlists={self.nlists}, d={int(table.shape[1])}) tensor")
+            start = self.centroids.detach().to(device, torch.float32).contiguous()
+        else:
+            perm = torch.randperm(n, generator=torch.Generator().manual_seed(self.seed))[:self.nlists]
+            start = x[perm.to(device)].contiguous()
+        return HipIvfIndexer(table, train_centroids(x, start, self.niter, ops), self.metric, device, self.nprobe)
 
     @contextlib.contextmanager
     def from_embeddings(self, embeddings):
-        yield HipIndexer(embeddings, self.metric, self.device)
+        if self.index_type == "IVF":
+            yield self._ivf(embeddings)
+        else:
+            yield HipIndexer(embeddings, self.metric, self.device)
 
     @contextlib.contextmanager
     def from_index_file(self, index_file):
-        metric, table = load_index(index_file)
-        yield HipIndexer(table, metric, self.device)
+        blob = torch.load(index_file, map_location="cpu", weights_only=True)
+        if isinstance(blob, dict) and set(blob) == _IVF_KEYS and blob["index_type"] == "IVF":
+            yield HipIvfIndexer(blob["table"], blob["centroids"], _check_metric(blob["metric"]), self.device,
+                                blob["nprobe"])
+        else:
+            metric, table = load_index(index_file)
+            yield HipIndexer(table, metric, self.device)
