@@ -1304,6 +1304,44 @@ int rh_rank_metrics(const int64_t* pred, int64_t ld, int M, int K, const int64_t
                     int64_t n_truth, const int* cutoffs, int n_k, const double* gain, const double* ideal, double* partial,
                     int64_t* hits, int64_t* gts, double* sums, double* per_user, void* stream);
 
+/* Beyond-accuracy metrics over the same pred (M, K) int64, row stride ld >= K, 1 <= K <= 256, M >= 1; cutoffs: a HOST
+ * array of 1 <= n_k <= 8 ints in [1, K], in any order, duplicates allowed; outputs are in the caller's order of cut-offs.
+ * An id below 0 is an absent position (the -1 padding of rh_topk): the user's list is shorter there -- the reference run
+ * on the rows with the negative entries removed.  K or n_k outside its range: RH_E_UNSUPPORTED before any launch; a
+ * cut-off outside [1, K], ld < K, M < 1 or a null pointer: RH_E_BADARG before any launch.  No float atomics: a wavefront
+ * adds its users one after the other, a workgroup its wavefronts in index order into one partial, one workgroup the
+ * partials in index order -- two calls give the same bits, and a user's value does not depend on the other users.
+ * rh_ild: intra-list diversity.  table (V, D) float32 with row stride table_stride >= D, V >= 1, 1 <= D <= 1024 (else
+ *   RH_E_UNSUPPORTED before any launch).  Per user and cut-off k: the items are the entries among the first k with
+ *   0 <= id < V (an id >= V is unknown and dropped; duplicates are separate entries); with n < 2 of them the user is left
+ *   out; else, e_i the rows widened to double and u_i = e_i / max(||e_i||, 1e-10), the value is the mean over the pairs
+ *   i < j of 1 - u_i . u_j, computed as 1 - (||sum u_i||^2 - sum ||u_i||^2) / (n (n - 1)) in double, O(k D) per user:
+ *   nothing of size (M, K, D) or (M, K, K) is formed.  sums (n_k,) double = the values added over the users, counts (n_k,)
+ *   int64 = the users that contributed (exact; zeroed by the call), per_user (M, n_k) double = the values, nan where the
+ *   user was left out, or null.  partial: *partial_doubles of rh_ild_plan, which also reports (HOST pointers) the users per
+ *   workgroup and the grid cap (more users than their product: further trips).
+ * rh_coverage: counts (n_k,) int64 (zeroed by the call) = the distinct ids in [0, n_slots) among pred[:, :k], for every
+ *   cut-off in one pass; ids outside are ignored.  first (n_slots,) int32 of workspace (*workspace_bytes of
+ *   rh_coverage_plan), which the call sets to K and then lowers to the first column of every id by integer atomic minima:
+ *   exact in any order of arrival.  1 <= n_slots < 2^31, else RH_E_UNSUPPORTED before any launch.  rh_coverage_plan also
+ *   reports (HOST pointers) the rows a workgroup marks per trip and the grid cap of both passes (the counting pass takes
+ *   256 slots per workgroup and trip).
+ * rh_novelty: pop (V,) of pop_dtype (0 float32, 1 float64), V >= 1.  An id >= 0 adds -log2(max(p, 1e-10)) in double,
+ *   p = pop[id] widened, p = 1e-10 for id >= V.  Per user and cut-off: the mean over the present positions among the first
+ *   k, added in a fixed order; a user with none is left out.  sums, counts, per_user, partial and rh_novelty_plan: as for
+ *   rh_ild.
+ * replaces: the loops of diversity_score torch_rechub/basic/metric.py:203-251, coverage_score metric.py:254-277 and
+ *           novelty_score metric.py:280-313. */
+int rh_ild_plan(int M, int* users_per_workgroup, int* max_grid, int64_t* partial_doubles);
+int rh_ild(const int64_t* pred, int64_t ld, int M, int K, const float* table, int64_t table_stride, int64_t V, int D,
+           const int* cutoffs, int n_k, double* partial, double* sums, int64_t* counts, double* per_user, void* stream);
+int rh_coverage_plan(int64_t n_slots, int* rows_per_workgroup, int* max_grid, int64_t* workspace_bytes);
+int rh_coverage(const int64_t* pred, int64_t ld, int M, int K, int64_t n_slots, const int* cutoffs, int n_k, int32_t* first,
+                int64_t* counts, void* stream);
+int rh_novelty_plan(int M, int* users_per_workgroup, int* max_grid, int64_t* partial_doubles);
+int rh_novelty(const int64_t* pred, int64_t ld, int M, int K, const void* pop, int pop_dtype, int64_t V, const int* cutoffs,
+               int n_k, double* partial, double* sums, int64_t* counts, double* per_user, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,16 @@ Python loop over users -- and return the same Python objects:
 * ``topk_metrics(y_true, y_pred, topKs)``: ``y_pred`` an (M, K) int64 id tensor (what ``ops.topk_items`` leaves on the
   device), ``y_true`` an ``(offsets, ids)`` CSR pair of device tensors or a row-aligned list of id lists.
 
-The beyond-accuracy trio has no kernel: device tensors are copied to the host for it.
+The beyond-accuracy trio runs on the device too when ``y_pred`` is such an (M, K) int64 HIP id tensor (rows are users; an
+id below 0 is an absent position, the -1 padding of ``ops.topk_items``: that user's list is shorter there):
+
+* ``diversity_score(y_pred, item_embeddings, topKs)`` with ``item_embeddings`` a 2-D float32 HIP tensor indexed by item id:
+  ``ops.ild``, O(k D) per user, no (M, K, D) gather and no k x k matrix;
+* ``novelty_score(y_pred, item_popularity, topKs)`` with ``item_popularity`` a 1-D HIP tensor indexed by item id;
+* ``coverage_score(y_pred, all_items, topKs)`` with ``all_items`` anything with a ``len``, or the catalogue size as an int.
+
+The oracle of each is the reference run on a dict of the rows with the negative entries removed.  Every other combination
+of inputs (dicts, host tensors, a dict of embeddings beside a device ``y_pred``) takes the host loops below.
 """
 from collections import defaultdict
 
@@ -172,12 +181,38 @@ def _mean_score(values):
     return round(np.mean(values), 4) if values else 0.0
 
 
+def _device_lists(y_pred):
+    """True for the device form of a recommendation: an (M, K) int64 HIP tensor."""
+    import torch
+    return _on_device(y_pred) and y_pred.dim() == 2 and y_pred.dtype == torch.int64
+
+
+def _device_table(x):
+    import torch
+    return _on_device(x) and x.dim() == 2 and x.dtype == torch.float32
+
+
+def _device_means(name, topKs, raw):
+    """The reference's result object from the raw sums of ``ops.ild`` / ``ops.novelty``: the mean over the users that
+    contributed, 0.0 when nobody did."""
+    results = defaultdict(list)
+    for k, total, count in zip(topKs, raw["sums"].tolist(), raw["counts"].tolist()):
+        results[name].append(f"{name}@{k}: {round(np.float64(total) / count, 4) if count else 0.0}")
+    return results
+
+
 def diversity_score(y_pred, item_embeddings, topKs=None):
     """Intra-list diversity: the mean pairwise cosine distance inside each user's top-k list, averaged over the users whose
     list has at least two items with a known embedding.  ``item_embeddings``: {item id: vector} or a 2-D array indexed by
-    item id.  -> {'Diversity': ['Diversity@5: 0.xxxx', ...]}."""
+    item id.  -> {'Diversity': ['Diversity@5: 0.xxxx', ...]}.
+
+    Device form: ``y_pred`` an (M, K) int64 HIP tensor, ``item_embeddings`` a (V, D) float32 HIP tensor; the result is the
+    reference's on a dict of the rows with the negative entries (absent positions) removed."""
     if topKs is None:
         topKs = [5]
+    if _device_lists(y_pred) and _device_table(item_embeddings):
+        from .. import ops
+        return _device_means("Diversity", topKs, ops.ild(y_pred, item_embeddings, topKs))
     y_pred, item_embeddings = _host_lists(y_pred), _host(item_embeddings)
     known = (lambda i: i in item_embeddings) if isinstance(item_embeddings, dict) else (lambda i: i < len(item_embeddings))
     results = defaultdict(list)
@@ -201,9 +236,21 @@ def diversity_score(y_pred, item_embeddings, topKs=None):
 
 def coverage_score(y_pred, all_items, topKs=None):
     """Catalogue coverage: the share of ``all_items`` that appears in at least one user's top-k list.
-    -> {'Coverage': ['Coverage@5: 0.xxxx', ...]}."""
+    -> {'Coverage': ['Coverage@5: 0.xxxx', ...]}.
+
+    Device form: ``y_pred`` an (M, K) int64 HIP tensor, ``all_items`` anything with a ``len`` or the catalogue size as an
+    int; the result is the reference's on a dict of the rows with the negative entries (absent positions) removed."""
     if topKs is None:
         topKs = [5]
+    if _device_lists(y_pred):
+        from .. import ops
+        n_items = all_items if isinstance(all_items, int) else len(all_items)
+        n_slots = max(int(y_pred.max()), 0) + 1  # every id >= 0 counts, inside ``all_items`` or not, as in the reference
+        counts = ops.coverage(y_pred, n_slots, topKs)["counts"].tolist()
+        results = defaultdict(list)
+        for k, count in zip(topKs, counts):
+            results["Coverage"].append(f"Coverage@{k}: {round(count / n_items, 4)}")
+        return results
     y_pred = _host_lists(y_pred)
     results = defaultdict(list)
     for k in topKs:
@@ -216,9 +263,15 @@ def coverage_score(y_pred, all_items, topKs=None):
 
 def novelty_score(y_pred, item_popularity, topKs=None):
     """Mean self-information -log2(popularity) of the recommended items, per user and then over users; an unknown item
-    and a popularity below 1e-10 count as 1e-10.  -> {'Novelty': ['Novelty@5: x.xxxx', ...]}."""
+    and a popularity below 1e-10 count as 1e-10.  -> {'Novelty': ['Novelty@5: x.xxxx', ...]}.
+
+    Device form: ``y_pred`` an (M, K) int64 HIP tensor, ``item_popularity`` a 1-D float32 or float64 HIP tensor indexed by
+    item id; the result is the reference's on a dict of the rows with the negative entries (absent positions) removed."""
     if topKs is None:
         topKs = [5]
+    if _device_lists(y_pred) and _on_device(item_popularity) and item_popularity.dim() == 1:
+        from .. import ops
+        return _device_means("Novelty", topKs, ops.novelty(y_pred, item_popularity, topKs))
     y_pred = _host_lists(y_pred)
     results = defaultdict(list)
     for k in topKs:

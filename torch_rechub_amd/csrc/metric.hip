@@ -1,5 +1,6 @@
 // Evaluation metrics on the device (rh_auc_*, rh_gauc_reduce, rh_log_loss, rh_rank_metrics; replaces the host loops of the
-// reference's basic/metric.py: roc_auc_score, the per-user dict of gauc_score, the quadruple loop of topk_metrics).
+// reference's basic/metric.py: roc_auc_score, the per-user dict of gauc_score, the quadruple loop of topk_metrics).  The
+// beyond-accuracy metrics (rh_ild, rh_coverage, rh_novelty) have their own section at the end of the file.
 //
 // Rank statistic.  The caller sorts (group, prediction) ascending (torch.sort over the int64 keys of rh_auc_keys: plumbing)
 // and hands the permutation `order` over.  With Npre[k] = the negatives among the first k sorted elements, a positive i of
@@ -754,5 +755,485 @@ extern "C" int rh_rank_metrics(const int64_t* pred, int64_t ld, int M, int K, co
   hipLaunchKernelGGL(rank_metrics_kernel, dim3(grid), dim3(RH_BLOCK), 0, st, a);
   hipLaunchKernelGGL(rank_final_kernel, dim3(1), dim3(kRankFinalParts * kRankMaxCut * 4), 0, st, partial, grid, n_k, sums);
   RH_LAUNCH_CHECK("rh_rank_metrics");
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Beyond-accuracy metrics (rh_ild, rh_coverage, rh_novelty; replaces the per-user loops of diversity_score,
+// coverage_score and novelty_score).  An id below 0 is an absent position: the user's list is shorter there.
+//
+// rh_ild: one wavefront per user.  sum_{i<j} u_i . u_j = (||sum u_i||^2 - sum ||u_i||^2) / 2, so a user costs O(k D): the
+// wavefront keeps S = sum u_i (D doubles spread over the lanes) and Q = sum ||u_i||^2 while it walks the positions in
+// ascending order, and emits 1 - (||S||^2 - Q) / (n (n - 1)) at every cut-off.  LPI lanes share an item (VEC floats each,
+// NCH times), so a trip of the wavefront takes 64 / LPI items; every lane group keeps the S, Q and n of its own items and
+// the groups are added at the cut-offs by a butterfly (a fixed order).  The cut-offs arrive sorted and cut the walk into
+// segments, so that a trip never holds an item beyond the cut-off it is followed by.  The user's ids go to LDS once, as
+// table rows or -1 (the next user's ids are already on their way); the rows of the next kIldTrips trips are loaded
+// before the current ones are reduced, so two steps of row gathers are in flight per wavefront.
+//
+// rh_novelty: one wavefront per user, lane l owns the positions l, l + 64, ...; per cut-off a masked butterfly sum.
+// Both add a wavefront's users in LDS (lane 0, user after user), the workgroup's wavefronts in index order into one
+// partial per workgroup, and the partials in index order: no float atomics, the same bits every time.
+//
+// rh_coverage: first[id] = the lowest column at which id appears (integer atomicMin, skipped when a plain read already
+// shows a value that low); a second pass counts per cut-off the slots with first < k.  Integers: exact in any order.
+namespace {
+
+constexpr int kListUsers = RH_BLOCK / RH_WAVE, kListMaxGrid = 2048, kListMaxK = 256, kListMaxCut = 8;
+constexpr int kListPer = kListMaxK / RH_WAVE;
+constexpr int kIldMaxD = 1024, kIldTrips = 2;
+constexpr int kSumParts = 32;
+constexpr int kCovRows = 256, kCovMaxGrid = 2048;
+
+struct ListCuts {
+  int n_k;
+  int cut[kListMaxCut];   // ascending
+  int slot[kListMaxCut];  // the position of cut[q] in the caller's list
+};
+
+struct IldArgs {
+  const int64_t* pred;
+  int64_t ld;
+  int M, K;
+  const float* table;
+  int64_t lt, V;
+  int D;
+  ListCuts c;
+  double* partial;  // (gridDim.x, n_k)
+  u64* counts;      // (n_k,)
+  double* per_user; // (M, n_k) or null
+};
+
+__device__ __forceinline__ double shfl_xor_f64(double v, int m) { return __shfl_xor(v, m, RH_WAVE); }
+
+template <int VEC, int LPI, int NCH>
+__global__ __launch_bounds__(RH_BLOCK) void ild_kernel(const IldArgs a) {
+  constexpr int IPT = RH_WAVE / LPI, NE = NCH * VEC, STEP = IPT * kIldTrips;
+  __shared__ int64_t row[kListUsers][kListMaxK];
+  __shared__ double wsum[kListUsers][kListMaxCut];
+  __shared__ u64 wcnt[kListUsers][kListMaxCut];
+  __shared__ int scut[kListMaxCut], sslot[kListMaxCut];
+  const int tid = threadIdx.x, lane = tid % RH_WAVE, w = tid / RH_WAVE;
+  const int g = lane / LPI, sub = lane % LPI;
+#pragma unroll
+  for (int q = 0; q < kListMaxCut; ++q) {
+    if (tid == q) {
+      scut[q] = a.c.cut[q];
+      sslot[q] = a.c.slot[q];
+    }
+    if (lane == q) {
+      wsum[w][q] = 0.0;
+      wcnt[w][q] = 0;
+    }
+  }
+  __syncthreads();
+  const int n_k = a.c.n_k, kmax = scut[n_k - 1];
+  const int64_t ustep = (int64_t)gridDim.x * kListUsers;
+  int64_t u = (int64_t)blockIdx.x * kListUsers + w;
+  int64_t idn[kListPer];
+#pragma unroll
+  for (int r = 0; r < kListPer; ++r) {
+    const int j = r * RH_WAVE + lane;
+    idn[r] = (u < a.M && j < kmax) ? a.pred[u * a.ld + j] : -1;
+  }
+  for (; u < a.M; u += ustep) {
+    rank_wave_sync();  // the previous user's rows have been read
+#pragma unroll
+    for (int r = 0; r < kListPer; ++r) row[w][r * RH_WAVE + lane] = (idn[r] >= 0 && idn[r] < a.V) ? idn[r] : -1;
+    rank_wave_sync();
+#pragma unroll
+    for (int r = 0; r < kListPer; ++r) {  // the next user's ids travel while this one's rows do
+      const int j = r * RH_WAVE + lane;
+      idn[r] = (u + ustep < a.M && j < kmax) ? a.pred[(u + ustep) * a.ld + j] : -1;
+    }
+    float cur[kIldTrips][NE], nxt[kIldTrips][NE];
+    bool cok[kIldTrips], nok[kIldTrips];
+    // the rows of the positions p0 + t IPT + g, t < kIldTrips, of which the first cnt exist
+    auto load = [&](float (&e)[kIldTrips][NE], bool (&ok)[kIldTrips], int p0, int cnt) {
+#pragma unroll
+      for (int t = 0; t < kIldTrips; ++t) {
+        const int o = t * IPT + g;
+        const int64_t id = o < cnt ? row[w][p0 + o] : -1;
+        ok[t] = id >= 0;
+        const float* src = a.table + (ok[t] ? id : 0) * a.lt;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+          const int col = (c * LPI + sub) * VEC;
+          const bool in = ok[t] && col < a.D;
+          if constexpr (VEC == 4) {
+            const float4 v = in ? gload<float4>(src + col) : f4_zero();
+            e[t][c * 4 + 0] = v.x;
+            e[t][c * 4 + 1] = v.y;
+            e[t][c * 4 + 2] = v.z;
+            e[t][c * 4 + 3] = v.w;
+          } else {
+            e[t][c] = in ? gload<float>(src + col) : 0.f;
+          }
+        }
+      }
+    };
+    double S[NE];
+#pragma unroll
+    for (int i = 0; i < NE; ++i) S[i] = 0.0;
+    double Q = 0.0;
+    int n = 0, p = 0, q = 0;
+    load(cur, cok, 0, min(STEP, scut[0]));
+    while (p < kmax) {
+      const int cnt = min(STEP, scut[q] - p), pn = p + cnt;
+      int qn = q;
+      while (qn < n_k && scut[qn] <= pn) ++qn;
+      if (pn < kmax) load(nxt, nok, pn, min(STEP, scut[qn] - pn));
+#pragma unroll
+      for (int t = 0; t < kIldTrips; ++t) {
+        double ss = 0.0;
+#pragma unroll
+        for (int i = 0; i < NE; ++i) ss = fma((double)cur[t][i], (double)cur[t][i], ss);
+#pragma unroll
+        for (int m = 1; m < LPI; m <<= 1) ss += shfl_xor_f64(ss, m);
+        // 1 / max(||e||, 1e-10); rsqrt, not sqrt and a division: the kernel is bound by its double arithmetic
+        const double inv = cok[t] ? (ss >= 1e-20 ? rsqrt(ss) : 1e10) : 0.0;
+#pragma unroll
+        for (int i = 0; i < NE; ++i) S[i] = fma((double)cur[t][i], inv, S[i]);
+        Q += ss * inv * inv;
+        n += cok[t] ? 1 : 0;
+      }
+      if (qn > q) {  // pn is a cut-off: the lane groups' sums are added, the running ones stay as they are
+        double nrm2 = 0.0;
+#pragma unroll
+        for (int i = 0; i < NE; ++i) {
+          double T = S[i];
+#pragma unroll
+          for (int m = LPI; m < RH_WAVE; m <<= 1) T += shfl_xor_f64(T, m);
+          nrm2 = fma(T, T, nrm2);
+        }
+#pragma unroll
+        for (int m = 1; m < LPI; m <<= 1) nrm2 += shfl_xor_f64(nrm2, m);
+        double Qt = Q;
+        int nt = n;
+#pragma unroll
+        for (int m = LPI; m < RH_WAVE; m <<= 1) {
+          Qt += shfl_xor_f64(Qt, m);
+          nt += __shfl_xor(nt, m, RH_WAVE);
+        }
+        const double value = nt >= 2 ? 1.0 - (nrm2 - Qt) / ((double)nt * (double)(nt - 1)) : (double)NAN;
+        if (lane == 0) {
+          for (int qq = q; qq < qn; ++qq) {
+            const int s = sslot[qq];
+            if (nt >= 2) {
+              wsum[w][s] += value;
+              wcnt[w][s] += 1;
+            }
+            if (a.per_user != nullptr) a.per_user[u * n_k + s] = value;
+          }
+        }
+      }
+      if (pn < kmax) {
+#pragma unroll
+        for (int t = 0; t < kIldTrips; ++t) {
+          cok[t] = nok[t];
+#pragma unroll
+          for (int i = 0; i < NE; ++i) cur[t][i] = nxt[t][i];
+        }
+      }
+      p = pn;
+      q = qn;
+    }
+  }
+  rank_wave_sync();
+  if (lane < n_k && wcnt[w][lane] != 0) atomicAdd(a.counts + lane, wcnt[w][lane]);
+  __syncthreads();
+  if (tid < n_k) {
+    double s = wsum[0][tid];
+    for (int ww = 1; ww < kListUsers; ++ww) s += wsum[ww][tid];
+    a.partial[(int64_t)blockIdx.x * n_k + tid] = s;
+  }
+}
+
+// ONE workgroup of kSumParts x kListMaxCut threads: thread (part, e) adds the partials b = part, part + kSumParts, ... of
+// sum e in ascending b, then thread e adds the parts in ascending order: a fixed order
+__global__ __launch_bounds__(kSumParts * kListMaxCut) void list_final_kernel(const double* partial, int nblocks, int n_k,
+                                                                              double* sums) {
+  __shared__ double part_sum[kSumParts][kListMaxCut];
+  const int e = threadIdx.x % kListMaxCut, part = threadIdx.x / kListMaxCut;
+  double s = 0.0;
+  if (e < n_k)
+    for (int b = part; b < nblocks; b += kSumParts) s += partial[(int64_t)b * n_k + e];
+  part_sum[part][e] = s;
+  __syncthreads();
+  if (part == 0 && e < n_k) {
+    s = part_sum[0][e];
+    for (int q = 1; q < kSumParts; ++q) s += part_sum[q][e];
+    sums[e] = s;
+  }
+}
+
+struct NoveltyArgs {
+  const int64_t* pred;
+  int64_t ld;
+  int M, K;
+  const void* pop;
+  int pdt;  // 0 float32, 1 float64
+  int64_t V;
+  ListCuts c;  // in the caller's order
+  double* partial;
+  u64* counts;
+  double* per_user;
+};
+
+__global__ __launch_bounds__(RH_BLOCK) void novelty_kernel(const NoveltyArgs a) {
+  __shared__ double wsum[kListUsers][kListMaxCut];
+  __shared__ u64 wcnt[kListUsers][kListMaxCut];
+  const int tid = threadIdx.x, lane = tid % RH_WAVE, w = tid / RH_WAVE;
+  const int n_k = a.c.n_k;
+  if (lane < kListMaxCut) {
+    wsum[w][lane] = 0.0;
+    wcnt[w][lane] = 0;
+  }
+  rank_wave_sync();
+  for (int64_t u = (int64_t)blockIdx.x * kListUsers + w; u < a.M; u += (int64_t)gridDim.x * kListUsers) {
+    double term[kListPer];
+    bool have[kListPer];
+#pragma unroll
+    for (int r = 0; r < kListPer; ++r) {
+      const int j = r * RH_WAVE + lane;
+      const int64_t id = j < a.K ? a.pred[u * a.ld + j] : -1;
+      have[r] = id >= 0;
+      double p = 1e-10;  // an id beyond the table: the reference's .get(item, 1e-10)
+      if (have[r] && id < a.V) p = a.pdt == 0 ? (double)static_cast<const float*>(a.pop)[id] : static_cast<const double*>(a.pop)[id];
+      term[r] = have[r] ? -log2(fmax(p, 1e-10)) : 0.0;
+    }
+#pragma unroll
+    for (int q = 0; q < kListMaxCut; ++q) {
+      if (q >= n_k) break;
+      const int k = a.c.cut[q];
+      double s = 0.0;
+      int cnt = 0;
+#pragma unroll
+      for (int r = 0; r < kListPer; ++r) {
+        const bool in = have[r] && r * RH_WAVE + lane < k;
+        s += in ? term[r] : 0.0;
+        cnt += __popcll(__ballot(in));
+      }
+#pragma unroll
+      for (int m = 1; m < RH_WAVE; m <<= 1) s += shfl_xor_f64(s, m);
+      const double value = cnt > 0 ? s / (double)cnt : (double)NAN;
+      if (lane == 0) {
+        if (cnt > 0) {
+          wsum[w][q] += value;
+          wcnt[w][q] += 1;
+        }
+        if (a.per_user != nullptr) a.per_user[u * n_k + q] = value;
+      }
+    }
+  }
+  rank_wave_sync();
+  if (lane < n_k && wcnt[w][lane] != 0) atomicAdd(a.counts + lane, wcnt[w][lane]);
+  __syncthreads();
+  if (tid < n_k) {
+    double s = wsum[0][tid];
+    for (int ww = 1; ww < kListUsers; ++ww) s += wsum[ww][tid];
+    a.partial[(int64_t)blockIdx.x * n_k + tid] = s;
+  }
+}
+
+// a workgroup takes kCovRows rows per trip and walks their first kmax columns as one flat range: coalesced for any K
+__global__ __launch_bounds__(RH_BLOCK) void coverage_mark_kernel(const int64_t* pred, int64_t ld, int M, int kmax,
+                                                                 int64_t n_slots, int32_t* first) {
+  for (int64_t r0 = (int64_t)blockIdx.x * kCovRows; r0 < M; r0 += (int64_t)gridDim.x * kCovRows) {
+    const int rows = M - r0 < kCovRows ? (int)(M - r0) : kCovRows;
+    const int total = rows * kmax;
+    for (int e = threadIdx.x; e < total; e += RH_BLOCK) {
+      const int ul = e / kmax, j = e - ul * kmax;
+      const int64_t id = pred[(r0 + ul) * ld + j];
+      if (id < 0 || id >= n_slots) continue;
+      if (first[id] > j) atomicMin(first + id, j);  // a popular item is settled by the read: no atomic
+    }
+  }
+}
+
+__global__ __launch_bounds__(RH_BLOCK) void coverage_count_kernel(const int32_t* first, int64_t n_slots, const ListCuts c,
+                                                                  u64* counts) {
+  __shared__ int64_t wc[kListUsers][kListMaxCut];
+  const int tid = threadIdx.x, lane = tid % RH_WAVE, w = tid / RH_WAVE;
+  int64_t cnt[kListMaxCut];
+#pragma unroll
+  for (int q = 0; q < kListMaxCut; ++q) cnt[q] = 0;
+  for (int64_t base = (int64_t)blockIdx.x * RH_BLOCK; base < n_slots; base += (int64_t)gridDim.x * RH_BLOCK) {
+    const int64_t i = base + tid;
+    const int f = i < n_slots ? first[i] : 0x7fffffff;
+#pragma unroll
+    for (int q = 0; q < kListMaxCut; ++q)
+      if (q < c.n_k) cnt[q] += __popcll(__ballot(f < c.cut[q]));
+  }
+#pragma unroll
+  for (int q = 0; q < kListMaxCut; ++q)
+    if (lane == 0) wc[w][q] = cnt[q];
+  __syncthreads();
+  if (tid < c.n_k) {
+    int64_t s = 0;
+    for (int ww = 0; ww < kListUsers; ++ww) s += wc[ww][tid];
+    if (s != 0) atomicAdd(counts + tid, (u64)s);
+  }
+}
+
+int list_grid(int M) {
+  const int64_t b = ((int64_t)M + kListUsers - 1) / kListUsers;
+  return (int)(b < 1 ? 1 : (b > kListMaxGrid ? kListMaxGrid : b));
+}
+
+int list_plan(const char* who, int M, int* users_per_workgroup, int* max_grid, int64_t* partial_doubles) {
+  RH_REQUIRE(users_per_workgroup && max_grid && partial_doubles, RH_E_BADARG, "%s: null pointer", who);
+  RH_REQUIRE(M >= 0, RH_E_BADARG, "%s: M=%d", who, M);
+  *users_per_workgroup = kListUsers;
+  *max_grid = kListMaxGrid;
+  *partial_doubles = (int64_t)list_grid(M) * kListMaxCut;
+  return 0;
+}
+
+// the checks the three list entries share; the cut-offs in the caller's order
+int list_check(const char* who, int64_t ld, int M, int K, const int* cutoffs, int n_k, ListCuts* c) {
+  RH_REQUIRE(K >= 1 && K <= kListMaxK, RH_E_UNSUPPORTED, "%s: K=%d unsupported (1 <= K <= %d)", who, K, kListMaxK);
+  RH_REQUIRE(n_k >= 1 && n_k <= kListMaxCut, RH_E_UNSUPPORTED, "%s: %d cut-offs (1 <= n_k <= %d)", who, n_k, kListMaxCut);
+  RH_REQUIRE(M >= 1 && ld >= K, RH_E_BADARG, "%s: M=%d ld=%lld K=%d", who, M, (long long)ld, K);
+  RH_REQUIRE(cutoffs != nullptr, RH_E_BADARG, "%s: null pointer", who);
+  c->n_k = n_k;
+  for (int q = 0; q < kListMaxCut; ++q) {
+    c->cut[q] = 0;
+    c->slot[q] = 0;
+  }
+  for (int q = 0; q < n_k; ++q) {
+    RH_REQUIRE(cutoffs[q] >= 1 && cutoffs[q] <= K, RH_E_BADARG, "%s: cut-off %d outside [1, K=%d]", who, cutoffs[q], K);
+    c->cut[q] = cutoffs[q];
+    c->slot[q] = q;
+  }
+  return 0;
+}
+
+template <int VEC, int LPI, int NCH>
+void ild_launch(const IldArgs& a, int grid, hipStream_t st) {
+  hipLaunchKernelGGL((ild_kernel<VEC, LPI, NCH>), dim3(grid), dim3(RH_BLOCK), 0, st, a);
+}
+
+}  // namespace
+
+extern "C" int rh_ild_plan(int M, int* users_per_workgroup, int* max_grid, int64_t* partial_doubles) {
+  return list_plan("rh_ild_plan", M, users_per_workgroup, max_grid, partial_doubles);
+}
+
+extern "C" int rh_ild(const int64_t* pred, int64_t ld, int M, int K, const float* table, int64_t table_stride, int64_t V,
+                      int D, const int* cutoffs, int n_k, double* partial, double* sums, int64_t* counts, double* per_user,
+                      void* stream) {
+  IldArgs a{};
+  if (int rc = list_check("rh_ild", ld, M, K, cutoffs, n_k, &a.c)) return rc;
+  RH_REQUIRE(D >= 1 && D <= kIldMaxD, RH_E_UNSUPPORTED, "rh_ild: D=%d unsupported (1 <= D <= %d)", D, kIldMaxD);
+  RH_REQUIRE(V >= 1 && table_stride >= D, RH_E_BADARG, "rh_ild: V=%lld table_stride=%lld D=%d", (long long)V,
+             (long long)table_stride, D);
+  RH_REQUIRE(pred && table && partial && sums && counts, RH_E_BADARG, "rh_ild: null pointer");
+  for (int q = 1; q < n_k; ++q)  // ascending, every cut-off with its place in the caller's list
+    for (int r = q; r > 0 && a.c.cut[r - 1] > a.c.cut[r]; --r) {
+      const int c = a.c.cut[r], s = a.c.slot[r];
+      a.c.cut[r] = a.c.cut[r - 1];
+      a.c.slot[r] = a.c.slot[r - 1];
+      a.c.cut[r - 1] = c;
+      a.c.slot[r - 1] = s;
+    }
+  a.pred = pred;
+  a.ld = ld;
+  a.M = M;
+  a.K = K;
+  a.table = table;
+  a.lt = table_stride;
+  a.V = V;
+  a.D = D;
+  a.partial = partial;
+  a.counts = reinterpret_cast<u64*>(counts);
+  a.per_user = per_user;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipError_t e = hipMemsetAsync(counts, 0, (size_t)n_k * 8, st);
+  RH_REQUIRE(e == hipSuccess, (int)e, "rh_ild: memset failed: %s", hipGetErrorString(e));
+  const int grid = list_grid(M);
+  if (D % 4 == 0) {  // a float4 per lane: 4 to 64 lanes per item
+    if (D <= 16) ild_launch<4, 4, 1>(a, grid, st);
+    else if (D <= 32) ild_launch<4, 8, 1>(a, grid, st);
+    else if (D <= 64) ild_launch<4, 16, 1>(a, grid, st);
+    else if (D <= 128) ild_launch<4, 32, 1>(a, grid, st);
+    else if (D <= 256) ild_launch<4, 64, 1>(a, grid, st);
+    else if (D <= 512) ild_launch<4, 64, 2>(a, grid, st);
+    else ild_launch<4, 64, 4>(a, grid, st);
+  } else {  // a float per lane
+    if (D <= 16) ild_launch<1, 16, 1>(a, grid, st);
+    else if (D <= 32) ild_launch<1, 32, 1>(a, grid, st);
+    else if (D <= 64) ild_launch<1, 64, 1>(a, grid, st);
+    else if (D <= 128) ild_launch<1, 64, 2>(a, grid, st);
+    else if (D <= 256) ild_launch<1, 64, 4>(a, grid, st);
+    else if (D <= 512) ild_launch<1, 64, 8>(a, grid, st);
+    else ild_launch<1, 64, 16>(a, grid, st);
+  }
+  hipLaunchKernelGGL(list_final_kernel, dim3(1), dim3(kSumParts * kListMaxCut), 0, st, partial, grid, n_k, sums);
+  RH_LAUNCH_CHECK("rh_ild");
+  return 0;
+}
+
+extern "C" int rh_coverage_plan(int64_t n_slots, int* rows_per_workgroup, int* max_grid, int64_t* workspace_bytes) {
+  RH_REQUIRE(rows_per_workgroup && max_grid && workspace_bytes, RH_E_BADARG, "rh_coverage_plan: null pointer");
+  RH_REQUIRE(n_slots >= 1 && n_slots < (1ll << 31), RH_E_UNSUPPORTED, "rh_coverage_plan: n_slots=%lld outside [1, 2^31)",
+             (long long)n_slots);
+  *rows_per_workgroup = kCovRows;
+  *max_grid = kCovMaxGrid;
+  *workspace_bytes = n_slots * 4;
+  return 0;
+}
+
+extern "C" int rh_coverage(const int64_t* pred, int64_t ld, int M, int K, int64_t n_slots, const int* cutoffs, int n_k,
+                           int32_t* first, int64_t* counts, void* stream) {
+  ListCuts c{};
+  if (int rc = list_check("rh_coverage", ld, M, K, cutoffs, n_k, &c)) return rc;
+  RH_REQUIRE(n_slots >= 1 && n_slots < (1ll << 31), RH_E_UNSUPPORTED, "rh_coverage: n_slots=%lld outside [1, 2^31)",
+             (long long)n_slots);
+  RH_REQUIRE(pred && first && counts, RH_E_BADARG, "rh_coverage: null pointer");
+  int kmax = 0;
+  for (int q = 0; q < n_k; ++q) kmax = c.cut[q] > kmax ? c.cut[q] : kmax;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(first), K, (size_t)n_slots, st);
+  if (e == hipSuccess) e = hipMemsetAsync(counts, 0, (size_t)n_k * 8, st);
+  RH_REQUIRE(e == hipSuccess, (int)e, "rh_coverage: memset failed: %s", hipGetErrorString(e));
+  const int64_t mark = ((int64_t)M + kCovRows - 1) / kCovRows, count = (n_slots + RH_BLOCK - 1) / RH_BLOCK;
+  hipLaunchKernelGGL(coverage_mark_kernel, dim3((unsigned)(mark > kCovMaxGrid ? kCovMaxGrid : mark)), dim3(RH_BLOCK), 0, st,
+                     pred, ld, M, kmax, n_slots, first);
+  hipLaunchKernelGGL(coverage_count_kernel, dim3((unsigned)(count > kCovMaxGrid ? kCovMaxGrid : count)), dim3(RH_BLOCK), 0,
+                     st, first, n_slots, c, reinterpret_cast<u64*>(counts));
+  RH_LAUNCH_CHECK("rh_coverage");
+  return 0;
+}
+
+extern "C" int rh_novelty_plan(int M, int* users_per_workgroup, int* max_grid, int64_t* partial_doubles) {
+  return list_plan("rh_novelty_plan", M, users_per_workgroup, max_grid, partial_doubles);
+}
+
+extern "C" int rh_novelty(const int64_t* pred, int64_t ld, int M, int K, const void* pop, int pop_dtype, int64_t V,
+                          const int* cutoffs, int n_k, double* partial, double* sums, int64_t* counts, double* per_user,
+                          void* stream) {
+  NoveltyArgs a{};
+  if (int rc = list_check("rh_novelty", ld, M, K, cutoffs, n_k, &a.c)) return rc;
+  RH_REQUIRE(pop_dtype == 0 || pop_dtype == 1, RH_E_BADARG, "rh_novelty: pop_dtype=%d outside [0, 1]", pop_dtype);
+  RH_REQUIRE(V >= 1, RH_E_BADARG, "rh_novelty: V=%lld", (long long)V);
+  RH_REQUIRE(pred && pop && partial && sums && counts, RH_E_BADARG, "rh_novelty: null pointer");
+  a.pred = pred;
+  a.ld = ld;
+  a.M = M;
+  a.K = K;
+  a.pop = pop;
+  a.pdt = pop_dtype;
+  a.V = V;
+  a.partial = partial;
+  a.counts = reinterpret_cast<u64*>(counts);
+  a.per_user = per_user;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipError_t e = hipMemsetAsync(counts, 0, (size_t)n_k * 8, st);
+  RH_REQUIRE(e == hipSuccess, (int)e, "rh_novelty: memset failed: %s", hipGetErrorString(e));
+  const int grid = list_grid(M);
+  hipLaunchKernelGGL(novelty_kernel, dim3(grid), dim3(RH_BLOCK), 0, st, a);
+  hipLaunchKernelGGL(list_final_kernel, dim3(1), dim3(kSumParts * kListMaxCut), 0, st, partial, grid, n_k, sums);
+  RH_LAUNCH_CHECK("rh_novelty");
   return 0;
 }

@@ -4759,3 +4759,128 @@ def rank_metrics(pred_ids, truth, cutoffs, per_user=False):
               ctypes.c_void_p(ctypes.addressof(cuts)), n_k, _p(tables[0]), _p(tables[1]), _p(partial), _p(hits), _p(gts),
               _p(sums), _p(users), _stream())
     return {"hits": hits, "gts": gts, "sums": sums, "per_user": users}
+
+
+# beyond-accuracy metrics (rh_ild, rh_coverage, rh_novelty): intra-list diversity, catalogue coverage, novelty
+_ILD_MAX_D = 1024
+_POP_DTYPES = {torch.float32: 0, torch.float64: 1}
+
+
+def _list_plan(name, M):
+    vals = [ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)]
+    _lib.call(name, int(M), *[ctypes.c_void_p(ctypes.addressof(v)) for v in vals])
+    return tuple(v.value for v in vals)
+
+
+def ild_plan(M):
+    """(users_per_workgroup, max_grid, partial_doubles) of rh_ild over M users."""
+    return _list_plan("rh_ild_plan", M)
+
+
+def novelty_plan(M):
+    """(users_per_workgroup, max_grid, partial_doubles) of rh_novelty over M users."""
+    return _list_plan("rh_novelty_plan", M)
+
+
+def coverage_plan(n_slots):
+    """(rows_per_workgroup, max_grid, workspace_bytes) of rh_coverage over n_slots item slots: the rows a workgroup marks
+    per trip, the grid cap of both passes (the counting pass takes 256 slots per workgroup and trip) and the scratch size."""
+    rows, grid, nbytes = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
+    _lib.call("rh_coverage_plan", int(n_slots), *[ctypes.c_void_p(ctypes.addressof(v)) for v in (rows, grid, nbytes)])
+    return rows.value, grid.value, nbytes.value
+
+
+def _list_inputs(what, pred_ids, cutoffs, *more):
+    """The guards the list metrics share, before anything is allocated or launched.  -> (pred_ids readable in place, ld, M,
+    K, the cut-offs as a C array, n_k)."""
+    require_hip(pred_ids, *more)
+    if pred_ids.dim() != 2 or pred_ids.dtype != torch.int64:
+        raise ValueError(f"torch_rechub_amd: {what} takes an (M, K) int64 id tensor")
+    M, K = (int(v) for v in pred_ids.shape)
+    if M == 0 or K == 0:
+        raise ValueError(f"torch_rechub_amd: {what} of an empty input")
+    if K > _RANK_MAX_K:
+        from .models.matching._listwise import no_kernel
+        raise no_kernel(f"{what} over K={K} recommendations (1 <= K <= {_RANK_MAX_K})")
+    cutoffs = [int(k) for k in cutoffs]
+    if not cutoffs or any(not 1 <= k <= K for k in cutoffs):
+        raise ValueError(f"torch_rechub_amd: {what} takes cut-offs within [1, K={K}], got {cutoffs}")
+    if len(cutoffs) > _RANK_MAX_CUTOFFS:
+        from .models.matching._listwise import no_kernel
+        raise no_kernel(f"{what} at {len(cutoffs)} cut-offs (1 to {_RANK_MAX_CUTOFFS})")
+    pred_ids = pred_ids.detach()
+    if pred_ids.stride(1) != 1 or (M > 1 and pred_ids.stride(0) < K):
+        pred_ids = pred_ids.contiguous()
+    ld = int(pred_ids.stride(0)) if M > 1 else K
+    return pred_ids, ld, M, K, (ctypes.c_int * len(cutoffs))(*cutoffs), len(cutoffs)
+
+
+def ild(pred_ids, table, cutoffs, per_user=False):
+    """The raw sums behind intra-list diversity.  ``pred_ids`` (M, K) int64 (what ``topk_items`` returns; a strided
+    ``ids[:, :k]`` view is read in place; an id below 0 is an absent position), ``table`` (V, D) float32, read in place
+    under a row stride, ``cutoffs`` at most 8 ints in [1, K].  Per user and cut-off k the mean over the pairs i < j of
+    1 - cos(e_i, e_j) among the first k entries with 0 <= id < V (norms clamped at 1e-10, in double), for users with at
+    least two such entries -- the reference run on the rows with the negative entries removed.  -> dict: ``sums`` (n_k,)
+    float64 over the users, ``counts`` (n_k,) int64 = the users that contributed, ``per_user`` (M, n_k) float64 (nan where
+    the user was left out) or None.  O(k D) per user; no (M, K, D) gather.  No autograd; current stream."""
+    pred_ids, ld, M, K, cuts, n_k = _list_inputs("ild", pred_ids, cutoffs, table)
+    if table.dim() != 2 or table.dtype != torch.float32:
+        raise ValueError("torch_rechub_amd: ild takes a (V, D) float32 embedding table")
+    V, D = (int(v) for v in table.shape)
+    if V == 0 or D == 0:
+        raise ValueError("torch_rechub_amd: ild of an empty embedding table")
+    if D > _ILD_MAX_D:
+        from .models.matching._listwise import no_kernel
+        raise no_kernel(f"intra-list diversity over embeddings of width {D} (1 <= D <= {_ILD_MAX_D})")
+    table = table.detach()
+    if table.stride(1) != 1 or (V > 1 and table.stride(0) < D):
+        table = table.contiguous()
+    lt = int(table.stride(0)) if V > 1 else D
+    dev = pred_ids.device
+    partial = torch.empty((ild_plan(M)[2],), dtype=torch.float64, device=dev)
+    sums = torch.empty((n_k,), dtype=torch.float64, device=dev)
+    counts = torch.empty((n_k,), dtype=torch.int64, device=dev)
+    users = torch.empty((M, n_k), dtype=torch.float64, device=dev) if per_user else None
+    _lib.call("rh_ild", _p(pred_ids), ld, M, K, _p(table), lt, V, D, ctypes.c_void_p(ctypes.addressof(cuts)), n_k,
+              _p(partial), _p(sums), _p(counts), _p(users), _stream())
+    return {"sums": sums, "counts": counts, "per_user": users}
+
+
+def coverage(pred_ids, n_slots, cutoffs):
+    """The distinct ids in [0, n_slots) among ``pred_ids[:, :k]`` for every cut-off, in one pass: -> dict ``counts`` (n_k,)
+    int64.  Ids outside [0, n_slots) -- the -1 padding among them -- are ignored.  Exact.  No autograd; current stream."""
+    pred_ids, ld, M, K, cuts, n_k = _list_inputs("coverage", pred_ids, cutoffs)
+    n_slots = int(n_slots)
+    if n_slots < 1:
+        raise ValueError(f"torch_rechub_amd: coverage takes n_slots >= 1, got {n_slots}")
+    if n_slots >= 2 ** 31:
+        from .models.matching._listwise import no_kernel
+        raise no_kernel(f"coverage over {n_slots} item slots (fewer than 2**31)")
+    dev = pred_ids.device
+    first = torch.empty((coverage_plan(n_slots)[2] // 4,), dtype=torch.int32, device=dev)
+    counts = torch.empty((n_k,), dtype=torch.int64, device=dev)
+    _lib.call("rh_coverage", _p(pred_ids), ld, M, K, n_slots, ctypes.c_void_p(ctypes.addressof(cuts)), n_k, _p(first),
+              _p(counts), _stream())
+    return {"counts": counts}
+
+
+def novelty(pred_ids, popularity, cutoffs, per_user=False):
+    """The raw sums behind novelty.  ``popularity`` (V,) float32 or float64, indexed by item id.  An id >= 0 adds
+    -log2(max(p, 1e-10)) in double, p = 1e-10 for an id >= V; an id below 0 is an absent position.  Per user and cut-off k
+    the mean over the present positions among the first k; a user with none is left out -- the reference run on the rows
+    with the negative entries removed.  -> dict like ``ild``'s.  No autograd; current stream."""
+    pred_ids, ld, M, K, cuts, n_k = _list_inputs("novelty", pred_ids, cutoffs, popularity)
+    if popularity.dim() != 1 or popularity.dtype not in _POP_DTYPES:
+        raise ValueError("torch_rechub_amd: novelty takes a 1-D float32 or float64 popularity tensor indexed by item id")
+    V = int(popularity.numel())
+    if V == 0:
+        raise ValueError("torch_rechub_amd: novelty of an empty popularity tensor")
+    popularity = popularity.detach().contiguous()
+    dev = pred_ids.device
+    partial = torch.empty((novelty_plan(M)[2],), dtype=torch.float64, device=dev)
+    sums = torch.empty((n_k,), dtype=torch.float64, device=dev)
+    counts = torch.empty((n_k,), dtype=torch.int64, device=dev)
+    users = torch.empty((M, n_k), dtype=torch.float64, device=dev) if per_user else None
+    _lib.call("rh_novelty", _p(pred_ids), ld, M, K, _p(popularity), _POP_DTYPES[popularity.dtype], V,
+              ctypes.c_void_p(ctypes.addressof(cuts)), n_k, _p(partial), _p(sums), _p(counts), _p(users), _stream())
+    return {"sums": sums, "counts": counts, "per_user": users}
