@@ -163,6 +163,8 @@ int rh_cross_fwd(const float* x0, int64_t x0_stride, const float* x, int64_t x_s
                  const float* w, const float* b, int B, int d, int L, float* out,
                  int64_t out_stride, void* stream);
 int rh_cross_bwd_nblocks(int B);
+/* *nblocks (a HOST int) = the workgroups rh_cross_fwd launches for B rows (four rows each per trip of its grid-stride loop) */
+int rh_cross_fwd_nblocks(int B, int* nblocks);
 int rh_cross_max_layers(int d); /* layers one call can take for width d (4 for d <= 512) */
 int rh_cross_bwd(const float* x0, int64_t x0_stride, const float* x, int64_t x_stride,
                  const float* w, const float* b, int B, int d, int L, const float* g_out,
@@ -187,7 +189,10 @@ int rh_cross_mix_epilogue_fwd(const float* x0, const float* xl, const float* uv,
                               int B, int d, int E, float* out, void* stream);
 int rh_cross_mix_epilogue_bwd(const float* x0, const float* uv, const float* gate, const float* bias, const float* g,
                               int B, int d, int E, float* g_x0, float* g_uv, float* g_gate, void* stream);
-/* the same, also emitting the bias gradient as rh_cross_mix_nblocks(B) x d per-block partial rows (summed by the caller) */
+/* *nblocks (a HOST int) = the workgroups of either rh_cross_v2_epilogue_* launch (256 elements each per trip) */
+int rh_cross_v2_epilogue_nblocks(int B, int d, int* nblocks);
+/* the same, also emitting the bias gradient as rh_cross_mix_nblocks(B) x d per-block partial rows (summed by the caller);
+ * rh_cross_mix_nblocks(B) is the grid of all three rh_cross_mix_epilogue_* launches (four rows each per trip) */
 int rh_cross_mix_nblocks(int B);
 int rh_cross_mix_epilogue_bwd_b(const float* x0, const float* uv, const float* gate, const float* bias, const float* g, int B,
                                 int d, int E, float* g_x0, float* g_uv, float* g_gate, float* g_bias_partial, void* stream);
@@ -215,6 +220,17 @@ int rh_cross_mix_epilogue_bwd_b(const float* x0, const float* uv, const float* g
 int rh_cross_moe_kp(int E, int r);
 int rh_cross_moe_supported(int L, int E, int d, int r);
 int rh_cross_moe_mid_blocks(int B, int E, int r);
+/* The grids of the other launches, each answered through HOST ints by the function the launch itself calls:
+ *   rh_cross_moe_mid_fwd_blocks: workgroups of rh_cross_moe_mid_fwd, each taking 256 / (E r) samples per trip;
+ *   rh_cross_moe_res_blocks:     workgroups of rh_cross_moe_res_bwd, 256 of the B d elements each per trip;
+ *   rh_cross_moe_pack_blocks:    workgroups of rh_cross_moe_pack, 256 of the 2 L KP d elements each per trip;
+ *   rh_cross_moe_unpack_blocks:  *blocks = the workgroups of rh_cross_moe_unpack that walk the L (2 E d r + d) + E d outputs of
+ *                                g_U / g_V / g_bias / g_Wg (256 each per trip), *c_blocks = the ones in front of them that sum
+ *                                the g_C partials (64 outputs each, no loop over outputs). */
+int rh_cross_moe_mid_fwd_blocks(int B, int E, int r, int* blocks);
+int rh_cross_moe_res_blocks(int B, int d, int* blocks);
+int rh_cross_moe_pack_blocks(int L, int E, int d, int r, int* blocks);
+int rh_cross_moe_unpack_blocks(int L, int E, int d, int r, int* blocks, int* c_blocks);
 int rh_cross_moe_pack(const float* const* U, const float* const* V, const float* const* bias, const float* const* Wg, int L,
                       int E, int d, int r, float* VgT, float* UTb, void* stream);
 int rh_cross_moe_mid_fwd(const float* PG, const float* C, int B, int E, int r, float* v1, float* v2, float* gate, float* wp,

@@ -158,6 +158,13 @@ __global__ __launch_bounds__(RH_BLOCK) void cross_bwd_kernel(
   }
 }
 
+// forward grid: one wavefront per sample while they last, then a grid-stride loop over the samples
+int fwd_grid(int B) {
+  int64_t blocks = ((int64_t)B + kWavesPerBlock - 1) / kWavesPerBlock;
+  if (blocks > 256 * 8) blocks = 256 * 8;
+  return blocks < 1 ? 1 : (int)blocks;
+}
+
 int epl_for(int d) {
   int epl = 1;
   while (epl * RH_WAVE < d) epl *= 2;
@@ -167,9 +174,7 @@ int epl_for(int d) {
 template <int EPL, int NL>
 int launch_fwd(const float* x0, int64_t x0s, const float* x, int64_t xs, const float* w, const float* b,
                int B, int d, float* out, int64_t os, hipStream_t s) {
-  int64_t blocks = ((int64_t)B + kWavesPerBlock - 1) / kWavesPerBlock;
-  if (blocks > 256 * 8) blocks = 256 * 8;
-  hipLaunchKernelGGL((cross_fwd_kernel<EPL, NL>), dim3((unsigned)blocks), dim3(RH_BLOCK), 0, s, x0, x0s, x,
+  hipLaunchKernelGGL((cross_fwd_kernel<EPL, NL>), dim3((unsigned)fwd_grid(B)), dim3(RH_BLOCK), 0, s, x0, x0s, x,
                      xs, w, b, B, d, out, os);
   return 0;
 }
@@ -254,6 +259,12 @@ extern "C" int rh_cross_fwd(const float* x0, int64_t x0_stride, const float* x, 
     return rc;
   }
   RH_LAUNCH_CHECK("rh_cross_fwd");
+  return 0;
+}
+
+extern "C" int rh_cross_fwd_nblocks(int B, int* nblocks) {
+  RH_REQUIRE(nblocks != nullptr && B >= 0, RH_E_BADARG, "rh_cross_fwd_nblocks: bad arguments");
+  *nblocks = B < 1 ? 0 : fwd_grid(B);
   return 0;
 }
 

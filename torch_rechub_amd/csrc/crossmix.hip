@@ -23,6 +23,14 @@ unsigned wave_grid(int B) {
   return (unsigned)g;
 }
 
+// grid of cross_v2_kernel (both directions): four elements per thread while the workgroups last
+unsigned v2_grid(int64_t n) {
+  int64_t g = (n + RH_BLOCK * 4 - 1) / (RH_BLOCK * 4);
+  if (g > 256 * 16) g = 256 * 16;
+  if (g < 1) g = 1;
+  return (unsigned)g;
+}
+
 // BWD = false: out = x0*y + b + x.   BWD = true: g_x0 = g*y, g_y = g*x0 (g_x = g and g_b = colsum(g) are the caller's)
 template <bool BWD>
 __global__ __launch_bounds__(RH_BLOCK) void cross_v2_kernel(const float* __restrict__ x0, const float* __restrict__ y,
@@ -155,9 +163,7 @@ extern "C" int rh_cross_v2_epilogue_fwd(const float* x0, const float* y, const f
   RH_REQUIRE(x0 && y && b && x && out && B >= 0 && d >= 1, RH_E_BADARG, "rh_cross_v2_epilogue_fwd: bad arguments");
   if (B == 0) return 0;
   const int64_t n = (int64_t)B * d;
-  int64_t grid = (n + RH_BLOCK * 4 - 1) / (RH_BLOCK * 4);
-  if (grid > 256 * 16) grid = 256 * 16;
-  hipLaunchKernelGGL((cross_v2_kernel<false>), dim3((unsigned)grid), dim3(RH_BLOCK), 0,
+  hipLaunchKernelGGL((cross_v2_kernel<false>), dim3(v2_grid(n)), dim3(RH_BLOCK), 0,
                      reinterpret_cast<hipStream_t>(stream), x0, y, b, x, nullptr, n, d, out, nullptr);
   RH_LAUNCH_CHECK("rh_cross_v2_epilogue_fwd");
   return 0;
@@ -168,9 +174,7 @@ extern "C" int rh_cross_v2_epilogue_bwd(const float* x0, const float* y, const f
   RH_REQUIRE(x0 && y && g && g_x0 && g_y && B >= 0 && d >= 1, RH_E_BADARG, "rh_cross_v2_epilogue_bwd: bad arguments");
   if (B == 0) return 0;
   const int64_t n = (int64_t)B * d;
-  int64_t grid = (n + RH_BLOCK * 4 - 1) / (RH_BLOCK * 4);
-  if (grid > 256 * 16) grid = 256 * 16;
-  hipLaunchKernelGGL((cross_v2_kernel<true>), dim3((unsigned)grid), dim3(RH_BLOCK), 0,
+  hipLaunchKernelGGL((cross_v2_kernel<true>), dim3(v2_grid(n)), dim3(RH_BLOCK), 0,
                      reinterpret_cast<hipStream_t>(stream), x0, y, nullptr, nullptr, g, n, d, g_x0, g_y);
   RH_LAUNCH_CHECK("rh_cross_v2_epilogue_bwd");
   return 0;
@@ -186,6 +190,12 @@ extern "C" int rh_cross_mix_epilogue_fwd(const float* x0, const float* xl, const
   int rc = mix_dispatch<false>(a, reinterpret_cast<hipStream_t>(stream));
   if (rc) return rc;
   RH_LAUNCH_CHECK("rh_cross_mix_epilogue_fwd");
+  return 0;
+}
+
+extern "C" int rh_cross_v2_epilogue_nblocks(int B, int d, int* nblocks) {
+  RH_REQUIRE(nblocks != nullptr && B >= 0 && d >= 1, RH_E_BADARG, "rh_cross_v2_epilogue_nblocks: bad arguments");
+  *nblocks = B < 1 ? 0 : (int)v2_grid((int64_t)B * d);
   return 0;
 }
 

@@ -350,6 +350,26 @@ int mid_grid(int B, int E, int r, bool bwd) {
   return g < 1 ? 1 : (int)g;
 }
 
+// grid-stride launches over flat element counts: pack (2 L KP d elements), the residual backward (B d) and the streaming
+// part of unpack (one thread per output of g_U / g_V / g_bias / g_gating)
+int64_t pack_total(int L, int E, int d, int r) { return 2 * (int64_t)L * rh_cross_moe_kp(E, r) * d; }
+
+int64_t unpack_total(int L, int E, int d, int r) { return (int64_t)L * (2 * (int64_t)E * d * r + d) + (int64_t)E * d; }
+
+int unpack_cblocks(int L, int E, int r) { return L * (int)(((int64_t)E * r * r + RH_WAVE - 1) / RH_WAVE); }
+
+int flat_grid(int64_t total, int64_t cap) {
+  int64_t g = (total + RH_BLOCK - 1) / RH_BLOCK;
+  if (g > cap) g = cap;
+  return g < 1 ? 1 : (int)g;
+}
+
+int pack_grid(int L, int E, int d, int r) { return flat_grid(pack_total(L, E, d, r), 2048); }
+
+int unpack_grid(int L, int E, int d, int r) { return flat_grid(unpack_total(L, E, d, r), 2048); }
+
+int res_grid(int B, int d) { return flat_grid((int64_t)B * d, 256 * 16); }
+
 size_t mid_lds(int E, int r, bool bwd) {
   const int ER = E * r, spb = RH_BLOCK / ER;
   size_t n = ((size_t)E * r * (r + 1) + 3) / 4 * 4 + (size_t)spb * ER;
@@ -404,6 +424,36 @@ extern "C" int rh_cross_moe_supported(int L, int E, int d, int r) {
 
 extern "C" int rh_cross_moe_mid_blocks(int B, int E, int r) { return mid_grid(B, E, r, true); }
 
+// the grids of the launches below, for callers that size their cases by them (*blocks = workgroups of the launch)
+extern "C" int rh_cross_moe_mid_fwd_blocks(int B, int E, int r, int* blocks) {
+  RH_REQUIRE(blocks != nullptr && B >= 0, RH_E_BADARG, "rh_cross_moe_mid_fwd_blocks: bad arguments");
+  if (int rc = check_shape("rh_cross_moe_mid_fwd_blocks", E, 1, r)) return rc;
+  *blocks = B < 1 ? 0 : mid_grid(B, E, r, false);
+  return 0;
+}
+
+extern "C" int rh_cross_moe_res_blocks(int B, int d, int* blocks) {
+  RH_REQUIRE(blocks != nullptr && B >= 0 && d >= 1, RH_E_BADARG, "rh_cross_moe_res_blocks: bad arguments");
+  *blocks = B < 1 ? 0 : res_grid(B, d);
+  return 0;
+}
+
+extern "C" int rh_cross_moe_pack_blocks(int L, int E, int d, int r, int* blocks) {
+  RH_REQUIRE(blocks != nullptr && L >= 1 && L <= kMaxLayers, RH_E_BADARG, "rh_cross_moe_pack_blocks: bad arguments");
+  if (int rc = check_shape("rh_cross_moe_pack_blocks", E, d, r)) return rc;
+  *blocks = pack_grid(L, E, d, r);
+  return 0;
+}
+
+extern "C" int rh_cross_moe_unpack_blocks(int L, int E, int d, int r, int* blocks, int* c_blocks) {
+  RH_REQUIRE(blocks != nullptr && c_blocks != nullptr && L >= 1 && L <= kMaxLayers, RH_E_BADARG,
+             "rh_cross_moe_unpack_blocks: bad arguments");
+  if (int rc = check_shape("rh_cross_moe_unpack_blocks", E, d, r)) return rc;
+  *blocks = unpack_grid(L, E, d, r);
+  *c_blocks = unpack_cblocks(L, E, r);
+  return 0;
+}
+
 extern "C" int rh_cross_moe_pack(const float* const* U, const float* const* V, const float* const* bias,
                                  const float* const* Wg, int L, int E, int d, int r, float* VgT, float* UTb, void* stream) {
   RH_REQUIRE(U && V && bias && Wg && VgT && UTb, RH_E_BADARG, "rh_cross_moe_pack: null pointer");
@@ -413,10 +463,8 @@ extern "C" int rh_cross_moe_pack(const float* const* U, const float* const* V, c
   for (int l = 0; l < L; ++l) a.U[l] = U[l], a.V[l] = V[l], a.bias[l] = bias[l];
   for (int e = 0; e < E; ++e) a.Wg[e] = Wg[e];
   a.VgT = VgT, a.UTb = UTb, a.L = L, a.E = E, a.d = d, a.r = r, a.KP = rh_cross_moe_kp(E, r);
-  const int64_t total = 2 * (int64_t)L * a.KP * d;
-  int64_t grid = (total + RH_BLOCK - 1) / RH_BLOCK;
-  if (grid > 2048) grid = 2048;
-  hipLaunchKernelGGL(moe_pack_kernel, dim3((unsigned)grid), dim3(RH_BLOCK), 0, reinterpret_cast<hipStream_t>(stream), a);
+  hipLaunchKernelGGL(moe_pack_kernel, dim3((unsigned)pack_grid(L, E, d, r)), dim3(RH_BLOCK), 0,
+                     reinterpret_cast<hipStream_t>(stream), a);
   RH_LAUNCH_CHECK("rh_cross_moe_pack");
   return 0;
 }
@@ -450,10 +498,8 @@ extern "C" int rh_cross_moe_res_bwd(const float* g, int64_t ldg, const float* x0
   RH_REQUIRE(B >= 0 && d >= 1 && ldg >= d && ldx0 >= d, RH_E_BADARG, "rh_cross_moe_res_bwd: bad shape");
   RH_REQUIRE(mode >= 0 && mode <= 3, RH_E_BADARG, "rh_cross_moe_res_bwd: mode %d (bit 0 first, bit 1 last)", mode);
   if (B == 0) return 0;
-  int64_t grid = ((int64_t)B * d + RH_BLOCK - 1) / RH_BLOCK;
-  if (grid > 256 * 16) grid = 256 * 16;
-  hipLaunchKernelGGL(moe_res_bwd_kernel, dim3((unsigned)grid), dim3(RH_BLOCK), 0, reinterpret_cast<hipStream_t>(stream), g,
-                     ldg, x0, ldx0, Y, B, d, mode, g_Y, acc);
+  hipLaunchKernelGGL(moe_res_bwd_kernel, dim3((unsigned)res_grid(B, d)), dim3(RH_BLOCK), 0,
+                     reinterpret_cast<hipStream_t>(stream), g, ldg, x0, ldx0, Y, B, d, mode, g_Y, acc);
   RH_LAUNCH_CHECK("rh_cross_moe_res_bwd");
   return 0;
 }
@@ -475,11 +521,8 @@ extern "C" int rh_cross_moe_unpack(const float* const* slabV, const int* S1, con
     a.g_U[l] = g_U[l], a.g_V[l] = g_V[l], a.g_bias[l] = g_bias[l], a.g_C[l] = g_C[l];
   }
   for (int e = 0; e < E; ++e) a.g_Wg[e] = g_Wg[e];
-  const int64_t total = (int64_t)L * (2 * (int64_t)E * d * r + d) + (int64_t)E * d;
-  int64_t grid = (total + RH_BLOCK - 1) / RH_BLOCK;
-  if (grid > 2048) grid = 2048;
-  const int cblocks = L * (int)(((int64_t)E * r * r + RH_WAVE - 1) / RH_WAVE);
-  hipLaunchKernelGGL(moe_unpack_kernel, dim3((unsigned)(grid + cblocks)), dim3(RH_BLOCK), 0,
+  const int cblocks = unpack_cblocks(L, E, r);
+  hipLaunchKernelGGL(moe_unpack_kernel, dim3((unsigned)(unpack_grid(L, E, d, r) + cblocks)), dim3(RH_BLOCK), 0,
                      reinterpret_cast<hipStream_t>(stream), a, cblocks);
   RH_LAUNCH_CHECK("rh_cross_moe_unpack");
   return 0;
