@@ -159,8 +159,8 @@ def test_second_trip_of_the_row_grid():
 def test_wgrad_chunks_with_a_ragged_last_one():
     """M = 2500 rows, one 64 x 64 output tile: 16 chunks asked for, 3 tiles (192 rows) each, so 14 chunks and the last holds
     4 rows."""
-    from torch_rechub_amd import ops
-    assert ops._sine_query("rh_cin_wgrad_chunks", 2500, 1, 8, 8, 64) == 14
+    from torch_rechub_amd import _lib
+    assert _lib.query("rh_cin_wgrad_chunks", 2500, 1, 8, 8, 64) == 14
     inputs, want, cpu32 = make_case(2500, 1, 8, 8, 64, seed=4)
     check("ragged_chunks", run_kernel(inputs), want, cpu32)
 

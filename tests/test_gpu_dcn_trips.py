@@ -108,9 +108,7 @@ def check(case, pairs):
 # ---- the library's own grids ------------------------------------------------------------------------------------------------
 def query(name, *args, n=1):
     from torch_rechub_amd import _lib
-    outs = [ctypes.c_int(-1) for _ in range(n)]
-    _lib.call(name, *args, *[ctypes.c_void_p(ctypes.addressof(o)) for o in outs])
-    return outs[0].value if n == 1 else tuple(o.value for o in outs)
+    return _lib.query(name, *args, out=(ctypes.c_int,) * n)
 
 
 def mid_blocks(B, E, r, bwd):

@@ -150,10 +150,15 @@ def test_batch_independence_and_reproducibility():
         assert one_i.tobytes() == ids[i:i + 1].tobytes() and one_s.tobytes() == sc[i:i + 1].tobytes()
 
 
-@pytest.mark.parametrize("data", ["int", "normal"])
-def test_every_list_probed_is_the_flat_scan_bit_for_bit(data):
+@pytest.mark.parametrize("data,shape", [
+    pytest.param("int", (70, 65, 3000, 50, 12, 5), id="int"),
+    pytest.param("normal", (70, 65, 3000, 50, 12, 5), id="normal"),
+    # three k chunks, 32-row tiles with a ragged last one and 65 exclusions per query at once
+    pytest.param("int", (67, 130, 400, 129, 12, 65), id="int-three-chunks-rb32-exclude"),
+])
+def test_every_list_probed_is_the_flat_scan_bit_for_bit(data, shape):
     from torch_rechub_amd import ops
-    M, D, V, K, L, S = 70, 65, 3000, 50, 12, 5
+    M, D, V, K, L, S = shape
     q, x, bias = (O.int_data if data == "int" else O.normal_data)(7, M, D, V, with_bias=True)
     rng = np.random.default_rng(7)
     exclude = rng.integers(-1, V, size=(M, S))

@@ -43,9 +43,7 @@ def close(got, want, what, rows=False):
 def rows_per_trip():
     """Rows one trip of the capped launches covers (the cap's workgroups x four wavefronts)."""
     from torch_rechub_amd import _lib
-    n = ctypes.c_int(0)
-    _lib.call("rh_twotower_nblocks", 1 << 30, ctypes.c_void_p(ctypes.addressof(n)))
-    return 4 * n.value
+    return 4 * _lib.query("rh_twotower_nblocks", 1 << 30)
 
 
 def strided(t, pad=3):

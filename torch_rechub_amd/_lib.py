@@ -89,3 +89,11 @@ def call(name, *args):
         msg = lib.rh_last_error()
         raise RuntimeError(f"{name} failed (rc={rc}): {msg.decode() if msg else ''}")
     return 0
+
+
+def query(name, *args, out=(ctypes.c_int,)):
+    """The answer of an entry point that writes it to host integers behind its last arguments (the ``*_supported``,
+    ``*_plan`` and block-count queries): the value, or a tuple of them when ``out`` names several types."""
+    outs = [t(0) for t in out]
+    call(name, *args, *[ctypes.c_void_p(ctypes.addressof(o)) for o in outs])
+    return outs[0].value if len(outs) == 1 else tuple(o.value for o in outs)

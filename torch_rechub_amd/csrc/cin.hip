@@ -334,22 +334,11 @@ int wgrad_chunks(int64_t M, int Ho, int K, int64_t* rpc) {
 size_t fwd_lds(int F, int Hp) { return sizeof(float) * (size_t)(kT * ((F | 1) + (Hp | 1)) + 2 * kT * kLd); }
 size_t bwd_lds(int F, int Hp) { return sizeof(float) * (size_t)(kT * ((F | 1) + (Hp | 1)) + 2 * kT * kLd); }
 
-// the attribute belongs to the function on ONE device: once per device this process launches on
+// both kernels at their largest, whichever entry point comes first
 int reserve_lds(const char* who) {
-  static bool attr_set[64] = {};
-  int device = 0;
-  hipError_t e = hipGetDevice(&device);
-  RH_REQUIRE(e == hipSuccess, (int)e, "%s: no current device: %s", who, hipGetErrorString(e));
-  if (device < 0 || device >= 64 || !attr_set[device]) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(cin_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)fwd_lds(kMaxF, kMaxHp));
-    RH_REQUIRE(e == hipSuccess, (int)e, "%s: cannot reserve LDS: %s", who, hipGetErrorString(e));
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(cin_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)bwd_lds(kMaxF, kMaxHp));
-    RH_REQUIRE(e == hipSuccess, (int)e, "%s: cannot reserve LDS: %s", who, hipGetErrorString(e));
-    if (device >= 0 && device < 64) attr_set[device] = true;
-  }
-  return 0;
+  static RhLdsReserved fwd, bwd;
+  if (int rc = rh_reserve_lds(fwd, cin_fwd_kernel, fwd_lds(kMaxF, kMaxHp), who)) return rc;
+  return rh_reserve_lds(bwd, cin_bwd_kernel, bwd_lds(kMaxF, kMaxHp), who);
 }
 
 unsigned row_grid(int64_t M) {

@@ -31,6 +31,26 @@ extern "C" int rh_linear_set_tuning(int key, int value);
     }                                                                       \
   } while (0)
 
+// Dynamic LDS above the default limit has to be granted to a kernel (hipFuncAttributeMaxDynamicSharedMemorySize), and the
+// attribute belongs to the function on ONE device.  A launch site declares `static RhLdsReserved` for its kernel (per
+// instantiation, for a template) and calls rh_reserve_lds before a launch that needs `bytes`: the attribute is raised
+// once per device this process launches on, and again on a device only when more is asked for than it was given there.
+struct RhLdsReserved {
+  size_t bytes[64];  // by device ordinal; a device outside the table is asked every time
+};
+template <typename Kernel>
+static inline int rh_reserve_lds(RhLdsReserved& got, Kernel* kernel, size_t bytes, const char* who) {
+  int device = 0;
+  hipError_t e = hipGetDevice(&device);
+  RH_REQUIRE(e == hipSuccess, (int)e, "%s: no current device: %s", who, hipGetErrorString(e));
+  const bool known = device >= 0 && device < 64;
+  if (known && got.bytes[device] >= bytes) return 0;
+  e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  RH_REQUIRE(e == hipSuccess, (int)e, "%s: cannot reserve %zu B of LDS: %s", who, bytes, hipGetErrorString(e));
+  if (known) got.bytes[device] = bytes;
+  return 0;
+}
+
 // Wave priority of the step's latency-bound chain kernels (s_setprio 3 = highest): when the optimizer's VALU-saturating
 // window sweep is resident on the same SIMD (deferred sweep on a side stream), the chain's waves win instruction issue.
 #define RH_CHAIN_PRIO() __builtin_amdgcn_s_setprio(3)

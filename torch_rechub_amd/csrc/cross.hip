@@ -184,12 +184,9 @@ int launch_bwd(const float* x0, int64_t x0s, const float* x, int64_t xs, const f
                int B, int d, const float* g, int64_t gs, float* gx0, float* gx, int64_t gxs, int sum_into,
                float* partials, int nblocks, hipStream_t s) {
   const size_t shmem = (size_t)kWavesPerBlock * 2 * NL * EPL * RH_WAVE * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set && shmem > 64 * 1024) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cross_bwd_kernel<EPL, NL>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    attr_set = true;
-  }
+  static RhLdsReserved reserved;  // per instantiation
+  if (shmem > 64 * 1024)
+    if (int rc = rh_reserve_lds(reserved, &cross_bwd_kernel<EPL, NL>, shmem, "rh_cross_bwd")) return rc;
   hipLaunchKernelGGL((cross_bwd_kernel<EPL, NL>), dim3((unsigned)nblocks), dim3(RH_BLOCK), shmem, s, x0, x0s,
                      x, xs, w, b, B, d, g, gs, gx0, gx, gxs, sum_into, partials);
   return 0;
@@ -289,10 +286,8 @@ extern "C" int rh_cross_bwd(const float* x0, int64_t x0_stride, const float* x, 
   const int nblocks = rh_cross_bwd_nblocks(B);
   int rc = dispatch_bwd(epl_for(d), L, x0, x0_stride, x, x_stride, w, b, B, d, g_out, g_stride, g_x0, g_x,
                         gx_stride, sum_into_gx, wb_partials, nblocks, reinterpret_cast<hipStream_t>(stream));
-  if (rc != 0) {
-    rh_set_error("rh_cross_bwd: no kernel for d=%d L=%d", d, L);
-    return rc;
-  }
+  if (rc == RH_E_UNSUPPORTED) rh_set_error("rh_cross_bwd: no kernel for d=%d L=%d", d, L);
+  if (rc != 0) return rc;  // (a failed LDS reservation has left its own message)
   RH_LAUNCH_CHECK("rh_cross_bwd");
   return 0;
 }

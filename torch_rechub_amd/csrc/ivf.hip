@@ -5,10 +5,11 @@
 // Scan kernel, list-centric: the M nprobe (query, slot) pairs arrive grouped by list (pair = the pair indices
 // i nprobe + slot in list order, group 0 = the pairs with no list, group l + 1 = list l; pair_off = the groups' offsets;
 // tile_off = the prefix sum of ceil(group size / RB)).  The grid is the fixed upper bound of the tile count; a workgroup
-// finds its (group, tile of RB pairs) by binary search in tile_off and leaves if there is none.  It gathers its pairs'
-// query rows into the q half of LDS and walks its list's rows in tiles of 64 exactly as topk_scan_kernel walks a column
-// range: the score tile of mfma_tile.h (one score depends on q_i, x_j and D alone), the K-lists of topk_list.h with
-// row_id[c] as the id of column c.  Ids ascend inside a list, so the list is the top K of the probed list under (score
+// finds its (group, tile of RB pairs) by binary search in tile_off and leaves if there is none.  It puts its pairs'
+// indices into LDS and hands its list's rows to topk_scan_tiles of topk_list.h, the one scan body that topk_scan_kernel
+// runs over a column range (the score tile of mfma_tile.h: one score depends on q_i, x_j and D alone; the K-lists),
+// under IvfRule: tile row r is the query of pair r, row_id[c] is the id of column c, the list goes to the pair's place
+// in the partials.  Ids ascend inside a list, so the list is the top K of the probed list under (score
 // descending, id ascending).  Every pair belongs to exactly one tile, which writes the pair's list to the partials at
 // (query, slot) (unused tail: -inf, -1) -- also where the list is empty or absent: every element the merge reads is
 // written.  Merge kernel: topk_merge_row with one list per slot.  The union of the probed lists' top K holds the top K
@@ -23,38 +24,36 @@ namespace {
 constexpr int kIvfMaxProbe = 256;
 
 struct IvfArgs {
-  const float* q;           // (M, D), row stride ldq
-  int64_t ldq;
-  const float* xs;          // (V, D) contiguous, grouped by list
-  const float* bias;        // (V,) or null, grouped alike
+  TopkScanArgs s;           // x, bias = the rows grouped by list; exclude = original ids; nlist = nprobe
   const int32_t* row_id;    // (V,) original ids
   const int32_t* list_off;  // (nlists + 1,)
-  const int64_t* exclude;   // (M, S) or null, original ids
   const int32_t* pair;      // (M nprobe,) pair indices grouped by list
   const int32_t* pair_off;  // (nlists + 2,)
   const int32_t* tile_off;  // (nlists + 2,)
-  int S, M, D, V, K, nprobe, nlists;
-  int RB;                   // pairs per workgroup
-  float* part_s;            // (M, nprobe, K)
-  int32_t* part_i;          // (M, nprobe, K) original ids, -1 = no entry
-  int64_t* ids;             // (M, K)
-  float* scores;            // (M, K)
+  int nlists;
 };
 
 size_t ivf_lds_bytes(int K) { return topk_lds_bytes(K) + (size_t)kT * 4; }
 
+// tile row r holds the pair prs[r] = query nprobe + slot (-1: no row), whose list in the partials is the pair's; the id
+// of a grouped row is row_id's
+struct IvfRule {
+  const int* prs;  // [64] in LDS
+  const int32_t* row_id;
+  int nprobe, K;
+  static constexpr const int64_t* invalid = nullptr;
+  static constexpr int n_inv = 0;
+  __device__ __forceinline__ bool has_row(int r) const { return prs[r] >= 0; }
+  __device__ __forceinline__ int64_t query_row(int r) const { return prs[r] / nprobe; }
+  __device__ __forceinline__ int64_t id_of(int64_t c) const { return row_id[c]; }
+  __device__ __forceinline__ int64_t list_offset(int r) const { return (int64_t)prs[r] * K; }
+};
+
 __global__ __launch_bounds__(RH_BLOCK) void ivf_scan_kernel(const IvfArgs a) {
   extern __shared__ __align__(16) float lds[];
-  float* ws = lds;                  // x chunk (64 columns x 64 k), then the score tile [row][column]
-  float* hs = ws + kT * kLd;        // q chunk (64 rows x 64 k)
-  float* ls = hs + kT * kLd;        // [RB][K] list scores
-  int* li = reinterpret_cast<int*>(ls + a.RB * a.K);   // [RB][K] list ids
-  float* thr = reinterpret_cast<float*>(li + a.RB * a.K);  // [64] K-th score of a full list
-  int* cnt = reinterpret_cast<int*>(thr + kT);         // [64] entries of the list
-  int* prs = cnt + kT;                                 // [64] pair index of the row, -1 = no row
-  const int tid = threadIdx.x, lane = tid % RH_WAVE, w = tid / RH_WAVE;
-  const int l32 = lane % 32, kk = lane / 32, wm = w & 1, wn = w >> 1;
-  const int K = a.K, RB = a.RB;
+  const TopkScanArgs& s = a.s;
+  int* prs = reinterpret_cast<int*>(lds + topk_lds_bytes(s.K) / sizeof(float));  // [64] pair index of the row, -1 = no row
+  const int tid = threadIdx.x, RB = s.RB;
   const int b = blockIdx.x;
   if (b >= a.tile_off[a.nlists + 1]) return;
   int g = 0;  // the last group with tile_off[g] <= b: tile_off[g + 1] > b, so the group has the tile
@@ -63,21 +62,15 @@ __global__ __launch_bounds__(RH_BLOCK) void ivf_scan_kernel(const IvfArgs a) {
     if (a.tile_off[mid] <= b) g = mid; else hi_g = mid - 1;
   }
   const int64_t p0 = (int64_t)a.pair_off[g] + (int64_t)(b - a.tile_off[g]) * RB, p1 = a.pair_off[g + 1];
-  const int64_t npair = (int64_t)a.M * a.nprobe;
+  const int64_t npair = (int64_t)s.M * s.nlist;
   int64_t lo = 0, hi = 0;  // group 0: no list
   if (g > 0) {
     lo = a.list_off[g - 1];
     hi = a.list_off[g];
     if (lo < 0) lo = 0;
-    if (hi > a.V) hi = a.V;
+    if (hi > s.V) hi = s.V;
   }
-  const int nkc = (a.D + kT - 1) / kT;
-  const bool work = wm * 32 < RB;   // RB = 32: the lower row half of the tile is empty
-  const int rpw = RB / 4;           // list rows per wavefront
-  const int nch = (K + RH_WAVE - 1) / RH_WAVE;
   if (tid < kT) {
-    thr[tid] = -INFINITY;
-    cnt[tid] = 0;
     int p = -1;
     if (tid < RB && p0 >= 0 && p0 + tid < p1 && p0 + tid < npair) {
       p = a.pair[p0 + tid];
@@ -86,74 +79,16 @@ __global__ __launch_bounds__(RH_BLOCK) void ivf_scan_kernel(const IvfArgs a) {
     prs[tid] = p;
   }
   __syncthreads();
-  if (nkc == 1) {  // one k chunk: the q tile is loaded once
-    for (int e = tid; e < kT * kT; e += RH_BLOCK) {
-      const int r = e / kT, c = e % kT;
-      const int p = prs[r];
-      hs[r * kLd + c] = (p >= 0 && c < a.D) ? a.q[(int64_t)(p / a.nprobe) * a.ldq + c] : 0.f;
-    }
-  }
-  for (int64_t c0 = lo; c0 < hi; c0 += kT) {
-    v16f acc = zero16();
-    for (int k0 = 0; k0 < a.D; k0 += kT) {
-      __syncthreads();
-      for (int e = tid; e < kT * kT; e += RH_BLOCK) {
-        const int r = e / kT, c = e % kT, k = k0 + c;
-        ws[r * kLd + c] = (c0 + r < hi && k < a.D) ? a.xs[(c0 + r) * a.D + k] : 0.f;
-        if (nkc > 1) {
-          const int p = prs[r];
-          hs[r * kLd + c] = (p >= 0 && k < a.D) ? a.q[(int64_t)(p / a.nprobe) * a.ldq + k] : 0.f;
-        }
-      }
-      __syncthreads();
-      const int kc = a.D - k0 < kT ? a.D - k0 : kT;
-      if (work) acc = mma_lds(acc, hs + wm * 32 * kLd, kLd, 1, ws + wn * 32 * kLd, 1, kLd, (kc + 1) & ~1, l32, kk);
-    }
-    __syncthreads();
-    if (work) {
-      const int64_t c = c0 + wn * 32 + l32;
-      const float bv = (a.bias != nullptr && c < hi) ? a.bias[c] : 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        ws[(wm * 32 + acc_row(r, kk)) * kLd + wn * 32 + l32] = a.bias != nullptr ? acc[r] + bv : acc[r];
-    }
-    __syncthreads();
-    for (int i = 0; i < rpw; ++i) {
-      const int row = w * rpw + i;
-      const int p = prs[row];
-      if (p < 0) continue;
-      const float s = ws[row * kLd + lane];
-      int n = cnt[row];
-      float t = thr[row];
-      const uint64_t m = __ballot(c0 + lane < hi && (n < K || s > t));
-      if (m == 0) continue;
-      const int64_t* ex = a.S > 0 ? a.exclude + (int64_t)(p / a.nprobe) * a.S : nullptr;
-      topk_row_hits(m, s, ls + row * K, li + row * K, n, t, K, nch, ex, a.S, nullptr, 0, lane,
-                    [&](int j) { return (int64_t)a.row_id[c0 + j]; });
-      if (lane == 0) {
-        cnt[row] = n;
-        thr[row] = t;
-      }
-    }
-  }
-  __syncthreads();
-  for (int e = tid; e < RB * K; e += RH_BLOCK) {
-    const int row = e / K, k = e % K;
-    const int p = prs[row];
-    if (p < 0) continue;
-    const bool have = k < cnt[row];
-    const int64_t o = (int64_t)p * K + k;
-    a.part_s[o] = have ? ls[e] : -INFINITY;
-    a.part_i[o] = have ? li[e] : -1;
-  }
+  topk_scan_tiles(s, IvfRule{prs, a.row_id, s.nlist, s.K}, lo, hi, lds);
 }
 
 // one wavefront per query: one list per slot
 __global__ __launch_bounds__(RH_WAVE) void ivf_merge_kernel(const IvfArgs a) {
   __shared__ int hp[kIvfMaxProbe];
   const int64_t row = blockIdx.x;
-  topk_merge_row(a.part_s + row * a.nprobe * a.K, a.part_i + row * a.nprobe * a.K, a.nprobe, a.K, a.ids + row * a.K,
-                 a.scores + row * a.K, hp, threadIdx.x);
+  const TopkScanArgs& s = a.s;
+  topk_merge_row(s.part_s + row * s.nlist * s.K, s.part_i + row * s.nlist * s.K, s.nlist, s.K, s.ids + row * s.K,
+                 s.scores + row * s.K, hp, threadIdx.x);
 }
 
 __global__ __launch_bounds__(RH_BLOCK) void ivf_list_mean_kernel(const float* __restrict__ xs,
@@ -182,8 +117,7 @@ __global__ __launch_bounds__(RH_BLOCK) void ivf_list_mean_kernel(const float* __
 }
 
 bool ivf_shape_ok(int D, int K, int S, int nprobe) {
-  return D >= 1 && D <= kTopkMaxD && K >= 1 && K <= kTopkMaxK && S >= 0 && S <= kTopkMaxS && nprobe >= 1 &&
-         nprobe <= kIvfMaxProbe;
+  return topk_shape_ok(D, K, S) && nprobe >= 1 && nprobe <= kIvfMaxProbe;
 }
 
 }  // namespace
@@ -216,49 +150,24 @@ extern "C" int rh_ivf_scan(const float* q, int64_t ldq, const float* xs, const f
   RH_REQUIRE(ivf_shape_ok(D, K, S, nprobe), RH_E_UNSUPPORTED,
              "rh_ivf_scan: D=%d K=%d S=%d nprobe=%d unsupported (1 <= D <= %d, 1 <= K <= %d, 0 <= S <= %d, "
              "1 <= nprobe <= %d)", D, K, S, nprobe, kTopkMaxD, kTopkMaxK, kTopkMaxS, kIvfMaxProbe);
-  RH_REQUIRE(M >= 0 && V >= 1 && nlists >= 1 && ldq >= D, RH_E_BADARG, "rh_ivf_scan: M=%d V=%d nlists=%d ldq=%lld D=%d", M,
-             V, nlists, (long long)ldq, D);
+  if (int rc = topk_scan_sizes("rh_ivf_scan", M, V, "nlists", nlists, nlists >= 1, ldq, D)) return rc;
   const int RB = topk_rows(K);
   const int64_t npair = (int64_t)M * nprobe, grid = (npair + RB - 1) / RB + nlists + 1;
   RH_REQUIRE(grid < ((int64_t)1 << 31), RH_E_UNSUPPORTED, "rh_ivf_scan: M nprobe = %lld pairs are too many",
              (long long)npair);
   if (M == 0) return 0;
-  RH_REQUIRE(q && xs && row_id && list_off && pair && pair_off && tile_off && partials && ids && scores &&
-                 (S == 0 || exclude), RH_E_BADARG, "rh_ivf_scan: null pointer");
   IvfArgs a{};
-  a.q = q;
-  a.ldq = ldq;
-  a.xs = xs;
-  a.bias = bias_s;
+  if (int rc = topk_scan_args("rh_ivf_scan", &a.s, q, ldq, xs, bias_s, exclude, S, M, D, V, K, nprobe, partials, ids, scores))
+    return rc;
+  RH_REQUIRE(row_id && list_off && pair && pair_off && tile_off, RH_E_BADARG, "rh_ivf_scan: null pointer");
   a.row_id = row_id;
   a.list_off = list_off;
-  a.exclude = exclude;
   a.pair = pair;
   a.pair_off = pair_off;
   a.tile_off = tile_off;
-  a.S = S;
-  a.M = M;
-  a.D = D;
-  a.V = V;
-  a.K = K;
-  a.nprobe = nprobe;
   a.nlists = nlists;
-  a.RB = RB;
-  a.part_s = static_cast<float*>(partials);
-  a.part_i = reinterpret_cast<int32_t*>(a.part_s + npair * K);
-  a.ids = ids;
-  a.scores = scores;
-  // the attribute belongs to the function on ONE device: once per device this process launches on
-  static bool attr_set[64] = {};
-  int device = 0;
-  hipError_t e = hipGetDevice(&device);
-  RH_REQUIRE(e == hipSuccess, (int)e, "rh_ivf_scan: no current device: %s", hipGetErrorString(e));
-  if (device < 0 || device >= 64 || !attr_set[device]) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(ivf_scan_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)ivf_lds_bytes(128));
-    RH_REQUIRE(e == hipSuccess, (int)e, "rh_ivf_scan: cannot reserve LDS: %s", hipGetErrorString(e));
-    if (device >= 0 && device < 64) attr_set[device] = true;
-  }
+  static RhLdsReserved reserved;
+  if (int rc = rh_reserve_lds(reserved, ivf_scan_kernel, ivf_lds_bytes(128), "rh_ivf_scan")) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(ivf_scan_kernel, dim3((unsigned)grid), dim3(RH_BLOCK), ivf_lds_bytes(K), st, a);
   hipLaunchKernelGGL(ivf_merge_kernel, dim3((unsigned)M), dim3(RH_WAVE), 0, st, a);

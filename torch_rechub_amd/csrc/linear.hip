@@ -807,13 +807,9 @@ static int wgrad_impl(const float* g, int64_t ldg, const float* x, int64_t ldx, 
   a.direct = (reduce && a.S == 1) ? 1 : 0;
   const bool long_form = B < kLongRows || g_long_blocks > 0;
   const size_t lds = (size_t)(long_form ? 1 : kWaves) * kPartStride * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(linear_wgrad_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kWaves * kPartStride * sizeof(float)));
-    RH_REQUIRE(e == hipSuccess, (int)e, "rh_linear_wgrad: cannot reserve LDS: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
+  static RhLdsReserved reserved;
+  if (int rc = rh_reserve_lds(reserved, linear_wgrad_kernel, kWaves * kPartStride * sizeof(float), "rh_linear_wgrad"))
+    return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (wgrad_rows_form(B, N, K)) {
     // two tiles per wavefront along K when the K tiles pair up, else along N

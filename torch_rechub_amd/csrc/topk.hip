@@ -13,115 +13,46 @@
 // Merge kernel: one wavefront per row merges the nsplit sorted lists under the same total order.  Every range's top K
 // under a total order holds the global top K's members of that range, so the result does not depend on nsplit.
 // No atomics; every element of the partials is written (unused tail: -inf, -1).
-// The K-list (threshold, ballot, cooperative insert) and the merge of one row live in topk_list.h, shared with ivf.hip.
+// The scan of one workgroup (topk_scan_tiles), its K-list (threshold, ballot, cooperative insert) and the merge of one row
+// live in topk_list.h, shared with ivf.hip: topk_scan_kernel only names its column range and, in FlatRule, its rows.
 #include "topk_list.h"
 
 namespace {
 
 struct TopkArgs {
-  const float* q;          // (M, D), row stride ldq
-  int64_t ldq;
-  const float* x;          // (V, D) contiguous
-  const float* bias;       // (V,) or null
-  const int64_t* exclude;  // (M, S) or null
+  TopkScanArgs s;          // nlist = nsplit
   const int64_t* invalid;  // (n_inv,) or null
-  int S, n_inv;
-  int M, D, V, K, nsplit;
-  int RB;                  // query rows per workgroup
-  float* part_s;           // (M, nsplit, K) scores of the per-range lists
-  int32_t* part_i;         // (M, nsplit, K) their ids, -1 = no entry
-  int64_t* ids;            // (M, K)
-  float* scores;           // (M, K)
+  int n_inv;
+};
+
+// tile row r is query row r0 + r where r < rows, a column's id is its index, range `split` is the query's list `split`
+struct FlatRule {
+  int64_t r0;
+  int rows, nsplit, split, K;
+  const int64_t* invalid;
+  int n_inv;
+  __device__ __forceinline__ bool has_row(int r) const { return r < rows; }
+  __device__ __forceinline__ int64_t query_row(int r) const { return r0 + r; }
+  __device__ __forceinline__ int64_t id_of(int64_t c) const { return c; }
+  __device__ __forceinline__ int64_t list_offset(int r) const { return ((r0 + r) * nsplit + split) * K; }
 };
 
 __global__ __launch_bounds__(RH_BLOCK) void topk_scan_kernel(const TopkArgs a) {
   extern __shared__ __align__(16) float lds[];
-  float* ws = lds;                  // x chunk (64 columns x 64 k), then the score tile [row][column]
-  float* hs = ws + kT * kLd;        // q chunk (64 rows x 64 k)
-  float* ls = hs + kT * kLd;        // [RB][K] list scores
-  int* li = reinterpret_cast<int*>(ls + a.RB * a.K);   // [RB][K] list ids
-  float* thr = reinterpret_cast<float*>(li + a.RB * a.K);  // [64] K-th score of a full list
-  int* cnt = reinterpret_cast<int*>(thr + kT);         // [64] entries of the list
-  const int tid = threadIdx.x, lane = tid % RH_WAVE, w = tid / RH_WAVE;
-  const int l32 = lane % 32, kk = lane / 32, wm = w & 1, wn = w >> 1;
-  const int K = a.K, RB = a.RB;
-  const int64_t r0 = (int64_t)blockIdx.x * RB;
+  const TopkScanArgs& s = a.s;
   const int split = blockIdx.y;
-  const int64_t lo = (int64_t)a.V * split / a.nsplit, hi = (int64_t)a.V * (split + 1) / a.nsplit;
-  const int nkc = (a.D + kT - 1) / kT;
-  const bool work = wm * 32 < RB;   // RB = 32: the lower row half of the tile is empty
-  const int rpw = RB / 4;           // list rows per wavefront
-  const int nch = (K + RH_WAVE - 1) / RH_WAVE;
-  if (tid < kT) {
-    thr[tid] = -INFINITY;
-    cnt[tid] = 0;
-  }
-  if (nkc == 1) {  // one k chunk: the q tile is loaded once
-    for (int e = tid; e < kT * kT; e += RH_BLOCK) {
-      const int r = e / kT, c = e % kT;
-      hs[r * kLd + c] = (r < RB && r0 + r < a.M && c < a.D) ? a.q[(r0 + r) * a.ldq + c] : 0.f;
-    }
-  }
-  for (int64_t c0 = lo; c0 < hi; c0 += kT) {
-    v16f acc = zero16();
-    for (int k0 = 0; k0 < a.D; k0 += kT) {
-      __syncthreads();
-      for (int e = tid; e < kT * kT; e += RH_BLOCK) {
-        const int r = e / kT, c = e % kT, k = k0 + c;
-        ws[r * kLd + c] = (c0 + r < hi && k < a.D) ? a.x[(c0 + r) * a.D + k] : 0.f;
-        if (nkc > 1) hs[r * kLd + c] = (r < RB && r0 + r < a.M && k < a.D) ? a.q[(r0 + r) * a.ldq + k] : 0.f;
-      }
-      __syncthreads();
-      const int kc = a.D - k0 < kT ? a.D - k0 : kT;
-      if (work) acc = mma_lds(acc, hs + wm * 32 * kLd, kLd, 1, ws + wn * 32 * kLd, 1, kLd, (kc + 1) & ~1, l32, kk);
-    }
-    __syncthreads();
-    if (work) {
-      const int64_t c = c0 + wn * 32 + l32;
-      const float b = (a.bias != nullptr && c < hi) ? a.bias[c] : 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        ws[(wm * 32 + acc_row(r, kk)) * kLd + wn * 32 + l32] = a.bias != nullptr ? acc[r] + b : acc[r];
-    }
-    __syncthreads();
-    for (int i = 0; i < rpw; ++i) {
-      const int row = w * rpw + i;
-      if (r0 + row >= a.M) break;
-      const float s = ws[row * kLd + lane];
-      int n = cnt[row];
-      float t = thr[row];
-      const uint64_t m = __ballot(c0 + lane < hi && (n < K || s > t));
-      if (m == 0) continue;
-      const int64_t* ex = a.S > 0 ? a.exclude + (r0 + row) * a.S : nullptr;
-      topk_row_hits(m, s, ls + row * K, li + row * K, n, t, K, nch, ex, a.S, a.invalid, a.n_inv, lane,
-                    [&](int j) { return c0 + j; });
-      if (lane == 0) {
-        cnt[row] = n;
-        thr[row] = t;
-      }
-    }
-  }
-  __syncthreads();
-  for (int e = tid; e < RB * K; e += RH_BLOCK) {
-    const int row = e / K, k = e % K;
-    if (r0 + row >= a.M) break;
-    const bool have = k < cnt[row];
-    const int64_t o = ((r0 + row) * a.nsplit + split) * K + k;
-    a.part_s[o] = have ? ls[e] : -INFINITY;
-    a.part_i[o] = have ? li[e] : -1;
-  }
+  const int64_t r0 = (int64_t)blockIdx.x * s.RB;
+  const FlatRule rule{r0, (int)(s.M - r0 < s.RB ? s.M - r0 : s.RB), s.nlist, split, s.K, a.invalid, a.n_inv};
+  topk_scan_tiles(s, rule, (int64_t)s.V * split / s.nlist, (int64_t)s.V * (split + 1) / s.nlist, lds);
 }
 
 // one wavefront per row
 __global__ __launch_bounds__(RH_WAVE) void topk_merge_kernel(const TopkArgs a) {
   __shared__ int hp[kTopkMaxSplit];
   const int64_t row = blockIdx.x;
-  topk_merge_row(a.part_s + row * a.nsplit * a.K, a.part_i + row * a.nsplit * a.K, a.nsplit, a.K, a.ids + row * a.K,
-                 a.scores + row * a.K, hp, threadIdx.x);
-}
-
-bool topk_shape_ok(int D, int K, int S) {
-  return D >= 1 && D <= kTopkMaxD && K >= 1 && K <= kTopkMaxK && S >= 0 && S <= kTopkMaxS;
+  const TopkScanArgs& s = a.s;
+  topk_merge_row(s.part_s + row * s.nlist * s.K, s.part_i + row * s.nlist * s.K, s.nlist, s.K, s.ids + row * s.K,
+                 s.scores + row * s.K, hp, threadIdx.x);
 }
 
 // default ranges: enough workgroups for one round over the chip's 256 compute units, ranges of at least 4096 columns (the
@@ -159,45 +90,20 @@ extern "C" int rh_topk_fwd(const float* q, int64_t ldq, const float* x, const fl
   RH_REQUIRE(topk_shape_ok(D, K, S), RH_E_UNSUPPORTED,
              "rh_topk_fwd: D=%d K=%d S=%d unsupported (1 <= D <= %d, 1 <= K <= %d, 0 <= S <= %d)", D, K, S, kTopkMaxD,
              kTopkMaxK, kTopkMaxS);
-  RH_REQUIRE(M >= 0 && V >= 1 && n_inv >= 0 && ldq >= D, RH_E_BADARG, "rh_topk_fwd: M=%d V=%d n_inv=%d ldq=%lld D=%d", M, V,
-             n_inv, (long long)ldq, D);
+  if (int rc = topk_scan_sizes("rh_topk_fwd", M, V, "n_inv", n_inv, n_inv >= 0, ldq, D)) return rc;
   RH_REQUIRE(nsplit >= 1 && nsplit <= kTopkMaxSplit && nsplit <= V, RH_E_BADARG,
              "rh_topk_fwd: nsplit=%d outside [1, min(V, %d)]", nsplit, kTopkMaxSplit);
   if (M == 0) return 0;
-  RH_REQUIRE(q && x && workspace && ids && scores && (S == 0 || exclude) && (n_inv == 0 || invalid), RH_E_BADARG,
-             "rh_topk_fwd: null pointer");
   TopkArgs a{};
-  a.q = q;
-  a.ldq = ldq;
-  a.x = x;
-  a.bias = bias;
-  a.exclude = exclude;
+  if (int rc = topk_scan_args("rh_topk_fwd", &a.s, q, ldq, x, bias, exclude, S, M, D, V, K, nsplit, workspace, ids, scores))
+    return rc;
+  RH_REQUIRE(n_inv == 0 || invalid, RH_E_BADARG, "rh_topk_fwd: null pointer");
   a.invalid = invalid;
-  a.S = S;
   a.n_inv = n_inv;
-  a.M = M;
-  a.D = D;
-  a.V = V;
-  a.K = K;
-  a.nsplit = nsplit;
-  a.RB = topk_rows(K);
-  a.part_s = static_cast<float*>(workspace);
-  a.part_i = reinterpret_cast<int32_t*>(a.part_s + (int64_t)M * nsplit * K);
-  a.ids = ids;
-  a.scores = scores;
-  // the attribute belongs to the function on ONE device: once per device this process launches on
-  static bool attr_set[64] = {};
-  int device = 0;
-  hipError_t e = hipGetDevice(&device);
-  RH_REQUIRE(e == hipSuccess, (int)e, "rh_topk_fwd: no current device: %s", hipGetErrorString(e));
-  if (device < 0 || device >= 64 || !attr_set[device]) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(topk_scan_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)topk_lds_bytes(128));
-    RH_REQUIRE(e == hipSuccess, (int)e, "rh_topk_fwd: cannot reserve LDS: %s", hipGetErrorString(e));
-    if (device >= 0 && device < 64) attr_set[device] = true;
-  }
+  static RhLdsReserved reserved;
+  if (int rc = rh_reserve_lds(reserved, topk_scan_kernel, topk_lds_bytes(128), "rh_topk_fwd")) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int64_t nrt = ((int64_t)M + a.RB - 1) / a.RB;
+  const int64_t nrt = ((int64_t)M + a.s.RB - 1) / a.s.RB;
   hipLaunchKernelGGL(topk_scan_kernel, dim3((unsigned)nrt, nsplit), dim3(RH_BLOCK), topk_lds_bytes(K), st, a);
   hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)M), dim3(RH_WAVE), 0, st, a);
   RH_LAUNCH_CHECK("rh_topk_fwd");

@@ -2977,7 +2977,7 @@ class _SineInterestFn(torch.autograd.Function):
         if B == 0:
             g_C.zero_()
         else:
-            nch = _sine_query("rh_sine_nchunks", B)
+            nch = _lib.query("rh_sine_nchunks", B)
             rows = torch.empty((B, K, E), dtype=torch.float32, device=dev)
             part = torch.empty((nch, T * E), dtype=torch.float32, device=dev)
             _lib.call("rh_sine_interest_bwd", _p(X), _p(Y), _p(C), _p(idx), _p(P1), _p(P2), _p(PU), _p(g_phi), _p(g_xhat), B,
@@ -3015,15 +3015,8 @@ class _SineAggregateFn(torch.autograd.Function):
         return g_xhat, g_a3, None, g_phi, None
 
 
-def _sine_query(name, *args):
-    """An entry point that answers through a host int (rh_sine_supported, rh_sine_nchunks)."""
-    out = ctypes.c_int(0)
-    _lib.call(name, *args, ctypes.c_void_p(ctypes.addressof(out)))
-    return out.value
-
-
 def sine_supported(S, E, T, K):
-    return bool(_sine_query("rh_sine_supported", int(S), int(E), int(T), int(K)))
+    return bool(_lib.query("rh_sine_supported", int(S), int(E), int(T), int(K)))
 
 
 def _sine_check(what, tensors, mask, S, E, T, K):
@@ -3062,20 +3055,11 @@ def sine_aggregate(xhat, a3, mask, phi, temperature):
 
 # --------------------------------------------------------------------------------------------
 # RQ-VAE's residual quantizer (csrc/rq.hip)
-def _rq_query(name, *args):
-    """(a, b) of an entry point that answers through two host ints (rh_rq_nchunks)."""
-    a, b = ctypes.c_int(0), ctypes.c_int(0)
-    _lib.call(name, *args, ctypes.c_void_p(ctypes.addressof(a)), ctypes.c_void_p(ctypes.addressof(b)))
-    return a.value, b.value
-
-
 def rq_supported(E, sizes):
     """Whether csrc/rq.hip takes rows of width E against codebooks of these sizes (E <= 128, sizes <= 1024, <= 8 levels)."""
     sizes = [int(v) for v in sizes]
-    out = ctypes.c_int(0)
     arr = _int_array(sizes)
-    _lib.call("rh_rq_supported", int(E), len(sizes), ctypes.cast(arr, ctypes.c_void_p), ctypes.c_void_p(ctypes.addressof(out)))
-    return bool(out.value)
+    return bool(_lib.query("rh_rq_supported", int(E), len(sizes), ctypes.cast(arr, ctypes.c_void_p)))
 
 
 def _rq_check(x, codebooks):
@@ -3115,7 +3099,7 @@ def rq_forward(r_in, codebooks, l0=0, l1=None, given=0, idx=None, sse=None):
     r_out = torch.empty((N, E), dtype=torch.float32, device=dev)
     x_q = torch.empty((N, E), dtype=torch.float32, device=dev)
     if N:
-        blocks, _ = _rq_query("rh_rq_nchunks", N)
+        blocks, _ = _lib.query("rh_rq_nchunks", N, out=(ctypes.c_int, ctypes.c_int))
         part = torch.empty((blocks, l1 - l0), dtype=torch.float32, device=dev)
         _lib.call("rh_rq_fwd", _p(r_in), ctypes.cast(_ptr_array(codebooks), ctypes.c_void_p),
                   ctypes.cast(_int_array(sizes), ctypes.c_void_p), N, E, L, int(l0), l1, int(given), _p(idx), _p(r_out),
@@ -3173,7 +3157,7 @@ class _ResidualQuantizeFn(torch.autograd.Function):
         if N == 0:
             g_C.zero_()
         else:
-            _, nch = _rq_query("rh_rq_nchunks", N)
+            _, nch = _lib.query("rh_rq_nchunks", N, out=(ctypes.c_int, ctypes.c_int))
             part = torch.empty((nch, total), dtype=torch.float32, device=dev)
             g_loss, g_xq = g_loss.to(torch.float32).contiguous(), g_xq.contiguous()
             _lib.call("rh_rq_bwd", _p(x), ctypes.cast(_ptr_array(cbs), ctypes.c_void_p),
@@ -3638,18 +3622,45 @@ def session_lengths(seq, check_full=False):
 # --------------------------------------------------------------------------------------------
 def topk_supported(D, K, S=0):
     """Whether csrc/topk.hip takes width D, K results and S exclusions per query (D <= 1024, K <= 256, S <= 1024)."""
-    out = ctypes.c_int(0)
-    _lib.call("rh_topk_supported", int(D), int(K), int(S), ctypes.c_void_p(ctypes.addressof(out)))
-    return bool(out.value)
+    return bool(_lib.query("rh_topk_supported", int(D), int(K), int(S)))
 
 
 def topk_plan(M, V, K):
     """(nsplit, workspace_bytes): the default number of item ranges for M queries over V items and the size of the
     partial lists for it (8 M nsplit K bytes)."""
-    nsplit, nbytes = ctypes.c_int(0), ctypes.c_int64(0)
-    _lib.call("rh_topk_plan", int(M), int(V), int(K), ctypes.c_void_p(ctypes.addressof(nsplit)),
-              ctypes.c_void_p(ctypes.addressof(nbytes)))
-    return nsplit.value, nbytes.value
+    return _lib.query("rh_topk_plan", int(M), int(V), int(K), out=(ctypes.c_int, ctypes.c_int64))
+
+
+def _scan_inputs(what, tname, q, table, k, bias, exclude, refuse):
+    """What ``topk_items`` and ``ivf_scan`` check and prepare alike: q (M, D) and the table (V, D; ``tname`` in the
+    messages) float32, the table contiguous, bias (V,) float32, exclude (M, S).  ``refuse(M, D, V, k, S)`` makes the
+    caller's own checks and raises where there is no kernel, before anything is allocated.  Returns q with unit column
+    stride and its row stride, bias and exclude as the kernels read them, S and the empty (ids, scores) (M, k)."""
+    if q.dim() != 2 or table.dim() != 2 or q.shape[1] != table.shape[1]:
+        raise ValueError(f"{what}: q (M, D) and {tname} (V, D) expected")
+    if q.dtype != torch.float32 or table.dtype != torch.float32 or (bias is not None and bias.dtype != torch.float32):
+        raise ValueError(f"torch_rechub_amd: {what} takes float32 tensors")
+    if not table.is_contiguous():
+        raise ValueError(f"{what}: the table must be contiguous")
+    M, D = (int(v) for v in q.shape)
+    V, k = int(table.shape[0]), int(k)
+    if exclude is not None and (exclude.dim() != 2 or exclude.shape[0] != M):
+        raise ValueError(f"{what}: exclude (M, S) expected")
+    S = 0 if exclude is None else int(exclude.shape[1])
+    if bias is not None and tuple(bias.shape) != (V,):
+        raise ValueError(f"{what}: bias (V,) expected")
+    refuse(M, D, V, k, S)
+    q = q.detach()
+    if M > 0 and (q.stride(1) != 1 or q.stride(0) < D):
+        q = q.contiguous()
+    ldq = int(q.stride(0)) if M > 1 else D
+    if bias is not None:
+        bias = bias.detach().contiguous()
+    if S > 0:
+        exclude = exclude.to(torch.int64).contiguous()
+    ids = torch.empty((M, k), dtype=torch.int64, device=q.device)
+    scores = torch.empty((M, k), dtype=torch.float32, device=q.device)
+    return q, ldq, bias, exclude, S, ids, scores
 
 
 def topk_items(q, table, k, bias=None, exclude=None, invalid=None, nsplit=None):
@@ -3662,31 +3673,15 @@ def topk_items(q, table, k, bias=None, exclude=None, invalid=None, nsplit=None):
     if invalid is not None and not torch.is_tensor(invalid):
         invalid = torch.as_tensor(list(invalid), dtype=torch.int64, device=q.device)
     require_hip(q, table, bias, exclude, invalid)
-    if q.dim() != 2 or table.dim() != 2 or q.shape[1] != table.shape[1]:
-        raise ValueError("topk_items: q (M, D) and table (V, D) expected")
-    if q.dtype != torch.float32 or table.dtype != torch.float32 or (bias is not None and bias.dtype != torch.float32):
-        raise ValueError("torch_rechub_amd: topk_items takes float32 tensors")
-    if not table.is_contiguous():
-        raise ValueError("topk_items: the table must be contiguous")
-    M, D = (int(v) for v in q.shape)
-    V, k = int(table.shape[0]), int(k)
-    if exclude is not None and (exclude.dim() != 2 or exclude.shape[0] != M):
-        raise ValueError("topk_items: exclude (M, S) expected")
-    S = 0 if exclude is None else int(exclude.shape[1])
-    if bias is not None and tuple(bias.shape) != (V,):
-        raise ValueError("topk_items: bias (V,) expected")
-    if V < 1 or not topk_supported(D, k, S):
-        from .models.matching._listwise import no_kernel
-        raise no_kernel(f"top-k retrieval at D={D}, k={k}, {S} exclusions per query, V={V} "
-                        "(1 <= D <= 1024, 1 <= k <= 256, S <= 1024, V >= 1)")
-    q, table = q.detach(), table.detach()
-    if M > 0 and (q.stride(1) != 1 or q.stride(0) < D):
-        q = q.contiguous()
-    ldq = int(q.stride(0)) if M > 1 else D
-    if bias is not None:
-        bias = bias.detach().contiguous()
-    if S > 0:
-        exclude = exclude.to(torch.int64).contiguous()
+
+    def refuse(M, D, V, k, S):
+        if V < 1 or not topk_supported(D, k, S):
+            from .models.matching._listwise import no_kernel
+            raise no_kernel(f"top-k retrieval at D={D}, k={k}, {S} exclusions per query, V={V} "
+                            "(1 <= D <= 1024, 1 <= k <= 256, S <= 1024, V >= 1)")
+
+    q, ldq, bias, exclude, S, ids, scores = _scan_inputs("topk_items", "table", q, table, k, bias, exclude, refuse)
+    (M, D), V, k = q.shape, int(table.shape[0]), int(k)
     n_inv = 0
     if invalid is not None:
         invalid = invalid.to(torch.int64).reshape(-1).contiguous()
@@ -3696,13 +3691,10 @@ def topk_items(q, table, k, bias=None, exclude=None, invalid=None, nsplit=None):
     nsplit = int(nsplit)
     if not 1 <= nsplit <= min(V, 1024):
         raise ValueError(f"topk_items: nsplit={nsplit} outside [1, min(V, 1024)]")
-    dev = q.device
-    ids = torch.empty((M, k), dtype=torch.int64, device=dev)
-    scores = torch.empty((M, k), dtype=torch.float32, device=dev)
     if M == 0:
         return ids, scores
-    work = torch.empty((8 * M * nsplit * k,), dtype=torch.uint8, device=dev)
-    _lib.call("rh_topk_fwd", _p(q), ldq, _p(table), _p(bias), _p(exclude) if S > 0 else _NULL, S,
+    work = torch.empty((8 * M * nsplit * k,), dtype=torch.uint8, device=q.device)
+    _lib.call("rh_topk_fwd", _p(q), ldq, _p(table.detach()), _p(bias), _p(exclude) if S > 0 else _NULL, S,
               _p(invalid) if n_inv > 0 else _NULL, n_inv, M, D, V, k, nsplit, _p(work), _p(ids), _p(scores), _stream())
     return ids, scores
 
@@ -3713,19 +3705,15 @@ def topk_items(q, table, k, bias=None, exclude=None, invalid=None, nsplit=None):
 def ivf_supported(D, K, S=0, nprobe=1):
     """Whether csrc/ivf.hip takes width D, K results, S exclusions per query and nprobe lists per query (D <= 1024,
     K <= 256, S <= 1024, nprobe <= 256)."""
-    out = ctypes.c_int(0)
-    _lib.call("rh_ivf_supported", int(D), int(K), int(S), int(nprobe), ctypes.c_void_p(ctypes.addressof(out)))
-    return bool(out.value)
+    return bool(_lib.query("rh_ivf_supported", int(D), int(K), int(S), int(nprobe)))
 
 
 def ivf_plan(M, nlists, nprobe, K):
     """(rows_per_tile, grid, workspace_bytes) of ``ivf_scan``: the (query, slot) pairs one workgroup takes, the fixed grid
     bound ceil(M nprobe / rows_per_tile) + nlists + 1, and 8 M nprobe K bytes of partial lists + 4 M nprobe of pair
     indices + 8 (nlists + 2) of group and tile offsets."""
-    rb, grid, nbytes = ctypes.c_int(0), ctypes.c_int64(0), ctypes.c_int64(0)
-    _lib.call("rh_ivf_plan", int(M), int(nlists), int(nprobe), int(K), ctypes.c_void_p(ctypes.addressof(rb)),
-              ctypes.c_void_p(ctypes.addressof(grid)), ctypes.c_void_p(ctypes.addressof(nbytes)))
-    return rb.value, grid.value, nbytes.value
+    return _lib.query("rh_ivf_plan", int(M), int(nlists), int(nprobe), int(K),
+                      out=(ctypes.c_int, ctypes.c_int64, ctypes.c_int64))
 
 
 def ivf_scan(q, table_sorted, row_ids, list_offsets, probe, k, bias=None, exclude=None):
@@ -3739,46 +3727,27 @@ def ivf_scan(q, table_sorted, row_ids, list_offsets, probe, k, bias=None, exclud
     With every list probed the result is ``topk_items``' on the un-grouped table, bit for bit.  The pairs are grouped by
     list with a stable ``torch.sort``; nothing synchronises with the host.  No autograd; runs on the current stream."""
     require_hip(q, table_sorted, row_ids, list_offsets, probe, bias, exclude)
-    if q.dim() != 2 or table_sorted.dim() != 2 or q.shape[1] != table_sorted.shape[1]:
-        raise ValueError("ivf_scan: q (M, D) and table_sorted (V, D) expected")
-    if q.dtype != torch.float32 or table_sorted.dtype != torch.float32 or \
-            (bias is not None and bias.dtype != torch.float32):
-        raise ValueError("torch_rechub_amd: ivf_scan takes float32 tensors")
-    if row_ids.dtype != torch.int32 or list_offsets.dtype != torch.int32 or probe.dtype != torch.int32:
-        raise ValueError("ivf_scan: row_ids, list_offsets and probe are int32 tensors")
-    if not table_sorted.is_contiguous():
-        raise ValueError("ivf_scan: the table must be contiguous")
-    M, D = (int(v) for v in q.shape)
-    V, k = int(table_sorted.shape[0]), int(k)
-    if tuple(row_ids.shape) != (V,) or list_offsets.dim() != 1 or list_offsets.shape[0] < 2:
-        raise ValueError("ivf_scan: row_ids (V,) and list_offsets (nlists + 1,) expected")
-    nlists = int(list_offsets.shape[0]) - 1
-    if probe.dim() != 2 or probe.shape[0] != M:
-        raise ValueError("ivf_scan: probe (M, nprobe) expected")
-    nprobe = int(probe.shape[1])
-    if exclude is not None and (exclude.dim() != 2 or exclude.shape[0] != M):
-        raise ValueError("ivf_scan: exclude (M, S) expected")
-    S = 0 if exclude is None else int(exclude.shape[1])
-    if bias is not None and tuple(bias.shape) != (V,):
-        raise ValueError("ivf_scan: bias (V,) expected")
-    if V < 1 or M * nprobe >= 2 ** 31 - 64 * (nlists + 2) or not ivf_supported(D, k, S, nprobe):
-        from .models.matching._listwise import no_kernel
-        raise no_kernel(f"the inverted-file scan at D={D}, k={k}, {S} exclusions per query, nprobe={nprobe}, V={V} "
-                        "(1 <= D <= 1024, 1 <= k <= 256, S <= 1024, 1 <= nprobe <= 256, V >= 1, M nprobe < 2^31)")
-    q, table_sorted = q.detach(), table_sorted.detach()
-    if M > 0 and (q.stride(1) != 1 or q.stride(0) < D):
-        q = q.contiguous()
-    ldq = int(q.stride(0)) if M > 1 else D
-    row_ids, list_offsets = row_ids.contiguous(), list_offsets.contiguous()
-    if bias is not None:
-        bias = bias.detach().contiguous()
-    if S > 0:
-        exclude = exclude.to(torch.int64).contiguous()
-    dev = q.device
-    ids = torch.empty((M, k), dtype=torch.int64, device=dev)
-    scores = torch.empty((M, k), dtype=torch.float32, device=dev)
+
+    def refuse(M, D, V, k, S):
+        if row_ids.dtype != torch.int32 or list_offsets.dtype != torch.int32 or probe.dtype != torch.int32:
+            raise ValueError("ivf_scan: row_ids, list_offsets and probe are int32 tensors")
+        if tuple(row_ids.shape) != (V,) or list_offsets.dim() != 1 or list_offsets.shape[0] < 2:
+            raise ValueError("ivf_scan: row_ids (V,) and list_offsets (nlists + 1,) expected")
+        if probe.dim() != 2 or probe.shape[0] != M:
+            raise ValueError("ivf_scan: probe (M, nprobe) expected")
+        nlists, nprobe = int(list_offsets.shape[0]) - 1, int(probe.shape[1])
+        if V < 1 or M * nprobe >= 2 ** 31 - 64 * (nlists + 2) or not ivf_supported(D, k, S, nprobe):
+            from .models.matching._listwise import no_kernel
+            raise no_kernel(f"the inverted-file scan at D={D}, k={k}, {S} exclusions per query, nprobe={nprobe}, V={V} "
+                            "(1 <= D <= 1024, 1 <= k <= 256, S <= 1024, 1 <= nprobe <= 256, V >= 1, M nprobe < 2^31)")
+
+    q, ldq, bias, exclude, S, ids, scores = _scan_inputs("ivf_scan", "table_sorted", q, table_sorted, k, bias, exclude,
+                                                         refuse)
+    (M, D), V, k, dev = q.shape, int(table_sorted.shape[0]), int(k), q.device
+    nlists, nprobe = int(list_offsets.shape[0]) - 1, int(probe.shape[1])
     if M == 0:
         return ids, scores
+    table_sorted, row_ids, list_offsets = table_sorted.detach(), row_ids.contiguous(), list_offsets.contiguous()
     rb = ivf_plan(M, nlists, nprobe, k)[0]
     # the pairs grouped by list: group 0 = no list, group l + 1 = list l (a stable sort: reproducible pair order)
     key = torch.where((probe >= 0) & (probe < nlists), probe + 1, torch.zeros_like(probe)).reshape(-1)
@@ -3838,9 +3807,7 @@ def _sasrec_check(what, D, *tensors):
 
 
 def _sasrec_ntiles(M, D):
-    out = ctypes.c_int(0)
-    _lib.call("rh_sasrec_ntiles", int(M), int(D), ctypes.c_void_p(ctypes.addressof(out)))
-    return out.value
+    return _lib.query("rh_sasrec_ntiles", int(M), int(D))
 
 
 def _ln_param_grads(part, D):
@@ -4247,7 +4214,7 @@ class _SenetFn(torch.autograd.Function):
         if g.stride(2) != 1 or g.stride(1) != D or g.stride(0) < F * D:
             g = g.contiguous()
         g_x = torch.empty((B, F, D), dtype=torch.float32, device=dev)
-        nb = _sine_query("rh_twotower_nblocks", B)  # (answers through a host int)
+        nb = _lib.query("rh_twotower_nblocks", B)
         partial = torch.empty((nb, 2 * R * F), dtype=torch.float32, device=dev)
         _lib.call("rh_senet_bwd", _p(x), x.stride(0), _p(w1), _p(w2), _p(z), _p(h), _p(a), _p(g), g.stride(0), B, F, R, D,
                   _p(g_x), _p(partial), _stream())
@@ -4361,7 +4328,7 @@ class _T5AttnFn(torch.autograd.Function):
         delta = torch.empty((B, H, Lq), dtype=torch.float32, device=dev)
         part = None
         if bias is not None:
-            part = torch.empty((_sine_query("rh_t5_attn_nparts", B, Lq, H), Lq + Lk - 1), dtype=torch.float32, device=dev)
+            part = torch.empty((_lib.query("rh_t5_attn_nparts", B, Lq, H), Lq + Lk - 1), dtype=torch.float32, device=dev)
         _lib.call("rh_t5_attn_bwd", _p(q), int(q.stride(1)), _p(k), _p(v), int(k.stride(1)), B, Lq, Lk, H, dh, _p(mask),
                   causal, _p(bias), _p(bucket), nb, p, _p(rng), _p(ctr), _p(out), _p(lse), _p(g), _p(delta), _p(g_q), W,
                   _p(g_k), _p(g_v), int(g_k.stride(1)), _p(part), _p(g_bias), _stream())
@@ -4440,7 +4407,7 @@ class _AddRmsNormFn(torch.autograd.Function):
         g_h = torch.empty((M, D), dtype=torch.float32, device=dev)
         g_w = torch.zeros((D,), dtype=torch.float32, device=dev)
         if M > 0:
-            n = _sine_query("rh_add_rms_norm_nparts", M)  # (answers through a host int)
+            n = _lib.query("rh_add_rms_norm_nparts", M)
             part = torch.empty((n, D), dtype=torch.float32, device=dev)
             _lib.call("rh_add_rms_norm_bwd", _p(hn), _p(w), _p(rstd), _p(g_y), _p(g_hn), M, D, _p(g_h), _p(part), _stream())
             _lib.call("rh_colsum", _p(part), n, D, _p(g_w), _NULL, 0, _NULL, _stream())
@@ -4516,7 +4483,7 @@ class _CinLayerFn(torch.autograd.Function):
             if B == 0:  # nothing is launched: the parameter gradients are exact zeros
                 both = torch.zeros((Ho * K + Ho,), dtype=torch.float32, device=dev)
             else:
-                nch = _sine_query("rh_cin_wgrad_chunks", B, D, F, Hp, Ho)  # (answers through a host int)
+                nch = _lib.query("rh_cin_wgrad_chunks", B, D, F, Hp, Ho)
                 part = torch.empty((nch, Ho * K + Ho), dtype=torch.float32, device=dev)
                 _lib.call("rh_cin_wgrad", _p(x0), xs, xf, _p(h), hs, _p(y), _p(g), B, D, F, Hp, Ho, _p(part), _stream())
                 both = torch.empty((Ho * K + Ho,), dtype=torch.float32, device=dev)
@@ -4560,15 +4527,13 @@ def cin_layer(x0, h, weight, bias):
 _LABEL_DTYPES = {torch.float32: 0, torch.float64: 1, torch.int64: 2, torch.uint8: 3, torch.bool: 3}
 _RANK_MAX_K, _RANK_MAX_CUTOFFS = 256, 8
 _rank_tables = {}
+_PLAN_OUT = (ctypes.c_int, ctypes.c_int, ctypes.c_int64)  # what the metric kernels' plans answer with
 
 
 def auc_plan(n):
     """(chunk, max_grid, workspace_bytes) of rh_auc_groups over n samples: the sorted elements a workgroup takes per trip,
     the grid cap (more chunks than that are further trips) and the scratch size."""
-    chunk, grid, nbytes = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
-    _lib.call("rh_auc_plan", int(n), ctypes.c_void_p(ctypes.addressof(chunk)), ctypes.c_void_p(ctypes.addressof(grid)),
-              ctypes.c_void_p(ctypes.addressof(nbytes)))
-    return chunk.value, grid.value, nbytes.value
+    return _lib.query("rh_auc_plan", int(n), out=_PLAN_OUT)
 
 
 def _metric_inputs(what, pred, label, *more):
@@ -4683,9 +4648,7 @@ def log_loss(pred, label):
 
 def rank_metrics_plan(M):
     """(stage, users_per_workgroup, max_grid, partial_doubles) of rh_rank_metrics over M users."""
-    vals = [ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)]
-    _lib.call("rh_rank_metrics_plan", int(M), *[ctypes.c_void_p(ctypes.addressof(v)) for v in vals])
-    return tuple(v.value for v in vals)
+    return _lib.query("rh_rank_metrics_plan", int(M), out=(ctypes.c_int,) + _PLAN_OUT)
 
 
 def rank_gain_tables(K):
@@ -4766,28 +4729,20 @@ _ILD_MAX_D = 1024
 _POP_DTYPES = {torch.float32: 0, torch.float64: 1}
 
 
-def _list_plan(name, M):
-    vals = [ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)]
-    _lib.call(name, int(M), *[ctypes.c_void_p(ctypes.addressof(v)) for v in vals])
-    return tuple(v.value for v in vals)
-
-
 def ild_plan(M):
     """(users_per_workgroup, max_grid, partial_doubles) of rh_ild over M users."""
-    return _list_plan("rh_ild_plan", M)
+    return _lib.query("rh_ild_plan", int(M), out=_PLAN_OUT)
 
 
 def novelty_plan(M):
     """(users_per_workgroup, max_grid, partial_doubles) of rh_novelty over M users."""
-    return _list_plan("rh_novelty_plan", M)
+    return _lib.query("rh_novelty_plan", int(M), out=_PLAN_OUT)
 
 
 def coverage_plan(n_slots):
     """(rows_per_workgroup, max_grid, workspace_bytes) of rh_coverage over n_slots item slots: the rows a workgroup marks
     per trip, the grid cap of both passes (the counting pass takes 256 slots per workgroup and trip) and the scratch size."""
-    rows, grid, nbytes = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
-    _lib.call("rh_coverage_plan", int(n_slots), *[ctypes.c_void_p(ctypes.addressof(v)) for v in (rows, grid, nbytes)])
-    return rows.value, grid.value, nbytes.value
+    return _lib.query("rh_coverage_plan", int(n_slots), out=_PLAN_OUT)
 
 
 def _list_inputs(what, pred_ids, cutoffs, *more):

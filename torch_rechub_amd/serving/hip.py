@@ -48,6 +48,29 @@ def _unit_rows(x):
     return torch.where(n > 0, x / n.clamp_min(torch.finfo(torch.float32).tiny), torch.zeros_like(x))
 
 
+def _metric_query(metric, dev, embeddings, exclude, bias, search):
+    """``query`` of both indexers: ``search(q, bias, exclude) -> (ids, scores)`` is the inner-product search on the device
+    ``dev``, given the queries as the metric has them ranked (2 q with the index's ``bias`` = -|x|^2 for "L2", unit rows
+    for "angular"); the scores become the metric's values and everything returns to the queries' device."""
+    if embeddings.dim() != 2:
+        raise ValueError("query takes a 2D (n, d) tensor")
+    q = embeddings.detach().to(dev, torch.float32)
+    if exclude is not None:
+        exclude = exclude.to(dev)
+    if metric == "L2":
+        qn = (q * q).sum(dim=1, keepdim=True)
+        ids, s = search(q * 2.0, bias, exclude)
+        val = (qn - s).clamp_min(0.0)
+    elif metric == "angular":
+        ids, s = search(_unit_rows(q), None, exclude)
+        val = (2.0 - 2.0 * s).clamp_min(0.0).sqrt()
+    else:
+        ids, val = search(q, None, exclude)
+    if metric != "IP":
+        val = torch.where(ids < 0, torch.full_like(val, float("inf")), val)
+    return ids.to(embeddings.device), val.to(embeddings.device)
+
+
 class HipIndexer(BaseIndexer):
     """``table`` (n, d) on the device, searched exactly."""
 
@@ -73,25 +96,10 @@ class HipIndexer(BaseIndexer):
     def query(self, embeddings, top_k, *, exclude=None):
         """(ids (n, top_k) int64, values (n, top_k) float32) on the queries' device, best first.  ``exclude`` (n, S) int64:
         per-query ids that are never returned (entries outside [0, len(index)) are padding)."""
-        if embeddings.dim() != 2:
-            raise ValueError("query takes a 2D (n, d) tensor")
-        out_dev = embeddings.device
-        dev = self._table.device
-        q = embeddings.detach().to(dev, torch.float32)
-        if exclude is not None:
-            exclude = exclude.to(dev)
-        if self.metric == "L2":
-            qn = (q * q).sum(dim=1, keepdim=True)
-            ids, s = self._ops.topk_items(q * 2.0, self._search, top_k, bias=self._bias, exclude=exclude)
-            val = (qn - s).clamp_min(0.0)
-        elif self.metric == "angular":
-            ids, s = self._ops.topk_items(_unit_rows(q), self._search, top_k, exclude=exclude)
-            val = (2.0 - 2.0 * s).clamp_min(0.0).sqrt()
-        else:
-            ids, val = self._ops.topk_items(q, self._search, top_k, exclude=exclude)
-        if self.metric != "IP":
-            val = torch.where(ids < 0, torch.full_like(val, float("inf")), val)
-        return ids.to(out_dev), val.to(out_dev)
+        def search(q, bias, exclude):
+            return self._ops.topk_items(q, self._search, top_k, bias=bias, exclude=exclude)
+
+        return _metric_query(self.metric, self._table.device, embeddings, exclude, self._bias, search)
 
     def save(self, file_path):
         save_index(file_path, self.metric, self._table)
@@ -173,35 +181,20 @@ class HipIvfIndexer(BaseIndexer):
 
     def query(self, embeddings, top_k, *, exclude=None, nprobe=None):
         """As ``HipIndexer.query``, over the ``nprobe`` (default: the index's) nearest lists of every query."""
-        if embeddings.dim() != 2:
-            raise ValueError("query takes a 2D (n, d) tensor")
         nprobe = self.nprobe if nprobe is None else self._clip(nprobe)
-        out_dev = embeddings.device
-        dev = self._table.device
-        q = embeddings.detach().to(dev, torch.float32)
-        if exclude is not None:
-            exclude = exclude.to(dev)
         ops = self._ops
-        if self.metric == "angular":
-            q = _unit_rows(q)
-        if self.metric == "IP":
-            probe = ops.topk_items(q, self.centroids, nprobe)[0]
-        else:
-            probe = ops.topk_items(q * 2.0, self.centroids, nprobe, bias=self._cbias)[0]
-        probe = probe.to(torch.int32)
-        scan = (self._search, self._row_id, self._list_off, probe, top_k)
-        if self.metric == "L2":
-            qn = (q * q).sum(dim=1, keepdim=True)
-            ids, s = ops.ivf_scan(q * 2.0, *scan, bias=self._bias, exclude=exclude)
-            val = (qn - s).clamp_min(0.0)
-        elif self.metric == "angular":
-            ids, s = ops.ivf_scan(q, *scan, exclude=exclude)
-            val = (2.0 - 2.0 * s).clamp_min(0.0).sqrt()
-        else:
-            ids, val = ops.ivf_scan(q, *scan, exclude=exclude)
-        if self.metric != "IP":
-            val = torch.where(ids < 0, torch.full_like(val, float("inf")), val)
-        return ids.to(out_dev), val.to(out_dev)
+
+        def search(q, bias, exclude):
+            # the nearest lists under L2: by 2 q . c - |c|^2 ("L2" hands 2 q in already); under "IP": by q . c
+            if self.metric == "IP":
+                probe = ops.topk_items(q, self.centroids, nprobe)[0]
+            else:
+                q2 = q if self.metric == "L2" else q * 2.0
+                probe = ops.topk_items(q2, self.centroids, nprobe, bias=self._cbias)[0]
+            return ops.ivf_scan(q, self._search, self._row_id, self._list_off, probe.to(torch.int32), top_k, bias=bias,
+                                exclude=exclude)
+
+        return _metric_query(self.metric, self._table.device, embeddings, exclude, self._bias, search)
 
     def save(self, file_path):
         """One ``torch.save`` dict: the metric, the table in its original row order, the centroids and ``nprobe``.
