@@ -312,6 +312,19 @@ def test_novelty_over_the_shape_edges(ops):
         ops.novelty(ids, dev(pop).reshape(5, 10), [1])
 
 
+@pytest.mark.parametrize("cutoffs", [[65], [1, 2, 3, 5, 8, 13, 21, 65]])
+def test_ild_and_novelty_over_a_ragged_count_of_partials(ops, cutoffs):
+    """133 users are 34 workgroups, the last with one user: more partials than the final sum has parts (32) and no multiple
+    of them, at one cut-off and at eight.  The other tests end in 1, 2, at most 10, 1024 or 2048 partials."""
+    pred, table, pop = C.make(133, 133, 65, 400, 16)
+    raw, _ = check_ild(ops, pred, table, cutoffs)
+    again = ops.ild(dev(pred), dev(table), cutoffs)
+    assert torch.equal(again["sums"], raw["sums"]) and torch.equal(again["counts"], raw["counts"])
+    raw, _ = check_novelty(ops, pred, pop, cutoffs)
+    again = ops.novelty(dev(pred), dev(pop), cutoffs)
+    assert torch.equal(again["sums"], raw["sums"]) and torch.equal(again["counts"], raw["counts"])
+
+
 # ---- basic.metric --------------------------------------------------------------------------------------------------
 def all_cases():
     c = load_golden("metric_cases.npz")

@@ -352,15 +352,19 @@ def test_list_metrics_over_the_width_range(ops, rank_plan, K):
     check_lists(ops, pred, truth, [1, K], device_pred=view)
 
 
-@pytest.mark.parametrize("which", ["1", "upw-1", "upw+1", "past the cap"])
+@pytest.mark.parametrize("which", ["1", "upw-1", "upw+1", "past the cap", "34 partials"])
 def test_list_metrics_over_the_user_range(ops, rank_plan, which):
+    """The "34 partials" case: 133 users are 34 workgroups, the last with one user -- more partials than the final sum has parts
+    (32) and no multiple of them, at one cut-off and at eight; the other cases end in 1, 2 or 1024 partials."""
     _, upw, cap = rank_plan
-    M = {"1": 1, "upw-1": upw - 1, "upw+1": upw + 1, "past the cap": cap * upw + 3}[which]
+    M = {"1": 1, "upw-1": upw - 1, "upw+1": upw + 1, "past the cap": cap * upw + 3, "34 partials": 133}[which]
     rng = np.random.default_rng(M)
-    K = 8
+    K, cuts = (65, ([65], [1, 2, 3, 5, 8, 13, 21, 65])) if which == "34 partials" else (8, ([3, 8],))
     truth = truth_of_lengths(rng, rng.integers(0, 6, M).tolist(), K)
     truth[-1] = [3]
-    check_lists(ops, rng.integers(0, 3 * K, (M, K)), truth, [3, 8])
+    pred = rng.integers(0, 3 * K, (M, K))
+    for cut in cuts:
+        check_lists(ops, pred, truth, cut)
 
 
 def test_all_truth_lists_empty(ops, metric):

@@ -37,10 +37,24 @@ constexpr int kAucChunk = 1024, kAucWords = kAucChunk / 64, kAucItems = kAucChun
 constexpr int kAucAgg = 5;    // int32 per chunk: neg, head_n, tail_run, tail_grp, flags
 constexpr int kAucCarry = 4;  // int64 per chunk: P, run_in, grp_in, run_out
 constexpr int kFullRun = 1, kFullGrp = 2, kOpensRun = 4, kOpensGrp = 8;
+// rechub_hip.h documents the `partial` of rh_gauc_reduce as 3072 doubles and that of rh_log_loss as 1024, and callers
+// allocate exactly that; the kernels write 3 and 1 doubles per workgroup of a grid of at most kReduceMaxGrid
 constexpr int kReduceMaxGrid = 1024;
-constexpr int kRankStage = 256, kRankUsers = RH_BLOCK / RH_WAVE, kRankMaxGrid = 1024, kRankMaxK = 256, kRankMaxCut = 8;
+static_assert(3 * kReduceMaxGrid <= 3072, "rh_gauc_reduce writes past the 3072 doubles its contract gives it");
+static_assert(kReduceMaxGrid <= 1024, "rh_log_loss writes past the 1024 doubles its contract gives it");
+// the list kernels (rank metrics, ild, novelty): one wavefront per user, at most kListMaxCut cut-offs over K <= kListMaxK
+constexpr int kListUsers = RH_BLOCK / RH_WAVE, kListMaxK = 256, kListMaxCut = 8, kListPer = kListMaxK / RH_WAVE;
+constexpr int kListMaxGrid = 2048;  // ild, novelty
+constexpr int kRankStage = 256, kRankMaxGrid = 1024, kRankSums = 4;
+constexpr int kSumParts = 32;
 
 typedef unsigned long long u64;
+
+// workgroups for `count` items at `per` a workgroup: at least one, at most `cap` (what is left over is further trips)
+int grid_for(int64_t count, int per, int cap) {
+  const int64_t b = (count + per - 1) / per;
+  return (int)(b < 1 ? 1 : (b > cap ? cap : b));
+}
 
 struct AucArgs {
   const uint32_t* pred;  // float32 bit patterns, element stride ps
@@ -432,19 +446,34 @@ __global__ __launch_bounds__(RH_BLOCK) void gauc_partial_kernel(const int64_t* s
   }
 }
 
-__global__ __launch_bounds__(RH_BLOCK) void gauc_final_kernel(const double* partial, int nblocks, double* result,
-                                                              int64_t* single_class) {
+// ONE workgroup: the NV values of every per-workgroup partial, thread-strided adds in ascending index and then the
+// block_sum tree; thread 0 hands the NV totals to `done`
+template <int NV, typename Done>
+__global__ __launch_bounds__(RH_BLOCK) void tree_final_kernel(const double* partial, int nblocks, const Done done) {
   __shared__ double red[RH_BLOCK];
-  double v[3] = {0.0, 0.0, 0.0};
+  double v[NV];
+  for (int k = 0; k < NV; ++k) v[k] = 0.0;
   for (int b = threadIdx.x; b < nblocks; b += RH_BLOCK)
-    for (int k = 0; k < 3; ++k) v[k] += partial[b * 3 + k];
-  for (int k = 0; k < 3; ++k) v[k] = block_sum(v[k], red);
-  if (threadIdx.x == 0) {
+    for (int k = 0; k < NV; ++k) v[k] += partial[b * NV + k];
+  for (int k = 0; k < NV; ++k) v[k] = block_sum(v[k], red);
+  if (threadIdx.x == 0) done(v);
+}
+
+struct GaucDone {
+  double* result;
+  int64_t* single_class;
+  __device__ void operator()(const double* v) const {
     result[0] = v[0];
     result[1] = v[1];
     single_class[0] = (int64_t)v[2];
   }
-}
+};
+
+struct LogLossDone {
+  double* result;
+  int64_t n;
+  __device__ void operator()(const double* v) const { result[0] = -v[0] / (double)n; }
+};
 
 __device__ __forceinline__ double label_value(const void* p, int dt, int64_t i) {
   switch (dt) {
@@ -467,25 +496,17 @@ __global__ __launch_bounds__(RH_BLOCK) void log_loss_partial_kernel(const float*
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
-__global__ __launch_bounds__(RH_BLOCK) void log_loss_final_kernel(const double* partial, int nblocks, int64_t n,
-                                                                  double* result) {
-  __shared__ double red[RH_BLOCK];
-  double s = 0.0;
-  for (int b = threadIdx.x; b < nblocks; b += RH_BLOCK) s += partial[b];
-  s = block_sum(s, red);
-  if (threadIdx.x == 0) result[0] = -s / (double)n;
-}
-
-int reduce_grid(int64_t n) {
-  const int64_t b = (n + RH_BLOCK - 1) / RH_BLOCK;
-  return (int)(b < 1 ? 1 : (b > kReduceMaxGrid ? kReduceMaxGrid : b));
-}
+struct ListCuts {
+  int n_k;
+  int cut[kListMaxCut];   // in the caller's order, or ascending (rh_ild)
+  int slot[kListMaxCut];  // the position of cut[q] in the caller's list
+};
 
 struct RankArgs {
   const int64_t* pred;
   int64_t ld;
-  int M, K, n_k;
-  int cut[kRankMaxCut];
+  int M, K;
+  ListCuts c;  // in the caller's order
   const int64_t* off;
   const int64_t* ids;
   int64_t n_truth;
@@ -503,26 +524,67 @@ __device__ __forceinline__ void rank_wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-__global__ __launch_bounds__(RH_BLOCK) void rank_metrics_kernel(const RankArgs a) {
-  __shared__ int64_t stage[kRankUsers][kRankStage];
-  __shared__ double wsum[kRankUsers][kRankMaxCut][4];
+// butterfly sum over the 64 lanes, masks ascending: every lane gets the total through the same order of additions
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int m = 1; m < RH_WAVE; m <<= 1) v += __shfl_xor(v, m, RH_WAVE);
+  return v;
+}
+
+// A wavefront's running sums over its users, in two LDS arrays that the kernel declares: NS = W / kListMaxCut doubles per
+// cut-off (wsum[w][q * NS + t]) and one exact count (wcnt[w][q]).
+//   wave_acc_zero  the low lanes zero their wavefront's row; the caller syncs the wavefront (or the workgroup) behind it
+//   wave_acc_add   called by ONE lane per user and cut-off, so that a wavefront adds user after user: a fixed order
+//   wave_acc_tail  called by the whole workgroup: the counts leave as integer atomics, the wavefronts' sums are added in
+//                  index order into the workgroup's partial (n_k * NS doubles)
+template <int W>
+__device__ __forceinline__ void wave_acc_zero(double (&wsum)[kListUsers][W], u64 (&wcnt)[kListUsers][kListMaxCut], int w,
+                                              int lane) {
+  if (lane < W) wsum[w][lane] = 0.0;
+  if (lane < kListMaxCut) wcnt[w][lane] = 0;
+}
+
+template <int W>
+__device__ __forceinline__ void wave_acc_add(double (&wsum)[kListUsers][W], u64 (&wcnt)[kListUsers][kListMaxCut], int w,
+                                             int q, const double* v, u64 n) {
+  constexpr int NS = W / kListMaxCut;
+  wcnt[w][q] += n;
+  for (int t = 0; t < NS; ++t) wsum[w][q * NS + t] += v[t];
+}
+
+template <int W>
+__device__ __forceinline__ void wave_acc_tail(double (&wsum)[kListUsers][W], u64 (&wcnt)[kListUsers][kListMaxCut], int n_k,
+                                              u64* counts, double* partial) {
+  constexpr int NS = W / kListMaxCut;
   const int tid = threadIdx.x, lane = tid % RH_WAVE, w = tid / RH_WAVE;
-  constexpr int kPer = kRankMaxK / RH_WAVE;
+  rank_wave_sync();
+  if (lane < n_k && wcnt[w][lane] != 0) atomicAdd(counts + lane, wcnt[w][lane]);
+  __syncthreads();
+  if (tid < n_k * NS) {
+    double s = wsum[0][tid];
+    for (int ww = 1; ww < kListUsers; ++ww) s += wsum[ww][tid];
+    partial[(int64_t)blockIdx.x * n_k * NS + tid] = s;
+  }
+}
+
+__global__ __launch_bounds__(RH_BLOCK) void rank_metrics_kernel(const RankArgs a) {
+  __shared__ int64_t stage[kListUsers][kRankStage];
   // the wavefront's running sums live in LDS (lane 0 adds user after user: a fixed order), not in 80 registers per lane
-  __shared__ u64 whit[kRankUsers][kRankMaxCut];
-  if (lane < kRankMaxCut * 4) (&wsum[w][0][0])[lane] = 0.0;
-  if (lane < kRankMaxCut) whit[w][lane] = 0;
+  __shared__ double wsum[kListUsers][kListMaxCut * kRankSums];
+  __shared__ u64 whit[kListUsers][kListMaxCut];
+  const int tid = threadIdx.x, lane = tid % RH_WAVE, w = tid / RH_WAVE;
+  wave_acc_zero(wsum, whit, w, lane);
   rank_wave_sync();
   u64 gts = 0;
-  for (int64_t u = (int64_t)blockIdx.x * kRankUsers + w; u < a.M; u += (int64_t)gridDim.x * kRankUsers) {
+  for (int64_t u = (int64_t)blockIdx.x * kListUsers + w; u < a.M; u += (int64_t)gridDim.x * kListUsers) {
     int64_t lo = a.off[u], hi = a.off[u + 1];
     lo = lo < 0 ? 0 : (lo > a.n_truth ? a.n_truth : lo);
     hi = hi < lo ? lo : (hi > a.n_truth ? a.n_truth : hi);
     const int64_t len = hi - lo;
-    int64_t id[kPer];
-    bool hit[kPer];
+    int64_t id[kListPer];
+    bool hit[kListPer];
 #pragma unroll
-    for (int r = 0; r < kPer; ++r) {
+    for (int r = 0; r < kListPer; ++r) {
       const int j = r * RH_WAVE + lane;
       id[r] = j < a.K ? a.pred[u * a.ld + j] : 0;
       hit[r] = false;
@@ -535,18 +597,18 @@ __global__ __launch_bounds__(RH_BLOCK) void rank_metrics_kernel(const RankArgs a
       for (int e = 0; e < cnt; ++e) {
         const int64_t t = stage[w][e];
 #pragma unroll
-        for (int r = 0; r < kPer; ++r) hit[r] |= id[r] == t;
+        for (int r = 0; r < kListPer; ++r) hit[r] |= id[r] == t;
       }
     }
     if (len > 0) gts += (u64)len;
 #pragma unroll
-    for (int q = 0; q < kRankMaxCut; ++q) {
-      if (q >= a.n_k) break;
-      const int k = a.cut[q];
-      uint64_t m[kPer];
+    for (int q = 0; q < kListMaxCut; ++q) {
+      if (q >= a.c.n_k) break;
+      const int k = a.c.cut[q];
+      uint64_t m[kListPer];
       int nhit = 0;
 #pragma unroll
-      for (int r = 0; r < kPer; ++r) {
+      for (int r = 0; r < kListPer; ++r) {
         m[r] = __ballot(hit[r] && r * RH_WAVE + lane < k && r * RH_WAVE + lane < a.K);
         nhit += __popcll(m[r]);
       }
@@ -555,7 +617,7 @@ __global__ __launch_bounds__(RH_BLOCK) void rank_metrics_kernel(const RankArgs a
         double dcg = 0.0;
         int first = -1;
 #pragma unroll
-        for (int r = 0; r < kPer; ++r) {
+        for (int r = 0; r < kListPer; ++r) {
           uint64_t x = m[r];
           while (x != 0) {  // ascending positions: the order in which the reference adds
             const int j = r * RH_WAVE + __ffsll((unsigned long long)x) - 1;
@@ -570,57 +632,70 @@ __global__ __launch_bounds__(RH_BLOCK) void rank_metrics_kernel(const RankArgs a
         v[2] = (double)nhit / (double)len;
         v[3] = (double)nhit / (double)k;
         v[4] = dcg / a.ideal[il];
-        if (lane == 0) {
-          whit[w][q] += (u64)nhit;
-          for (int t = 0; t < 4; ++t) wsum[w][q][t] += v[t + 1];
-        }
+        if (lane == 0) wave_acc_add(wsum, whit, w, q, v + 1, (u64)nhit);
       }
       if (a.per_user != nullptr && lane < 5) {
         double o = v[0];
         for (int t = 1; t < 5; ++t) o = lane == t ? v[t] : o;
-        a.per_user[(u * a.n_k + q) * 5 + lane] = o;
+        a.per_user[(u * a.c.n_k + q) * 5 + lane] = o;
       }
     }
   }
-  if (lane == 0) {
-#pragma unroll
-    for (int q = 0; q < kRankMaxCut; ++q) {
-      if (q >= a.n_k) break;
-      if (whit[w][q] != 0) atomicAdd(a.hits + q, whit[w][q]);
-    }
-    if (gts != 0) atomicAdd(a.gts, gts);
-  }
-  __syncthreads();
-  if (tid < a.n_k * 4) {
-    const int q = tid / 4, t = tid % 4;
-    double s = wsum[0][q][t];
-    for (int ww = 1; ww < kRankUsers; ++ww) s += wsum[ww][q][t];
-    a.partial[((int64_t)blockIdx.x * a.n_k + q) * 4 + t] = s;
-  }
+  if (lane == 0 && gts != 0) atomicAdd(a.gts, gts);
+  wave_acc_tail(wsum, whit, a.c.n_k, a.hits, a.partial);
 }
 
-// ONE workgroup of 32 x 32 threads: thread (part, e) adds the partials b = part, part + 32, ... of sum e in ascending b,
-// then thread e adds the 32 parts in ascending order: a fixed order
-constexpr int kRankFinalParts = 32;
-__global__ __launch_bounds__(kRankFinalParts * kRankMaxCut * 4) void rank_final_kernel(const double* partial, int nblocks,
-                                                                                       int n_k, double* sums) {
-  __shared__ double part_sum[kRankFinalParts][kRankMaxCut * 4];
-  const int e = threadIdx.x % (kRankMaxCut * 4), part = threadIdx.x / (kRankMaxCut * 4);
+// ONE workgroup of kSumParts x WIDTH threads over partials of n <= WIDTH sums each: thread (part, e) adds the partials
+// b = part, part + kSumParts, ... of sum e in ascending b, then thread e adds the parts in ascending order: a fixed order
+template <int WIDTH>
+__global__ __launch_bounds__(kSumParts * WIDTH) void final_sum_kernel(const double* partial, int nblocks, int n,
+                                                                      double* sums) {
+  __shared__ double part_sum[kSumParts][WIDTH];
+  const int e = threadIdx.x % WIDTH, part = threadIdx.x / WIDTH;
   double s = 0.0;
-  if (e < n_k * 4)
-    for (int b = part; b < nblocks; b += kRankFinalParts) s += partial[(int64_t)b * n_k * 4 + e];
+  if (e < n)
+    for (int b = part; b < nblocks; b += kSumParts) s += partial[(int64_t)b * n + e];
   part_sum[part][e] = s;
   __syncthreads();
-  if (part == 0 && e < n_k * 4) {
+  if (part == 0 && e < n) {
     s = part_sum[0][e];
-    for (int q = 1; q < kRankFinalParts; ++q) s += part_sum[q][e];
+    for (int q = 1; q < kSumParts; ++q) s += part_sum[q][e];
     sums[e] = s;
   }
 }
 
-int rank_grid(int M) {
-  const int64_t b = ((int64_t)M + kRankUsers - 1) / kRankUsers;
-  return (int)(b < 1 ? 1 : (b > kRankMaxGrid ? kRankMaxGrid : b));
+template <int WIDTH>
+void final_sum_launch(const double* partial, int nblocks, int n, double* sums, hipStream_t st) {
+  hipLaunchKernelGGL((final_sum_kernel<WIDTH>), dim3(1), dim3(kSumParts * WIDTH), 0, st, partial, nblocks, n, sums);
+}
+
+// what the plans of the list kernels answer: `width` doubles per workgroup of a grid of at most `cap`
+int list_plan(const char* who, int M, int cap, int width, int* users_per_workgroup, int* max_grid, int64_t* partial_doubles) {
+  RH_REQUIRE(users_per_workgroup && max_grid && partial_doubles, RH_E_BADARG, "%s: null pointer", who);
+  RH_REQUIRE(M >= 0, RH_E_BADARG, "%s: M=%d", who, M);
+  *users_per_workgroup = kListUsers;
+  *max_grid = cap;
+  *partial_doubles = (int64_t)grid_for(M, kListUsers, cap) * width;
+  return 0;
+}
+
+// the checks the list entries share; the cut-offs in the caller's order
+int list_check(const char* who, int64_t ld, int M, int K, const int* cutoffs, int n_k, ListCuts* c) {
+  RH_REQUIRE(K >= 1 && K <= kListMaxK, RH_E_UNSUPPORTED, "%s: K=%d unsupported (1 <= K <= %d)", who, K, kListMaxK);
+  RH_REQUIRE(n_k >= 1 && n_k <= kListMaxCut, RH_E_UNSUPPORTED, "%s: %d cut-offs (1 <= n_k <= %d)", who, n_k, kListMaxCut);
+  RH_REQUIRE(M >= 1 && ld >= K, RH_E_BADARG, "%s: M=%d ld=%lld K=%d", who, M, (long long)ld, K);
+  RH_REQUIRE(cutoffs != nullptr, RH_E_BADARG, "%s: null pointer", who);
+  c->n_k = n_k;
+  for (int q = 0; q < kListMaxCut; ++q) {
+    c->cut[q] = 0;
+    c->slot[q] = 0;
+  }
+  for (int q = 0; q < n_k; ++q) {
+    RH_REQUIRE(cutoffs[q] >= 1 && cutoffs[q] <= K, RH_E_BADARG, "%s: cut-off %d outside [1, K=%d]", who, cutoffs[q], K);
+    c->cut[q] = cutoffs[q];
+    c->slot[q] = q;
+  }
+  return 0;
 }
 
 }  // namespace
@@ -686,9 +761,10 @@ extern "C" int rh_gauc_reduce(const int64_t* stats, const double* weights, int64
   RH_REQUIRE(G >= 1 && G < (1ll << 31), RH_E_BADARG, "rh_gauc_reduce: G=%lld outside [1, 2^31)", (long long)G);
   RH_REQUIRE(stats && partial && result && single_class, RH_E_BADARG, "rh_gauc_reduce: null pointer");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int grid = reduce_grid(G);
+  const int grid = grid_for(G, RH_BLOCK, kReduceMaxGrid);
   hipLaunchKernelGGL(gauc_partial_kernel, dim3(grid), dim3(RH_BLOCK), 0, st, stats, weights, G, partial);
-  hipLaunchKernelGGL(gauc_final_kernel, dim3(1), dim3(RH_BLOCK), 0, st, partial, grid, result, single_class);
+  hipLaunchKernelGGL((tree_final_kernel<3, GaucDone>), dim3(1), dim3(RH_BLOCK), 0, st, partial, grid,
+                     GaucDone{result, single_class});
   RH_LAUNCH_CHECK("rh_gauc_reduce");
   return 0;
 }
@@ -699,21 +775,21 @@ extern "C" int rh_log_loss(const float* pred, int64_t pred_stride, const void* l
   RH_REQUIRE(label_dtype >= 0 && label_dtype <= 3, RH_E_BADARG, "rh_log_loss: label_dtype=%d outside [0, 3]", label_dtype);
   RH_REQUIRE(pred && label && partial && result, RH_E_BADARG, "rh_log_loss: null pointer");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int grid = reduce_grid(n);
+  const int grid = grid_for(n, RH_BLOCK, kReduceMaxGrid);
   hipLaunchKernelGGL(log_loss_partial_kernel, dim3(grid), dim3(RH_BLOCK), 0, st, pred, pred_stride, label, label_dtype, n,
                      partial);
-  hipLaunchKernelGGL(log_loss_final_kernel, dim3(1), dim3(RH_BLOCK), 0, st, partial, grid, n, result);
+  hipLaunchKernelGGL((tree_final_kernel<1, LogLossDone>), dim3(1), dim3(RH_BLOCK), 0, st, partial, grid,
+                     LogLossDone{result, n});
   RH_LAUNCH_CHECK("rh_log_loss");
   return 0;
 }
 
 extern "C" int rh_rank_metrics_plan(int M, int* stage, int* users_per_workgroup, int* max_grid, int64_t* partial_doubles) {
-  RH_REQUIRE(stage && users_per_workgroup && max_grid && partial_doubles, RH_E_BADARG, "rh_rank_metrics_plan: null pointer");
-  RH_REQUIRE(M >= 0, RH_E_BADARG, "rh_rank_metrics_plan: M=%d", M);
+  RH_REQUIRE(stage != nullptr, RH_E_BADARG, "rh_rank_metrics_plan: null pointer");
+  if (int rc = list_plan("rh_rank_metrics_plan", M, kRankMaxGrid, kListMaxCut * kRankSums, users_per_workgroup, max_grid,
+                         partial_doubles))
+    return rc;
   *stage = kRankStage;
-  *users_per_workgroup = kRankUsers;
-  *max_grid = kRankMaxGrid;
-  *partial_doubles = (int64_t)rank_grid(M) * kRankMaxCut * 4;
   return 0;
 }
 
@@ -721,23 +797,15 @@ extern "C" int rh_rank_metrics(const int64_t* pred, int64_t ld, int M, int K, co
                                const int64_t* truth_ids, int64_t n_truth, const int* cutoffs, int n_k, const double* gain,
                                const double* ideal, double* partial, int64_t* hits, int64_t* gts, double* sums,
                                double* per_user, void* stream) {
-  RH_REQUIRE(K >= 1 && K <= kRankMaxK, RH_E_UNSUPPORTED, "rh_rank_metrics: K=%d unsupported (1 <= K <= %d)", K, kRankMaxK);
-  RH_REQUIRE(n_k >= 1 && n_k <= kRankMaxCut, RH_E_UNSUPPORTED, "rh_rank_metrics: %d cut-offs (1 <= n_k <= %d)", n_k,
-             kRankMaxCut);
-  RH_REQUIRE(M >= 1 && ld >= K && n_truth >= 0, RH_E_BADARG, "rh_rank_metrics: M=%d ld=%lld K=%d n_truth=%lld", M,
-             (long long)ld, K, (long long)n_truth);
-  RH_REQUIRE(pred && truth_off && truth_ids && cutoffs && gain && ideal && partial && hits && gts && sums, RH_E_BADARG,
-             "rh_rank_metrics: null pointer");
   RankArgs a{};
-  for (int q = 0; q < n_k; ++q) {
-    RH_REQUIRE(cutoffs[q] >= 1 && cutoffs[q] <= K, RH_E_BADARG, "rh_rank_metrics: cut-off %d outside [1, K=%d]", cutoffs[q], K);
-    a.cut[q] = cutoffs[q];
-  }
+  if (int rc = list_check("rh_rank_metrics", ld, M, K, cutoffs, n_k, &a.c)) return rc;
+  RH_REQUIRE(n_truth >= 0, RH_E_BADARG, "rh_rank_metrics: n_truth=%lld", (long long)n_truth);
+  RH_REQUIRE(pred && truth_off && truth_ids && gain && ideal && partial && hits && gts && sums, RH_E_BADARG,
+             "rh_rank_metrics: null pointer");
   a.pred = pred;
   a.ld = ld;
   a.M = M;
   a.K = K;
-  a.n_k = n_k;
   a.off = truth_off;
   a.ids = truth_ids;
   a.n_truth = n_truth;
@@ -751,9 +819,9 @@ extern "C" int rh_rank_metrics(const int64_t* pred, int64_t ld, int M, int K, co
   hipError_t e = hipMemsetAsync(hits, 0, (size_t)n_k * 8, st);
   if (e == hipSuccess) e = hipMemsetAsync(gts, 0, 8, st);
   RH_REQUIRE(e == hipSuccess, (int)e, "rh_rank_metrics: memset failed: %s", hipGetErrorString(e));
-  const int grid = rank_grid(M);
+  const int grid = grid_for(M, kListUsers, kRankMaxGrid);
   hipLaunchKernelGGL(rank_metrics_kernel, dim3(grid), dim3(RH_BLOCK), 0, st, a);
-  hipLaunchKernelGGL(rank_final_kernel, dim3(1), dim3(kRankFinalParts * kRankMaxCut * 4), 0, st, partial, grid, n_k, sums);
+  final_sum_launch<kListMaxCut * kRankSums>(partial, grid, n_k * kRankSums, sums, st);
   RH_LAUNCH_CHECK("rh_rank_metrics");
   return 0;
 }
@@ -773,23 +841,17 @@ extern "C" int rh_rank_metrics(const int64_t* pred, int64_t ld, int M, int K, co
 //
 // rh_novelty: one wavefront per user, lane l owns the positions l, l + 64, ...; per cut-off a masked butterfly sum.
 // Both add a wavefront's users in LDS (lane 0, user after user), the workgroup's wavefronts in index order into one
-// partial per workgroup, and the partials in index order: no float atomics, the same bits every time.
+// partial per workgroup, and the partials in index order: no float atomics, the same bits every time.  That is
+// final_sum_kernel and, in novelty_kernel, the wave_acc_* functions of the rank metrics above, with one sum per cut-off
+// where those carry four.  ild_kernel writes the same steps out: on the shared functions its D = 64 instantiation measured
+// 1 - 1.5 % slower at M = 1 M (profiles/metric_tail_ab.txt), so it keeps its own copy of the tail.
 //
 // rh_coverage: first[id] = the lowest column at which id appears (integer atomicMin, skipped when a plain read already
 // shows a value that low); a second pass counts per cut-off the slots with first < k.  Integers: exact in any order.
 namespace {
 
-constexpr int kListUsers = RH_BLOCK / RH_WAVE, kListMaxGrid = 2048, kListMaxK = 256, kListMaxCut = 8;
-constexpr int kListPer = kListMaxK / RH_WAVE;
 constexpr int kIldMaxD = 1024, kIldTrips = 2;
-constexpr int kSumParts = 32;
 constexpr int kCovRows = 256, kCovMaxGrid = 2048;
-
-struct ListCuts {
-  int n_k;
-  int cut[kListMaxCut];   // ascending
-  int slot[kListMaxCut];  // the position of cut[q] in the caller's list
-};
 
 struct IldArgs {
   const int64_t* pred;
@@ -798,13 +860,11 @@ struct IldArgs {
   const float* table;
   int64_t lt, V;
   int D;
-  ListCuts c;
+  ListCuts c;       // ascending
   double* partial;  // (gridDim.x, n_k)
   u64* counts;      // (n_k,)
   double* per_user; // (M, n_k) or null
 };
-
-__device__ __forceinline__ double shfl_xor_f64(double v, int m) { return __shfl_xor(v, m, RH_WAVE); }
 
 template <int VEC, int LPI, int NCH>
 __global__ __launch_bounds__(RH_BLOCK) void ild_kernel(const IldArgs a) {
@@ -889,7 +949,7 @@ __global__ __launch_bounds__(RH_BLOCK) void ild_kernel(const IldArgs a) {
 #pragma unroll
         for (int i = 0; i < NE; ++i) ss = fma((double)cur[t][i], (double)cur[t][i], ss);
 #pragma unroll
-        for (int m = 1; m < LPI; m <<= 1) ss += shfl_xor_f64(ss, m);
+        for (int m = 1; m < LPI; m <<= 1) ss += __shfl_xor(ss, m, RH_WAVE);
         // 1 / max(||e||, 1e-10); rsqrt, not sqrt and a division: the kernel is bound by its double arithmetic
         const double inv = cok[t] ? (ss >= 1e-20 ? rsqrt(ss) : 1e10) : 0.0;
 #pragma unroll
@@ -903,16 +963,16 @@ __global__ __launch_bounds__(RH_BLOCK) void ild_kernel(const IldArgs a) {
         for (int i = 0; i < NE; ++i) {
           double T = S[i];
 #pragma unroll
-          for (int m = LPI; m < RH_WAVE; m <<= 1) T += shfl_xor_f64(T, m);
+          for (int m = LPI; m < RH_WAVE; m <<= 1) T += __shfl_xor(T, m, RH_WAVE);
           nrm2 = fma(T, T, nrm2);
         }
 #pragma unroll
-        for (int m = 1; m < LPI; m <<= 1) nrm2 += shfl_xor_f64(nrm2, m);
+        for (int m = 1; m < LPI; m <<= 1) nrm2 += __shfl_xor(nrm2, m, RH_WAVE);
         double Qt = Q;
         int nt = n;
 #pragma unroll
         for (int m = LPI; m < RH_WAVE; m <<= 1) {
-          Qt += shfl_xor_f64(Qt, m);
+          Qt += __shfl_xor(Qt, m, RH_WAVE);
           nt += __shfl_xor(nt, m, RH_WAVE);
         }
         const double value = nt >= 2 ? 1.0 - (nrm2 - Qt) / ((double)nt * (double)(nt - 1)) : (double)NAN;
@@ -949,24 +1009,6 @@ __global__ __launch_bounds__(RH_BLOCK) void ild_kernel(const IldArgs a) {
   }
 }
 
-// ONE workgroup of kSumParts x kListMaxCut threads: thread (part, e) adds the partials b = part, part + kSumParts, ... of
-// sum e in ascending b, then thread e adds the parts in ascending order: a fixed order
-__global__ __launch_bounds__(kSumParts * kListMaxCut) void list_final_kernel(const double* partial, int nblocks, int n_k,
-                                                                              double* sums) {
-  __shared__ double part_sum[kSumParts][kListMaxCut];
-  const int e = threadIdx.x % kListMaxCut, part = threadIdx.x / kListMaxCut;
-  double s = 0.0;
-  if (e < n_k)
-    for (int b = part; b < nblocks; b += kSumParts) s += partial[(int64_t)b * n_k + e];
-  part_sum[part][e] = s;
-  __syncthreads();
-  if (part == 0 && e < n_k) {
-    s = part_sum[0][e];
-    for (int q = 1; q < kSumParts; ++q) s += part_sum[q][e];
-    sums[e] = s;
-  }
-}
-
 struct NoveltyArgs {
   const int64_t* pred;
   int64_t ld;
@@ -985,10 +1027,7 @@ __global__ __launch_bounds__(RH_BLOCK) void novelty_kernel(const NoveltyArgs a) 
   __shared__ u64 wcnt[kListUsers][kListMaxCut];
   const int tid = threadIdx.x, lane = tid % RH_WAVE, w = tid / RH_WAVE;
   const int n_k = a.c.n_k;
-  if (lane < kListMaxCut) {
-    wsum[w][lane] = 0.0;
-    wcnt[w][lane] = 0;
-  }
+  wave_acc_zero(wsum, wcnt, w, lane);
   rank_wave_sync();
   for (int64_t u = (int64_t)blockIdx.x * kListUsers + w; u < a.M; u += (int64_t)gridDim.x * kListUsers) {
     double term[kListPer];
@@ -1014,26 +1053,15 @@ __global__ __launch_bounds__(RH_BLOCK) void novelty_kernel(const NoveltyArgs a) 
         s += in ? term[r] : 0.0;
         cnt += __popcll(__ballot(in));
       }
-#pragma unroll
-      for (int m = 1; m < RH_WAVE; m <<= 1) s += shfl_xor_f64(s, m);
+      s = wave_sum_f64(s);
       const double value = cnt > 0 ? s / (double)cnt : (double)NAN;
       if (lane == 0) {
-        if (cnt > 0) {
-          wsum[w][q] += value;
-          wcnt[w][q] += 1;
-        }
+        if (cnt > 0) wave_acc_add(wsum, wcnt, w, q, &value, 1);
         if (a.per_user != nullptr) a.per_user[u * n_k + q] = value;
       }
     }
   }
-  rank_wave_sync();
-  if (lane < n_k && wcnt[w][lane] != 0) atomicAdd(a.counts + lane, wcnt[w][lane]);
-  __syncthreads();
-  if (tid < n_k) {
-    double s = wsum[0][tid];
-    for (int ww = 1; ww < kListUsers; ++ww) s += wsum[ww][tid];
-    a.partial[(int64_t)blockIdx.x * n_k + tid] = s;
-  }
+  wave_acc_tail(wsum, wcnt, n_k, a.counts, a.partial);
 }
 
 // a workgroup takes kCovRows rows per trip and walks their first kmax columns as one flat range: coalesced for any K
@@ -1076,39 +1104,6 @@ __global__ __launch_bounds__(RH_BLOCK) void coverage_count_kernel(const int32_t*
   }
 }
 
-int list_grid(int M) {
-  const int64_t b = ((int64_t)M + kListUsers - 1) / kListUsers;
-  return (int)(b < 1 ? 1 : (b > kListMaxGrid ? kListMaxGrid : b));
-}
-
-int list_plan(const char* who, int M, int* users_per_workgroup, int* max_grid, int64_t* partial_doubles) {
-  RH_REQUIRE(users_per_workgroup && max_grid && partial_doubles, RH_E_BADARG, "%s: null pointer", who);
-  RH_REQUIRE(M >= 0, RH_E_BADARG, "%s: M=%d", who, M);
-  *users_per_workgroup = kListUsers;
-  *max_grid = kListMaxGrid;
-  *partial_doubles = (int64_t)list_grid(M) * kListMaxCut;
-  return 0;
-}
-
-// the checks the three list entries share; the cut-offs in the caller's order
-int list_check(const char* who, int64_t ld, int M, int K, const int* cutoffs, int n_k, ListCuts* c) {
-  RH_REQUIRE(K >= 1 && K <= kListMaxK, RH_E_UNSUPPORTED, "%s: K=%d unsupported (1 <= K <= %d)", who, K, kListMaxK);
-  RH_REQUIRE(n_k >= 1 && n_k <= kListMaxCut, RH_E_UNSUPPORTED, "%s: %d cut-offs (1 <= n_k <= %d)", who, n_k, kListMaxCut);
-  RH_REQUIRE(M >= 1 && ld >= K, RH_E_BADARG, "%s: M=%d ld=%lld K=%d", who, M, (long long)ld, K);
-  RH_REQUIRE(cutoffs != nullptr, RH_E_BADARG, "%s: null pointer", who);
-  c->n_k = n_k;
-  for (int q = 0; q < kListMaxCut; ++q) {
-    c->cut[q] = 0;
-    c->slot[q] = 0;
-  }
-  for (int q = 0; q < n_k; ++q) {
-    RH_REQUIRE(cutoffs[q] >= 1 && cutoffs[q] <= K, RH_E_BADARG, "%s: cut-off %d outside [1, K=%d]", who, cutoffs[q], K);
-    c->cut[q] = cutoffs[q];
-    c->slot[q] = q;
-  }
-  return 0;
-}
-
 template <int VEC, int LPI, int NCH>
 void ild_launch(const IldArgs& a, int grid, hipStream_t st) {
   hipLaunchKernelGGL((ild_kernel<VEC, LPI, NCH>), dim3(grid), dim3(RH_BLOCK), 0, st, a);
@@ -1117,7 +1112,7 @@ void ild_launch(const IldArgs& a, int grid, hipStream_t st) {
 }  // namespace
 
 extern "C" int rh_ild_plan(int M, int* users_per_workgroup, int* max_grid, int64_t* partial_doubles) {
-  return list_plan("rh_ild_plan", M, users_per_workgroup, max_grid, partial_doubles);
+  return list_plan("rh_ild_plan", M, kListMaxGrid, kListMaxCut, users_per_workgroup, max_grid, partial_doubles);
 }
 
 extern "C" int rh_ild(const int64_t* pred, int64_t ld, int M, int K, const float* table, int64_t table_stride, int64_t V,
@@ -1151,7 +1146,7 @@ extern "C" int rh_ild(const int64_t* pred, int64_t ld, int M, int K, const float
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   hipError_t e = hipMemsetAsync(counts, 0, (size_t)n_k * 8, st);
   RH_REQUIRE(e == hipSuccess, (int)e, "rh_ild: memset failed: %s", hipGetErrorString(e));
-  const int grid = list_grid(M);
+  const int grid = grid_for(M, kListUsers, kListMaxGrid);
   if (D % 4 == 0) {  // a float4 per lane: 4 to 64 lanes per item
     if (D <= 16) ild_launch<4, 4, 1>(a, grid, st);
     else if (D <= 32) ild_launch<4, 8, 1>(a, grid, st);
@@ -1169,7 +1164,7 @@ extern "C" int rh_ild(const int64_t* pred, int64_t ld, int M, int K, const float
     else if (D <= 512) ild_launch<1, 64, 8>(a, grid, st);
     else ild_launch<1, 64, 16>(a, grid, st);
   }
-  hipLaunchKernelGGL(list_final_kernel, dim3(1), dim3(kSumParts * kListMaxCut), 0, st, partial, grid, n_k, sums);
+  final_sum_launch<kListMaxCut>(partial, grid, n_k, sums, st);
   RH_LAUNCH_CHECK("rh_ild");
   return 0;
 }
@@ -1207,7 +1202,7 @@ extern "C" int rh_coverage(const int64_t* pred, int64_t ld, int M, int K, int64_
 }
 
 extern "C" int rh_novelty_plan(int M, int* users_per_workgroup, int* max_grid, int64_t* partial_doubles) {
-  return list_plan("rh_novelty_plan", M, users_per_workgroup, max_grid, partial_doubles);
+  return list_plan("rh_novelty_plan", M, kListMaxGrid, kListMaxCut, users_per_workgroup, max_grid, partial_doubles);
 }
 
 extern "C" int rh_novelty(const int64_t* pred, int64_t ld, int M, int K, const void* pop, int pop_dtype, int64_t V,
@@ -1231,9 +1226,9 @@ extern "C" int rh_novelty(const int64_t* pred, int64_t ld, int M, int K, const v
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   hipError_t e = hipMemsetAsync(counts, 0, (size_t)n_k * 8, st);
   RH_REQUIRE(e == hipSuccess, (int)e, "rh_novelty: memset failed: %s", hipGetErrorString(e));
-  const int grid = list_grid(M);
+  const int grid = grid_for(M, kListUsers, kListMaxGrid);
   hipLaunchKernelGGL(novelty_kernel, dim3(grid), dim3(RH_BLOCK), 0, st, a);
-  hipLaunchKernelGGL(list_final_kernel, dim3(1), dim3(kSumParts * kListMaxCut), 0, st, partial, grid, n_k, sums);
+  final_sum_launch<kListMaxCut>(partial, grid, n_k, sums, st);
   RH_LAUNCH_CHECK("rh_novelty");
   return 0;
 }

@@ -4678,19 +4678,10 @@ def rank_metrics(pred_ids, truth, cutoffs, per_user=False):
     id lists, ``cutoffs`` at most 8 ints in [1, K].  -> dict: ``hits`` (n_k,) int64, ``gts`` (1,) int64, ``sums`` (n_k, 4)
     float64 = mrr, recall, precision, ndcg summed over users, ``per_user`` (M, n_k, 5) float64 = hit, mrr, recall,
     precision, ndcg or None.  No autograd; current stream."""
-    require_hip(pred_ids)
-    if pred_ids.dim() != 2 or pred_ids.dtype != torch.int64:
-        raise ValueError("torch_rechub_amd: rank_metrics takes an (M, K) int64 id tensor")
-    M, K = (int(v) for v in pred_ids.shape)
-    if M == 0 or K == 0:
-        raise ValueError("torch_rechub_amd: rank_metrics of an empty input")
-    if K > _RANK_MAX_K:
-        from .models.matching._listwise import no_kernel
-        raise no_kernel(f"list metrics over K={K} recommendations (1 <= K <= {_RANK_MAX_K})")
     cutoffs = [int(k) for k in cutoffs]
-    if not 1 <= len(cutoffs) <= _RANK_MAX_CUTOFFS or any(not 1 <= k <= K for k in cutoffs):
-        raise ValueError(f"torch_rechub_amd: rank_metrics takes 1 to {_RANK_MAX_CUTOFFS} cut-offs within [1, K={K}], got "
-                         f"{cutoffs}")
+    if len(cutoffs) > _RANK_MAX_CUTOFFS:  # the newer list metrics answer this with "no HIP kernel"; here it stays a ValueError
+        raise ValueError(f"torch_rechub_amd: rank_metrics takes 1 to {_RANK_MAX_CUTOFFS} cut-offs, got {cutoffs}")
+    pred_ids, ld, M, K, cuts, n_k = _list_inputs("rank_metrics", pred_ids, cutoffs)
     if isinstance(truth, (tuple, list)) and len(truth) == 2 and all(torch.is_tensor(t) for t in truth):
         off, ids = truth
         require_hip(off, ids)
@@ -4703,16 +4694,10 @@ def rank_metrics(pred_ids, truth, cutoffs, per_user=False):
         off, ids = pack_truth(truth, pred_ids.device)
     if off.numel() != M + 1:
         raise ValueError(f"torch_rechub_amd: rank_metrics: {off.numel()} truth offsets for {M} users (M + 1 expected)")
-    pred_ids = pred_ids.detach()
-    if pred_ids.stride(1) != 1 or (M > 1 and pred_ids.stride(0) < K):
-        pred_ids = pred_ids.contiguous()
-    ld = int(pred_ids.stride(0)) if M > 1 else K
     dev = pred_ids.device
     tables = _rank_tables.get((K, dev))
     if tables is None:
         tables = _rank_tables[(K, dev)] = tuple(torch.from_numpy(t).to(dev) for t in rank_gain_tables(K))
-    n_k = len(cutoffs)
-    cuts = (ctypes.c_int * n_k)(*cutoffs)
     partial = torch.empty((rank_metrics_plan(M)[3],), dtype=torch.float64, device=dev)
     hits = torch.empty((n_k,), dtype=torch.int64, device=dev)
     gts = torch.empty((1,), dtype=torch.int64, device=dev)
