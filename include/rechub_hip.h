@@ -1243,6 +1243,30 @@ int rh_add_rms_norm_fwd(const float* h, const float* delta, const float* w, floa
 int rh_add_rms_norm_bwd(const float* h_new, const float* w, const float* rstd, const float* g_y, const float* g_res, int M,
                         int D, float* g_h, float* part, void* stream);
 
+/* ---- TIGER: one step of the constrained beam search over a flat trie (csrc/beam.hip) --------------------------------
+ * The constraint is a trie in CSR form: node 0 is the root, the edges of node n are [child_off[n], child_off[n + 1]) of
+ * child_tok (ascending and distinct inside a node) and child_node; child_off (n_nodes + 1,), all int32.
+ * logits (B K, V) fp32 with row stride ld >= V: row b K + k is beam k of query b.  running (B, K) fp32 the beams' scores,
+ * node (B, K) int32 their trie nodes; a node outside [0, n_nodes) (-1) is a dead beam.
+ * Per query: lse_k = max + log(sum exp(x - max)) over the V values of beam k's row, fp32, accurate expf / logf; it
+ * depends on the row's values alone (not on b, k, B or ld).  The candidates are the edges (k, e) of every live beam's
+ * node, score = running[b, k] + ((logits[row, tok_e] - max) - log(sum)) in fp32: the log-softmax runs over the whole
+ * vocabulary and is not renormalised over the allowed tokens.  Slot j of running_out, parent_out, tok_out, node_out (B, K)
+ * gets score, beam, token and child node of the j-th best candidate under (score descending, beam ascending, token
+ * ascending).  A candidate whose score is -inf (an allowed token with a -inf logit) is never listed, as the dense
+ * formulation cannot tell it from a masked token; a token outside [0, V) is no candidate.  With fewer than K candidates
+ * above -inf the unused slots get (-inf, -1, -1, -1) and short_out (B,) int32 = 1, else 0.  Every output element is
+ * written on every call.  A dead beam and a node without children add nothing and index no edge array; a dead beam's row
+ * is not read.  No atomics, no workspace, one launch: two runs give the same bits.
+ * Outside the contract: a row with a NaN or a +inf, or without a finite value (the row of a dead beam may hold anything).
+ * 1 <= K <= 64, 1 <= V <= 2^25, n_nodes >= 1, B K < 2^31; beyond that, on a null pointer, on ld < V or on an output that
+ * overlaps logits, running or node: RH_E_BADARG before any launch.  B = 0 returns at once.
+ * replaces: per decoding step of generate (models/generative/tiger.py), the prefix_allowed_tokens_fn calls of
+ *           Trie.get (utils/data.py:798-886), the (B K, V) mask, log_softmax and torch.topk over (B, K V). */
+int rh_beam_step(const float* logits, int64_t ld, const float* running, const int32_t* node, const int32_t* child_off,
+                 const int32_t* child_tok, const int32_t* child_node, int n_nodes, int B, int K, int V, float* running_out,
+                 int32_t* parent_out, int32_t* tok_out, int32_t* node_out, int32_t* short_out, void* stream);
+
 /* Compressed Interaction Network, one layer (csrc/cin.hip): a GEMM over rows m = (b, d) and channels c = f Hp + h whose A
  * operand x0[b, f, d] h[b, h, d] is formed in registers from two LDS tiles; the (B, F Hp, D) product never exists in HBM.
  * fp32, the 64 x 64 tile on v_mfma_f32_32x32x2_f32, K = F Hp walked in chunks of 64 (an odd K ends in a zero-filled step).

@@ -253,7 +253,7 @@ class TIGERModel(nn.Module):
 
     @torch.no_grad()
     def generate(self, input_ids, attention_mask=None, max_new_tokens=10, num_beams=1, num_return_sequences=1,
-                 prefix_allowed_tokens_fn=None):
+                 prefix_allowed_tokens_fn=None, constraint=None):
         """Constrained beam search as the reference's examples run it (``early_stopping=True``, length penalty 1): the
         encoder runs once, the decoder is recomputed on the growing prefix; tokens outside
         ``prefix_allowed_tokens_fn(batch_id, prefix)`` get -inf on their log-probabilities (which are not renormalised);
@@ -261,12 +261,22 @@ class TIGERModel(nn.Module):
         num_return_sequences, 1 + n) int64, "sequences_scores": (B * num_return_sequences,)}``, per query by descending score.
 
         Supported: every candidate of the constraint has the same length (the semantic-ID case: all beams end at the same
-        step) and there are at least ``num_beams`` candidates; anything else raises."""
+        step) and there are at least ``num_beams`` candidates; anything else raises.
+
+        ``constraint``: the candidates as a ``utils.data.DeviceTrie`` (each starting with ``decoder_start_token_id`` and
+        ending with EOS) instead of the callback.  The search then stays on the device -- one ``ops.beam_step`` per step
+        over the children of the beams' trie nodes, no callback, no (B K, V) mask, one host read after the last step -- and
+        the result also holds ``"item_index"``: (B, num_return_sequences) int64, the candidates' indices in the trie's
+        order, which ``basic.metric.topk_metrics`` takes as it is."""
         cfg = self.config
         K = int(num_beams)
         R = int(num_return_sequences)
         if not 1 <= R <= K:
             raise ValueError(f"generate: num_return_sequences={R} must be in [1, num_beams={K}]")
+        if constraint is not None:
+            if prefix_allowed_tokens_fn is not None:
+                raise ValueError("generate: constraint and prefix_allowed_tokens_fn are two forms of one thing: give one")
+            return self._generate_on_trie(input_ids, attention_mask, int(max_new_tokens), K, R, constraint)
         B = int(input_ids.shape[0])
         dev = input_ids.device
         V = cfg.vocab_size
@@ -320,5 +330,57 @@ class TIGERModel(nn.Module):
             scores = running / float(done)
             seqs = seqs.view(B, K, -1)[:, :R].reshape(B * R, -1)
             return {"sequences": seqs, "sequences_scores": scores[:, :R].reshape(-1)}
+        finally:
+            self.train(was_training)
+
+    def _generate_on_trie(self, input_ids, attention_mask, max_new_tokens, K, R, trie):
+        """``generate`` with the candidates as a DeviceTrie: decode, ``ops.beam_step``, reorder -- all on the device.
+
+        Nothing is read back inside the loop, so a query that runs short of candidates is noticed only after the last
+        step: until then its unused slots (parent -1, token -1) stay dead in the kernel, and the decoder is fed row 0 of
+        the query and token 0 for them on every remaining step.  That work is wasted, never returned: the one host read
+        behind the loop raises for such a query."""
+        cfg = self.config
+        steps = trie.depth - 1  # a candidate is the start token, the codes and EOS
+        if trie.find([cfg.decoder_start_token_id]) < 0 or steps < 1:
+            raise ValueError(f"generate: the constraint's candidates do not start with decoder_start_token_id="
+                             f"{cfg.decoder_start_token_id} followed by at least one token")
+        if steps > max_new_tokens:
+            raise ValueError(f"generate: no candidate ended within max_new_tokens={max_new_tokens}: the constraint's "
+                             f"candidates take {steps} steps")
+        if trie.last_tokens_equal != cfg.eos_token_id:
+            raise ValueError(f"generate: the constraint's candidates do not all end with eos_token_id={cfg.eos_token_id}")
+        if trie.max_token >= cfg.vocab_size:
+            raise ValueError(f"generate: the constraint holds token {trie.max_token}, outside vocab_size={cfg.vocab_size}")
+        B = int(input_ids.shape[0])
+        dev = input_ids.device
+        was_training = self.training
+        self.eval()
+        try:
+            hidden = self.encode(input_ids, attention_mask).repeat_interleave(K, 0)
+            mask = None if attention_mask is None else attention_mask.repeat_interleave(K, 0)
+            seqs = torch.full((B * K, 1), cfg.decoder_start_token_id, dtype=torch.int64, device=dev)
+            node = torch.full((B, K), trie.find([cfg.decoder_start_token_id]), dtype=torch.int32, device=dev)
+            running = torch.zeros((B, K), dtype=torch.float32, device=dev)
+            running[:, 1:] = -1e9  # as the callback path starts
+            short = torch.zeros((B,), dtype=torch.int32, device=dev)
+            first = torch.arange(B, device=dev).view(B, 1) * K
+            for _ in range(steps):
+                logits = self.decode(seqs, hidden, mask)[:, -1, :].float()
+                running, parent, tok, node, short_now = ops.beam_step(logits, running, node, trie)
+                short |= short_now
+                # (an unused slot holds -1, -1: it stays dead in the kernel, the decoder is given row 0 / token 0 for it)
+                rows = (first + parent.clamp_min(0)).view(-1)
+                seqs = torch.cat((seqs[rows], tok.clamp_min(0).view(-1, 1).to(torch.int64)), 1)
+            bad = torch.stack((short.any(), (running < -1e8).any())).tolist()  # the search's one host read
+            if bad[0]:
+                raise ValueError(f"generate: fewer than num_beams={K} continuations are allowed: the constraint has "
+                                 "fewer candidates than beams, which is not supported")
+            if bad[1]:
+                raise ValueError(f"generate: the constraint has fewer than num_beams={K} candidates, which is not supported")
+            scores = running / float(steps)
+            items = trie.leaf_item[node[:, :R].reshape(-1).to(torch.int64)].view(B, R).to(torch.int64)
+            seqs = seqs.view(B, K, -1)[:, :R].reshape(B * R, -1)
+            return {"sequences": seqs, "sequences_scores": scores[:, :R].reshape(-1), "item_index": items}
         finally:
             self.train(was_training)

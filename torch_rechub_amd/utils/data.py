@@ -549,3 +549,88 @@ class Trie(object):
 
     def __getitem__(self, value):
         return self.get(value)
+
+    def to_device(self, device):
+        """This trie as a ``DeviceTrie`` on ``device`` (sequences in iteration order)."""
+        return DeviceTrie(self, device)
+
+
+class DeviceTrie(object):
+    """A trie of equal-length token sequences as flat arrays on ``device``: the constraint of
+    ``TIGERModel.generate(constraint=...)`` and ``ops.beam_step``.  Built once on the host from a list of sequences or a
+    ``Trie`` (whose iteration order numbers the sequences).
+
+    CSR form, int32, node 0 the root, nodes numbered level by level: the edges of node ``n`` are
+    ``child_tok[child_off[n]:child_off[n + 1]]`` (ascending) leading to ``child_node[...]``; ``leaf_item[n]`` is the index
+    of the sequence that ends at ``n``, -1 for an inner node.  ``depth`` = tokens per sequence, ``max_token``, ``n_items``,
+    ``n_nodes``, ``n_edges``; ``last_tokens_equal`` = the last token if all sequences share it (TIGER's EOS), else None.
+
+    ValueError for: sequences that differ in length, a ``Trie`` with an ``append_trie``, duplicates, an empty set, negative
+    tokens."""
+
+    def __init__(self, sequences, device="cpu"):
+        if isinstance(sequences, Trie):
+            if sequences.append_trie is not None:
+                raise ValueError("DeviceTrie: a Trie with an append_trie has no flat form")
+            declared = len(sequences)
+            sequences = list(sequences)
+            if sequences == [[]]:
+                sequences = []
+            if sequences and declared != len(sequences):
+                raise ValueError(f"DeviceTrie: the Trie counts {declared} sequences and holds {len(sequences)}: duplicate "
+                                 "sequences, or sequences that differ in length (one a prefix of another)")
+        else:
+            sequences = [list(s) for s in sequences]
+        if not sequences:
+            raise ValueError("DeviceTrie: an empty set of sequences")
+        depth = len(sequences[0])
+        if depth == 0 or any(len(s) != depth for s in sequences):
+            raise ValueError("DeviceTrie: the sequences differ in length (or are empty): one length for all is supported")
+        seqs = np.asarray(sequences, dtype=np.int64)
+        if int(seqs.min()) < 0:
+            raise ValueError("DeviceTrie: negative tokens")
+        n = int(seqs.shape[0])
+        self.depth, self.n_items, self.max_token = depth, n, int(seqs.max())
+        if self.max_token >= 2**31 - 1:
+            raise ValueError("DeviceTrie: tokens must fit int32")
+        width = self.max_token + 1
+        cur = np.zeros(n, dtype=np.int64)  # the node of every sequence's prefix
+        parents, toks, n_nodes = [], [], 1
+        for level in range(depth):
+            uniq, inv = np.unique(cur * width + seqs[:, level], return_inverse=True)  # by (parent node, token)
+            parents.append(uniq // width)
+            toks.append(uniq % width)
+            cur = n_nodes + inv.reshape(-1)
+            n_nodes += int(uniq.size)
+        if np.unique(cur).size != n:
+            raise ValueError("DeviceTrie: duplicate sequences")
+        parent = np.concatenate(parents)  # ascending: the levels' nodes are numbered in this very order
+        if n_nodes >= 2**31 - 1:
+            raise ValueError("DeviceTrie: more than 2^31 nodes")
+        self.n_nodes, self.n_edges = n_nodes, int(parent.size)
+        off = np.zeros(n_nodes + 1, dtype=np.int64)
+        np.cumsum(np.bincount(parent, minlength=n_nodes), out=off[1:])
+        leaf = np.full(n_nodes, -1, dtype=np.int64)
+        leaf[cur] = np.arange(n)
+        last = seqs[:, -1]
+        self.last_tokens_equal = int(last[0]) if bool((last == last[0]).all()) else None
+        self._host = (off.astype(np.int32), np.concatenate(toks).astype(np.int32),
+                      np.arange(1, n_nodes, dtype=np.int32), leaf.astype(np.int32))
+        self.device = torch.device(device)
+        self.child_off, self.child_tok, self.child_node, self.leaf_item = (torch.from_numpy(a).to(self.device)
+                                                                            for a in self._host)
+
+    def find(self, prefix):
+        """The node ``prefix`` leads to from the root, or -1 (a host lookup)."""
+        off, tok, child, _ = self._host
+        node = 0
+        for t in prefix:
+            lo, hi = int(off[node]), int(off[node + 1])
+            e = lo + int(np.searchsorted(tok[lo:hi], int(t)))
+            if e >= hi or int(tok[e]) != int(t):
+                return -1
+            node = int(child[e])
+        return node
+
+    def __len__(self):
+        return self.n_items
