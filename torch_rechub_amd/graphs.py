@@ -8,6 +8,9 @@ launch at a given point of the step calls ``cut(fn)`` there while the capture is
 closed, ``fn`` is remembered, and a new segment begins.  ``replay()`` launches segment, fn, segment, fn ...
 
 Only one SegmentedGraph can capture at a time; ``active()`` returns it (or None).
+
+``StepGraphs`` is the simple case beside it: a step with nothing eager inside, warmed up, captured as one plain graph per
+batch shape and replayed.
 """
 import gc
 
@@ -31,7 +34,8 @@ def role_stream(role, device=None):
     asynchronous RCCL all-reduces 32 ``torch.cuda.Stream()`` calls earlier (tools/probe/stream_trace.py); one extra pool
     stream drawn anywhere in between -- any change of that distance -- and the same sequence runs through
     (``PROBE_SKEW`` of the probe).  With one stream per role no hipStream ever changes its role, and a
-    long-lived process uses a handful of streams however many trainers it builds."""
+    long-lived process uses a handful of streams however many trainers it builds.  "warmup" and "capture" serve CTRTrainer (its
+    warm-up steps; ``SegmentedGraph.capture``) and, through ``StepGraphs``, the RQ-VAE Trainer."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     if dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
@@ -132,3 +136,50 @@ class SegmentedGraph(object):
 
     def pool(self):
         return self._pool
+
+
+class StepGraphs(object):
+    """A whole train step as one plain hipGraph per batch shape (the RQ-VAE Trainer): ``self(*inputs)`` runs
+    ``eager_step(*inputs)`` on the "warmup" role stream for the first ``warmup`` calls of a key (the inputs' shapes and dtypes),
+    captures ``body`` on static copies of the inputs at the next call, and from that call on copies the inputs in, replays and
+    returns clones of the static outputs.  Both callables return a tensor or a tuple of tensors.  ``before_capture()`` runs
+    first at the capturing call: it may raise to refuse the capture, and it is where the caller drops its gradients
+    (``zero_grad(set_to_none=True)``: the captured backward allocates them from the graph's pool).  An entry is stored only
+    when its capture has come through, so a call that raised is tried again by the next one.  A plain capture, not a
+    SegmentedGraph: ``active()`` stays None, which is how optim.py tells the two apart."""
+
+    def __init__(self, device, warmup, eager_step, body, before_capture=None):
+        self.device, self.warmup = torch.device(device), int(warmup)
+        self.eager_step, self.body, self.before_capture = eager_step, body, before_capture
+        self.graphs = {}  # key -> (CUDAGraph, static inputs, static outputs)
+        self._eager_steps = {}
+
+    def __call__(self, *inputs):
+        key = tuple((tuple(t.shape), t.dtype) for t in inputs)
+        entry = self.graphs.get(key)
+        if entry is None:
+            n = self._eager_steps.get(key, 0)
+            if n < self.warmup:
+                cur, side = torch.cuda.current_stream(self.device), role_stream("warmup", self.device)
+                side.wait_stream(cur)
+                with torch.cuda.stream(side):
+                    out = self.eager_step(*inputs)
+                cur.wait_stream(side)
+                self._eager_steps[key] = n + 1
+                return out
+            entry = self.graphs[key] = self._capture(inputs)
+        graph, static_in, static_out = entry
+        for s, t in zip(static_in, inputs):
+            s.copy_(t)
+        graph.replay()
+        return static_out.clone() if torch.is_tensor(static_out) else tuple(o.clone() for o in static_out)
+
+    def _capture(self, inputs):
+        if self.before_capture is not None:
+            self.before_capture()
+        gc.collect()  # (a dead trainer and its StepGraphs hold each other, and the graphs' memory with them, until collected)
+        static_in = tuple(t.clone() for t in inputs)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=role_stream("capture", self.device), capture_error_mode="thread_local"):
+            static_out = self.body(*static_in)
+        return graph, static_in, static_out

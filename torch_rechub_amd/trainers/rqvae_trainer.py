@@ -2,10 +2,11 @@
 collision rate as the evaluation metric, the reference's two checkpoints and logger calls.  Like the reference,
 ``trainers/__init__`` does not export it.
 
-``use_graph=True`` captures the whole step (forward, loss, backward, optimizer) as one hipGraph per batch shape after
-``GRAPH_WARMUP`` eager steps, as SeqTrainer does; later batches of that shape are copied into the graph's input buffer
-and replayed.  A Sinkhorn level runs host-dependent code and is refused at the first step; k-means initialisation happens in
-the eager warm-up steps (the first training forward), and capture is refused only if a codebook still waits for it then.  The optimizer is built with ``capturable=True`` when it takes that option.
+``use_graph=True`` hands the whole step (forward, loss, backward, optimizer) to ``graphs.StepGraphs``: one hipGraph per batch
+shape after ``GRAPH_WARMUP`` eager steps, on the process's one warm-up and one capture stream; later batches of that shape are
+copied into the graph's input buffer and replayed.  A Sinkhorn level runs host-dependent code and is refused at the first
+step; k-means initialisation happens in the eager warm-up steps (the first training forward), and capture is refused only if
+a codebook still waits for it then.  The optimizer is built with ``capturable=True`` when it takes that option.
 """
 import inspect
 import os
@@ -14,6 +15,8 @@ from time import time
 import numpy as np
 import torch
 from tqdm import tqdm
+
+from .. import graphs
 
 
 class Trainer(object):
@@ -43,8 +46,9 @@ class Trainer(object):
         self.best_collision_rate = np.inf
         self.best_loss_ckpt = "best_loss_model.pth"
         self.best_collision_ckpt = "best_collision_model.pth"
-        self._graphs = {}  # batch shape -> (graph, static batch, loss, reconstruction loss)
-        self._eager_steps = {}
+        self._step_graphs = graphs.StepGraphs(self.device, self.GRAPH_WARMUP, self._warmup_step, self._step_body,
+                                              before_capture=self._before_capture)
+        self._graphs = self._step_graphs.graphs  # batch shape -> (graph, static batch, (loss, reconstruction loss))
 
     def _check_nan(self, loss):
         if torch.isnan(loss):
@@ -73,51 +77,28 @@ class Trainer(object):
             raise RuntimeError("torch_rechub_amd: use_graph=True cannot capture a step with a Sinkhorn level (sk_epsilon > 0 at "
                                f"levels {levels}): its assignment runs outside the fused quantizer")
 
-    def _check_capturable(self):
+    def _warmup_step(self, data):
+        self._check_sinkhorn()  # (known up front; the codebooks are looked at when the warm-up is over, in _before_capture)
+        return self._eager_step(data)
+
+    def _before_capture(self):
         self._check_sinkhorn()
         if not all(vq.initted for vq in self.model.rq.vq_layers):
             raise RuntimeError("torch_rechub_amd: use_graph=True cannot capture while a codebook waits for its k-means "
                                "initialisation (a training-mode forward runs it on the host; the eager warm-up steps did not: "
                                "is the model in eval mode?)")
-
-    def _capture(self, key, data):
-        self._check_capturable()
-        s_data = data.clone()
         self.optimizer.zero_grad(set_to_none=True)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            loss, loss_recon = self._forward_loss(s_data)
-            loss.backward()
-            self.optimizer.step()
-            s_loss, s_recon = loss.detach(), loss_recon.detach()
-        entry = self._graphs[key] = (graph, s_data, s_loss, s_recon)
-        return entry
+
+    def _step_body(self, data):
+        """What a capture records: the step without ``zero_grad`` and without the NaN check (a host read)."""
+        loss, loss_recon = self._forward_loss(data)
+        loss.backward()
+        self.optimizer.step()
+        return loss.detach(), loss_recon.detach()
 
     def train_step(self, data):
         """One forward / backward / optimizer step on a device batch; (loss, reconstruction loss) as device tensors."""
-        if not self.use_graph:
-            return self._eager_step(data)
-        key = (tuple(data.shape), data.dtype)
-        entry = self._graphs.get(key)
-        if entry is None:
-            self._check_sinkhorn()  # (known up front; the codebooks are looked at when the warm-up is over, in _capture)
-            n = self._eager_steps.get(key, 0)
-            cur = torch.cuda.current_stream(self.device)
-            side = torch.cuda.Stream(self.device)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                if n < self.GRAPH_WARMUP:
-                    losses = self._eager_step(data)
-                else:
-                    entry = self._capture(key, data)
-            cur.wait_stream(side)
-            if entry is None:
-                self._eager_steps[key] = n + 1
-                return losses
-        graph, s_data, s_loss, s_recon = entry
-        s_data.copy_(data)
-        graph.replay()
-        return s_loss.clone(), s_recon.clone()
+        return (self._step_graphs if self.use_graph else self._eager_step)(data)
 
     def train_one_epoch(self, data_loader):
         """(sum of the total loss, sum of the reconstruction loss) over the epoch."""
