@@ -502,6 +502,9 @@ int rh_bce_bwd(const float* y, const float* t, const float* g_loss, int64_t B, f
  * reads saved_ctr and advances nothing.
  */
 int rh_bn_act_nchunks(int B);
+/* *nblocks (a HOST int) = the workgroups of the apply launch of the three-launch path over n = B * C elements, either
+ * direction, and of the eval-mode forward (1024 elements each per trip) */
+int rh_bn_apply_nblocks(int64_t n, int* nblocks);
 int rh_bn_relu_dropout_fwd(const float* h, int B, int C, const float* gamma, const float* beta, float* running_mean,
                            float* running_var, int64_t* num_batches_tracked, float momentum, float eps, float p_drop,
                            int training, int64_t* rng, int64_t* saved_ctr, float* partial, int partial_rows, float* stat,

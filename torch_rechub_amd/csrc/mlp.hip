@@ -545,6 +545,12 @@ static int big_chunk_rows(int B) {
 
 extern "C" int rh_bn_act_nchunks(int B) { return (B + kRowsPerChunk - 1) / kRowsPerChunk; }  // upper bound (workspace size)
 
+extern "C" int rh_bn_apply_nblocks(int64_t n, int* nblocks) {
+  RH_REQUIRE(nblocks != nullptr && n >= 0, RH_E_BADARG, "rh_bn_apply_nblocks: bad arguments");
+  *nblocks = n < 1 ? 0 : (int)apply_grid(n);
+  return 0;
+}
+
 static int bn_fwd_impl(const float* h, int B, int C, const float* gamma, const float* beta, float* running_mean,
                        float* running_var, int64_t* num_batches_tracked, float momentum, float eps, float p_drop,
                        int training, int64_t* rng, int64_t* saved_ctr, float* partial, int partial_rows, float* stat,
