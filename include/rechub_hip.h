@@ -710,6 +710,15 @@ int rh_adam_lazy_step_mode_idx(const int64_t* ldesc, int T, const int64_t* h_row
                                int sweep_mode, void* stream);
 int rh_adam_lazy_sweep(const int64_t* ldesc, int T, const int64_t* h_rows, const int64_t* h_window, int D,
                        const double* hyper, const float* ring, int ring_size, int mode, int64_t t_value, void* stream);
+/* The launch plan of a window sweep, from the function rh_adam_lazy_sweep and the merged rh_adam_lazy_step* launches take their
+ * grid from (host arrays and HOST outputs, nothing is launched).  touch_blocks = touched-rows workgroups of a merged launch
+ * (64-sample chunks x fields; mode RH_SWEEP_WINDOW or RH_SWEEP_DENSE_TABLES, t_value < 0), 0 = a plain rh_adam_lazy_sweep.
+ * *total_vblocks = work units (256 / (D / 4) rows each; twice that when *wide), *grid = sweep workgroups after the cap
+ * (RH_TUNE_SWEEP_GRID, RH_TUNE_DEFERRED_GRID for a sweep by value; a merged launch adds touch_blocks to them; 0 = no launch),
+ * *touch_period = every how-many-th workgroup of a merged launch is a touched-rows one, *wide = the two-float4-per-lane kernel
+ * of the deferred sweep is taken. */
+int rh_adam_lazy_sweep_plan(int T, const int64_t* h_rows, const int64_t* h_window, int D, int mode, int64_t t_value,
+                            int touch_blocks, int64_t* total_vblocks, int* grid, int* touch_period, int* wide);
 
 /* ---------------------------------------------------------------------------------------------
  * Device-resident minibatch assembly (columnar dataset already in HBM)

@@ -1,6 +1,6 @@
 """The end-of-step launch of the step-ahead form (rh_adam_lazy_step_ahead_wgrad: refresh of the next batch's rows, touched-rows
 step, lookahead, batch assembly, dense tables, weight-gradient rider) across the shapes at which its parts take different paths:
-batches of less than one workgroup pass / a partial last chunk / several chunks, embed_dim 4 .. 32 (1 .. 8 lanes per row),
+batches of less than one workgroup pass / a partial last chunk / several chunks, embed_dim 4 .. 128 (1 .. 32 lanes per row),
 tables from a thousand to 150 000 rows, duplicated samples, a padding row, and lookahead workgroups that collect their hits over
 several rounds of samples (carried over / flushed early / two workgroups per field).  Small twins of
 test_gpu_models.py::test_full_size_graph_step_with_long_sweeps_equals_dense_adam_bitwise: a blocked-lazy trainer (lazy_k = 8,
@@ -96,6 +96,8 @@ CASES = [  # (B, embed_dim, layout)
     (200, 4, "plain"),    # one lane per row
     (200, 8, "plain"),
     (200, 32, "plain"),   # eight lanes per row
+    (200, 64, "plain"),   # sixteen lanes per row: four rows per wavefront, 16 rows per pass of the refresh's re-deal
+    (200, 128, "plain"),  # thirty-two lanes per row: two rows per wavefront, 8 rows per pass
     (200, 16, "dup"),     # two lookups race for one claim; a row wanted by the touched-rows step AND the refresh of one launch
     (200, 16, "pad"),     # the padding-row pass
     (600, 16, "carry"),   # lookahead: 1200 samples = two rounds, the first round's hits carried into the second

@@ -977,71 +977,96 @@ __global__ __launch_bounds__(RH_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))
   step_ahead_body<LPR>(a, parts, bx, nrest);
 }
 
+// What a window-sweep launch looks like, worked out on the host: launch_sweep / launch_sweep_wide take their grid from here
+// and rh_adam_lazy_sweep_plan answers with the same figures, so a test that asks "is this shape past the cap?" asks the launch.
+// touch_blocks > 0: the merged launch (touched-rows workgroups interleaved with the sweep's); 0: a plain sweep.
+struct SweepPlan {
+  int64_t total_vblocks;  // work units: RH_BLOCK / (D / 4) rows each, twice that under the wide kernel
+  int64_t grid;           // sweep workgroups after the cap (the merged launch adds touch_blocks to them); 0 = nothing to launch
+  int touch_period;
+  bool wide;
+};
+
+// the deferred window sweep of the lazy tables (by value, no claims) takes two float4 per lane from embed_dim 8 on
+static bool sweep_takes_wide(int D, int mode, int64_t t_value, int touch_blocks) {
+  return D >= 8 && mode == RH_SWEEP_LAZY_TABLES && t_value >= 0 && touch_blocks == 0;
+}
+
+// vb_prefix (nullable): T + 1 entries, the work units in front of every table
+static SweepPlan sweep_plan(int T, const int64_t* h_rows, const int64_t* h_window, int D, int mode, int64_t t_value,
+                            int touch_blocks, int64_t* vb_prefix) {
+  SweepPlan pl;
+  pl.wide = sweep_takes_wide(D, mode, t_value, touch_blocks);
+  const int64_t rpb = RH_BLOCK / (D / 4) * (pl.wide ? 2 : 1);
+  int64_t total = 0;
+  if (vb_prefix != nullptr) vb_prefix[0] = 0;
+  for (int t = 0; t < T; ++t) {
+    int64_t w = mode == RH_SWEEP_FLUSH ? h_rows[t] : (h_window[t] < h_rows[t] ? h_window[t] : h_rows[t]);
+    const bool dense_table = h_window[t] >= h_rows[t];  // K_t == 1
+    if ((mode == RH_SWEEP_LAZY_TABLES && dense_table) || (mode == RH_SWEEP_DENSE_TABLES && !dense_table)) w = 0;
+    total += (w + rpb - 1) / rpb;
+    if (vb_prefix != nullptr) vb_prefix[t + 1] = total;
+  }
+  pl.total_vblocks = total;
+  pl.touch_period = 1;
+  // persistent-style grid: each workgroup walks several virtual blocks so the prefetch has something to overlap
+  int64_t grid = total;
+  const int64_t cap = (t_value >= 0 && touch_blocks == 0 && g_deferred_grid > 0) ? g_deferred_grid
+                      : (g_sweep_grid > 0 ? g_sweep_grid : 256 * 32);
+  if (grid > cap) grid = cap;
+  if (touch_blocks > 0) {
+    if (grid < 1) grid = 1;
+    // every period-th workgroup is a touched one: (touch_blocks - 1) * period < grid + touch_blocks, so all of them exist;
+    // fewer sweep than touched workgroups (small tables): period 1 = touched first
+    int64_t period = (grid + touch_blocks) / touch_blocks;
+    if (period > 1 && period % 8 == 0) period -= 1;  // block id mod 8 = XCD: keep the touched workgroups on all of them
+    pl.touch_period = (int)period;
+  }
+  pl.grid = grid;
+  return pl;
+}
+
+static SweepPlan sweep_plan_into(LazySweepArgs& a, const int64_t* h_rows, const int64_t* h_window, int D, int mode) {
+  const SweepPlan pl = sweep_plan(a.T, h_rows, h_window, D, mode, a.t_value, a.touch_blocks, a.vb_prefix);
+  for (int t = a.T + 1; t <= kMaxTensors; ++t) a.vb_prefix[t] = a.vb_prefix[a.T];
+  a.total_vblocks = pl.total_vblocks;
+  a.touch_period = pl.touch_period;
+  return pl;
+}
+
 // the deferred window sweep of the lazy tables, VPL float4 per lane (lazy_sweep_wide_body)
 template <int LPR, int VPL>
 int launch_sweep_wide(LazySweepArgs& a, const int64_t* h_rows, const int64_t* h_window, hipStream_t s) {
-  constexpr int RPB = RH_BLOCK / LPR;
-  a.vb_prefix[0] = 0;
-  for (int t = 0; t < a.T; ++t) {
-    int64_t w = h_window[t] < h_rows[t] ? h_window[t] : h_rows[t];
-    if (h_window[t] >= h_rows[t]) w = 0;  // K_t == 1: a dense table, not this launch's
-    a.vb_prefix[t + 1] = a.vb_prefix[t] + (w + RPB - 1) / RPB;
-  }
-  for (int t = a.T + 1; t <= kMaxTensors; ++t) a.vb_prefix[t] = a.vb_prefix[a.T];
-  a.total_vblocks = a.vb_prefix[a.T];
   a.touch_blocks = a.touch_chunks = 0;
-  a.touch_period = 1;
-  if (a.total_vblocks == 0) return 0;
-  int64_t grid = a.total_vblocks;
-  const int64_t cap = g_deferred_grid > 0 ? g_deferred_grid : (g_sweep_grid > 0 ? g_sweep_grid : 256 * 32);
-  if (grid > cap) grid = cap;
-  hipLaunchKernelGGL((adam_lazy_sweep_wide_kernel<LPR, VPL>), dim3((unsigned)grid), dim3(RH_BLOCK), 0, s, a);
+  const SweepPlan pl = sweep_plan_into(a, h_rows, h_window, 4 * LPR * VPL, RH_SWEEP_LAZY_TABLES);
+  if (!pl.wide) return RH_E_UNSUPPORTED;  // (launch_sweep asked sweep_takes_wide first)
+  if (pl.grid == 0) return 0;
+  hipLaunchKernelGGL((adam_lazy_sweep_wide_kernel<LPR, VPL>), dim3((unsigned)pl.grid), dim3(RH_BLOCK), 0, s, a);
   return 0;
 }
 
 template <int LPR>
 int launch_sweep(LazySweepArgs& a, int mode, const int64_t* h_rows, const int64_t* h_window, hipStream_t s,
                  const LazyTouchedArgs* touch = nullptr) {
-  constexpr int RPB = RH_BLOCK / LPR;
   // (four float4 per lane, measured in round 5: 148 registers -- two such wavefronts leave a SIMD no room for the chain's
   // 235-register GEMM prologue -- 0.2696 ms per step against 0.2408; not built)
   if constexpr (LPR >= 2) {
-    if (mode == RH_SWEEP_LAZY_TABLES && a.t_value >= 0 && touch == nullptr)
+    if (sweep_takes_wide(4 * LPR, mode, a.t_value, touch != nullptr ? 1 : 0))
       return launch_sweep_wide<LPR / 2, 2>(a, h_rows, h_window, s);
   }
-  a.vb_prefix[0] = 0;
-  for (int t = 0; t < a.T; ++t) {
-    int64_t w = a.flush ? h_rows[t] : (h_window[t] < h_rows[t] ? h_window[t] : h_rows[t]);
-    const bool dense_table = h_window[t] >= h_rows[t];  // K_t == 1
-    if ((mode == RH_SWEEP_LAZY_TABLES && dense_table) || (mode == RH_SWEEP_DENSE_TABLES && !dense_table)) w = 0;
-    a.vb_prefix[t + 1] = a.vb_prefix[t] + (w + RPB - 1) / RPB;
-  }
-  for (int t = a.T + 1; t <= kMaxTensors; ++t) a.vb_prefix[t] = a.vb_prefix[a.T];
-  a.total_vblocks = a.vb_prefix[a.T];
   a.touch_blocks = a.touch_chunks = 0;
-  a.touch_period = 1;
   if (touch != nullptr) {
     a.touch = *touch;
     a.touch_chunks = (touch->B + touch->spb - 1) / touch->spb;
     a.touch_blocks = a.touch_chunks * touch->F;
   }
-  if (a.total_vblocks == 0 && a.touch_blocks == 0) return 0;
-  // persistent-style grid: each workgroup walks several virtual blocks so the prefetch has something to overlap
-  int64_t grid = a.total_vblocks;
-  const int64_t cap = (a.t_value >= 0 && touch == nullptr && g_deferred_grid > 0) ? g_deferred_grid
-                      : (g_sweep_grid > 0 ? g_sweep_grid : 256 * 32);
-  if (grid > cap) grid = cap;
+  const SweepPlan pl = sweep_plan_into(a, h_rows, h_window, 4 * LPR, mode);
   if (touch != nullptr) {
-    if (grid < 1) grid = 1;
-    // every period-th workgroup is a touched one: (touch_blocks - 1) * period < grid + touch_blocks, so all of them exist;
-    // fewer sweep than touched workgroups (small tables): period 1 = touched first
-    int64_t period = (grid + a.touch_blocks) / a.touch_blocks;
-    if (period > 1 && period % 8 == 0) period -= 1;  // block id mod 8 = XCD: keep the touched workgroups on all of them
-    a.touch_period = (int)period;
-    hipLaunchKernelGGL((adam_lazy_sweep_kernel<LPR, true>), dim3((unsigned)(grid + a.touch_blocks)), dim3(RH_BLOCK), 0, s,
+    hipLaunchKernelGGL((adam_lazy_sweep_kernel<LPR, true>), dim3((unsigned)(pl.grid + a.touch_blocks)), dim3(RH_BLOCK), 0, s,
                        a);
   } else {
-    hipLaunchKernelGGL((adam_lazy_sweep_kernel<LPR, false>), dim3((unsigned)grid), dim3(RH_BLOCK), 0, s, a);
+    if (pl.grid == 0) return 0;
+    hipLaunchKernelGGL((adam_lazy_sweep_kernel<LPR, false>), dim3((unsigned)pl.grid), dim3(RH_BLOCK), 0, s, a);
   }
   return 0;
 }
@@ -1366,6 +1391,26 @@ extern "C" int rh_adam_lazy_sweep(const int64_t* ldesc, int T, const int64_t* h_
   }
   RH_REQUIRE(rc == 0 && D % 4 == 0, RH_E_UNSUPPORTED, "rh_adam_lazy_sweep: embed_dim %d unsupported", D);
   RH_LAUNCH_CHECK("rh_adam_lazy_sweep");
+  return 0;
+}
+
+extern "C" int rh_adam_lazy_sweep_plan(int T, const int64_t* h_rows, const int64_t* h_window, int D, int mode, int64_t t_value,
+                                       int touch_blocks, int64_t* total_vblocks, int* grid, int* touch_period, int* wide) {
+  RH_REQUIRE(h_rows && h_window && total_vblocks && grid && touch_period && wide, RH_E_BADARG,
+             "rh_adam_lazy_sweep_plan: null pointer");
+  RH_REQUIRE(mode >= RH_SWEEP_WINDOW && mode <= RH_SWEEP_DENSE_TABLES && touch_blocks >= 0, RH_E_BADARG,
+             "rh_adam_lazy_sweep_plan: mode %d, touch_blocks %d", mode, touch_blocks);
+  RH_REQUIRE(T >= 1 && T <= kMaxTensors, RH_E_UNSUPPORTED, "rh_adam_lazy_sweep_plan: T=%d (max %d)", T, kMaxTensors);
+  RH_REQUIRE(D == 4 || D == 8 || D == 16 || D == 32 || D == 64 || D == 128, RH_E_UNSUPPORTED,
+             "rh_adam_lazy_sweep_plan: embed_dim %d unsupported", D);
+  // (the merged launches sweep RH_SWEEP_WINDOW or RH_SWEEP_DENSE_TABLES in line: lazy_step_impl)
+  RH_REQUIRE(touch_blocks == 0 || ((mode == RH_SWEEP_WINDOW || mode == RH_SWEEP_DENSE_TABLES) && t_value < 0), RH_E_BADARG,
+             "rh_adam_lazy_sweep_plan: a merged launch sweeps mode 0 or 3 in line");
+  const SweepPlan pl = sweep_plan(T, h_rows, h_window, D, mode, t_value, touch_blocks, nullptr);
+  *total_vblocks = pl.total_vblocks;
+  *grid = (int)pl.grid;
+  *touch_period = pl.touch_period;
+  *wide = pl.wide ? 1 : 0;
   return 0;
 }
 
