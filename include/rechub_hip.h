@@ -148,6 +148,11 @@ int rh_seq_pool_bwd(float* grad_table, int64_t vocab, const void* idx, int idx_i
                     int64_t idx_stride_b, int64_t idx_stride_l, int B, int L, int D, int mode,
                     int64_t mask_sentinel, int64_t padding_idx, const float* g_out,
                     int64_t g_stride, float scale, int32_t* err_flag, void* stream);
+/* Reports the lane split both launches above use for rows of D floats and L positions (HOST ints, launches nothing; the
+ * function the launches themselves call): *lanes_per_row = D / 4 lanes on one table row, *pos_groups = the interleaved
+ * position groups LS a sample's positions are dealt over (lane group ls takes l = j LS + ls), *trips = the passes of a lane
+ * group's gather loop, 8 positions each: ceil(ceil(L / LS) / 8). */
+int rh_seq_pool_split(int D, int L, int* lanes_per_row, int* pos_groups, int* trips);
 
 /* ---------------------------------------------------------------------------------------------
  * K5  CrossNetwork  x_{l+1} = x0 * (w_l . x_l) + b_l + x_l
@@ -302,6 +307,10 @@ int rh_din_pool_fwd(const float* hist, int64_t hist_stride, const float* w, int 
                     void* stream);
 int rh_din_pool_bwd(const float* hist, int64_t hist_stride, const float* w, const float* g, int B, int L, int D,
                     float* g_hist, float* g_w, void* stream);
+/* Reports the lane split the four launches above use for a history of L rows of D floats (HOST ints, launches nothing; the
+ * function the launches themselves call): *lanes_per_row = D / 4, *pos_groups = the position groups LS (1, 4 or 16) a
+ * sample's rows are dealt over. */
+int rh_din_att_split(int D, int L, int* lanes_per_row, int* pos_groups);
 /* First layer of the ActivationUnit's MLP with the operand built in registers (csrc/dinmlp.hip); replaces
  * models/ranking/din.py:81-85 (expand + cat + view) and the Linear(4 D, N) of basic/layers.py:279 on it:
  *   z (B L, N) = [t, h, t - h, t * h] W^T + bias;  the (B L, 4 D) operand never exists in memory.

@@ -589,11 +589,19 @@ int att_launch_ls(const AttArgs& a, int ls, hipStream_t s) {
 #undef RH_ATT
 }
 
+// The position groups LS of a launch (rh_din_att_split reports it): 1, 4 or 16, times four while a sample still fits a
+// wavefront and every group has a row to take.
+int att_pos_groups(int D, int L) {
+  const int lpr = D / 4;
+  int ls = 1;
+  while (ls < 16 && lpr * ls * 4 <= RH_WAVE && ls * 4 <= L) ls *= 4;
+  return ls;
+}
+
 template <int MODE>
 int att_dispatch(const AttArgs& a, hipStream_t s) {
   const int lpr = a.D / 4;
-  int ls = 1;
-  while (ls < 16 && lpr * ls * 4 <= RH_WAVE && ls * 4 <= a.L) ls *= 4;
+  const int ls = att_pos_groups(a.D, a.L);
   switch (lpr) {
     case 1: return att_launch_ls<1, MODE>(a, ls, s);
     case 2: return att_launch_ls<2, MODE>(a, ls, s);
@@ -787,6 +795,14 @@ extern "C" int rh_bn_dice_head_bwd_apply(const float* h, const float* g, const f
   int rc = dice_dispatch<3, true>(a, reinterpret_cast<hipStream_t>(stream));
   if (rc) return rc;
   RH_LAUNCH_CHECK("rh_bn_dice_head_bwd_apply");
+  return 0;
+}
+
+extern "C" int rh_din_att_split(int D, int L, int* lanes_per_row, int* pos_groups) {
+  RH_REQUIRE(lanes_per_row && pos_groups, RH_E_BADARG, "rh_din_att_split: null pointer");
+  if (int rc = att_check("rh_din_att_split", 0, L, D)) return rc;
+  *lanes_per_row = D / 4;
+  *pos_groups = att_pos_groups(D, L);
   return 0;
 }
 

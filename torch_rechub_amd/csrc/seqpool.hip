@@ -27,12 +27,23 @@ struct SeqArgs {
   int* err;
 };
 
+constexpr int kGather = 8;  // positions a lane gathers per trip of its loop
+
+// The position groups LS of a launch (rh_seq_pool_split reports it): doubled while a sample still fits a wavefront and a
+// group would keep more than one trip's worth of positions.
+int seq_pos_groups(int D, int L) {
+  const int lpr = D / 4;
+  int ls = 1;
+  while (ls < 16 && lpr * ls * 2 <= RH_WAVE && ls * kGather < L) ls *= 2;
+  return ls;
+}
+
 template <int LPR, int LS, typename IdxT, bool BWD>
 __global__ __launch_bounds__(RH_BLOCK) void seq_pool_kernel(const SeqArgs a) {
   RH_CHAIN_PRIO();
   constexpr int G = LPR * LS;
   constexpr int SPB = RH_BLOCK / G;
-  constexpr int U = 8;
+  constexpr int U = kGather;
   const int lig = threadIdx.x % G;
   const int q = lig % LPR;
   const int ls = lig / LPR;
@@ -149,8 +160,7 @@ int dispatch_ls(const SeqArgs& a, int ls, hipStream_t s) {
 template <typename IdxT, bool BWD>
 int dispatch(const SeqArgs& a, hipStream_t s) {
   const int lpr = a.D / 4;
-  int ls = 1;
-  while (ls < 16 && lpr * ls * 2 <= RH_WAVE && ls * 8 < a.L) ls *= 2;
+  const int ls = seq_pos_groups(a.D, a.L);
   switch (lpr) {
     case 1: return dispatch_ls<1, IdxT, BWD>(a, ls, s);
     case 2: return dispatch_ls<2, IdxT, BWD>(a, ls, s);
@@ -162,15 +172,29 @@ int dispatch(const SeqArgs& a, hipStream_t s) {
   }
 }
 
-int check(const char* who, const void* idx, int B, int L, int D, int mode, int64_t vocab) {
-  RH_REQUIRE(idx != nullptr && B >= 0 && L > 0 && vocab > 0, RH_E_BADARG, "%s: bad arguments", who);
-  RH_REQUIRE(mode >= 0 && mode <= 2, RH_E_BADARG, "%s: mode %d (0 sum, 1 mean, 2 concat)", who, mode);
+int check_dim(const char* who, int D) {
   RH_REQUIRE(D > 0 && D % 4 == 0 && D <= 128 && ((D / 4) & (D / 4 - 1)) == 0, RH_E_UNSUPPORTED,
              "%s: embed_dim %d unsupported (need 4,8,16,32,64,128)", who, D);
   return 0;
 }
 
+int check(const char* who, const void* idx, int B, int L, int D, int mode, int64_t vocab) {
+  RH_REQUIRE(idx != nullptr && B >= 0 && L > 0 && vocab > 0, RH_E_BADARG, "%s: bad arguments", who);
+  RH_REQUIRE(mode >= 0 && mode <= 2, RH_E_BADARG, "%s: mode %d (0 sum, 1 mean, 2 concat)", who, mode);
+  return check_dim(who, D);
+}
+
 }  // namespace
+
+extern "C" int rh_seq_pool_split(int D, int L, int* lanes_per_row, int* pos_groups, int* trips) {
+  RH_REQUIRE(lanes_per_row && pos_groups && trips && L > 0, RH_E_BADARG, "rh_seq_pool_split: bad arguments");
+  if (int rc = check_dim("rh_seq_pool_split", D)) return rc;
+  const int ls = seq_pos_groups(D, L);
+  *lanes_per_row = D / 4;
+  *pos_groups = ls;
+  *trips = ((L + ls - 1) / ls + kGather - 1) / kGather;
+  return 0;
+}
 
 extern "C" int rh_seq_pool_fwd(const float* table, int64_t vocab, const void* idx, int idx_is_i64,
                                int64_t idx_stride_b, int64_t idx_stride_l, int B, int L, int D, int mode,
