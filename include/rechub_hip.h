@@ -15,6 +15,9 @@
  *     so every call may be captured into a hipGraph;
  *   - `err_flag` (device int32, may be NULL) is OR-ed with RH_FLAG_* bits by kernels that
  *     validate indices; the host reads it at its own sync points.
+ *   - a shape limit (a bound answered with RH_E_UNSUPPORTED, or the size of a fixed LDS / register array) is an integer macro
+ *     RH_<FAMILY>_MAX_<DIM> (or _MIN_) beside the family's declarations: the kernels take it from here, Python reads it
+ *     as _lib.H.RH_..., tests/test_abi.py holds the values in one table.
  *
  * Field descriptor tables (device int64 arrays, struct-of-arrays, F = number of fields):
  *   fdesc[0*F + f] = const float* table base of field f        (vocab_f x D, row-major, fp32)
@@ -83,9 +86,12 @@ int rh_set_tuning(int key, int value);
  *         lr_out (B,) = emb . lr_w + lr_b
  * fm_out: (B,) or NULL = 0.5 * sum_d[(sum_f v)^2 - sum_f v^2]
  * s_out : (B, D) or NULL = sum_f v  (saved for the backward)
- * D must be a multiple of 4 and <= 128 (16-byte lanes); idx_is_i64: 1 = int64 indices, 0 = int32.
+ * D must be a multiple of 4 and <= RH_EMBED_MAX_D (16-byte lanes); idx_is_i64: 1 = int64 indices, 0 = int32.
+ * lr_out needs F * D <= RH_EMBED_MAX_LR_FD (the LR weights are kept in LDS).
  * field_split: 0 = auto, else 1/2/4/8 lanes-groups per sample (tuning knob).
  */
+#define RH_EMBED_MAX_D 128
+#define RH_EMBED_MAX_LR_FD 12288
 int rh_embed_fwd(const int64_t* fdesc, const int64_t* idesc, int idx_is_i64, int B, int F, int D,
                  const int64_t* ddesc, int n_dense, int dense_col, float* out, int64_t out_stride,
                  const float* lr_w, const float* lr_b, float* lr_out, float* fm_out, float* s_out,
@@ -137,8 +143,9 @@ int rh_fm_bwd(const float* x, int64_t x_stride, int B, int F, int D, int reduce_
  * idx (B, L) with sample stride idx_stride_b and position stride idx_stride_l (elements)
  * mode 0 = sum, 1 = mean (divide by count + 1e-16), 2 = concat (no mask, out (B, L, D))
  * mask_sentinel = padding_idx if set else -1 (positions equal to it are excluded from sum/mean)
- * out row b at out + b*out_stride (D floats, or L*D floats for concat).
+ * out row b at out + b*out_stride (D floats, or L*D floats for concat).  D a power-of-two multiple of 4, <= RH_SEQ_POOL_MAX_D.
  */
+#define RH_SEQ_POOL_MAX_D 128
 int rh_seq_pool_fwd(const float* table, int64_t vocab, const void* idx, int idx_is_i64,
                     int64_t idx_stride_b, int64_t idx_stride_l, int B, int L, int D, int mode,
                     int64_t mask_sentinel, float* out, int64_t out_stride, int32_t* err_flag,
@@ -158,12 +165,13 @@ int rh_seq_pool_split(int D, int L, int* lanes_per_row, int* pos_groups, int* tr
  * K5  CrossNetwork  x_{l+1} = x0 * (w_l . x_l) + b_l + x_l
  * replaces: CrossNetwork.forward torch_rechub/basic/layers.py:412-420 and its autograd
  * x0, x : (B, d) with row strides; w, b : (L, d) contiguous; L <= 4 per call (chain calls for more,
- * passing the original x0).  One wavefront per sample, d <= 2048.
+ * passing the original x0).  One wavefront per sample, d <= RH_CROSS_MAX_D.
  * bwd: g_x0 / g_x may alias-sum: if sum_into_gx != 0 the x0-gradient is added into g_x and g_x0 is
  * ignored (the x0 == x case of the first segment).
  * wb_partials: (nblocks, 2, L, d) per-block partial sums of (dW, dB); nblocks is returned by
  * rh_cross_bwd_nblocks(B); the caller reduces over dim 0.
  */
+#define RH_CROSS_MAX_D 2048
 int rh_cross_fwd(const float* x0, int64_t x0_stride, const float* x, int64_t x_stride,
                  const float* w, const float* b, int B, int d, int L, float* out,
                  int64_t out_stride, void* stream);
@@ -184,8 +192,11 @@ int rh_cross_bwd(const float* x0, int64_t x0_stride, const float* x, int64_t x_s
  *   fwd: out = sum_e gate[b,e] * x0 * (uv[e,b,:] + bias) + xl     uv (E,B,d) = U_e v_e from the batched GEMM,
  *        gate (B,E) = softmax of the gating scores;
  *   bwd: g_x0 = g * sum_e gate_e (uv_e + bias), g_uv[e] = g * gate_e * x0, g_gate[b,e] = sum_d g*x0*(uv_e + bias)
- *        (g_xl = g, g_bias = colsum(g * x0 * sum_e gate_e) are the caller's).  d <= 2048, E <= 16.
+ *        (g_xl = g, g_bias = colsum(g * x0 * sum_e gate_e) are the caller's).  d <= RH_CROSS_MIX_MAX_D,
+ *        E <= RH_CROSS_MIX_MAX_E.
  */
+#define RH_CROSS_MIX_MAX_D 2048
+#define RH_CROSS_MIX_MAX_E 16
 int rh_cross_v2_epilogue_fwd(const float* x0, const float* y, const float* b, const float* x, int B, int d, float* out,
                              void* stream);
 int rh_cross_v2_epilogue_bwd(const float* x0, const float* y, const float* g, int B, int d, float* g_x0, float* g_y,
@@ -219,9 +230,13 @@ int rh_cross_mix_epilogue_bwd_b(const float* x0, const float* uv, const float* g
  *   rh_cross_moe_unpack: sums the weight-gradient slabs of the two products (rh_linear_wgrad_partial: slabV_l = S1_l slabs
  *                      (KP, d) of g_PG^T x_l, slabU_l = S2_l slabs (d, KP) of g_Y^T wp) and the g_C partials into g_U, g_V
  *                      (E, d, r), g_bias (d,), g_C (E, r, r) per layer and g_Wg (d,) per expert (summed over the layers).
- *   Supported: L <= 8, E <= 16, r in {4, 8, 16, 32, 64}, E r <= 256 (rh_cross_moe_supported); anything else runs the
- *   batched-GEMM formulation with rh_cross_mix_epilogue_*.
+ *   Supported: L <= RH_CROSS_MOE_MAX_L, E <= RH_CROSS_MOE_MAX_E, r in {4, 8, 16, 32, 64} (RH_CROSS_MOE_MAX_R), E r <=
+ *   RH_CROSS_MOE_MAX_ER (rh_cross_moe_supported); anything else runs the batched-GEMM formulation with rh_cross_mix_epilogue_*.
  */
+#define RH_CROSS_MOE_MAX_L 8
+#define RH_CROSS_MOE_MAX_E 16
+#define RH_CROSS_MOE_MAX_R 64
+#define RH_CROSS_MOE_MAX_ER 256
 int rh_cross_moe_kp(int E, int r);
 int rh_cross_moe_supported(int L, int E, int d, int r);
 int rh_cross_moe_mid_blocks(int B, int E, int r);
@@ -258,7 +273,12 @@ int rh_cross_moe_unpack(const float* const* slabV, const int* S1, const float* c
  *   out (B*L, 4D);  bwd: g (B*L, 4D) -> g_hist (B, L, D) contiguous, g_tgt (B, D)
  * rh_din_pool_fwd/bwd replaces: (att_weight.unsqueeze(-1) * history).sum(dim=1), models/ranking/din.py:92
  *   w (B, L) contiguous -> out (B, D);  bwd: g (B, D) -> g_hist (B, L, D), g_w (B, L)
+ * Dice takes C <= RH_DICE_MAX_C neurons, the BatchNorm-folded passes C <= RH_BN_DICE_MAX_C; the attention ends take D a
+ * power-of-two multiple of 4 up to RH_DIN_ATT_MAX_D.
  */
+#define RH_DICE_MAX_C 2048
+#define RH_BN_DICE_MAX_C 512
+#define RH_DIN_ATT_MAX_D 128
 int rh_dice_nblocks(int64_t N);
 int rh_dice_fwd(const float* x, const float* alpha, float eps, int64_t N, int C, const float* bn_scale,
                 const float* bn_shift, float* out, void* stream);
@@ -270,7 +290,7 @@ int rh_dice_bwd(const float* x, const float* g, const float* alpha, float eps, i
  *             num_batches_tracked; eval: from the running statistics) then rh_dice_fwd(h, ..., stat + 4C, stat + 5C, out)
  *   backward: rh_bn_dice_bwd_stats (g = dL/d out -> per-block (sum g_x, sum g_x * xhat) rows, col_partial
  *             (rh_bn_dice_stats_blocks(N), 2, C), and alpha partial sums (same number of blocks)),
- *             rh_bn_finalize_bwd (-> stat rows 2, 3, dgamma, dbeta), rh_bn_dice_bwd_apply (-> dh).   C <= 512. */
+ *             rh_bn_finalize_bwd (-> stat rows 2, 3, dgamma, dbeta), rh_bn_dice_bwd_apply (-> dh).   C <= RH_BN_DICE_MAX_C. */
 int rh_bn_stats_fwd(const float* h, int B, int C, const float* gamma, const float* beta, float* running_mean,
                     float* running_var, int64_t* num_batches_tracked, float momentum, float eps, int training,
                     float* partial, float* stat, void* stream);
@@ -316,7 +336,10 @@ int rh_din_att_split(int D, int L, int* lanes_per_row, int* pos_groups);
  *   z (B L, N) = [t, h, t - h, t * h] W^T + bias;  the (B L, 4 D) operand never exists in memory.
  *   partial (optional): ceil(B L / rh_din_att_l1_chunk_rows(B L)) x 2 x N per-chunk (sum, M2 about the chunk mean) of z --
  *   the BatchNorm statistics, combined by rh_bn_stats_from_partial (no pass over z).
- *   Supported (rh_din_att_l1_supported): D in {4, 8, 16}, N a multiple of 64 up to 256. */
+ *   Supported (rh_din_att_l1_supported): D in {4, 8, 16} (RH_DIN_ATT_L1_MAX_D), N a multiple of 64 up to
+ *   RH_DIN_ATT_L1_MAX_N. */
+#define RH_DIN_ATT_L1_MAX_D 16
+#define RH_DIN_ATT_L1_MAX_N 256
 /* nn.PReLU() with one slope (activation_layer("prelu"), torch_rechub/basic/activation.py:40-41; the DSSM towers): x contiguous,
  * n elements; bwd writes gx and rh_prelu_nblocks(n) per-block partial sums of d / d slope. */
 int rh_prelu_nblocks(int64_t n);
@@ -325,7 +348,8 @@ int rh_prelu_bwd(const float* x, const float* g, const float* slope, int64_t n, 
 /* In-batch negatives without the (B, C) score matrix (csrc/match.hip); replaces, for RANDOM negatives,
  * `scores = user @ item.T` + `gather_inbatch_logits(scores, neg_indices)` of trainers/match_trainer.py:118-138 /
  * utils/match.py:148-153 and their autograd:  logits[i, 0] = u_i . v_(row0 + i),  logits[i, 1 + k] = u_i . v_neg[i, k];
- * bwd: g_u (B, D) written, g_v (C, D) accumulated with float atomics into a buffer the caller zeroed.  D <= 1024. */
+ * bwd: g_u (B, D) written, g_v (C, D) accumulated with float atomics into a buffer the caller zeroed.  D <= RH_INBATCH_MAX_D. */
+#define RH_INBATCH_MAX_D 1024
 int rh_inbatch_logits_fwd(const float* u, int64_t ldu, const float* v, int64_t ldv, const int64_t* neg, int B, int C, int D,
                           int K, int row0, float* logits, int32_t* err_flag, void* stream);
 int rh_inbatch_logits_bwd(const float* u, int64_t ldu, const float* v, int64_t ldv, const int64_t* neg, const float* g, int B,
@@ -334,13 +358,16 @@ int rh_inbatch_logits_bwd(const float* u, int64_t ldu, const float* v, int64_t l
 /* Two-tower glue as single launches.
  * rh_l2norm_fwd/bwd: F.normalize(x, p=2, dim=1) of the towers' outputs (torch_rechub/models/matching/dssm.py:56,66):
  *   y = x / max(||x||_2, eps) row-wise, nrm (B,) = ||x|| saved; gx = (g - y (g . y)) / ||x||, or g / eps where the norm was
- *   clamped.  x / g row stride ldx / ldg (multiples of 4), d % 4 == 0, d <= 4096; y, gx contiguous (B, d).
+ *   clamped.  x / g row stride ldx / ldg (multiples of 4), d % 4 == 0, RH_L2NORM_MIN_D <= d <= RH_L2NORM_MAX_D; y, gx contiguous (B, d).
  * rh_ce_fwd/bwd: torch.nn.CrossEntropyLoss() (mean) over the (B, C) in-batch logits (trainers/match_trainer.py:60,136;
  *   target int64 (B,), null = class 0 for every row as the trainer's zero targets): lse (B,) = logsumexp per row, loss_partial
  *   (rh_ce_nblocks(B),) per-block sums of lse - x[target] (the caller sums them and divides by B: rh_colsum);
  *   g_logits = g_loss[0] / B * (softmax - onehot), the softmax taken from the logits again as exp((x - max) - log sum): the
- *   backward requires lse but does not read it (its rounding would be the error of p - 1 at the target).  C <= 1024; an
+ *   backward requires lse but does not read it (its rounding would be the error of p - 1 at the target).  C <= RH_CE_MAX_C; an
  *   out-of-range target sets RH_FLAG_INDEX_OOB. */
+#define RH_L2NORM_MIN_D 4
+#define RH_L2NORM_MAX_D 4096
+#define RH_CE_MAX_C 1024
 int rh_l2norm_fwd(const float* x, int64_t ldx, int B, int d, float eps, float* y, float* nrm, void* stream);
 int rh_l2norm_bwd(const float* y, const float* nrm, const float* g, int64_t ldg, int B, int d, float eps, float* gx, void* stream);
 int rh_ce_nblocks(int B);
@@ -366,10 +393,11 @@ int rh_bn_stats_from_partial(const float* partial, int rows_per_chunk, int B, in
  * rh_head_fwd/bwd replaces: MLP's output Linear(K, 1) + `y_linear + y_fm + y_deep` + torch.sigmoid(y.squeeze(1)),
  *   models/ranking/deepfm.py:39-43, widedeep.py:35-39:  y (B,) = sigmoid(h w^T + bias + e0 + e1)  (bias, e0, e1 optional)
  *   bwd: g_z = g_y y (1 - y) (also the gradient of e0 / e1), g_h (B, K) = g_z w, g_w (K,) = g_z^T h, g_b = sum g_z.
- *   1 <= K <= 1024 (rows of h may be only 4-byte aligned).  partial: rh_head_nblocks(B) * (K + 1) floats.
+ *   1 <= K <= RH_HEAD_MAX_K (rows of h may be only 4-byte aligned).  partial: rh_head_nblocks(B) * (K + 1) floats.
  * rh_bce_fwd/bwd replaces: torch.nn.BCELoss() (mean) of trainers/ctr_trainer.py:62,:93-95: log terms clamped at -100;
  *   loss (1,), g_loss (1,) device scalars.
  */
+#define RH_HEAD_MAX_K 1024
 /* rh_linear_fwd / rh_linear_dgrad replace: the forward y = x W^T + b and the input gradient g_x = g W of the same
  *   nn.Linear modules (aten::addmm / mm) at CTR batch sizes, where one 64x64 f32-MFMA tile per workgroup fills the chip
  *   exactly once (csrc/gemm.hip).  x (M, K) row stride ldx, w (N, K) row stride ldw, bias (N,) or NULL, y (M, N).
@@ -398,7 +426,9 @@ int rh_linear_dgrad(const float* g, int64_t ldg, const float* w, int64_t ldw, in
  * rh_cross_v2_fwd: x0, x (M, d), w (d, d) row-major as nn.Linear.weight, b (d,) -> y (M, d) = x w^T (kept for the backward) and
  * out (M, d) = x0 * y + b + x.  rh_cross_v2_dgrad: gx (M, d) = g_y w + g with g_y = g * x0 (rh_cross_v2_epilogue_bwd forms g_y
  * and g_x0 = g * y): the layer's gradient with respect to x, residual path included.  Every operand contiguous (row stride d);
- * 1 <= M <= 16384, 1 <= d <= 1024, else RH_E_UNSUPPORTED. */
+ * 1 <= M <= RH_CROSS_V2_MAX_M, 1 <= d <= RH_CROSS_V2_MAX_D, else RH_E_UNSUPPORTED. */
+#define RH_CROSS_V2_MAX_M 16384
+#define RH_CROSS_V2_MAX_D 1024
 int rh_cross_v2_fwd(const float* x0, const float* x, const float* w, const float* b, int M, int d, float* y, float* out,
                     void* stream);
 int rh_cross_v2_dgrad(const float* g_y, const float* w, const float* g, int M, int d, float* gx, void* stream);
@@ -410,7 +440,7 @@ int rh_cross_v2_dgrad(const float* g_y, const float* w, const float* g, int M, i
  *   ctr: its nn.Dropout and the counter the producing GEMM drew for it (that call's bn_saved_ctr).  Written besides y:
  *   stat_out (>= 2, K) = mean, rstd of layer l; its running statistics; act_out (M, K) or NULL = the activations (this
  *   layer's weight gradient reads them); stats / bn_rng / bn_saved_ctr / bn_batches: as rh_linear_fwd, for y and the NEXT
- *   BatchNorm.  K % 4 == 0, K <= 1024, ldh % 4 == 0.  Same per-element arithmetic as rh_bn_relu_dropout_fwd.
+ *   BatchNorm.  K % 4 == 0, K <= RH_LINEAR_BNACT_MAX_K, ldh % 4 == 0.  Same per-element arithmetic as rh_bn_relu_dropout_fwd.
  * rh_linear_dgrad_bnbwd: rh_linear_dgrad whose epilogue also forms the BatchNorm-backward column sums of the hidden layer
  *   that produced this Linear's input: gx (M, K) = gradient of a = dropout(relu(batch_norm(h))), h (M, K) that layer's
  *   pre-BatchNorm activations, stat (>= 2, K) its mean / rstd, ctr its dropout counter.  bwd_partial (ceil(M / R), 2, K),
@@ -418,7 +448,9 @@ int rh_cross_v2_dgrad(const float* g_y, const float* w, const float* g, int M, i
  *   nchunks_pre = ceil(M / R) (replaces the statistics launch of the BatchNorm backward).
  * rh_head_bnact_fwd: the output head of such a chain, y = sigmoid(dropout(relu(batch_norm(z))) . w + b + e0 + e1), z (B, K)
  *   pre-BatchNorm, stats / stats_rows / ctr as above; t / loss_partial as rh_head_loss_fwd (both NULL: no loss terms).
- *   K % 4 == 0, K <= 256.  Its backward is rh_head_bwd_bn with h = NULL (the head's input is recomputed from z). */
+ *   K % 4 == 0, K <= RH_HEAD_BN_MAX_K.  Its backward is rh_head_bwd_bn with h = NULL (the head's input is recomputed from z). */
+#define RH_LINEAR_BNACT_MAX_K 1024
+#define RH_HEAD_BN_MAX_K 256
 int rh_linear_bnact_fwd(const float* h, int64_t ldh, int M, int K, const float* pro_stats, int pro_rows, const float* gamma,
                         const float* beta, float* running_mean, float* running_var, float momentum, float eps, float p_drop,
                         const int64_t* rng, const int64_t* ctr, float* stat_out, float* act_out, const float* w, int64_t ldw,
@@ -441,7 +473,9 @@ int rh_linear_wgrad_splits(int B, int N, int K);
 int rh_linear_wgrad_partial(const float* g, int64_t ldg, const float* x, int64_t ldx, int B, int N, int K, float* partial,
                             void* stream);
 /* n <= 8 independent rh_linear_wgrad_partial problems as ONE launch (the two weight gradients per layer of CrossNetMix's
- * backward, torch_rechub/basic/layers.py:470-506: nothing else in that backward waits for them).  Host arrays of n entries. */
+ * backward, torch_rechub/basic/layers.py:470-506: nothing else in that backward waits for them).  Host arrays of n entries.
+ * Every B[i] < RH_WGRAD_LONG_MIN_B: a reduction of that many rows or more is a long one and takes the single call. */
+#define RH_WGRAD_LONG_MIN_B 32768
 int rh_linear_wgrad_partial_group(int n, const float* const* g, const int64_t* ldg, const float* const* x, const int64_t* ldx,
                                   const int* B, const int* N, const int* K, float* const* partial, void* stream);
 int rh_head_nblocks(int B);
@@ -468,7 +502,7 @@ int rh_head_bwd_ex(const float* h, int64_t ldh, const float* w, const float* y, 
                    int reduce, void* stream);
 /* rh_head_bwd_ex + the BatchNorm-backward column sums of the hidden layer below the head, when h = dropout(relu(bn(bn_z)))
  * and the head is its only consumer: bn_partial (rh_head_nblocks(B), 2, K) per-block (sum g1, sum g1 * xhat) with the mask
- * arithmetic of rh_bn_relu_dropout_bwd; rh_bn_relu_dropout_bwd_pre then needs no statistics pass.  K % 4 == 0, K <= 256. */
+ * arithmetic of rh_bn_relu_dropout_bwd; rh_bn_relu_dropout_bwd_pre then needs no statistics pass.  K % 4 == 0, K <= RH_HEAD_BN_MAX_K. */
 int rh_head_bwd_bn(const float* h, int64_t ldh, const float* w, const float* y, const float* g_y, const float* t,
                    const float* g_loss, int B, int K, float* g_h, float* g_z, float* g_w, float* g_b, float* partial,
                    int reduce, const float* bn_z, const float* bn_stat, const float* bn_gamma, const float* bn_beta,
@@ -518,7 +552,9 @@ int rh_bn_relu_dropout_fwd(const float* h, int B, int C, const float* gamma, con
                            float* running_var, int64_t* num_batches_tracked, float momentum, float eps, float p_drop,
                            int training, int64_t* rng, int64_t* saved_ctr, float* partial, int partial_rows, float* stat,
                            float* out, int relu, void* stream);
-/* the same with the column sums already formed by the producer of dy (rh_head_bwd_bn): nchunks_pre <= 128 partial rows */
+/* the same with the column sums already formed by the producer of dy (rh_head_bwd_bn): nchunks_pre <= RH_BN_PRE_MAX_CHUNKS
+ * partial rows */
+#define RH_BN_PRE_MAX_CHUNKS 128
 int rh_bn_relu_dropout_bwd_pre(const float* h, const float* dy, int B, int C, const float* gamma, const float* beta,
                                float p_drop, const int64_t* rng, const int64_t* saved_ctr, const float* partial,
                                int nchunks_pre, float* stat, float* dx, float* dgamma, float* dbeta, int relu, void* stream);
@@ -541,7 +577,7 @@ int rh_bn_prelu_dropout_bwd(const float* h, const float* dy, int B, int C, const
 /* ---------------------------------------------------------------------------------------------
  * Dense Adam with coupled L2, torch.optim.Adam semantics over every row of every table
  * replaces: optimizer.step() torch_rechub/trainers/ctr_trainer.py:59-61,99 for embedding tables
- * tdesc (device int64 [5*T]): p, g, m, v pointers and numel per tensor (T <= 128)
+ * tdesc (device int64 [5*T]): p, g, m, v pointers and numel per tensor (T <= RH_ADAM_MAX_TENSORS)
  * h_numel (HOST int64 [T]): the same numel values (multiples of 4), used to size the launch
  * hyper (device double [16]): inputs  [0]=lr [1]=beta1 [2]=beta2 [3]=eps [4]=weight_decay
  *                             derived [8]=step_size=lr/(1-beta1^t) [9]=sqrt(1-beta2^t)
@@ -552,13 +588,14 @@ int rh_bn_prelu_dropout_bwd(const float* h, const float* dy, int B, int C, const
  *                     p -= step_size * m / (sqrt(v)/sqrt(1-b2^t) + eps)
  * zero_grad != 0: g <- 0 where it was non-zero (replaces model.zero_grad(), ctr_trainer.py:97)
  */
+#define RH_ADAM_MAX_TENSORS 128
 int rh_adam_prepare(double* hyper, int64_t* step, float* ring, int ring_size, void* stream);
 int rh_adam_dense(const int64_t* tdesc, int T, const int64_t* h_numel, const double* hyper,
                   int zero_grad, void* stream);
 
 /* Adam for the small dense parameters (MLP / LR / cross weights) in one launch; gradients are read from the packed
  * flat bucket (the buffer the RCCL all-reduce runs on).  Any numel, 4-byte alignment.  Uses hyper[] of rh_adam_prepare.
- * sdesc (device int64 [5*T]): p, m, v pointers, numel, offset of the parameter's gradient inside flat_g (T <= 128).
+ * sdesc (device int64 [5*T]): p, m, v pointers, numel, offset of the parameter's gradient inside flat_g (T <= RH_ADAM_MAX_TENSORS).
  * replaces: optimizer.step() for the non-embedding parameters, trainers/ctr_trainer.py:99 */
 int rh_adam_small(const int64_t* sdesc, int T, const int64_t* h_numel, const float* flat_g, const double* hyper,
                   void* stream);
@@ -590,7 +627,7 @@ int rh_pack_grads_adam_gate(const RhPackItem* items, int n, float* flat, const i
  * replaces: the same optimizer.step() (trainers/ctr_trainer.py:99).  Adam is element-wise and a row that is not in
  * the batch has the known gradient wd*p, so rows are brought up to date lazily by replaying the skipped steps in
  * registers; every row is refreshed at least every K steps (sweep window) and immediately when the batch touches it.
- * ring  (device float [2*ring_size], ring_size a power of two > K): per-step (A_t, E_t) written by rh_adam_prepare
+ * ring  (device float [2*ring_size], ring_size a power of two > K and <= RH_ADAM_MAX_RING): per-step (A_t, E_t) written by rh_adam_prepare
  *       (hyper[13] = A_t = step_size*sqrt(1-b2^t), hyper[14] = E_t = eps*sqrt(1-b2^t))
  * ldesc (device int64 [8*T]): p, g, m, v, last (int32 per row: step the row is up to date with) pointers,
  *       rows, K_t (1 = dense table, stepped with its gradient by the sweep), window rows w_t = ceil(rows/K_t)
@@ -610,6 +647,7 @@ int rh_pack_grads_adam_gate(const RhPackItem* items, int n, float* flat, const i
  * was launched (rh_adam_lazy_touched under the hyper of step s = the pre-gather refresh) and the sweep has finished
  * before step s + 2 refreshes its rows.
  */
+#define RH_ADAM_MAX_RING 1024
 #define RH_SWEEP_WINDOW 0
 #define RH_SWEEP_FLUSH 1
 #define RH_SWEEP_LAZY_TABLES 2
@@ -770,16 +808,16 @@ int rh_inbatch_sample_rows(const int64_t* rng, int B, int cols, int row0, int K,
  *           d_xw (B, T, 3D) = gradient of xw;  d_huh (B, T, D) = gradient of s_h (so that
  *           dU = [h_0 .. h_{T-1}]^T [d_xw_u | d_xw_r | d_huh] is one GEMM by the caller and d state_bias its column sum);
  *           d_attn (B, T) (may be null when attn is).
- * D in {4, 8, 16, 32} (rh_augru_max_dim()); D / 4 lanes per sample, state in registers, U in LDS. */
-int rh_augru_max_dim(void);
+ * D in {4, 8, 16, 32} (the largest is RH_AUGRU_MAX_D); D / 4 lanes per sample, state in registers, U in LDS. */
+#define RH_AUGRU_MAX_D 32
 int rh_augru_fwd(const float* xw, const float* attn, const float* U, const float* state_bias, int B, int T, int D,
                  float* h_all, void* stream);
 int rh_augru_bwd(const float* xw, const float* attn, const float* U, const float* state_bias, const float* h_all,
                  const float* g_hall, int B, int T, int D, float* d_xw, float* d_huh, float* d_attn, void* stream);
 
 /* ---- field-aware FM (DeepFFM / FAT-DeepFFM) ------------------------------------------------------------------------
- * F fields (2 .. 64), P = F(F-1)/2 pairs in the reference's order (i outer, j > i inner), D logical width (1 .. 128),
- * Dp physical row width of the tables (D <= Dp <= 128: PaddedEmbedding).  Pair side (i, j) is row x_i * F + j of field
+ * F fields (2 .. RH_FFM_MAX_F), P = F(F-1)/2 pairs in the reference's order (i outer, j > i inner), D logical width
+ * (1 .. RH_FFM_MAX_D), Dp physical row width of the tables (D <= Dp <= RH_FFM_MAX_D: PaddedEmbedding).  Pair side (i, j) is row x_i * F + j of field
  * i's table.  Two row-addressing modes, one kernel each way:
  *   table mode (fdesc, idesc as above, x = null): the raw (B,) index columns of the F fields;
  *   dense mode (fdesc = idesc = null, x (B, F, F, D) with sample stride x_stride): the layer-level FFM.
@@ -793,6 +831,8 @@ int rh_augru_bwd(const float* xw, const float* attn, const float* U, const float
  *   ordinary index columns (optimizer touch records, the data-parallel exchange).
  * replaces: DeepFFM.forward torch_rechub/models/ranking/deepffm.py:57-62 (x * F + fields_offset, (B, F, F, D) lookup),
  *           FFM.forward torch_rechub/basic/layers.py:736-746 and their autograd. */
+#define RH_FFM_MAX_F 64
+#define RH_FFM_MAX_D 128
 int rh_ffm_expand_index(const int64_t* idesc, int idx_is_i64, int B, int F, void* out, void* stream);
 int rh_ffm_fwd(const int64_t* fdesc, const int64_t* idesc, int idx_is_i64, const float* x, int64_t x_stride, int B, int F,
                int D, int Dp, int reduce_sum, float* out, int64_t out_stride, int32_t* err_flag, void* stream);
@@ -815,8 +855,8 @@ int rh_cen_rescale_bwd(const float* em, int64_t ld, const float* s, const float*
                        float* g_em, float* g_s, void* stream);
 
 /* ---- multi-interest user towers and list-wise scoring (YoutubeDNN / MIND / ComiRec) ----------------------------------
- * Capsule routing (CapsuleNetwork, bilinear types 0 / 1 / 2), B samples, L positions, I interests, width D (D <= 64,
- * I*D <= 256; type 2 also I*D*D <= 4096).  mask (B, L) int32, nonzero = kept.  Types 0 / 1: U (B, L, Iu*D) the Linear's
+ * Capsule routing (CapsuleNetwork, bilinear types 0 / 1 / 2), B samples, L positions, I interests, width D (D <= RH_CAPSULE_MAX_D,
+ * I*D <= RH_CAPSULE_MAX_ID; type 2 also I*D*D <= RH_CAPSULE_MAX_IDD).  mask (B, L) int32, nonzero = kept.  Types 0 / 1: U (B, L, Iu*D) the Linear's
  * output (Iu = 1 / I; type 0 repeats it over the interests); type 2: E (B, L, D) and W (L, I*D, D) (w[0, :L]).
  * init (B, I, L) the initial routing logits, or null for zeros.  Writes cap (B, I, D), and when not null the last
  * iteration's masked softmax weights sw (B, I, L) and pre-squash sums s (B, I, D) for the backward.
@@ -824,6 +864,9 @@ int rh_cen_rescale_bwd(const float* em, int64_t ld, const float* s, const float*
  * rh_capsule_wgrad (type 2): partial (rh_capsule_wgrad_nchunks(B), L*I*D*D) per-chunk sums of the weight gradient in a
  *   fixed order (g_w = rh_colsum of it: bitwise reproducible).
  * replaces: CapsuleNetwork.forward torch_rechub/basic/layers.py:657-712 and its autograd. */
+#define RH_CAPSULE_MAX_D 64
+#define RH_CAPSULE_MAX_ID 256
+#define RH_CAPSULE_MAX_IDD 4096
 int rh_capsule_supported(int L, int I, int D, int type);
 int rh_capsule_fwd(const float* U, const float* E, const float* W, const int32_t* mask, const float* init, int B, int L,
                    int I, int D, int type, int routing_times, float* cap, float* sw, float* s, void* stream);
@@ -834,19 +877,25 @@ int rh_capsule_wgrad(const float* g_s, const float* sw, const float* E, int B, i
                      void* stream);
 /* Self-attentive pooling (MultiInterestSA after A = tanh(E W1) W2): A (B, L, I), E (B, L, D), mask (B, L) int32 or null.
  * rh_sa_pool_fwd: P (B, L, I) = softmax over L of A + -1e9 (1 - mask); out (B, I, D) = P^T E.
- * rh_sa_pool_bwd: g (B, I, D) -> gA (B, L, I), gE (B, L, D).  D <= 64, L*I <= 1024, I*D <= 1024.
+ * rh_sa_pool_bwd: g (B, I, D) -> gA (B, L, I), gE (B, L, D).  D <= RH_SA_MAX_D, L*I <= RH_SA_MAX_LI, I*D <= RH_SA_MAX_ID.
  * replaces: MultiInterestSA.forward torch_rechub/basic/layers.py:601-609 (softmax, mask term, matmul) and its autograd. */
+#define RH_SA_MAX_D 64
+#define RH_SA_MAX_LI 1024
+#define RH_SA_MAX_ID 1024
 int rh_sa_supported(int L, int I, int D);
 int rh_sa_pool_fwd(const float* A, const float* E, const int32_t* mask, int B, int L, int I, int D, float* P, float* out,
                    void* stream);
 int rh_sa_pool_bwd(const float* P, const float* E, const float* g, int B, int L, int I, int D, float* gA, float* gE,
                    void* stream);
-/* List-wise scoring: u (B, I, D) normalised user vectors (I <= 16, D <= 64), pos (B, D) row stride ldp and neg (B, K, D)
- * raw item rows (K < 1024).  Rows are L2-normalised (F.normalize, eps 1e-12); best[b] = first argmax_i u_i . pos_hat;
+/* List-wise scoring: u (B, I, D) normalised user vectors (I <= RH_LISTWISE_MAX_I, D <= RH_LISTWISE_MAX_D), pos (B, D) row stride
+ * ldp and neg (B, K, D) raw item rows (K <= RH_LISTWISE_MAX_K).  Rows are L2-normalised (F.normalize, eps 1e-12); best[b] = first argmax_i u_i . pos_hat;
  * logits (B, 1 + K) = u_best . [pos_hat, neg_hat] / temperature; nrm (B, 1 + K) the row norms for the backward.
  * rh_listwise_bwd: g (B, 1 + K) -> g_u (B, I, D) (zero but the chosen interest), g_pos (B, D), g_neg (B, K, D).
  * replaces: the item towers' F.normalize + torch.cat and the bmm / argmax / gather / mul-sum of YoutubeDNN, MIND,
  *           ComirecDR and ComirecSA.forward (torch_rechub/models/matching/youtube_dnn.py, mind.py, comirec.py). */
+#define RH_LISTWISE_MAX_I 16
+#define RH_LISTWISE_MAX_D 64
+#define RH_LISTWISE_MAX_K 1023
 int rh_listwise_fwd(const float* u, const float* pos, int64_t ldp, const float* neg, int B, int I, int D, int K,
                     float temperature, float* logits, int32_t* best, float* nrm, void* stream);
 int rh_listwise_bwd(const float* u, const float* pos, int64_t ldp, const float* neg, const int32_t* best, const float* nrm,
@@ -855,7 +904,7 @@ int rh_listwise_bwd(const float* u, const float* pos, int64_t ldp, const float* 
 
 /* ---- SINE sparse-interest retrieval (csrc/sine.hip) ------------------------------------------------------------------
  * B samples, S = seq_max_len positions, width E, T concept prototypes, K intentions, one attention head.
- * 1 <= S <= 64, 1 <= E <= 128, 1 <= T <= 64, 1 <= K <= min(T, 8), else RH_E_UNSUPPORTED; B = 0 returns at once.
+ * 1 <= S <= RH_SINE_MAX_S, 1 <= E <= RH_SINE_MAX_E, 1 <= T <= RH_SINE_MAX_T, 1 <= K <= min(T, RH_SINE_MAX_K), else RH_E_UNSUPPORTED; B = 0 returns at once.
  * rh_sine_supported and rh_sine_nchunks answer through a HOST int (*supported = 0 / 1, *nchunks = the chunk count of a batch
  * of B) and return a status like every entry point that takes a pointer.  mask (B, S) int32, 1 = kept, any pattern; every softmax over S is of a + -1e9 (1 - mask) formed in
  * fp32 as the reference forms it (a fully padded row comes out uniform).  No atomics: two runs give the same bits.
@@ -881,6 +930,10 @@ int rh_listwise_bwd(const float* u, const float* pos, int64_t ldp, const float* 
  * rh_sine_aggregate_bwd: g_v (B, E) -> g_xhat (B, S, E), g_a3 (B, S), g_phi (B, K, E) (through e and directly).
  * replaces: sine.py:122-128 after h_3 w_5 (softmax, mask term, einsum, F.normalize, softmax over k, einsum) and their
  *           autograd. */
+#define RH_SINE_MAX_S 64
+#define RH_SINE_MAX_E 128
+#define RH_SINE_MAX_T 64
+#define RH_SINE_MAX_K 8
 int rh_sine_supported(int S, int E, int T, int K, int* supported);
 int rh_sine_nchunks(int B, int* nchunks);
 int rh_sine_interest_fwd(const float* X, const float* Y, const float* a1, const float* a2, const int32_t* mask,
@@ -897,7 +950,7 @@ int rh_sine_aggregate_bwd(const float* xhat, const float* a3, const int32_t* mas
 
 /* ---- RQ-VAE residual quantizer (csrc/rq.hip) -----------------------------------------------------------------------------
  * Rows (N, E) fp32, L codebooks C_l (n_e[l], E).  C: HOST array of L device pointers, n_e: HOST array of L sizes (as
- * rh_cross_moe_pack takes its arrays).  1 <= E <= 128, 1 <= n_e[l] <= 1024, 1 <= L <= 8, else RH_E_UNSUPPORTED; N = 0
+ * rh_cross_moe_pack takes its arrays).  1 <= E <= RH_RQ_MAX_E, 1 <= n_e[l] <= RH_RQ_MAX_CODES, 1 <= L <= RH_RQ_MAX_L, else RH_E_UNSUPPORTED; N = 0
  * returns at once.  rh_rq_supported and rh_rq_nchunks answer through HOST ints (*supported = 0 / 1; *fwd_blocks = the rows
  * of sse_partial, *bwd_chunks = the rows of c_partial for N rows) and return a status like every entry point that takes a
  * pointer.  No atomics: two runs give the same bits.
@@ -919,6 +972,9 @@ int rh_sine_aggregate_bwd(const float* xhat, const float* a3, const int32_t* mas
  * replaces: VectorQuantizer.forward torch_rechub/models/generative/rqvae.py:241-274 (distance matrix, argmin, embedding
  *           gather, the two mse_loss calls, the straight-through sum) and ResidualVectorQuantizer.forward :382-398 (the
  *           residual updates, the stacks and the mean), and their autograd. */
+#define RH_RQ_MAX_E 128
+#define RH_RQ_MAX_CODES 1024
+#define RH_RQ_MAX_L 8
 int rh_rq_supported(int E, int L, const int* n_e, int* supported);
 int rh_rq_nchunks(int N, int* fwd_blocks, int* bwd_chunks);
 int rh_rq_fwd(const float* r_in, const float* const* C, const int* n_e, int N, int E, int L, int l0, int l1, int given,
@@ -932,13 +988,16 @@ int rh_rq_bwd(const float* x, const float* const* C, const int* n_e, const int32
  * bias), kmask (B, L) int32 nonzero = kept key or null.  pos_w (2 N - 1, H), ts_w (nb + 1, H) contiguous; N = max_seq_len,
  * nb = num_time_buckets, fn_log 0 sqrt / 1 log, minutes 0 / 1, alpha = 1 / sqrt(dqk).
  * rh_hstu_attn_fwd: out (B, L, H dv) = (silu(alpha q k^T + pos + ts) / N, masked to 0 above the diagonal and at dropped
- *   keys) v.  1 <= L <= min(N, 1024), dqk, dv <= 64, nb <= 1023, else RH_E_UNSUPPORTED.
+ *   keys) v.  1 <= L <= min(N, RH_HSTU_MAX_L), dqk, dv <= RH_HSTU_MAX_DH, nb <= RH_HSTU_MAX_BUCKETS, else RH_E_UNSUPPORTED.
  * rh_hstu_attn_bwd: g_out (B, L, H dv) -> the q / k / v columns of g_proj (B, L, ld) (the other columns are not
  *   written), g_pos_w (2 N - 1, H) and g_ts_w (nb + 1, H), through per-workgroup partials pos_part
  *   (rh_hstu_attn_nparts(B, L, H), L) and ts_part (same rows, nb + 1; may be null when td is) summed in a fixed order.
  *   No atomics: bitwise reproducible.
  * replaces: HSTULayer.forward torch_rechub/basic/layers.py:916-933 (matmul, rab, tril, masked_fill, silu, /N, matmul) with
  *           RelativeBucketedTimeAndPositionBias.forward utils/hstu_utils.py:150-185, and their autograd. */
+#define RH_HSTU_MAX_L 1024
+#define RH_HSTU_MAX_DH 64
+#define RH_HSTU_MAX_BUCKETS 1023
 int rh_hstu_attn_nparts(int B, int L, int H);
 int rh_hstu_attn_fwd(const float* proj, int64_t ld, int B, int L, int H, int dqk, int dv, const int64_t* td,
                      const int32_t* kmask, const float* pos_w, const float* ts_w, int N, int nb, int fn_log, int minutes,
@@ -980,10 +1039,12 @@ int rh_hstu_head_bwd(const float* h, const float* W, const float* bias, const in
  * rh_softmax_attn_bwd: g_out (B, L, H dh) -> g_q, g_k, g_v ((B, L, H, dh) views, row stride ldg), g_bias (nb, H) when
  *   bias is given, through part (rh_softmax_attn_nparts(B, L, H), L) per-workgroup partials summed in a fixed order;
  *   delta (B, H, L) workspace.  Weights recomputed tile by tile; nothing of size L x L is written.  No atomics.
- * 1 <= L <= min(N, 1024), 1 <= dh <= 128, H >= 1, nb >= 1 or no bias, else RH_E_UNSUPPORTED; B = 0 returns at once.
+ * 1 <= L <= min(N, RH_ATTN_MAX_L), 1 <= dh <= RH_ATTN_MAX_DH (both shared with rh_t5_attn_*), H >= 1, nb >= 1 or no bias, else RH_E_UNSUPPORTED; B = 0 returns at once.
  * replaces: HLLMTransformerBlock.forward torch_rechub/models/generative/hllm.py:69-88 (view / transpose, matmul, tril,
  *           masked_fill, bias add, softmax, dropout, matmul, transpose / contiguous) with RelPosBias.forward
  *           utils/hstu_utils.py:54-68, and their autograd. */
+#define RH_ATTN_MAX_L 1024
+#define RH_ATTN_MAX_DH 128
 int rh_softmax_attn_nparts(int B, int L, int H);
 int rh_softmax_attn_fwd(const float* q, const float* k, const float* v, int64_t ld, int B, int L, int H, int dh,
                         const float* bias, int N, int nb, float scale, float p_drop, int64_t* rng, int64_t* saved_ctr,
@@ -1019,14 +1080,18 @@ int rh_catalogue_ce_bwd(const float* u, const float* E, const int64_t* labels, c
  * (K > V is legal).  Inputs are assumed finite (NaN is not checked).  The products are exact f32 accumulated in k order
  * from zero on the 64 x 64 MFMA tile, the bias is added last: one score depends on q_i, x_j and D only -- not on M, V,
  * the position in a tile or the split.  nsplit ranges [V s / nsplit, V (s + 1) / nsplit) are scanned by separate
- * workgroups and merged under the same total order: every nsplit in [1, min(V, 1024)] gives the same bits.  No atomics.
- * 1 <= D <= 1024, 1 <= K <= 256, 0 <= S <= 1024, 1 <= V < 2^31, any M, else RH_E_UNSUPPORTED; M = 0 returns at once.
+ * workgroups and merged under the same total order: every nsplit in [1, min(V, RH_TOPK_MAX_SPLIT)] gives the same bits.  No atomics.
+ * 1 <= D <= RH_TOPK_MAX_D, 1 <= K <= RH_TOPK_MAX_K, 0 <= S <= RH_TOPK_MAX_S, 1 <= V < 2^31, any M, else RH_E_UNSUPPORTED; M = 0 returns at once.
  * rh_topk_supported and rh_topk_plan answer through HOST pointers (*supported = 0 / 1; *nsplit = the default split,
  * *workspace_bytes = 8 M nsplit K for it -- a caller that passes another nsplit sizes the workspace by the same formula)
  * and return a status like every entry point that takes a pointer.
  * replaces: Annoy.fit / Annoy.query of examples/matching/movielens_utils.py:17-42, torch.topk over the (B, V) scores of
  *           examples/matching/run_sbr.py:53 and the masked torch.topk of examples/generative/run_hstu_movielens.py:109-114,
  *           the builders of torch_rechub/serving (annoy, faiss, milvus). */
+#define RH_TOPK_MAX_D 1024
+#define RH_TOPK_MAX_K 256
+#define RH_TOPK_MAX_S 1024
+#define RH_TOPK_MAX_SPLIT 1024
 int rh_topk_supported(int D, int K, int S, int* supported);
 int rh_topk_plan(int M, int V, int K, int* nsplit, int64_t* workspace_bytes);
 int rh_topk_fwd(const float* q, int64_t ldq, const float* x, const float* bias, const int64_t* exclude, int S,
@@ -1049,7 +1114,8 @@ int rh_topk_fwd(const float* q, int64_t ldq, const float* x, const float* bias, 
  * (score descending, id ascending); with fewer than K candidates the tail is id -1, score -inf.  A score is computed
  * exactly as rh_topk_fwd computes it (it depends on q_i, x_j and D only), so with every list probed the result equals
  * rh_topk_fwd's on the un-grouped table bit for bit.  No atomics: two runs give the same bits.
- * 1 <= D <= 1024, 1 <= K <= 256, 0 <= S <= 1024, 1 <= nprobe <= 256, 1 <= V < 2^31, else RH_E_UNSUPPORTED; M = 0 returns
+ * 1 <= D <= RH_TOPK_MAX_D, 1 <= K <= RH_TOPK_MAX_K, 0 <= S <= RH_TOPK_MAX_S, 1 <= nprobe <= RH_IVF_MAX_NPROBE, 1 <= V < 2^31, else
+ * RH_E_UNSUPPORTED; M = 0 returns
  * at once.  rh_ivf_supported and rh_ivf_plan answer through HOST pointers: *supported = 0 / 1; *rows_per_tile = 64 up to
  * K = 128, 32 above; *grid = the bound above; *workspace_bytes = 8 M nprobe K (partials) + 4 M nprobe (pair) +
  * 8 (nlists + 2) (pair_off, tile_off).
@@ -1057,6 +1123,7 @@ int rh_topk_fwd(const float* q, int64_t ldq, const float* x, const float* bias, 
  * summed in a fixed order (bit-reproducible, no atomics) and divided once; an empty list keeps previous (nlists, D)[l].
  * replaces: FaissBuilder of torch_rechub/serving/faiss.py with index_type="IVF" (faiss's `IVF{nlists},Flat` with its
  *           k-means training, and `nprobe`). */
+#define RH_IVF_MAX_NPROBE 256
 int rh_ivf_supported(int D, int K, int S, int nprobe, int* supported);
 int rh_ivf_plan(int M, int nlists, int nprobe, int K, int* rows_per_tile, int64_t* grid, int64_t* workspace_bytes);
 int rh_ivf_scan(const float* q, int64_t ldq, const float* xs, const float* bias_s, const int32_t* row_id,
@@ -1068,23 +1135,25 @@ int rh_ivf_list_mean(const float* xs, const int32_t* list_off, const float* prev
 
 /* ---- session-based retrieval (csrc/session.hip) ---------------------------------------------------------------------
  * GRU recurrence of nn.GRU (gate order r, z, n) from the zero state: xw (B, T, 3H) = x W_ih^T (+ b_ih) for every step,
- * w_hh (3H, H) = weight_hh, b_hh (3H,) or null.  1 <= H <= rh_gru_max_hidden() (128), else RH_E_UNSUPPORTED.
+ * w_hh (3H, H) = weight_hh, b_hh (3H,) or null.  1 <= H <= RH_GRU_MAX_H, else RH_E_UNSUPPORTED.
  * rh_gru_fwd: h_all (B, T, H) every state; hu (B, T, 3H) the state products h_{t-1} W_hh^T + b_hh (for the backward).
  * rh_gru_bwd: g (B, T, H) gradient of h_all -> d_xw (B, T, 3H) the input-side pre-activation gradients
  *   [r | z | n] and d_s (B, T, 3H) the state-side ones [r | z | hu_n] (weight gradients: d_s^T h_prev, d_xw^T x).
  * replaces: nn.GRU / pack_padded_sequence (models/matching/narm.py:55-57, gru4rec.py:60) and its autograd. */
-int rh_gru_max_hidden(void);
+#define RH_GRU_MAX_H 128
 int rh_gru_fwd(const float* xw, const float* w_hh, const float* b_hh, int B, int T, int H, float* h_all, float* hu,
                void* stream);
 int rh_gru_bwd(const float* xw, const float* w_hh, const float* h_all, const float* hu, const float* g, int B, int T, int H,
                float* d_xw, float* d_s, void* stream);
 /* Additive attention pooling: s_l = sum_h w0_h sigmoid(P_lh + r_h), e_l = exp(s_l) mask_l, a_l = e_l / den with
  * den = sum_l e_l (floor = 0) or max(sum_l e_l, 1e-12) (floor = 1), out (B, Dx) = sum_l a_l X_l (+ add).  P (B, L, H),
- * r (B, H), w0 (H,), mask (B, L) float 0 / 1, X (B, L, Dx), add (B, Dx) or null.  1 <= L <= 1024, 1 <= H, Dx <= 4096.
+ * r (B, H), w0 (H,), mask (B, L) float 0 / 1, X (B, L, Dx), add (B, Dx) or null.  1 <= L <= RH_ATTN_POOL_MAX_L, 1 <= H, Dx <= RH_ATTN_POOL_MAX_W.
  * rh_attn_pool_fwd: e (B, L), sums (B, 2) = (sum, den) for the backward.
  * rh_attn_pool_bwd: g (B, Dx) -> dP (B, L, H), dr (B, H), dw0 (H,) (per-sample partials dw0_part (B, H) summed in a
  *   fixed order; zero at B = 0), dX (B, L, Dx) the pooling term only.
  * replaces: NARM's q / alpha / c_l (models/matching/narm.py:60-63), STAMP's a / m_a (stamp.py:66-67), and autograd. */
+#define RH_ATTN_POOL_MAX_L 1024
+#define RH_ATTN_POOL_MAX_W 4096
 int rh_attn_pool_fwd(const float* P, const float* r, const float* w0, const float* mask, const float* X, const float* add,
                      int B, int L, int H, int Dx, int floor_, float* out, float* e, float* sums, void* stream);
 int rh_attn_pool_bwd(const float* P, const float* r, const float* w0, const float* X, const float* e, const float* sums,
@@ -1102,7 +1171,7 @@ int rh_session_dropout_bwd(const float* g, int64_t n, float p, const int64_t* rn
                            void* stream);
 
 /* ---- SASRec: the transformer block around the causal attention, fused per row tile (csrc/sasrec.hip) -----------------
- * fp32.  M = B L rows of width D, 1 <= D <= 128, any M >= 1, else RH_E_UNSUPPORTED before any launch; M = 0 returns at
+ * fp32.  M = B L rows of width D, 1 <= D <= RH_SASREC_MAX_D, any M >= 1, else RH_E_UNSUPPORTED before any launch; M = 0 returns at
  * once.  seq (B, L) int64: the history ids, 0 = pad (m = seq != 0).  Every LayerNorm: mean, then the variance as the mean
  * of (x - mean)^2 (two passes), rstd = 1 / sqrt(var + eps), out = (x - mean) rstd gamma + beta; stats (M, 2) = the rows'
  * (mean, rstd).  An all-zero row gives exactly beta.  No atomics: every reduction over rows goes through one partial per
@@ -1142,6 +1211,7 @@ int rh_session_dropout_bwd(const float* g, int64_t n, float p, const int64_t* rn
  *   part (ceil(M / 64), 2, D) = per-workgroup (g_gamma, g_beta).
  * replaces: sasrec.py:100 (last_layernorm) and 156-157 (the two masked products and sums), torch.nn.LayerNorm of the
  *           selected rows in user_tower, and their autograd. */
+#define RH_SASREC_MAX_D 128
 int rh_sasrec_ntiles(int M, int D, int* ntiles);
 int rh_sasrec_input_fwd(const int64_t* seq, const float* e, int64_t e_bstride, int64_t e_rstride, const float* P, int B, int L,
                         int D, int max_len, float scale, float p_drop, int64_t* rng, int64_t* saved_ctr, float* x0, void* stream);
@@ -1194,20 +1264,23 @@ int rh_shard_narrow(const int64_t* idx, int64_t ld, int64_t n_rows, int F, int32
  *   g_u[r] over the item rows (r + k) mod B, g_v[r] over the user rows (r - k) mod B, ascending k.  As in ATen, the clamp
  *   takes no part in the gradient: dc/du = (v^ - c u / ||u||) / max(||u||, eps), and v^ / eps for a zero row.  w gets no
  *   gradient.
- *   1 <= D <= 1024, 1 <= K1 <= B, else RH_E_UNSUPPORTED.
+ *   1 <= D <= RH_TWOTOWER_MAX_D, 1 <= K1 <= B, else RH_E_UNSUPPORTED.
  * replaces: torch.cosine_similarity(u.unsqueeze(1), v, dim=2), the broadcast log-weight subtraction, the [index0, index1]
  *           gather and the division of YoutubeSBC.forward torch_rechub/models/matching/youtube_sbc.py:61-80, whose
  *           intermediates are (B, B) and (B, B, D).
  * rh_pair_cosine_fwd: pos (B,) = n(hu) . n(hp), neg (B,) = n(hu) . n(hn), n(x) = x / max(||x||, eps) row-wise; nrm (3, B) =
- *   the three norms saved.  rh_pair_cosine_bwd: g_pos, g_neg (B,) -> g_hu, g_hp, g_hn (B, D) contiguous.  1 <= D <= 1024.
+ *   the three norms saved.  rh_pair_cosine_bwd: g_pos, g_neg (B,) -> g_hu, g_hp, g_hn (B, D) contiguous.  1 <= D <= RH_TWOTOWER_MAX_D.
  * replaces: the three F.normalize calls and two multiply-sum reductions of FaceBookDSSM
  *           torch_rechub/models/matching/dssm_facebook.py:52-53,64,75-76.
  * rh_senet_fwd: x (B, F, D) with sample stride ldx (a sample's F D values contiguous), w1 (R, F), w2 (F, R) ->
  *   z (B, F) = mean_d x, h (B, R) = relu(w1 z), a (B, F) = relu(w2 h), y (B, F D) contiguous = x a[..., None].
  * rh_senet_bwd: g (B, F, D) with sample stride ldg -> g_x (B, F D) contiguous; w_partial (*nblocks of rh_twotower_nblocks, 2 R F) =
  *   per-workgroup sums [g_w1 (R, F) | g_w2 (F, R)] over the workgroup's samples in ascending order (g_w = rh_colsum of it).
- *   ReLU's derivative at 0 is 0.  1 <= R <= F <= 64, 1 <= D <= 256, else RH_E_UNSUPPORTED.
+ *   ReLU's derivative at 0 is 0.  1 <= R <= F <= RH_SENET_MAX_F, 1 <= D <= RH_SENET_MAX_D, else RH_E_UNSUPPORTED.
  * replaces: SENETLayer.forward torch_rechub/basic/layers.py:525-529 and its autograd. */
+#define RH_TWOTOWER_MAX_D 1024
+#define RH_SENET_MAX_F 64
+#define RH_SENET_MAX_D 256
 int rh_twotower_nblocks(int B, int* nblocks);
 int rh_band_logits_fwd(const float* u, int64_t ldu, const float* v, int64_t ldv, const float* w, int B, int D, int K1,
                        float temperature, float eps, float* logits, float* nu, float* nv, void* stream);
@@ -1239,16 +1312,17 @@ int rh_senet_bwd(const float* x, int64_t ldx, const float* w1, const float* w2, 
  *   of size Lq x Lk is written; no atomics.
  * The two nparts functions answer through a HOST int, like rh_twotower_nblocks.
  * Lq <= 8 (the decoder side) runs one wavefront per (sample, head), four to a workgroup; longer queries the 64 x 64 MFMA tile.
- * 1 <= Lq, Lk <= 1024, 1 <= dh <= 128, H >= 1, nb >= 1 or no bias, else RH_E_UNSUPPORTED before any launch; B = 0
+ * 1 <= Lq, Lk <= RH_ATTN_MAX_L, 1 <= dh <= RH_ATTN_MAX_DH, H >= 1, nb >= 1 or no bias, else RH_E_UNSUPPORTED before any launch; B = 0
  * returns at once.
  * replaces: T5Attention.forward (projection reshapes, matmul, compute_bias, the additive mask, softmax, dropout, matmul)
  *           of the T5 stack under torch_rechub/models/generative/tiger.py, and its autograd.
  * rh_add_rms_norm_fwd: h_new (M, D) = h + delta (delta null: h_new = h, and h_new may be null), y = h_new *
  *   rsqrt(mean(h_new^2) + eps) * w, rstd (M,) saved.  rh_add_rms_norm_bwd: g_y (M, D), g_res (M, D) or null (the gradient
  *   that reached h_new directly) -> g_h (M, D) (= g_delta); part (*nparts of rh_add_rms_norm_nparts(M), D) per-workgroup sums of g_w
- *   over rows in a fixed order (g_w = rh_colsum of it).  One wavefront per row, one pass.  1 <= D <= 1024, else
+ *   over rows in a fixed order (g_w = rh_colsum of it).  One wavefront per row, one pass.  1 <= D <= RH_RMS_NORM_MAX_D, else
  *   RH_E_UNSUPPORTED; M = 0 returns at once.
  * replaces: the residual add and T5LayerNorm.forward of every T5 sub-layer, and their autograd. */
+#define RH_RMS_NORM_MAX_D 1024
 int rh_t5_attn_nparts(int B, int Lq, int H, int* nparts);
 int rh_t5_attn_fwd(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv, int B, int Lq, int Lk, int H,
                    int dh, const uint8_t* key_mask, int causal, const float* bias, const int32_t* bucket, int nb, float p_drop,
@@ -1280,10 +1354,11 @@ int rh_add_rms_norm_bwd(const float* h_new, const float* w, const float* rstd, c
  * written on every call.  A dead beam and a node without children add nothing and index no edge array; a dead beam's row
  * is not read.  No atomics, no workspace, one launch: two runs give the same bits.
  * Outside the contract: a row with a NaN or a +inf, or without a finite value (the row of a dead beam may hold anything).
- * 1 <= K <= 64, 1 <= V <= 2^25, n_nodes >= 1, B K < 2^31; beyond that, on a null pointer, on ld < V or on an output that
+ * 1 <= K <= RH_BEAM_MAX_K, 1 <= V <= 2^25, n_nodes >= 1, B K < 2^31; beyond that, on a null pointer, on ld < V or on an output that
  * overlaps logits, running or node: RH_E_BADARG before any launch.  B = 0 returns at once.
  * replaces: per decoding step of generate (models/generative/tiger.py), the prefix_allowed_tokens_fn calls of
  *           Trie.get (utils/data.py:798-886), the (B K, V) mask, log_softmax and torch.topk over (B, K V). */
+#define RH_BEAM_MAX_K 64
 int rh_beam_step(const float* logits, int64_t ld, const float* running, const int32_t* node, const int32_t* child_off,
                  const int32_t* child_tok, const int32_t* child_node, int n_nodes, int B, int K, int V, float* running_out,
                  int32_t* parent_out, int32_t* tok_out, int32_t* node_out, int32_t* short_out, void* stream);
@@ -1301,9 +1376,13 @@ int rh_beam_step(const float* logits, int64_t ld, const float* running, const in
  * rh_cin_wgrad: partial (*nchunks of rh_cin_wgrad_chunks, Ho F Hp + Ho) = per-chunk sums [g_w (Ho, F Hp) | g_bias (Ho,)]
  *   over consecutive rows in a fixed order ([g_w | g_bias] = rh_colsum of it: bitwise reproducible).  *nchunks <= 16,
  *   a HOST int, like rh_sine_nchunks.
- * B >= 0, 1 <= D <= 128, 1 <= F <= 64, 1 <= Hp <= 256, 1 <= Ho <= 512, else RH_E_UNSUPPORTED before any launch; B = 0
+ * B >= 0, 1 <= D <= RH_CIN_MAX_D, 1 <= F <= RH_CIN_MAX_F, 1 <= Hp <= RH_CIN_MAX_HP, 1 <= Ho <= RH_CIN_MAX_HO, else RH_E_UNSUPPORTED before any launch; B = 0
  * returns at once.  LDS: forward and bwd 4 (64 (F|1 + Hp|1) + 8320) bytes each (115712 at the limits), wgrad 33280.
  * replaces: CIN.forward torch_rechub/basic/layers.py:359-362 (broadcast product, view, Conv1d, relu) and its autograd. */
+#define RH_CIN_MAX_D 128
+#define RH_CIN_MAX_F 64
+#define RH_CIN_MAX_HP 256
+#define RH_CIN_MAX_HO 512
 int rh_cin_wgrad_chunks(int B, int D, int F, int Hp, int Ho, int* nchunks);
 int rh_cin_fwd(const float* x0, int64_t x0_sample_stride, int64_t x0_field_stride, const float* h, int64_t h_sample_stride,
                const float* w, const float* bias, int B, int D, int F, int Hp, int Ho, float* y, void* stream);
@@ -1340,8 +1419,8 @@ int rh_cin_wgrad(const float* x0, int64_t x0_sample_stride, int64_t x0_field_str
  *           gauc_score metric.py:25-74, log_loss metric.py:198-200, and the per-batch .cpu() of the trainers' evaluate
  *           (trainers/ctr_trainer.py:157-172, match_trainer.py:225-236, mtl_trainer.py:238-252).
  *
- * List metrics.  pred (M, K) int64 with row stride ld >= K, 1 <= K <= 256; truth as CSR: truth_off (M + 1,) and truth_ids
- * (n_truth,) int64 (offsets are clamped into [0, n_truth]).  cutoffs: a HOST array of n_k <= 8 ints in [1, K].  gain (K,)
+ * List metrics.  pred (M, K) int64 with row stride ld >= K, 1 <= K <= RH_RANK_MAX_K; truth as CSR: truth_off (M + 1,) and truth_ids
+ * (n_truth,) int64 (offsets are clamped into [0, n_truth]).  cutoffs: a HOST array of n_k <= RH_RANK_MAX_CUTOFFS ints in [1, K].  gain (K,)
  * double = 1 / log2(j + 2) and ideal (K + 1,) double = its sequential prefix sums, ideal[0] = 0, both built by the caller.
  * Membership is equality of ids; duplicates on either side count as the reference counts them.  Per user with a
  * non-empty list and cut-off k: hit = #{j < k: pred[j] in truth}, mrr = 1 / (1 + first hit), recall = hit / len,
@@ -1352,6 +1431,8 @@ int rh_cin_wgrad(const float* x0, int64_t x0_sample_stride, int64_t x0_field_str
  * recall, precision, ndcg, or null.  partial: *partial_doubles of rh_rank_metrics_plan, which also reports (HOST
  * pointers) *stage = the truth ids staged through LDS at a time, the users per workgroup and the grid cap.
  * replaces: the loops of topk_metrics torch_rechub/basic/metric.py:142-176. */
+#define RH_RANK_MAX_K 256
+#define RH_RANK_MAX_CUTOFFS 8
 int rh_auc_plan(int64_t n, int* chunk, int* max_grid, int64_t* workspace_bytes);
 int rh_auc_keys(const float* pred, int64_t pred_stride, const int64_t* g, int64_t n, int64_t* keys, void* stream);
 int rh_auc_groups(const float* pred, int64_t pred_stride, const void* label, int label_dtype, const int64_t* g,
@@ -1365,14 +1446,14 @@ int rh_rank_metrics(const int64_t* pred, int64_t ld, int M, int K, const int64_t
                     int64_t n_truth, const int* cutoffs, int n_k, const double* gain, const double* ideal, double* partial,
                     int64_t* hits, int64_t* gts, double* sums, double* per_user, void* stream);
 
-/* Beyond-accuracy metrics over the same pred (M, K) int64, row stride ld >= K, 1 <= K <= 256, M >= 1; cutoffs: a HOST
- * array of 1 <= n_k <= 8 ints in [1, K], in any order, duplicates allowed; outputs are in the caller's order of cut-offs.
+/* Beyond-accuracy metrics over the same pred (M, K) int64, row stride ld >= K, 1 <= K <= RH_RANK_MAX_K, M >= 1; cutoffs: a HOST
+ * array of 1 <= n_k <= RH_RANK_MAX_CUTOFFS ints in [1, K], in any order, duplicates allowed; outputs are in the caller's order of cut-offs.
  * An id below 0 is an absent position (the -1 padding of rh_topk): the user's list is shorter there -- the reference run
  * on the rows with the negative entries removed.  K or n_k outside its range: RH_E_UNSUPPORTED before any launch; a
  * cut-off outside [1, K], ld < K, M < 1 or a null pointer: RH_E_BADARG before any launch.  No float atomics: a wavefront
  * adds its users one after the other, a workgroup its wavefronts in index order into one partial, one workgroup the
  * partials in index order -- two calls give the same bits, and a user's value does not depend on the other users.
- * rh_ild: intra-list diversity.  table (V, D) float32 with row stride table_stride >= D, V >= 1, 1 <= D <= 1024 (else
+ * rh_ild: intra-list diversity.  table (V, D) float32 with row stride table_stride >= D, V >= 1, 1 <= D <= RH_ILD_MAX_D (else
  *   RH_E_UNSUPPORTED before any launch).  Per user and cut-off k: the items are the entries among the first k with
  *   0 <= id < V (an id >= V is unknown and dropped; duplicates are separate entries); with n < 2 of them the user is left
  *   out; else, e_i the rows widened to double and u_i = e_i / max(||e_i||, 1e-10), the value is the mean over the pairs
@@ -1393,6 +1474,7 @@ int rh_rank_metrics(const int64_t* pred, int64_t ld, int M, int K, const int64_t
  *   rh_ild.
  * replaces: the loops of diversity_score torch_rechub/basic/metric.py:203-251, coverage_score metric.py:254-277 and
  *           novelty_score metric.py:280-313. */
+#define RH_ILD_MAX_D 1024
 int rh_ild_plan(int M, int* users_per_workgroup, int* max_grid, int64_t* partial_doubles);
 int rh_ild(const int64_t* pred, int64_t ld, int M, int K, const float* table, int64_t table_stride, int64_t V, int D,
            const int* cutoffs, int n_k, double* partial, double* sums, int64_t* counts, double* per_user, void* stream);

@@ -118,7 +118,7 @@ def test_pack_item_layout_is_the_headers():
 
 def test_header_macros_are_exposed():
     from torch_rechub_amd import _lib
-    assert len(vars(_lib.H)) == 19
+    assert len(vars(_lib.H)) == 92
     assert (_lib.H.RH_E_BADARG, _lib.H.RH_E_UNSUPPORTED) == (-1, -2)
     assert (_lib.H.RH_FLAG_INDEX_OOB, _lib.H.RH_FLAG_TARGET_OOB, _lib.H.RH_ERR_GATE_TIMEOUT, _lib.H.RH_FLAG_SESSION_EMPTY,
             _lib.H.RH_FLAG_SESSION_SHORT) == (1, 2, 64, 128, 256)
@@ -128,7 +128,7 @@ def test_header_macros_are_exposed():
 def test_status_and_value_returns_are_told_apart():
     """A function without a pointer parameter returns a value; rh_set_tuning is the exception and returns a status."""
     from torch_rechub_amd import _lib
-    assert len(_lib._VALUE_RETURNING) == 34 and "rh_set_tuning" not in _lib._VALUE_RETURNING
+    assert len(_lib._VALUE_RETURNING) == 32 and "rh_set_tuning" not in _lib._VALUE_RETURNING
     assert "rh_last_error" not in _lib._VALUE_RETURNING and "rh_linear_wgrad_workspace" in _lib._VALUE_RETURNING
     with pytest.raises(RuntimeError, match="rh_set_tuning failed"):
         _lib.call("rh_set_tuning", 3, 0)  # key 3 was removed: the header says it fails
@@ -159,3 +159,44 @@ def test_a_missing_argument_is_a_type_error():
     from torch_rechub_amd import _lib
     with pytest.raises(TypeError):
         _lib.call("rh_cross_max_layers")
+
+
+# Every kernel shape limit, as the kernels and ops.py held it before the header did.  A limit changes on purpose in two
+# places: include/rechub_hip.h and this table.
+SHAPE_LIMITS = {
+    "RH_EMBED_MAX_D": 128, "RH_EMBED_MAX_LR_FD": 12288, "RH_SEQ_POOL_MAX_D": 128, "RH_DIN_ATT_MAX_D": 128,
+    "RH_CROSS_MAX_D": 2048, "RH_CROSS_MIX_MAX_D": 2048, "RH_CROSS_MIX_MAX_E": 16,
+    "RH_CROSS_MOE_MAX_L": 8, "RH_CROSS_MOE_MAX_E": 16, "RH_CROSS_MOE_MAX_R": 64, "RH_CROSS_MOE_MAX_ER": 256,
+    "RH_DICE_MAX_C": 2048, "RH_BN_DICE_MAX_C": 512, "RH_DIN_ATT_L1_MAX_D": 16, "RH_DIN_ATT_L1_MAX_N": 256,
+    "RH_INBATCH_MAX_D": 1024, "RH_L2NORM_MIN_D": 4, "RH_L2NORM_MAX_D": 4096, "RH_CE_MAX_C": 1024,
+    "RH_HEAD_MAX_K": 1024, "RH_HEAD_BN_MAX_K": 256, "RH_LINEAR_BNACT_MAX_K": 1024,
+    "RH_CROSS_V2_MAX_M": 16384, "RH_CROSS_V2_MAX_D": 1024, "RH_WGRAD_LONG_MIN_B": 32768, "RH_BN_PRE_MAX_CHUNKS": 128,
+    "RH_ADAM_MAX_TENSORS": 128, "RH_ADAM_MAX_RING": 1024, "RH_AUGRU_MAX_D": 32, "RH_FFM_MAX_F": 64, "RH_FFM_MAX_D": 128,
+    "RH_CAPSULE_MAX_D": 64, "RH_CAPSULE_MAX_ID": 256, "RH_CAPSULE_MAX_IDD": 4096,
+    "RH_SA_MAX_D": 64, "RH_SA_MAX_LI": 1024, "RH_SA_MAX_ID": 1024,
+    "RH_LISTWISE_MAX_I": 16, "RH_LISTWISE_MAX_D": 64, "RH_LISTWISE_MAX_K": 1023,
+    "RH_SINE_MAX_S": 64, "RH_SINE_MAX_E": 128, "RH_SINE_MAX_T": 64, "RH_SINE_MAX_K": 8,
+    "RH_RQ_MAX_E": 128, "RH_RQ_MAX_CODES": 1024, "RH_RQ_MAX_L": 8,
+    "RH_HSTU_MAX_L": 1024, "RH_HSTU_MAX_DH": 64, "RH_HSTU_MAX_BUCKETS": 1023,
+    "RH_ATTN_MAX_L": 1024, "RH_ATTN_MAX_DH": 128, "RH_RMS_NORM_MAX_D": 1024,
+    "RH_TOPK_MAX_D": 1024, "RH_TOPK_MAX_K": 256, "RH_TOPK_MAX_S": 1024, "RH_TOPK_MAX_SPLIT": 1024, "RH_IVF_MAX_NPROBE": 256,
+    "RH_GRU_MAX_H": 128, "RH_ATTN_POOL_MAX_L": 1024, "RH_ATTN_POOL_MAX_W": 4096, "RH_SASREC_MAX_D": 128,
+    "RH_TWOTOWER_MAX_D": 1024, "RH_SENET_MAX_F": 64, "RH_SENET_MAX_D": 256, "RH_BEAM_MAX_K": 64,
+    "RH_CIN_MAX_D": 128, "RH_CIN_MAX_F": 64, "RH_CIN_MAX_HP": 256, "RH_CIN_MAX_HO": 512,
+    "RH_RANK_MAX_K": 256, "RH_RANK_MAX_CUTOFFS": 8, "RH_ILD_MAX_D": 1024,
+}
+
+
+def test_every_shape_limit_keeps_its_value():
+    from torch_rechub_amd import _lib
+    have = {k: v for k, v in vars(_lib.H).items() if "_MAX_" in k or "_MIN_" in k}
+    assert have == SHAPE_LIMITS
+    assert len(SHAPE_LIMITS) == 73
+
+
+def test_the_functions_that_returned_a_constant_are_gone():
+    from torch_rechub_amd import _lib
+    lib = _lib.load()
+    for name in ("rh_gru_max_hidden", "rh_augru_max_dim"):
+        assert name not in _lib.SIGNATURES and not hasattr(lib, name)
+    assert lib.rh_abi_version() == 1

@@ -19,6 +19,7 @@ import torch
 
 import beam_oracle as BO
 import tiger_oracle as O
+from torch_rechub_amd._lib import H
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -205,7 +206,7 @@ def test_logits_of_magnitude_1e4_need_the_max_subtraction():
     assert np.isfinite(got[0][got[1] >= 0]).all()
 
 
-@pytest.mark.parametrize("K,c", [(3, 1), (5, 2), (64, 3), (4, 4)])
+@pytest.mark.parametrize("K,c", [(3, 1), (5, 2), (H.RH_BEAM_MAX_K, 3), (4, 4)])
 def test_the_step_one_form(K, c):
     """All beams of a query on one node with c children, equal rows, running = [0, -1e9, ...]: the c children of beam 0,
     then beam 1 upwards at exactly -1e9 in (beam, token) order."""

@@ -17,12 +17,13 @@ import torch
 import beyond_cases as C
 import beyond_oracle as O
 from conftest import load_golden
+from torch_rechub_amd._lib import H
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 ILD_TOL, NOV_TOL = 2e-12, 4e-12
-WIDTHS = [1, 3, 4, 5, 15, 16, 17, 63, 64, 65, 255, 256, 257, 1023, 1024]
-LENGTHS = [1, 2, 63, 64, 65, 128, 129, 256]
+WIDTHS = [1, 3, 4, 5, 15, 16, 17, 63, 64, 65, 255, 256, 257, 1023, H.RH_ILD_MAX_D]
+LENGTHS = [1, 2, 63, 64, 65, 128, 129, H.RH_RANK_MAX_K]
 EIGHT = [7, 2, 9, 1, 9, 4, 3, 8]  # unsorted, with a duplicate
 
 

@@ -20,6 +20,7 @@ import cin_oracle as O
 from conftest import assert_state_follows_reference_trajectory, golden_batch, golden_state, load_golden
 from test_cin_host import CIN_CASES, XDEEPFM_MODELS, build_xdeepfm_model, cin_case
 from test_gpu_session_hllm_shapes import compare, poison_small_blocks
+from torch_rechub_amd._lib import H
 
 pytestmark = pytest.mark.gpu
 
@@ -203,21 +204,21 @@ def test_one_past_each_limit_is_refused():
         assert not ops.cin_layer_ok(z(B, F, D), z(B, Hp, D), z(Ho, F * Hp, 1), z(Ho))
         return ops.cin_layer(z(B, F, D), z(B, Hp, D), z(Ho, F * Hp, 1), z(Ho))
 
-    with pytest.raises(RuntimeError, match="embed_dim 129 unsupported"):
-        call(2, 129, 2, 2, 2)
-    with pytest.raises(RuntimeError, match="num_fields 65 unsupported"):
-        call(2, 4, 65, 2, 2)
-    with pytest.raises(RuntimeError, match="input channels 257 unsupported"):
-        call(2, 4, 2, 257, 2)
-    with pytest.raises(RuntimeError, match="output channels 513 unsupported"):
-        call(2, 4, 2, 2, 513)
+    with pytest.raises(RuntimeError, match=f"embed_dim {H.RH_CIN_MAX_D + 1} unsupported"):
+        call(2, H.RH_CIN_MAX_D + 1, 2, 2, 2)
+    with pytest.raises(RuntimeError, match=f"num_fields {H.RH_CIN_MAX_F + 1} unsupported"):
+        call(2, 4, H.RH_CIN_MAX_F + 1, 2, 2)
+    with pytest.raises(RuntimeError, match=f"input channels {H.RH_CIN_MAX_HP + 1} unsupported"):
+        call(2, 4, 2, H.RH_CIN_MAX_HP + 1, 2)
+    with pytest.raises(RuntimeError, match=f"output channels {H.RH_CIN_MAX_HO + 1} unsupported"):
+        call(2, 4, 2, 2, H.RH_CIN_MAX_HO + 1)
     torch.cuda.synchronize()
     # the largest shape on every axis but the batch runs, and the layer falls back to torch ops one past a limit
-    inputs, want, cpu32 = make_case(1, 128, 64, 256, 512, seed=8)
+    inputs, want, cpu32 = make_case(1, H.RH_CIN_MAX_D, H.RH_CIN_MAX_F, H.RH_CIN_MAX_HP, H.RH_CIN_MAX_HO, seed=8)
     check("limits", run_kernel(inputs), want, cpu32)
     torch.manual_seed(0)
-    cin = CIN(65, [4], split_half=False).to(dev())
-    x = torch.randn(3, 65, 4, device=dev())
+    cin = CIN(H.RH_CIN_MAX_F + 1, [4], split_half=False).to(dev())
+    x = torch.randn(3, H.RH_CIN_MAX_F + 1, 4, device=dev())
     want = cin.fc(torch_layer(x, x, cin.conv_layers[0].weight, cin.conv_layers[0].bias).sum(2))
     torch.testing.assert_close(cin(x), want, rtol=1e-5, atol=1e-6)
 

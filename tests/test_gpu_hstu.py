@@ -8,6 +8,8 @@ import torch
 from test_hstu_host import BUCKET_CFGS, adversarial_deltas, np_attention, np_attention_bwd, np_head
 from torch_rechub_amd.utils.hstu_utils import bucketize_time
 
+from torch_rechub_amd._lib import H
+
 pytestmark = pytest.mark.gpu
 
 
@@ -43,7 +45,9 @@ def run_attn(proj, pos_w, ts_w, td, mask, H, dqk, dv, N, nb, fn, div, unit, gout
 
 
 @pytest.mark.parametrize("shape", [(128, 200, 1, 50, 50, 200, 128, "log", 0.301, "seconds", True),
-                                   (16, 256, 8, 64, 64, 256, 128, "sqrt", 1.0, "minutes", True),
+                                   (16, 256, 8, H.RH_HSTU_MAX_DH, H.RH_HSTU_MAX_DH, 256, 128, "sqrt", 1.0, "minutes", True),
+                                   (2, H.RH_HSTU_MAX_L, 1, 4, 4, H.RH_HSTU_MAX_L, 8, "sqrt", 1.0, "minutes", True),
+                                   (2, 8, 1, 4, 4, 8, H.RH_HSTU_MAX_BUCKETS, "log", 0.301, "seconds", True),
                                    (16, 130, 2, 12, 10, 150, 64, "sqrt", 1.0, "minutes", False)])
 def test_attention_kernel_full_size_against_float64(shape):
     B, L, H, dqk, dv, N, nb, fn, div, unit, with_time = shape

@@ -9,6 +9,8 @@ import torch
 from conftest import assert_state_follows_reference_trajectory, golden_state, load_golden
 from test_interest_host import MATCH_MODELS, build_match_model, np_capsule, np_listwise, squash_bwd
 
+from torch_rechub_amd._lib import H
+
 pytestmark = pytest.mark.gpu
 
 
@@ -25,9 +27,19 @@ def rand_mask(B, L, g):
 # ---- kernels at full size against float64 numpy -----------------------------------------------------------------------
 @pytest.mark.parametrize("kind", [0, 1, 2])
 def test_capsule_kernel_full_size_against_float64(kind):
+    capsule_case(kind, 4096, 50, 4, 16, 3)
+
+
+@pytest.mark.parametrize("kind,I,D", [(0, 1, H.RH_CAPSULE_MAX_D), (1, H.RH_CAPSULE_MAX_ID // H.RH_CAPSULE_MAX_D, H.RH_CAPSULE_MAX_D),
+                                      (1, H.RH_CAPSULE_MAX_ID, 1), (2, H.RH_CAPSULE_MAX_IDD // H.RH_CAPSULE_MAX_D ** 2, H.RH_CAPSULE_MAX_D)])
+def test_capsule_kernel_at_each_limit(kind, I, D):
+    """D, I D and (type 2) I D D at the limits of include/rechub_hip.h, two samples of two positions."""
+    capsule_case(kind, 2, 2, I, D, 3)
+
+
+def capsule_case(kind, B, L, I, D, rt):
     from torch_rechub_amd import ops
     g = torch.Generator().manual_seed(10 + kind)
-    B, L, I, D, rt = 4096, 50, 4, 16, 3
     mask = rand_mask(B, L, g)
     e = 0.5 * torch.randn(B, L, D, generator=g)
     init = torch.randn(B, I, L, generator=g) if kind == 0 else None

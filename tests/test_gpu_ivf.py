@@ -7,6 +7,7 @@ import torch
 
 import ivf_oracle as IO
 import topk_oracle as O
+from torch_rechub_amd._lib import H
 
 pytestmark = pytest.mark.gpu
 
@@ -126,7 +127,7 @@ def test_exclusions(S):
             assert not np.isin(ids[i][ids[i] >= 0], exclude[i]).any()
 
 
-@pytest.mark.parametrize("K", [1, 128, 129, 256])
+@pytest.mark.parametrize("K", [1, 128, 129, H.RH_TOPK_MAX_K])
 def test_k_range_and_k_above_the_union(K):
     """Query 0 probes 64 + 1 rows (fewer than K from 128 on), query 1 probes 129 + 65 + 63 = 257 rows."""
     q, x, bias = O.int_data(500 + K, 2, 7, sum(LENGTHS), with_bias=True)

@@ -12,6 +12,7 @@ import torch
 
 import metric_oracle as O
 from conftest import load_golden
+from torch_rechub_amd._lib import H
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -333,7 +334,7 @@ def truth_of_lengths(rng, lengths, K):
     return [rng.integers(0, max(3 * K, 2 * n), n).tolist() for n in lengths]
 
 
-@pytest.mark.parametrize("K", [1, 2, 63, 64, 65, 128, 255, 256])
+@pytest.mark.parametrize("K", [1, 2, 63, 64, 65, 128, 255, H.RH_RANK_MAX_K])
 def test_list_metrics_over_the_width_range(ops, rank_plan, K):
     s = rank_plan[0]
     rng = np.random.default_rng(K)

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from test_rqvae_host import draw_inputs, np_rq_backward, np_rq_forward
+from torch_rechub_amd._lib import H
 
 pytestmark = pytest.mark.gpu
 
@@ -20,9 +21,9 @@ MIN_GAP, MAX_EXCLUDED = 1e-4, 0.02
 #          N    E    sizes            seed
 CASES = [(130, 8, [3], 50),                  # one level
          (64, 20, [5, 7, 4], 51),            # unequal sizes, E not a multiple of 4
-         (33, 128, [1024, 1024], 52),        # both upper limits
+         (33, H.RH_RQ_MAX_E, [H.RH_RQ_MAX_CODES] * 2, 52),  # both upper limits
          (512, 32, [256, 256, 256], 53),     # the example's shape
-         (257, 64, [16] * 8, 54),            # eight levels
+         (257, 64, [16] * H.RH_RQ_MAX_L, 54),  # the most levels
          (70, 1, [4, 4], 55)]                # E = 1
 
 

@@ -610,7 +610,7 @@ def update_gate64(inp, states):
 @pytest.mark.parametrize("D", [4, 8, 16, 32])
 def test_augru_attention_weights_and_state_bias_together(D, T):
     from torch_rechub_amd import _lib
-    assert D <= _lib.call("rh_augru_max_dim")
+    assert D <= _lib.H.RH_AUGRU_MAX_D
     for B in (spw(D) - 1, spw(D), spw(D) + 1):
         inp, want = augru_case(B, T, D)
         got = augru_hip(inp)

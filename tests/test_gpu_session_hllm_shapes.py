@@ -20,6 +20,7 @@ import torch
 from test_gpu_session import chunked_ce64
 from test_hllm_host import np_softmax_attention, np_softmax_attention_bwd, torch_attention
 from test_session_host import np_attn_pool, np_attn_pool_bwd, np_catalogue_ce, np_gru, np_gru_bwd
+from torch_rechub_amd._lib import H
 
 pytestmark = pytest.mark.gpu
 
@@ -220,7 +221,7 @@ POOL_SHAPES = {
     "L1024_H40_D257": (4, 1024, 40, 257, True),
     "L50_H4096_D30": (3, 50, 4096, 30, False),
     "L20_H30_D4096": (3, 20, 30, 4096, True),
-    "guard_L1024_H4096_D4096": (2, 1024, 4096, 4096, False),
+    "guard_L1024_H4096_D4096": (2, H.RH_ATTN_POOL_MAX_L, H.RH_ATTN_POOL_MAX_W, H.RH_ATTN_POOL_MAX_W, False),
 }
 
 
@@ -568,7 +569,7 @@ ATTN_CASES = {
     "L129_dh127": (2, 129, 2, 127, 129, 32, True, None),
     "L65_N1000_nb1500": (2, 65, 2, 16, 1000, 1500, False, None),   # buckets 0, 1, 2, 4, 5, ...: most table rows untouched
     "L129_scale": (2, 129, 2, 33, 129, 32, False, 0.37),
-    "guard_L1024_dh128_nb1024": (1, 1024, 1, 128, 1024, 1024, False, None),
+    "guard_L1024_dh128_nb1024": (1, H.RH_ATTN_MAX_L, 1, H.RH_ATTN_MAX_DH, H.RH_ATTN_MAX_L, 1024, False, None),
 }
 
 

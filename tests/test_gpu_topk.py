@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import topk_oracle as O
+from torch_rechub_amd._lib import H
 
 pytestmark = pytest.mark.gpu
 
@@ -50,8 +51,8 @@ INT_CASES = [(1, 1, 1, 1, False),        # the smallest problem
              (1, 130, 1, 10, False),     # K > V = 1
              (3, 1, 4097, 1, True),      # D = 1: almost every score tied
              (1, 64, 4097, 200, False),  # the examples' K; 32-row blocks
-             (65, 7, 4097, 256, True),   # the largest K, three row blocks of 32
-             (3, 64, 65, 256, False),    # K > V at the largest K
+             (65, 7, 4097, H.RH_TOPK_MAX_K, True),   # the largest K, three row blocks of 32
+             (3, 64, 65, H.RH_TOPK_MAX_K, False),    # K > V at the largest K
              (65, 130, 63, 64, True)]
 
 

@@ -245,7 +245,7 @@ def test_entry_points_refuse_the_first_shape_past_each_limit():
     from torch_rechub_amd import _lib
     null = ctypes.c_void_p(0)
     fake = ctypes.c_void_p(4096)  # never dereferenced: validation fails first
-    assert _lib.call("rh_gru_max_hidden") == 128
+    assert _lib.H.RH_GRU_MAX_H == 128
     with pytest.raises(RuntimeError, match="hidden size 129 unsupported"):
         _lib.call("rh_gru_fwd", fake, fake, null, 4, 3, 129, fake, fake, null)
     with pytest.raises(RuntimeError, match="hidden size 129 unsupported"):

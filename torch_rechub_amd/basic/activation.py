@@ -6,7 +6,7 @@ NEURONS per row (dim=1) and the "variance" is the SUM of (x-mean)^2 + eps over t
 import torch
 from torch import nn
 
-from .. import ops
+from .. import _lib, ops
 
 
 class Dice(nn.Module):
@@ -18,7 +18,7 @@ class Dice(nn.Module):
         self.alpha = nn.Parameter(torch.randn(1))
 
     def forward(self, x):
-        if x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and x.shape[1] <= 2048:
+        if x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and x.shape[1] <= _lib.H.RH_DICE_MAX_C:
             return ops.dice(x, self.alpha, self.epsilon)  # one pass instead of ten elementwise kernels
         ops.require_hip(x)
         mu = x.mean(dim=1, keepdim=True)

@@ -8,12 +8,15 @@ kernels read ``embedding.weight`` in place through a pointer table.
 import torch
 from torch import nn
 
+from .. import _lib
 
-KERNEL_DIMS = (4, 8, 16, 32, 64, 128)  # row widths the gather / optimizer kernels handle (16-byte lanes, 2^k per row)
+
+# 4, 8, ..., RH_EMBED_MAX_D
+KERNEL_DIMS = tuple(4 << i for i in range((_lib.H.RH_EMBED_MAX_D // 4).bit_length()))  # row widths the gather / optimizer kernels handle (16-byte lanes, 2^k per row)
 
 
 def padded_dim(embed_dim):
-    """Physical row width of a table of logical width ``embed_dim``: the next kernel width (None beyond 128)."""
+    """Physical row width of a table of logical width ``embed_dim``: the next kernel width (None beyond RH_EMBED_MAX_D)."""
     for d in KERNEL_DIMS:
         if embed_dim <= d:
             return d
@@ -33,7 +36,7 @@ class PaddedEmbedding(nn.Embedding):
     def __init__(self, num_embeddings, embedding_dim, padding_idx=None):
         phys = padded_dim(embedding_dim)
         if phys is None:
-            raise ValueError(f"embed_dim {embedding_dim} > 128 has no HIP gather kernel")
+            raise ValueError(f"embed_dim {embedding_dim} > {_lib.H.RH_EMBED_MAX_D} has no HIP gather kernel")
         super().__init__(num_embeddings, phys, padding_idx=padding_idx)
         self.logical_dim = int(embedding_dim)
         self.embedding_dim = int(embedding_dim)

@@ -27,14 +27,14 @@ import math
 import torch
 from torch import nn
 
-from .. import ops, sharding
+from .. import _lib, ops, sharding
 from .activation import Dice, activation_layer
 from .features import DenseFeature, SequenceFeature, SparseFeature
 
 
 def _fusable_dim(d):
     q = d // 4
-    return d % 4 == 0 and 1 <= q <= 32 and (q & (q - 1)) == 0
+    return d % 4 == 0 and 4 <= d <= _lib.H.RH_SEQ_POOL_MAX_D and (q & (q - 1)) == 0
 
 
 def _as_index(t):
@@ -271,7 +271,7 @@ class EmbeddingLayer(nn.Module):
         if sharding.is_sharded(table):
             raise RuntimeError("torch_rechub_amd: shared_rows on a row-sharded table is not supported")
         if not _fusable_dim(int(table.weight.shape[1])):
-            raise RuntimeError(f"torch_rechub_amd: sequence embed_dim={features[0].embed_dim} has no HIP kernel (> 128)")
+            raise RuntimeError(f"torch_rechub_amd: sequence embed_dim={features[0].embed_dim} has no HIP kernel (> {_lib.H.RH_SEQ_POOL_MAX_D})")
         parts = [_as_index(x[f.name]) for f in features]
         B = int(parts[0].shape[0])
         if len(parts) == 1 and parts[0].dim() == 1:
@@ -336,7 +336,7 @@ class EmbeddingLayer(nn.Module):
         for (dim, sharded), members in groups.items():
             if not _fusable_dim(dim):
                 raise RuntimeError(f"torch_rechub_amd: embed_dim={dim} has no HIP gather kernel "
-                                   "(1 .. 128 supported, widths other than 4, 8, 16, 32, 64, 128 through padded storage); "
+                                   f"(1 .. {_lib.H.RH_EMBED_MAX_D} supported, widths that are no power-of-two multiple of 4 through padded storage); "
                                    "refusing to fall back to a CPU/eager path")
             feas = [table_feas[i] for i in members]
             if sharded:
@@ -348,7 +348,7 @@ class EmbeddingLayer(nn.Module):
         for i, fea in enumerate(table_feas):
             if isinstance(fea, SequenceFeature):
                 if not _fusable_dim(self.phys_dim(fea)):
-                    raise RuntimeError(f"torch_rechub_amd: sequence embed_dim={fea.embed_dim} has no HIP kernel (> 128)")
+                    raise RuntimeError(f"torch_rechub_amd: sequence embed_dim={fea.embed_dim} has no HIP kernel (> {_lib.H.RH_SEQ_POOL_MAX_D})")
                 table = self.table_of(fea)
                 idx = _as_index(x[fea.name])
                 if not sharding.is_sharded(table):
@@ -451,7 +451,7 @@ class MLP(nn.Module):
                 x = ops.bn_relu_dropout(h, bn, mods[i + 3].p if mods[i + 3].training else 0.0, stats=stats)
                 i += 4
             elif (i + 2 < len(mods) and isinstance(mods[i], nn.Linear) and type(mods[i + 1]) is nn.BatchNorm1d and
-                  type(mods[i + 2]) is Dice and self._bn_ok(mods[i + 1], x) and mods[i].out_features <= 512 and
+                  type(mods[i + 2]) is Dice and self._bn_ok(mods[i + 1], x) and mods[i].out_features <= _lib.H.RH_BN_DICE_MAX_C and
                   not (torch.is_grad_enabled() and not mods[i + 1].training)):
                 # Linear -> BatchNorm1d -> Dice (DIN's ActivationUnit): the normalisation is folded into the Dice passes
                 head = self.head_after(mods, i + 3, mods[i].out_features, mods[i + 1], mods[i + 2])
@@ -675,7 +675,7 @@ class CrossNetMix(nn.Module):
             v = v.view(B, E, r).transpose(0, 1)  # (E, B, r)
             v = torch.tanh(torch.bmm(v, C.transpose(1, 2)))  # (E, B, r): C_e v
             uv = torch.bmm(v, U.transpose(1, 2))  # (E, B, d): U_e v
-            if d <= 2048 and E <= 16:
+            if d <= _lib.H.RH_CROSS_MIX_MAX_D and E <= _lib.H.RH_CROSS_MIX_MAX_E:
                 # bias + Hadamard with x0 + gate-weighted expert mix + residual: one pass (csrc/crossmix.hip)
                 xl = ops.cross_mix_epilogue(x0, xl, uv, gate, self.bias[i])
             else:
@@ -688,7 +688,8 @@ class SENETLayer(nn.Module):
     """SENET field gating: a = relu(W2 relu(W1 mean_d(x))), out = x * a[..., None] (reference layers.py:509-529).
 
     ``fused`` (off unless the owner sets it: the SENet DSSM does, FiBiNET does not) runs the whole layer as one HIP launch
-    each way (csrc/twotower.hip) for a HIP float32 (B, F, D) block with F <= 64, D <= 256."""
+    each way (csrc/twotower.hip) for a HIP float32 (B, F, D) block with F <= RH_SENET_MAX_F, D <= RH_SENET_MAX_D
+    (ops.senet_ok)."""
 
     def __init__(self, num_fields, reduction_ratio=3):
         super().__init__()
@@ -804,7 +805,8 @@ class MultiInterestSA(nn.Module):
         B, L, D = (int(v) for v in seq_emb.shape)
         if not ops.sa_supported(L, self.interest_num, D):
             raise RuntimeError(f"torch_rechub_amd: MultiInterestSA with L={L}, interest_num={self.interest_num}, "
-                               f"embed_dim={D} has no HIP kernel (D <= 64, L * interest_num <= 1024)")
+                               f"embed_dim={D} has no HIP kernel (D <= {_lib.H.RH_SA_MAX_D}, "
+                               f"L * interest_num <= {_lib.H.RH_SA_MAX_LI})")
         H = torch.tanh(ops.linear(seq_emb.reshape(B * L, D), self.W1.t()))
         A = ops.linear(H, self.W2.t()).view(B, L, self.interest_num)
         return ops.sa_pool(A, seq_emb, None if mask is None else _interest_mask(mask, B, L))

@@ -269,7 +269,7 @@ __global__ __launch_bounds__(RH_WAVE) void augru_bwd_kernel(const float* __restr
 
 }  // namespace
 
-extern "C" int rh_augru_max_dim(void) { return 32; }
+static_assert(RH_AUGRU_MAX_D == 32, "the widths the entry points accept end at RH_AUGRU_MAX_D");
 
 extern "C" int rh_augru_fwd(const float* xw, const float* attn, const float* U, const float* state_bias, int B, int T,
                             int D, float* h_all, void* stream) {

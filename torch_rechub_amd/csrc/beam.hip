@@ -22,7 +22,7 @@
 
 namespace {
 
-constexpr int kBeamMaxK = 64;     // one list chunk per wavefront; a beam index takes 6 bits of an id
+constexpr int kBeamMaxK = RH_BEAM_MAX_K;     // one list chunk per wavefront; a beam index takes 6 bits of an id
 constexpr int kBeamEdgeBits = 25; // the offset of an edge inside its node takes the other 25 (distinct tokens: < V)
 
 struct BeamArgs {

@@ -30,10 +30,10 @@
 
 namespace {
 
-constexpr int kMaxF = 64;
-constexpr int kMaxHp = 256;
-constexpr int kMaxHo = 512;
-constexpr int kMaxD = 128;
+constexpr int kMaxF = RH_CIN_MAX_F;
+constexpr int kMaxHp = RH_CIN_MAX_HP;
+constexpr int kMaxHo = RH_CIN_MAX_HO;
+constexpr int kMaxD = RH_CIN_MAX_D;
 constexpr int kRowGrid = 1024;   // row tiles per launch; a workgroup loops over the rest
 constexpr int kMaxChunks = 16;   // wgrad: M chunks (rows of the partial workspace)
 constexpr int kFillTiles = 512;  // wgrad: workgroups aimed for (2 per CU)

@@ -233,7 +233,7 @@ int dispatch_bwd(int epl, int L, const float* x0, int64_t x0s, const float* x, i
 
 // max layers one call can take for feature width d (register budget: EPL*L <= 32)
 extern "C" int rh_cross_max_layers(int d) {
-  if (d <= 0 || d > 2048) return 0;
+  if (d <= 0 || d > RH_CROSS_MAX_D) return 0;
   const int epl = epl_for(d);
   if (epl <= 8) return 4;
   if (epl == 16) return 2;
@@ -244,7 +244,7 @@ extern "C" int rh_cross_fwd(const float* x0, int64_t x0_stride, const float* x, 
                             const float* w, const float* b, int B, int d, int L, float* out,
                             int64_t out_stride, void* stream) {
   RH_REQUIRE(x0 && x && w && b && out, RH_E_BADARG, "rh_cross_fwd: null pointer");
-  RH_REQUIRE(d > 0 && d <= 2048, RH_E_UNSUPPORTED, "rh_cross_fwd: d=%d unsupported (1..2048)", d);
+  RH_REQUIRE(d > 0 && d <= RH_CROSS_MAX_D, RH_E_UNSUPPORTED, "rh_cross_fwd: d=%d unsupported (1..%d)", d, RH_CROSS_MAX_D);
   RH_REQUIRE(L >= 1 && L <= rh_cross_max_layers(d), RH_E_UNSUPPORTED,
              "rh_cross_fwd: L=%d layers per call unsupported for d=%d (max %d; chain calls)", L, d,
              rh_cross_max_layers(d));
@@ -279,7 +279,7 @@ extern "C" int rh_cross_bwd(const float* x0, int64_t x0_stride, const float* x, 
                             float* wb_partials, void* stream) {
   RH_REQUIRE(x0 && x && w && b && g_out && g_x && wb_partials, RH_E_BADARG, "rh_cross_bwd: null pointer");
   RH_REQUIRE(sum_into_gx || g_x0, RH_E_BADARG, "rh_cross_bwd: g_x0 is null but sum_into_gx = 0");
-  RH_REQUIRE(d > 0 && d <= 2048, RH_E_UNSUPPORTED, "rh_cross_bwd: d=%d unsupported (1..2048)", d);
+  RH_REQUIRE(d > 0 && d <= RH_CROSS_MAX_D, RH_E_UNSUPPORTED, "rh_cross_bwd: d=%d unsupported (1..%d)", d, RH_CROSS_MAX_D);
   RH_REQUIRE(L >= 1 && L <= rh_cross_max_layers(d), RH_E_UNSUPPORTED,
              "rh_cross_bwd: L=%d layers per call unsupported for d=%d (max %d; chain calls)", L, d,
              rh_cross_max_layers(d));

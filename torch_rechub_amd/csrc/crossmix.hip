@@ -14,7 +14,7 @@
 namespace {
 
 constexpr int kWaves = RH_BLOCK / RH_WAVE;
-constexpr int kMaxExperts = 16;
+constexpr int kMaxExperts = RH_CROSS_MIX_MAX_E;
 
 unsigned wave_grid(int B) {
   int64_t g = ((int64_t)B + kWaves - 1) / kWaves;
@@ -183,8 +183,8 @@ extern "C" int rh_cross_v2_epilogue_bwd(const float* x0, const float* y, const f
 extern "C" int rh_cross_mix_epilogue_fwd(const float* x0, const float* xl, const float* uv, const float* gate,
                                          const float* bias, int B, int d, int E, float* out, void* stream) {
   RH_REQUIRE(x0 && xl && uv && gate && bias && out, RH_E_BADARG, "rh_cross_mix_epilogue_fwd: null pointer");
-  RH_REQUIRE(d >= 1 && d <= 2048 && E >= 1 && E <= kMaxExperts && B >= 0, RH_E_UNSUPPORTED,
-             "rh_cross_mix_epilogue_fwd: d=%d E=%d unsupported (d <= 2048, E <= %d)", d, E, kMaxExperts);
+  RH_REQUIRE(d >= 1 && d <= RH_CROSS_MIX_MAX_D && E >= 1 && E <= kMaxExperts && B >= 0, RH_E_UNSUPPORTED,
+             "rh_cross_mix_epilogue_fwd: d=%d E=%d unsupported (d <= %d, E <= %d)", d, E, RH_CROSS_MIX_MAX_D, kMaxExperts);
   if (B == 0) return 0;
   MixArgs a{x0, xl, uv, gate, bias, nullptr, out, nullptr, nullptr, B, d, E, nullptr};
   int rc = mix_dispatch<false>(a, reinterpret_cast<hipStream_t>(stream));
@@ -222,8 +222,8 @@ static int mix_bwd_impl(const float* x0, const float* uv, const float* gate, con
                         int E, float* g_x0, float* g_uv, float* g_gate, float* g_bias_partial, void* stream) {
   RH_REQUIRE(x0 && uv && gate && bias && g && g_x0 && g_uv && g_gate, RH_E_BADARG,
              "rh_cross_mix_epilogue_bwd: null pointer");
-  RH_REQUIRE(d >= 1 && d <= 2048 && E >= 1 && E <= kMaxExperts && B >= 0, RH_E_UNSUPPORTED,
-             "rh_cross_mix_epilogue_bwd: d=%d E=%d unsupported (d <= 2048, E <= %d)", d, E, kMaxExperts);
+  RH_REQUIRE(d >= 1 && d <= RH_CROSS_MIX_MAX_D && E >= 1 && E <= kMaxExperts && B >= 0, RH_E_UNSUPPORTED,
+             "rh_cross_mix_epilogue_bwd: d=%d E=%d unsupported (d <= %d, E <= %d)", d, E, RH_CROSS_MIX_MAX_D, kMaxExperts);
   if (B == 0) return 0;
   MixArgs a{x0, nullptr, uv, gate, bias, g, g_x0, g_uv, g_gate, B, d, E, g_bias_partial};
   int rc = mix_dispatch<true>(a, reinterpret_cast<hipStream_t>(stream));

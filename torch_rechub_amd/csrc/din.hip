@@ -615,8 +615,8 @@ int att_dispatch(const AttArgs& a, hipStream_t s) {
 
 int att_check(const char* who, int B, int L, int D) {
   RH_REQUIRE(B >= 0 && L >= 1, RH_E_BADARG, "%s: bad shape B=%d L=%d", who, B, L);
-  RH_REQUIRE(D > 0 && D % 4 == 0 && D <= 128 && ((D / 4) & (D / 4 - 1)) == 0, RH_E_UNSUPPORTED,
-             "%s: embed_dim %d unsupported (need 4,8,16,32,64,128)", who, D);
+  RH_REQUIRE(D > 0 && D % 4 == 0 && D <= RH_DIN_ATT_MAX_D && ((D / 4) & (D / 4 - 1)) == 0, RH_E_UNSUPPORTED,
+             "%s: embed_dim %d unsupported (a power-of-two multiple of 4 up to %d)", who, D, RH_DIN_ATT_MAX_D);
   return 0;
 }
 
@@ -710,7 +710,7 @@ extern "C" int rh_dice_fwd(const float* x, const float* alpha, float eps, int64_
                            const float* bn_shift, float* out, void* stream) {
   RH_REQUIRE(x && alpha && out && N >= 0 && C >= 1, RH_E_BADARG, "rh_dice_fwd: bad arguments");
   RH_REQUIRE((bn_scale == nullptr) == (bn_shift == nullptr), RH_E_BADARG, "rh_dice_fwd: scale and shift go together");
-  RH_REQUIRE(C <= 2048, RH_E_UNSUPPORTED, "rh_dice_fwd: %d neurons unsupported (max 2048)", C);
+  RH_REQUIRE(C <= RH_DICE_MAX_C, RH_E_UNSUPPORTED, "rh_dice_fwd: %d neurons unsupported (max %d)", C, RH_DICE_MAX_C);
   if (N == 0) return 0;
   DiceArgs a{x, nullptr, alpha, eps, N, C, out, nullptr, bn_scale, bn_shift, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   int rc = dice_dispatch<0>(a, reinterpret_cast<hipStream_t>(stream));
@@ -722,7 +722,7 @@ extern "C" int rh_dice_fwd(const float* x, const float* alpha, float eps, int64_
 extern "C" int rh_dice_bwd(const float* x, const float* g, const float* alpha, float eps, int64_t N, int C, float* gx,
                            float* alpha_partial, void* stream) {
   RH_REQUIRE(x && g && alpha && gx && alpha_partial && N >= 0 && C >= 1, RH_E_BADARG, "rh_dice_bwd: bad arguments");
-  RH_REQUIRE(C <= 2048, RH_E_UNSUPPORTED, "rh_dice_bwd: %d neurons unsupported (max 2048)", C);
+  RH_REQUIRE(C <= RH_DICE_MAX_C, RH_E_UNSUPPORTED, "rh_dice_bwd: %d neurons unsupported (max %d)", C, RH_DICE_MAX_C);
   DiceArgs a{x, g, alpha, eps, N, C, gx, alpha_partial, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   int rc = dice_dispatch<1>(a, reinterpret_cast<hipStream_t>(stream));
   if (rc) return rc;
@@ -735,7 +735,7 @@ extern "C" int rh_bn_dice_bwd_stats(const float* h, const float* g, const float*
                                     void* stream) {
   RH_REQUIRE(h && g && alpha && stat && gamma && col_partial && alpha_partial && N >= 1 && C >= 1, RH_E_BADARG,
              "rh_bn_dice_bwd_stats: bad arguments");
-  RH_REQUIRE(C <= 512, RH_E_UNSUPPORTED, "rh_bn_dice_bwd_stats: %d neurons unsupported (max 512)", C);
+  RH_REQUIRE(C <= RH_BN_DICE_MAX_C, RH_E_UNSUPPORTED, "rh_bn_dice_bwd_stats: %d neurons unsupported (max %d)", C, RH_BN_DICE_MAX_C);
   DiceArgs a{h, g, alpha, eps, N, C, nullptr, alpha_partial, stat + 4 * (int64_t)C, stat + 5 * (int64_t)C, stat, gamma,
              col_partial, nullptr, nullptr, nullptr};
   int rc = dice_dispatch<2>(a, reinterpret_cast<hipStream_t>(stream));
@@ -747,7 +747,7 @@ extern "C" int rh_bn_dice_bwd_stats(const float* h, const float* g, const float*
 extern "C" int rh_bn_dice_bwd_apply(const float* h, const float* g, const float* alpha, float eps, int64_t N, int C,
                                     const float* stat, const float* gamma, float* dh, void* stream) {
   RH_REQUIRE(h && g && alpha && stat && gamma && dh && N >= 1 && C >= 1, RH_E_BADARG, "rh_bn_dice_bwd_apply: bad arguments");
-  RH_REQUIRE(C <= 512, RH_E_UNSUPPORTED, "rh_bn_dice_bwd_apply: %d neurons unsupported (max 512)", C);
+  RH_REQUIRE(C <= RH_BN_DICE_MAX_C, RH_E_UNSUPPORTED, "rh_bn_dice_bwd_apply: %d neurons unsupported (max %d)", C, RH_BN_DICE_MAX_C);
   DiceArgs a{h, g, alpha, eps, N, C, dh, nullptr, stat + 4 * (int64_t)C, stat + 5 * (int64_t)C, stat, gamma, nullptr, nullptr, nullptr, nullptr};
   int rc = dice_dispatch<3>(a, reinterpret_cast<hipStream_t>(stream));
   if (rc) return rc;
@@ -760,7 +760,7 @@ extern "C" int rh_bn_dice_head_fwd(const float* h, const float* alpha, float eps
                                    void* stream) {
   RH_REQUIRE(h && alpha && bn_scale && bn_shift && head_w && out && N >= 0 && C >= 1, RH_E_BADARG,
              "rh_bn_dice_head_fwd: bad arguments");
-  RH_REQUIRE(C <= 512, RH_E_UNSUPPORTED, "rh_bn_dice_head_fwd: %d neurons unsupported (max 512)", C);
+  RH_REQUIRE(C <= RH_BN_DICE_MAX_C, RH_E_UNSUPPORTED, "rh_bn_dice_head_fwd: %d neurons unsupported (max %d)", C, RH_BN_DICE_MAX_C);
   if (N == 0) return 0;
   DiceArgs a{h, nullptr, alpha, eps, N, C, out, nullptr, bn_scale, bn_shift, nullptr, nullptr, nullptr, head_w, head_b,
              nullptr};
@@ -775,7 +775,7 @@ extern "C" int rh_bn_dice_head_bwd_stats(const float* h, const float* g, const f
                                          float* alpha_partial, float* head_partial, void* stream) {
   RH_REQUIRE(h && g && alpha && stat && gamma && head_w && col_partial && alpha_partial && head_partial && N >= 1 && C >= 1,
              RH_E_BADARG, "rh_bn_dice_head_bwd_stats: bad arguments");
-  RH_REQUIRE(C <= 512, RH_E_UNSUPPORTED, "rh_bn_dice_head_bwd_stats: %d neurons unsupported (max 512)", C);
+  RH_REQUIRE(C <= RH_BN_DICE_MAX_C, RH_E_UNSUPPORTED, "rh_bn_dice_head_bwd_stats: %d neurons unsupported (max %d)", C, RH_BN_DICE_MAX_C);
   DiceArgs a{h, g, alpha, eps, N, C, nullptr, alpha_partial, stat + 4 * (int64_t)C, stat + 5 * (int64_t)C, stat, gamma,
              col_partial, head_w, nullptr, head_partial};
   int rc = dice_dispatch<2, true>(a, reinterpret_cast<hipStream_t>(stream));
@@ -789,7 +789,7 @@ extern "C" int rh_bn_dice_head_bwd_apply(const float* h, const float* g, const f
                                          void* stream) {
   RH_REQUIRE(h && g && alpha && stat && gamma && head_w && dh && N >= 1 && C >= 1, RH_E_BADARG,
              "rh_bn_dice_head_bwd_apply: bad arguments");
-  RH_REQUIRE(C <= 512, RH_E_UNSUPPORTED, "rh_bn_dice_head_bwd_apply: %d neurons unsupported (max 512)", C);
+  RH_REQUIRE(C <= RH_BN_DICE_MAX_C, RH_E_UNSUPPORTED, "rh_bn_dice_head_bwd_apply: %d neurons unsupported (max %d)", C, RH_BN_DICE_MAX_C);
   DiceArgs a{h, g, alpha, eps, N, C, dh, nullptr, stat + 4 * (int64_t)C, stat + 5 * (int64_t)C, stat, gamma, nullptr, head_w,
              nullptr, nullptr};
   int rc = dice_dispatch<3, true>(a, reinterpret_cast<hipStream_t>(stream));

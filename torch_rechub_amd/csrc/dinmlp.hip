@@ -149,7 +149,8 @@ __global__ __launch_bounds__(RH_BLOCK) void din_att_l1_kernel(const AttL1Args a)
 }  // namespace
 
 extern "C" int rh_din_att_l1_supported(int D, int N) {
-  return ((D == 4 || D == 8 || D == 16) && N >= 64 && N <= 256 && N % 64 == 0) ? 1 : 0;
+  static_assert(RH_DIN_ATT_L1_MAX_D == 16, "the widths below end at RH_DIN_ATT_L1_MAX_D");
+  return ((D == 4 || D == 8 || D == 16) && N >= 64 && N <= RH_DIN_ATT_L1_MAX_N && N % 64 == 0) ? 1 : 0;
 }
 
 // rows per statistics chunk (= per workgroup): ~3 workgroups per CU, a multiple of 32
@@ -164,7 +165,7 @@ extern "C" int rh_din_att_l1_fwd(const float* hist, int64_t hist_stride, const f
                                  void* stream) {
   RH_REQUIRE(hist && tgt && W && z, RH_E_BADARG, "rh_din_att_l1_fwd: null pointer");
   RH_REQUIRE(rh_din_att_l1_supported(D, N), RH_E_UNSUPPORTED,
-             "rh_din_att_l1_fwd: D=%d N=%d unsupported (D in {4, 8, 16}, N a multiple of 64 up to 256)", D, N);
+             "rh_din_att_l1_fwd: D=%d N=%d unsupported (D in {4, 8, 16}, N a multiple of 64 up to %d)", D, N, RH_DIN_ATT_L1_MAX_N);
   RH_REQUIRE(B >= 0 && L >= 1 && hist_stride >= (int64_t)L * D && tgt_stride >= D, RH_E_BADARG,
              "rh_din_att_l1_fwd: bad shape B=%d L=%d", B, L);
   if (B == 0) return 0;

@@ -620,8 +620,8 @@ int dispatch_bwd(const EmbedBwdArgs& a, hipStream_t s) {
 int check_common(const char* who, const int64_t* fdesc, const int64_t* idesc, int B, int F, int D) {
   RH_REQUIRE(fdesc != nullptr && idesc != nullptr, RH_E_BADARG, "%s: null descriptor", who);
   RH_REQUIRE(B >= 0 && F > 0, RH_E_BADARG, "%s: bad shape B=%d F=%d", who, B, F);
-  RH_REQUIRE(D > 0 && D % 4 == 0 && D <= 128 && ((D / 4) & (D / 4 - 1)) == 0, RH_E_UNSUPPORTED,
-             "%s: embed_dim %d unsupported by the fused kernel (need 4,8,16,32,64,128)", who, D);
+  RH_REQUIRE(D > 0 && D % 4 == 0 && D <= RH_EMBED_MAX_D && ((D / 4) & (D / 4 - 1)) == 0, RH_E_UNSUPPORTED,
+             "%s: embed_dim %d unsupported by the fused kernel (a power-of-two multiple of 4 up to %d)", who, D, RH_EMBED_MAX_D);
   RH_REQUIRE(F <= 65535, RH_E_UNSUPPORTED, "%s: too many fields (%d)", who, F);
   return 0;
 }
@@ -645,8 +645,8 @@ extern "C" int rh_embed_fwd(const int64_t* fdesc, const int64_t* idesc, int idx_
              dense_col, n_dense);
   RH_REQUIRE(n_dense == 0 || ddesc != nullptr, RH_E_BADARG, "rh_embed_fwd: n_dense > 0 but ddesc is null");
   RH_REQUIRE(lr_out == nullptr || lr_w != nullptr, RH_E_BADARG, "rh_embed_fwd: lr_out without lr_w");
-  RH_REQUIRE(lr_out == nullptr || (int64_t)F * D <= 12288, RH_E_UNSUPPORTED,
-             "rh_embed_fwd: fused LR keeps the F*D = %lld weights in LDS (<= 12288 floats)", (long long)F * D);
+  RH_REQUIRE(lr_out == nullptr || (int64_t)F * D <= RH_EMBED_MAX_LR_FD, RH_E_UNSUPPORTED,
+             "rh_embed_fwd: fused LR keeps the F*D = %lld weights in LDS (<= %d floats)", (long long)F * D, RH_EMBED_MAX_LR_FD);
   if (B == 0) return 0;
   EmbedFwdArgs a{fdesc, idesc, ddesc, B, F, D, n_dense, dense_col, out, out_stride, lr_w, lr_b, lr_out, fm_out, s_out, err_flag};
   if (lr_out == nullptr) a.lr_w = nullptr;

@@ -19,9 +19,9 @@
 
 namespace {
 
-constexpr int kMaxF = 64;
+constexpr int kMaxF = RH_FFM_MAX_F;
 constexpr int kMaxP = kMaxF * (kMaxF - 1) / 2;
-constexpr int kMaxD = 128;
+constexpr int kMaxD = RH_FFM_MAX_D;
 constexpr int kCenRows = 64;  // samples per partial row of the CEN u gradient
 
 struct FfmArgs {

@@ -86,7 +86,7 @@ struct GemmArgs {
 };
 
 constexpr int kProMaxSlabs = 32;  // PRO: slabs per thread and round of loads of the statistics prologue (common.h)
-constexpr int kProMaxK = 1024;
+constexpr int kProMaxK = RH_LINEAR_BNACT_MAX_K;
 
 static __device__ __forceinline__ float4 load4_guard(const float* row, int k, int K, bool row_ok) {
   if (!row_ok || k >= K) return f4_zero();
@@ -641,7 +641,7 @@ extern "C" int rh_linear_dgrad_bnbwd(const float* g, int64_t ldg, const float* w
   return 0;
 }
 
-constexpr int kCrossV2MaxM = 16384, kCrossV2MaxD = 1024;  // = ops.CROSS_V2_MAX_B / CROSS_V2_MAX_D
+constexpr int kCrossV2MaxM = RH_CROSS_V2_MAX_M, kCrossV2MaxD = RH_CROSS_V2_MAX_D;
 
 // One CrossNetV2 layer forward in ONE launch (round 5; reference CrossNetV2.forward, torch_rechub/basic/layers.py:440-444:
 // x <- x0 * (W_l x) + b_l + x): y (M, d) = x W^T on the f32-MFMA tile GEMM, and from the accumulators out = x0 * y + b + x.
@@ -650,7 +650,7 @@ constexpr int kCrossV2MaxM = 16384, kCrossV2MaxD = 1024;  // = ops.CROSS_V2_MAX_
 extern "C" int rh_cross_v2_fwd(const float* x0, const float* x, const float* w, const float* b, int M, int d, float* y,
                                float* out, void* stream) {
   RH_REQUIRE(x0 && x && w && b && y && out, RH_E_BADARG, "rh_cross_v2_fwd: null pointer");
-  // (all operands contiguous: row stride d; the limits of the tile GEMM at batch size, ops.CROSS_V2_MAX_B / _MAX_D)
+  // (all operands contiguous: row stride d; the limits of the tile GEMM at batch size)
   RH_REQUIRE(M >= 1 && M <= kCrossV2MaxM && d >= 1 && d <= kCrossV2MaxD, RH_E_UNSUPPORTED,
              "rh_cross_v2_fwd: bad shape M=%d d=%d (1 <= M <= %d, 1 <= d <= %d)", M, d, kCrossV2MaxM, kCrossV2MaxD);
   GemmArgs a{};

@@ -24,9 +24,10 @@
 
 namespace {
 
-constexpr int kMaxDh = 64;      // dqk, dv <= 64
-constexpr int kMaxL = 1024;
+constexpr int kMaxDh = RH_HSTU_MAX_DH;  // dqk, dv
+constexpr int kMaxL = RH_HSTU_MAX_L;
 constexpr int kMaxBuckets = 1024;  // num_time_buckets + 1
+static_assert(kMaxBuckets - 1 == RH_HSTU_MAX_BUCKETS, "the table has num_time_buckets + 1 rows");
 
 __device__ __forceinline__ float silu_f(float x) { return x / (1.f + expf(-x)); }
 __device__ __forceinline__ float dsilu_f(float x) {

@@ -239,7 +239,9 @@ __global__ __launch_bounds__(RH_BLOCK) void capsule_bwd_kernel(const float* __re
 
 constexpr int kWgradChunks = 32;
 constexpr int kWgradTile = 16;        // samples staged in LDS at a time
-constexpr int kWgradMaxPerThread = 16;  // I*D*D <= 4096
+constexpr int kWgradMaxPerThread = 16;
+static_assert(RH_BLOCK == RH_CAPSULE_MAX_ID && RH_BLOCK * kWgradMaxPerThread == RH_CAPSULE_MAX_IDD,
+              "one thread per capsule element, kWgradMaxPerThread weight gradients each");
 
 // partial[c, l, j, k] = sum over the samples b of chunk c (in order) of sw[b, j/D, l] d_s[b, j] e[b, l, k]
 __global__ __launch_bounds__(RH_BLOCK) void capsule_wgrad_kernel(const float* __restrict__ gs, const float* __restrict__ sw,
@@ -288,17 +290,19 @@ __global__ __launch_bounds__(RH_BLOCK) void capsule_wgrad_kernel(const float* __
 int caps_check(const char* who, const CapsGeom& g) {
   RH_REQUIRE(g.B >= 0 && g.L >= 1 && g.I >= 1 && g.D >= 1 && g.type >= 0 && g.type <= 2 && g.iters >= 1, RH_E_BADARG,
              "%s: bad shape B=%d L=%d I=%d D=%d type=%d routing_times=%d", who, g.B, g.L, g.I, g.D, g.type, g.iters);
-  RH_REQUIRE(g.D <= 64 && g.I * g.D <= 256 && g.S >= 1 && (g.type != 2 || g.I * g.D * g.D <= 4096), RH_E_UNSUPPORTED,
-             "%s: L=%d I=%d D=%d (type %d) has no HIP kernel (D <= 64, I*D <= 256, I*D*D <= 4096 for type 2, "
-             "the routing state of one sample within 64 KB of LDS)", who, g.L, g.I, g.D, g.type);
+  RH_REQUIRE(g.D <= RH_CAPSULE_MAX_D && g.I * g.D <= RH_CAPSULE_MAX_ID && g.S >= 1 && (g.type != 2 || g.I * g.D * g.D <= RH_CAPSULE_MAX_IDD),
+             RH_E_UNSUPPORTED,
+             "%s: L=%d I=%d D=%d (type %d) has no HIP kernel (D <= %d, I*D <= %d, I*D*D <= %d for type 2, "
+             "the routing state of one sample within 64 KB of LDS)", who, g.L, g.I, g.D, g.type, RH_CAPSULE_MAX_D, RH_CAPSULE_MAX_ID,
+             RH_CAPSULE_MAX_IDD);
   return 0;
 }
 
 }  // namespace
 
 extern "C" int rh_capsule_supported(int L, int I, int D, int type) {
-  if (L < 1 || I < 1 || D < 1 || D > 64 || I * D > 256 || type < 0 || type > 2) return 0;
-  if (type == 2 && I * D * D > 4096) return 0;
+  if (L < 1 || I < 1 || D < 1 || D > RH_CAPSULE_MAX_D || I * D > RH_CAPSULE_MAX_ID || type < 0 || type > 2) return 0;
+  if (type == 2 && I * D * D > RH_CAPSULE_MAX_IDD) return 0;
   return caps_samples_per_block(L, I, D, type) >= 1;
 }
 
@@ -306,7 +310,7 @@ extern "C" int rh_capsule_fwd(const float* U, const float* E, const float* W, co
                               int L, int I, int D, int type, int routing_times, float* cap, float* sw, float* s,
                               void* stream) {
   CapsGeom g{B, L, I, D, type, routing_times, 0};
-  if (D >= 1 && I >= 1 && L >= 1 && I * D <= 256) g.S = caps_samples_per_block(L, I, D, type);
+  if (D >= 1 && I >= 1 && L >= 1 && I * D <= RH_CAPSULE_MAX_ID) g.S = caps_samples_per_block(L, I, D, type);
   if (int rc = caps_check("rh_capsule_fwd", g)) return rc;
   RH_REQUIRE(mask && cap && (type == 2 ? (E && W) : U != nullptr), RH_E_BADARG, "rh_capsule_fwd: null pointer");
   if (B == 0) return 0;
@@ -320,7 +324,7 @@ extern "C" int rh_capsule_fwd(const float* U, const float* E, const float* W, co
 extern "C" int rh_capsule_bwd(const float* g_cap, const float* s, const float* sw, const float* W, int B, int L, int I, int D,
                               int type, float* g_u, float* g_e, float* g_s, void* stream) {
   CapsGeom g{B, L, I, D, type, 3, 0};
-  if (D >= 1 && I >= 1 && L >= 1 && I * D <= 256) g.S = caps_samples_per_block(L, I, D, type);
+  if (D >= 1 && I >= 1 && L >= 1 && I * D <= RH_CAPSULE_MAX_ID) g.S = caps_samples_per_block(L, I, D, type);
   if (int rc = caps_check("rh_capsule_bwd", g)) return rc;
   RH_REQUIRE(g_cap && s && sw && (type == 2 ? (W && g_e && g_s) : g_u != nullptr), RH_E_BADARG,
              "rh_capsule_bwd: null pointer");
@@ -339,7 +343,9 @@ extern "C" int rh_capsule_wgrad_nchunks(int B) { return B < 1 ? 1 : (B < kWgradC
 extern "C" int rh_capsule_wgrad(const float* g_s, const float* sw, const float* E, int B, int L, int I, int D, float* partial,
                                 void* stream) {
   RH_REQUIRE(g_s && sw && E && partial, RH_E_BADARG, "rh_capsule_wgrad: null pointer");
-  RH_REQUIRE(B >= 1 && L >= 1 && I >= 1 && D >= 1 && D <= 64 && I * D <= 256 && I * D * D <= 4096, RH_E_UNSUPPORTED,
+  RH_REQUIRE(B >= 1 && L >= 1 && I >= 1 && D >= 1 && D <= RH_CAPSULE_MAX_D && I * D <= RH_CAPSULE_MAX_ID &&
+                 I * D * D <= RH_CAPSULE_MAX_IDD,
+             RH_E_UNSUPPORTED,
              "rh_capsule_wgrad: B=%d L=%d I=%d D=%d unsupported", B, L, I, D);
   CapsGeom g{B, L, I, D, 2, 3, 1};
   const int nch = rh_capsule_wgrad_nchunks(B);
@@ -355,7 +361,8 @@ extern "C" int rh_capsule_wgrad(const float* g_s, const float* sw, const float* 
 namespace {
 
 constexpr int kLwWaves = RH_BLOCK / RH_WAVE;
-constexpr int kSaMaxLI = 1024;  // L * I per sample (the softmax weights of one sample in LDS)
+constexpr int kSaMaxLI = RH_SA_MAX_LI;
+static_assert(RH_SA_MAX_ID == kSaMaxLI, "gk holds a sample's I * D gradients in an array of the same size");  // L * I per sample (the softmax weights of one sample in LDS)
 
 __global__ __launch_bounds__(RH_WAVE) void sa_fwd_kernel(const float* __restrict__ A, const float* __restrict__ E,
                                                           const int32_t* __restrict__ mask, int B, int L, int I, int D,
@@ -443,13 +450,13 @@ unsigned lw_grid(int B) {
 
 }  // namespace
 
-extern "C" int rh_sa_supported(int L, int I, int D) { return L >= 1 && I >= 1 && D >= 1 && D <= 64 && L * I <= kSaMaxLI && I * D <= kSaMaxLI; }
+extern "C" int rh_sa_supported(int L, int I, int D) { return L >= 1 && I >= 1 && D >= 1 && D <= RH_SA_MAX_D && L * I <= kSaMaxLI && I * D <= RH_SA_MAX_ID; }
 
 extern "C" int rh_sa_pool_fwd(const float* A, const float* E, const int32_t* mask, int B, int L, int I, int D, float* P,
                               float* out, void* stream) {
   RH_REQUIRE(A && E && P && out, RH_E_BADARG, "rh_sa_pool_fwd: null pointer");
   RH_REQUIRE(B >= 0 && rh_sa_supported(L, I, D), RH_E_UNSUPPORTED,
-             "rh_sa_pool_fwd: L=%d I=%d D=%d has no HIP kernel (D <= 64, L*I <= %d)", L, I, D, kSaMaxLI);
+             "rh_sa_pool_fwd: L=%d I=%d D=%d has no HIP kernel (D <= %d, L*I <= %d)", L, I, D, RH_SA_MAX_D, kSaMaxLI);
   if (B == 0) return 0;
   hipLaunchKernelGGL(sa_fwd_kernel, dim3(sa_grid(B)), dim3(RH_WAVE), 0, reinterpret_cast<hipStream_t>(stream), A, E, mask, B,
                      L, I, D, P, out);
@@ -472,7 +479,8 @@ extern "C" int rh_sa_pool_bwd(const float* P, const float* E, const float* g, in
 // List-wise scoring: one wavefront per sample, lane = embedding column (D <= 64).
 namespace {
 
-constexpr int kMaxInterests = 16;
+constexpr int kMaxInterests = RH_LISTWISE_MAX_I;
+static_assert(RH_WAVE == RH_LISTWISE_MAX_D, "lane = embedding column");
 constexpr float kNormEps = 1e-12f;
 
 struct ListwiseArgs {
@@ -564,8 +572,9 @@ __global__ __launch_bounds__(RH_BLOCK) void listwise_kernel(const ListwiseArgs a
 extern "C" int rh_listwise_fwd(const float* u, const float* pos, int64_t ldp, const float* neg, int B, int I, int D, int K,
                                float temperature, float* logits, int32_t* best, float* nrm, void* stream) {
   RH_REQUIRE(u && pos && logits && best && nrm && (neg || K == 0) && ldp >= D, RH_E_BADARG, "rh_listwise_fwd: bad arguments");
-  RH_REQUIRE(B >= 0 && I >= 1 && I <= kMaxInterests && D >= 1 && D <= RH_WAVE && K >= 0 && K <= 1023, RH_E_UNSUPPORTED,
-             "rh_listwise_fwd: I=%d D=%d K=%d has no HIP kernel (I <= %d, D <= 64, K < 1024)", I, D, K, kMaxInterests);
+  RH_REQUIRE(B >= 0 && I >= 1 && I <= kMaxInterests && D >= 1 && D <= RH_LISTWISE_MAX_D && K >= 0 && K <= RH_LISTWISE_MAX_K, RH_E_UNSUPPORTED,
+             "rh_listwise_fwd: I=%d D=%d K=%d has no HIP kernel (I <= %d, D <= %d, K <= %d)", I, D, K, kMaxInterests,
+             RH_LISTWISE_MAX_D, RH_LISTWISE_MAX_K);
   if (B == 0) return 0;
   ListwiseArgs a{u, pos, ldp, neg, nullptr, nullptr, nullptr, logits, best, nrm, nullptr, nullptr, nullptr, B, I, D, K,
                  temperature};
@@ -579,7 +588,7 @@ extern "C" int rh_listwise_bwd(const float* u, const float* pos, int64_t ldp, co
                                float* g_pos, float* g_neg, void* stream) {
   RH_REQUIRE(u && pos && best && nrm && g && g_u && g_pos && (K == 0 || (neg && g_neg)) && ldp >= D, RH_E_BADARG,
              "rh_listwise_bwd: bad arguments");
-  RH_REQUIRE(B >= 0 && I >= 1 && I <= kMaxInterests && D >= 1 && D <= RH_WAVE && K >= 0 && K <= 1023, RH_E_UNSUPPORTED,
+  RH_REQUIRE(B >= 0 && I >= 1 && I <= kMaxInterests && D >= 1 && D <= RH_LISTWISE_MAX_D && K >= 0 && K <= RH_LISTWISE_MAX_K, RH_E_UNSUPPORTED,
              "rh_listwise_bwd: I=%d D=%d K=%d unsupported", I, D, K);
   if (B == 0) return 0;
   ListwiseArgs a{u, pos, ldp, neg, g, best, nrm, nullptr, nullptr, nullptr, g_u, g_pos, g_neg, B, I, D, K, temperature};

@@ -21,7 +21,7 @@
 
 namespace {
 
-constexpr int kIvfMaxProbe = 256;
+constexpr int kIvfMaxProbe = RH_IVF_MAX_NPROBE;
 
 struct IvfArgs {
   TopkScanArgs s;           // x, bias = the rows grouped by list; exclude = original ids; nlist = nprobe

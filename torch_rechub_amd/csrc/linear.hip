@@ -185,7 +185,7 @@ __global__ __launch_bounds__(RH_BLOCK) void wgrad_reduce_kernel(const WgradArgs 
 // written and summed.  Long reductions (DIN's B * L = 409 600 rows): g_long_blocks, so that every SIMD holds enough
 // wavefronts to cover the latency of the operand loads (tuning knob RH_TUNE_WGRAD_BLOCKS).
 int g_long_blocks = 1024;   // negative: -value workgroups with the default build of the kernel (A/B)
-constexpr int kLongRows = 32768;
+constexpr int kLongRows = RH_WGRAD_LONG_MIN_B;
 // Batch-sized reductions (B < 32768) take the 128-register, one-LDS-tile build of the long reductions, not the round-1 form
 // (78 VGPRs + 128 AGPRs, four LDS tiles).  Beside the optimizer's resident sweep (2 wavefronts of 112 registers per SIMD) only
 // ONE wavefront of the 206-register build fits on a SIMD where the launch's ~500 workgroups want two: measured 28.5 us alone,
@@ -233,7 +233,8 @@ void wgrad_plan(int B, int N, int K, int* tiles_n, int* tiles_k, int* S, int* rp
 // ---------------------------------------------------------------------------------------------
 constexpr int kHeadLanes = 16;                       // lanes per row
 constexpr int kHeadRows = RH_BLOCK / kHeadLanes;     // rows per block pass
-constexpr int kHeadMaxV4 = 16;                       // float4 per lane -> K <= 1024
+constexpr int kHeadMaxV4 = 16;                       // float4 per lane
+static_assert(4 * kHeadLanes * kHeadMaxV4 == RH_HEAD_MAX_K, "a row's K values are dealt over kHeadLanes lanes");
 
 __device__ __forceinline__ float group_sum16(float v) {
   v += __shfl_xor(v, 8);
@@ -313,7 +314,8 @@ struct HeadBnFwdArgs {
   const float* t;
   float* loss_partial;
 };
-constexpr int kHeadBnMaxK = 256;
+constexpr int kHeadBnMaxK = RH_HEAD_BN_MAX_K;
+static_assert(4 * kHeadLanes * 4 == kHeadBnMaxK, "rh_head_bwd_bn: at most four float4 per lane");
 constexpr int kHeadBnMaxSlabs = 32;  // slabs per thread and round of loads (common.h, rh_combine_slabs)
 
 __global__ __launch_bounds__(RH_BLOCK) void head_bnact_fwd_kernel(const HeadBnFwdArgs a) {
@@ -1034,7 +1036,7 @@ static int head_bwd_impl(const float* h, int64_t ldh, const float* w, const floa
   if (bn != nullptr) {
     a.bn_z = bn->z, a.bn_stat = bn->stat, a.bn_gamma = bn->gamma, a.bn_beta = bn->beta, a.bn_rng = bn->rng;
     a.bn_ctr = bn->ctr, a.bn_partial = bn->partial, a.bn_p = bn->p, a.bn_relu = bn->relu;
-    RH_REQUIRE(need <= 4, RH_E_UNSUPPORTED, "rh_head_bwd_bn: K=%d too wide (max %d)", K, 4 * kHeadLanes * 4);
+    RH_REQUIRE(need <= 4, RH_E_UNSUPPORTED, "rh_head_bwd_bn: K=%d too wide (max %d)", K, kHeadBnMaxK);
     if (need <= 1) hipLaunchKernelGGL((head_bwd_kernel<1, true>), grid, block, 0, st, a);
     else if (need <= 2) hipLaunchKernelGGL((head_bwd_kernel<2, true>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((head_bwd_kernel<4, true>), grid, block, 0, st, a);

@@ -18,7 +18,8 @@
 namespace {
 
 constexpr int kWaves = RH_BLOCK / RH_WAVE;
-constexpr int kMaxPerLane = 16;  // D <= 1024
+constexpr int kMaxPerLane = 16;
+static_assert(RH_WAVE * kMaxPerLane == RH_INBATCH_MAX_D, "a row's D values are dealt over one wavefront");
 
 struct InbatchArgs {
   const float* u;  // (B, D), row stride ldu
@@ -251,8 +252,8 @@ __global__ __launch_bounds__(RH_BLOCK) void ce_bwd_kernel(const float* __restric
 
 extern "C" int rh_l2norm_fwd(const float* x, int64_t ldx, int B, int d, float eps, float* y, float* nrm, void* stream) {
   RH_REQUIRE(x && y && nrm, RH_E_BADARG, "rh_l2norm_fwd: null pointer");
-  RH_REQUIRE(B >= 0 && d >= 4 && d % 4 == 0 && d <= 4096 && ldx >= d && ldx % 4 == 0, RH_E_UNSUPPORTED,
-             "rh_l2norm_fwd: B=%d d=%d ldx=%lld unsupported (d, ldx multiples of 4, d <= 4096)", B, d, (long long)ldx);
+  RH_REQUIRE(B >= 0 && d >= RH_L2NORM_MIN_D && d % 4 == 0 && d <= RH_L2NORM_MAX_D && ldx >= d && ldx % 4 == 0, RH_E_UNSUPPORTED,
+             "rh_l2norm_fwd: B=%d d=%d ldx=%lld unsupported (d, ldx multiples of 4, d <= %d)", B, d, (long long)ldx, RH_L2NORM_MAX_D);
   if (B == 0) return 0;
   const int rows_per_block = RH_BLOCK / 16;
   int64_t grid = ((int64_t)B + rows_per_block - 1) / rows_per_block;
@@ -266,7 +267,7 @@ extern "C" int rh_l2norm_fwd(const float* x, int64_t ldx, int B, int d, float ep
 extern "C" int rh_l2norm_bwd(const float* y, const float* nrm, const float* g, int64_t ldg, int B, int d, float eps, float* gx,
                              void* stream) {
   RH_REQUIRE(y && nrm && g && gx, RH_E_BADARG, "rh_l2norm_bwd: null pointer");
-  RH_REQUIRE(B >= 0 && d >= 4 && d % 4 == 0 && d <= 4096 && ldg >= d && ldg % 4 == 0, RH_E_UNSUPPORTED,
+  RH_REQUIRE(B >= 0 && d >= RH_L2NORM_MIN_D && d % 4 == 0 && d <= RH_L2NORM_MAX_D && ldg >= d && ldg % 4 == 0, RH_E_UNSUPPORTED,
              "rh_l2norm_bwd: B=%d d=%d ldg=%lld unsupported", B, d, (long long)ldg);
   if (B == 0) return 0;
   const int rows_per_block = RH_BLOCK / 16;
@@ -283,7 +284,7 @@ extern "C" int rh_ce_nblocks(int B) { return (B + RH_BLOCK - 1) / RH_BLOCK; }
 extern "C" int rh_ce_fwd(const float* logits, const int64_t* target, int B, int C, float* lse, float* loss_partial,
                          int32_t* err_flag, void* stream) {
   RH_REQUIRE(logits && lse && loss_partial, RH_E_BADARG, "rh_ce_fwd: null pointer");
-  RH_REQUIRE(B >= 1 && C >= 1 && C <= 1024, RH_E_UNSUPPORTED, "rh_ce_fwd: B=%d C=%d unsupported (1 <= C <= 1024)", B, C);
+  RH_REQUIRE(B >= 1 && C >= 1 && C <= RH_CE_MAX_C, RH_E_UNSUPPORTED, "rh_ce_fwd: B=%d C=%d unsupported (1 <= C <= %d)", B, C, RH_CE_MAX_C);
   hipLaunchKernelGGL(ce_fwd_kernel, dim3((unsigned)rh_ce_nblocks(B)), dim3(RH_BLOCK), 0, reinterpret_cast<hipStream_t>(stream),
                      logits, target, B, C, lse, loss_partial, err_flag);
   RH_LAUNCH_CHECK("rh_ce_fwd");
@@ -293,7 +294,7 @@ extern "C" int rh_ce_fwd(const float* logits, const int64_t* target, int B, int 
 extern "C" int rh_ce_bwd(const float* logits, const int64_t* target, const float* lse, const float* g_loss, int B, int C,
                          float* g_logits, void* stream) {
   RH_REQUIRE(logits && lse && g_loss && g_logits, RH_E_BADARG, "rh_ce_bwd: null pointer");
-  RH_REQUIRE(B >= 1 && C >= 1 && C <= 1024, RH_E_UNSUPPORTED, "rh_ce_bwd: B=%d C=%d unsupported", B, C);
+  RH_REQUIRE(B >= 1 && C >= 1 && C <= RH_CE_MAX_C, RH_E_UNSUPPORTED, "rh_ce_bwd: B=%d C=%d unsupported", B, C);
   int G = 4;
   while (G < C && G < RH_WAVE) G *= 2;
   const int per = RH_BLOCK / G;

@@ -43,7 +43,7 @@ constexpr int kReduceMaxGrid = 1024;
 static_assert(3 * kReduceMaxGrid <= 3072, "rh_gauc_reduce writes past the 3072 doubles its contract gives it");
 static_assert(kReduceMaxGrid <= 1024, "rh_log_loss writes past the 1024 doubles its contract gives it");
 // the list kernels (rank metrics, ild, novelty): one wavefront per user, at most kListMaxCut cut-offs over K <= kListMaxK
-constexpr int kListUsers = RH_BLOCK / RH_WAVE, kListMaxK = 256, kListMaxCut = 8, kListPer = kListMaxK / RH_WAVE;
+constexpr int kListUsers = RH_BLOCK / RH_WAVE, kListMaxK = RH_RANK_MAX_K, kListMaxCut = RH_RANK_MAX_CUTOFFS, kListPer = kListMaxK / RH_WAVE;
 constexpr int kListMaxGrid = 2048;  // ild, novelty
 constexpr int kRankStage = 256, kRankMaxGrid = 1024, kRankSums = 4;
 constexpr int kSumParts = 32;
@@ -850,7 +850,7 @@ extern "C" int rh_rank_metrics(const int64_t* pred, int64_t ld, int M, int K, co
 // shows a value that low); a second pass counts per cut-off the slots with first < k.  Integers: exact in any order.
 namespace {
 
-constexpr int kIldMaxD = 1024, kIldTrips = 2;
+constexpr int kIldMaxD = RH_ILD_MAX_D, kIldTrips = 2;
 constexpr int kCovRows = 256, kCovMaxGrid = 2048;
 
 struct IldArgs {

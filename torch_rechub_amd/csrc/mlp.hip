@@ -405,7 +405,7 @@ __global__ __launch_bounds__(RH_BLOCK) void bn_apply_kernel(const BnArgs a) {
 // 64-row chunks give <= 128 partial rows, few enough for every apply block to re-reduce the partials of ITS 32 columns
 // (<= 32 KB from L2) instead of waiting for a finalize launch.  Block = 32 columns x 8 row lanes: 128-byte row segments.
 constexpr int kFusedRows = 64;       // rows per partial chunk on this path
-constexpr int kFusedMaxChunks = 128;
+constexpr int kFusedMaxChunks = RH_BN_PRE_MAX_CHUNKS;
 constexpr int kSlabCols = 32, kSlabLanes = RH_BLOCK / kSlabCols;
 
 template <int MODE>  // 0 forward, 1 backward

@@ -22,8 +22,9 @@
 
 namespace {
 
-constexpr int kMaxLayers = 8;
-constexpr int kMaxExperts = 16;
+constexpr int kMaxLayers = RH_CROSS_MOE_MAX_L;
+constexpr int kMaxExperts = RH_CROSS_MOE_MAX_E;
+static_assert(RH_BLOCK == RH_CROSS_MOE_MAX_ER, "one thread per (expert, rank) element of a sample");
 
 struct MoePackArgs {
   const float* U[kMaxLayers];     // (E, d, r)
@@ -377,6 +378,7 @@ size_t mid_lds(int E, int r, bool bwd) {
   return n * sizeof(float);
 }
 
+static_assert(RH_CROSS_MOE_MAX_R == 64, "the ranks below end at RH_CROSS_MOE_MAX_R");
 bool rank_ok(int r) { return r == 4 || r == 8 || r == 16 || r == 32 || r == 64; }
 
 template <int R, bool BWD>

@@ -13,8 +13,8 @@
 
 namespace {
 
-constexpr int kMaxTensors = 128;
-constexpr int kMaxRing = 1024;  // entries of the (A, E) ring kept in LDS by the lazy sweep
+constexpr int kMaxTensors = RH_ADAM_MAX_TENSORS;
+constexpr int kMaxRing = RH_ADAM_MAX_RING;  // entries of the (A, E) ring kept in LDS by the lazy sweep
 int g_sweep_grid = 0;  // tuning knob RH_TUNE_SWEEP_GRID (0 = default 8192 workgroups, the measured best)
 // A DEFERRED sweep (rh_adam_lazy_sweep with t_value >= 0) runs on a side stream BESIDE the step's launch chain.  Left at
 // its in-line shape (8192 persistent workgroups, every wave slot it can get) it starves the chain: measured on the DeepFM

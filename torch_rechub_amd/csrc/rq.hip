@@ -23,7 +23,7 @@
 
 namespace {
 
-constexpr int kMaxE = 128, kMaxCodes = 1024, kMaxL = 8;
+constexpr int kMaxE = RH_RQ_MAX_E, kMaxCodes = RH_RQ_MAX_CODES, kMaxL = RH_RQ_MAX_L;
 constexpr int kRowsPerWave = 4, kWaves = RH_BLOCK / RH_WAVE, kRows = kRowsPerWave * kWaves;  // 16 rows per workgroup
 constexpr int kColsPerStep = 4;
 constexpr int kTileFloats = 12288, kMaxTileCodes = 256;                                    // 48 KB of codes in LDS

@@ -17,7 +17,7 @@
 
 namespace {
 
-constexpr int kMaxD = 128;
+constexpr int kMaxD = RH_SASREC_MAX_D;
 constexpr int kKC = 32;    // reduction steps of a weight matrix held in LDS at a time
 constexpr int kHR = 64;    // rows per workgroup of the head's backward
 

@@ -173,8 +173,8 @@ int dispatch(const SeqArgs& a, hipStream_t s) {
 }
 
 int check_dim(const char* who, int D) {
-  RH_REQUIRE(D > 0 && D % 4 == 0 && D <= 128 && ((D / 4) & (D / 4 - 1)) == 0, RH_E_UNSUPPORTED,
-             "%s: embed_dim %d unsupported (need 4,8,16,32,64,128)", who, D);
+  RH_REQUIRE(D > 0 && D % 4 == 0 && D <= RH_SEQ_POOL_MAX_D && ((D / 4) & (D / 4 - 1)) == 0, RH_E_UNSUPPORTED,
+             "%s: embed_dim %d unsupported (a power-of-two multiple of 4 up to %d)", who, D, RH_SEQ_POOL_MAX_D);
   return 0;
 }
 

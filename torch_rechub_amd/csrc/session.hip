@@ -31,9 +31,9 @@
 namespace {
 
 constexpr int kS = 8;          // samples per GRU workgroup at most
-constexpr int kMaxH = 128;
-constexpr int kMaxL = 1024;    // attention pooling: positions per row
-constexpr int kMaxW = 4096;    // attention pooling: H, Dx
+constexpr int kMaxH = RH_GRU_MAX_H;
+constexpr int kMaxL = RH_ATTN_POOL_MAX_L;    // attention pooling: positions per row
+constexpr int kMaxW = RH_ATTN_POOL_MAX_W;    // attention pooling: H, Dx
 
 __device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
 
@@ -382,8 +382,6 @@ int grid_for(int64_t n) {
 }
 
 }  // namespace
-
-extern "C" int rh_gru_max_hidden(void) { return kMaxH; }
 
 extern "C" int rh_gru_fwd(const float* xw, const float* w_hh, const float* b_hh, int B, int T, int H, float* h_all, float* hu,
                           void* stream) {

@@ -19,10 +19,10 @@
 
 namespace {
 
-constexpr int kMaxS = 64;   // positions: one lane per position in the softmaxes over S
-constexpr int kMaxE = 128;  // embedding columns: two per lane
-constexpr int kMaxT = 64;   // concepts: one lane per concept in the top-k
-constexpr int kMaxK = 8;    // intentions: per-row scores in registers
+constexpr int kMaxS = RH_SINE_MAX_S;   // positions: one lane per position in the softmaxes over S
+constexpr int kMaxE = RH_SINE_MAX_E;  // embedding columns: two per lane
+constexpr int kMaxT = RH_SINE_MAX_T;   // concepts: one lane per concept in the top-k
+constexpr int kMaxK = RH_SINE_MAX_K;    // intentions: per-row scores in registers
 constexpr int kChunks = 64;
 constexpr int kWaves = RH_BLOCK / RH_WAVE;
 constexpr float kNormEps = 1e-12f;

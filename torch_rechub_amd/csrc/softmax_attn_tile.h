@@ -39,9 +39,9 @@
 
 #include "mfma_tile.h"
 
-constexpr int kMaxDh = 128;
+constexpr int kMaxDh = RH_ATTN_MAX_DH;
 constexpr int kNC = kMaxDh / kT;  // column chunks of a head
-constexpr int kMaxL = 1024;
+constexpr int kMaxL = RH_ATTN_MAX_L;
 
 struct AttnArgs {
   const float* q;         // (B, Lq, H, dh) view, row stride ldq

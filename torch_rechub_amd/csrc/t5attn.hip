@@ -362,7 +362,7 @@ AttnArgs t5_args(const float* q, int64_t ldq, const float* k, const float* v, in
 // ------------------------------------------------------------------------------------------------------------------
 // RMS norm with the residual add: one wavefront per row, the row's D <= 1024 values in 16 registers per lane
 // ------------------------------------------------------------------------------------------------------------------
-constexpr int kRmsMaxD = 1024;
+constexpr int kRmsMaxD = RH_RMS_NORM_MAX_D;
 constexpr int kRmsPer = kRmsMaxD / RH_WAVE;
 constexpr int kRmsGrid = 512;  // workgroups of a launch at most; each walks rows blockIdx.x * 4 + wave, + 4 * grid, ...
 

@@ -23,7 +23,7 @@
 
 #include "mfma_tile.h"
 
-constexpr int kTopkMaxD = 1024, kTopkMaxK = 256, kTopkMaxS = 1024, kTopkMaxSplit = 1024;
+constexpr int kTopkMaxD = RH_TOPK_MAX_D, kTopkMaxK = RH_TOPK_MAX_K, kTopkMaxS = RH_TOPK_MAX_S, kTopkMaxSplit = RH_TOPK_MAX_SPLIT;
 constexpr int kTopkListBytes = 64 * 1024;  // LDS of the K-lists of one workgroup
 
 __host__ __device__ inline int topk_rows(int K) { return K * 64 * 8 <= kTopkListBytes ? 64 : 32; }

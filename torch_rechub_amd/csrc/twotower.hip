@@ -22,7 +22,8 @@
 namespace {
 
 constexpr int kWaves = RH_BLOCK / RH_WAVE;
-constexpr int kMaxPerLane = 16;  // D <= 1024
+constexpr int kMaxPerLane = 16;
+static_assert(RH_WAVE * kMaxPerLane == RH_TWOTOWER_MAX_D, "a row's D values are dealt over one wavefront");
 constexpr int kGridCap = 1024;   // workgroups; more rows than kGridCap * kWaves take further trips of the row loop
 
 int grid_for(int B) {
@@ -262,8 +263,8 @@ int pair_check(const char* who, int B, int D, float eps) {
 }
 
 // ---- (c) SENET gate ----------------------------------------------------------------------------------------------------
-constexpr int kMaxFields = 64;
-constexpr int kMaxFieldDim = 256;
+constexpr int kMaxFields = RH_SENET_MAX_F;
+constexpr int kMaxFieldDim = RH_SENET_MAX_D;
 constexpr int kWeightRegs = kMaxFields * kMaxFields / RH_BLOCK;  // weight-gradient elements per thread
 
 struct SenetArgs {

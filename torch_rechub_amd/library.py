@@ -388,7 +388,7 @@ def cross_net_v2_backward(x: torch.Tensor, W: torch.Tensor, b: torch.Tensor,
         g_x0_total += g_x0
         g_b[l] = g.sum(0)
         g_W[l] = torch.mm(g_y.t(), xl)
-        if x0.dtype == torch.float32 and W.dtype == torch.float32 and 1 <= B <= 16384 and d <= 1024:
+        if x0.dtype == torch.float32 and W.dtype == torch.float32 and 1 <= B <= _lib.H.RH_CROSS_V2_MAX_M and d <= _lib.H.RH_CROSS_V2_MAX_D:
             g_next = torch.empty_like(g)  # g_y W_l + g: the input-gradient GEMM with the residual as its epilogue
             _lib.call("rh_cross_v2_dgrad", _p(g_y), _p(W[l].contiguous()), _p(g), B, d, _p(g_next), _stream())
             g = g_next

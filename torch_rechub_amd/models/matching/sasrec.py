@@ -15,12 +15,12 @@ Three things the reference cannot do work here:
     works on (B, L, D) for any B, L >= 1.
   * ``user_tower`` picks the last valid row first and normalises B rows, not B L.
 
-Limits, refused before anything launches: embed_dim <= 128, embed_dim divisible by num_heads, and a history of at most
-min(max_len, 1024) positions (the attention kernel's bound; max_len itself may be larger).
+Limits, refused before anything launches: embed_dim <= RH_SASREC_MAX_D, embed_dim divisible by num_heads, and a history of at
+most min(max_len, RH_ATTN_MAX_L) positions (the attention kernel's bound; max_len itself may be larger).
 """
 import torch
 
-from ... import ops
+from ... import _lib, ops
 from ._listwise import no_kernel
 
 
@@ -82,8 +82,8 @@ class SASRec(torch.nn.Module):
     def _check(self, L):
         """Everything that can be refused is refused before the first launch."""
         D = self.embed_dim
-        if not 1 <= D <= 128:
-            raise no_kernel(f"SASRec at embed_dim {D} (1 <= D <= 128)")
+        if not 1 <= D <= _lib.H.RH_SASREC_MAX_D:
+            raise no_kernel(f"SASRec at embed_dim {D} (1 <= D <= {_lib.H.RH_SASREC_MAX_D})")
         for mha in self.attention_layers:
             if D % mha.num_heads != 0:
                 raise ValueError(f"SASRec: embed_dim {D} is not divisible by num_heads {mha.num_heads}")
@@ -91,8 +91,9 @@ class SASRec(torch.nn.Module):
             raise IndexError("index out of range in self")
         if L < 1:
             raise ValueError("SASRec: the history holds no position")
-        if L > 1024:  # ops.softmax_attention's limit, met here so that no stage before it has launched
-            raise no_kernel(f"SASRec on a history of {L} positions (the causal attention kernel takes L <= 1024)")
+        if L > _lib.H.RH_ATTN_MAX_L:  # ops.softmax_attention's limit, met here so that no stage before it has launched
+            raise no_kernel(f"SASRec on a history of {L} positions (the causal attention kernel takes L <= "
+                            f"{_lib.H.RH_ATTN_MAX_L})")
         if self.item_emb.is_sharded(self.features):
             raise RuntimeError("torch_rechub_amd: SASRec on a row-sharded item table is not supported")
 

@@ -543,10 +543,6 @@ def scatter_rows(call, idx_all, rows_all):
 
 # --------------------------------------------------------------------------------------------
 # field-aware FM (DeepFFM / FAT-DeepFFM, csrc/ffm.hip)
-FFM_MAX_FIELDS = 64
-FFM_MAX_DIM = 128
-
-
 _ffm_xv = OrderedDict()
 _ffm_xv_pinned = {}
 
@@ -581,9 +577,9 @@ class FfmCall(object):
         self.base = EmbedCall(weights, pads, idx)
         self.F, self.B, self.Dp = self.base.F, self.base.B, self.base.D
         self.D = int(embed_dim)
-        if not 2 <= self.F <= FFM_MAX_FIELDS or not 1 <= self.D <= min(self.Dp, FFM_MAX_DIM):
+        if not 2 <= self.F <= _lib.H.RH_FFM_MAX_F or not 1 <= self.D <= min(self.Dp, _lib.H.RH_FFM_MAX_D):
             raise RuntimeError(f"torch_rechub_amd: field-aware FM with {self.F} fields of width {self.D} (row {self.Dp}) "
-                               f"has no HIP kernel (2 .. {FFM_MAX_FIELDS} fields, width 1 .. {FFM_MAX_DIM})")
+                               f"has no HIP kernel (2 .. {_lib.H.RH_FFM_MAX_F} fields, width 1 .. {_lib.H.RH_FFM_MAX_D})")
         self.P = self.F * (self.F - 1) // 2
         self.V = self.F * (self.F - 1)
         self.device = self.base.device
@@ -892,7 +888,7 @@ class _CrossFn(torch.autograd.Function):
         L = W.shape[0]
         seg = _lib.call("rh_cross_max_layers", d)
         if seg <= 0:
-            raise ValueError(f"CrossNetwork width {d} unsupported by the HIP kernel (1..2048)")
+            raise ValueError(f"CrossNetwork width {d} unsupported by the HIP kernel (1..{_lib.H.RH_CROSS_MAX_D})")
         xs = [x]
         cur = x
         for l0 in range(0, L, seg):
@@ -1148,7 +1144,7 @@ def linear_wgrad(g, x, want_bias=True, weight=None, bias=None, out=None):
         # (step-ahead graph being captured: the slabs feed nothing but the packing launch at the end of the step, so the launch
         # rides in the optimizer's end-of-step launch with the other weight gradients of the step -- wgrad_rider below)
         rider = wgrad_rider
-        if not (rider is not None and B < _WGRAD_GROUP_MAX_B and rider([(g, g.stride(0), x, x.stride(0), N, K, partial)], B)):
+        if not (rider is not None and B < _lib.H.RH_WGRAD_LONG_MIN_B and rider([(g, g.stride(0), x, x.stride(0), N, K, partial)], B)):
             _lib.call("rh_linear_wgrad_partial", _p(g), g.stride(0), _p(x), x.stride(0), B, N, K, _p(partial), _stream())
         return _offer_wgrad_slabs(weight, bias if want_bias else None, partial, B)
     if out is None:
@@ -1515,7 +1511,7 @@ class _HeadFn(torch.autograd.Function):
         else:
             g_y = g_y.contiguous()
         bn = ctx.bn_node
-        if bn is not None and K % 4 == 0 and K <= 256 and nblk <= 128 and h.stride(0) == K:
+        if bn is not None and K % 4 == 0 and K <= _lib.H.RH_HEAD_BN_MAX_K and nblk <= _lib.H.RH_BN_PRE_MAX_CHUNKS and h.stride(0) == K:
             z, gamma, beta, stat, saved_ctr = bn.saved_tensors
             bn_partial = torch.empty((nblk, 2, K), dtype=torch.float32, device=dev)
             _lib.call("rh_head_bwd_bn", _p(h), h.stride(0), _p(weight), _p(y), _p(g_y), _p(t), _p(gl), B, K, _p(g_h),
@@ -1544,7 +1540,6 @@ FUSE_MLP_CHAIN = _lib.ab("chain")
 # rounds: 0.2422 / 0.2424 -> 0.2411 / 0.2411 ms (profiles/r05_ab_chain_wgroup_same_box.txt): one launch less on a chain that is
 # co-critical with the deferred sweep, so most of the 5 us it saves on the chain is not a shorter step.
 CHAIN_WGRAD_GROUP = _lib.ab("chainwgroup")
-_WGRAD_GROUP_MAX_B = 32768  # kLongRows of csrc/linear.hip: the grouped launch takes batch-sized reductions only
 chain_gate = None      # the gate words of the optimizer whose step-ahead graph is being captured (optim.TableAdam), or None
 chain_gate_used = []   # ... and a mark per rh_linear_fwd_gate launch captured for it
 # Round 6: while optim.TableAdam captures a step-ahead graph, the chain's grouped weight gradients are not launched where the
@@ -1579,7 +1574,8 @@ def _reset_capture_state():
 from . import graphs as _graphs  # noqa: E402  (graphs imports torch only)
 
 _graphs.capture_end_hooks.append(_reset_capture_state)
-_CHAIN_MAX_B = 4096  # rh_head_bwd_bn hands over rh_head_nblocks(B) <= 128 partial rows up to here
+_CHAIN_MAX_K = min(_GEMM_MAX_NK, _lib.H.RH_LINEAR_BNACT_MAX_K)  # the tile GEMM's policy width and rh_linear_bnact_fwd's K limit
+_CHAIN_MAX_B = 4096  # rh_head_bwd_bn hands over rh_head_nblocks(B) <= RH_BN_PRE_MAX_CHUNKS partial rows up to here
 
 
 class _MlpChainFn(torch.autograd.Function):
@@ -1724,7 +1720,7 @@ class _MlpChainFn(torch.autograd.Function):
         # summed by the step's packing launch): with ops.deferred armed for every Linear of the chain they run as ONE
         # rh_linear_wgrad_partial_group launch behind the last input-gradient GEMM instead of one launch per layer between
         # the GEMMs -- same kernel body, same split plan per problem, hence the same slabs bit for bit.
-        group = (CHAIN_WGRAD_GROUP and 2 <= L <= 8 and armed is not None and B < _WGRAD_GROUP_MAX_B and
+        group = (CHAIN_WGRAD_GROUP and 2 <= L <= 8 and armed is not None and B < _lib.H.RH_WGRAD_LONG_MIN_B and
                  all(id(params[4 * l]) in armed and (params[4 * l + 1] is None or id(params[4 * l + 1]) in armed)
                      for l in range(L)))
         problems = []
@@ -1782,10 +1778,11 @@ def mlp_chain_ok(x, blocks, head, extras):
         if not (type(lin) is torch.nn.Linear and type(bn) is torch.nn.BatchNorm1d and bn.training and bn.affine and
                 bn.track_running_stats and bn.momentum is not None and lin.in_features == width and
                 lin.weight.is_contiguous() and lin.weight.dtype == torch.float32 and lin.out_features % 4 == 0 and
-                lin.out_features <= _GEMM_MAX_NK and width <= _GEMM_MAX_NK and 0.0 <= p < 1.0 and linear_ok(x, lin.weight)):
+                lin.out_features <= _CHAIN_MAX_K and width <= _CHAIN_MAX_K and 0.0 <= p < 1.0 and linear_ok(x, lin.weight)):
             return False
         width = lin.out_features
-    return width <= 256 and head.in_features == width and _lib.call("rh_head_nblocks", x.shape[0]) <= 128
+    return (width <= _lib.H.RH_HEAD_BN_MAX_K and head.in_features == width and
+            _lib.call("rh_head_nblocks", x.shape[0]) <= _lib.H.RH_BN_PRE_MAX_CHUNKS)
 
 
 def mlp_chain_sigmoid(x, blocks, head, *extras):
@@ -1800,7 +1797,7 @@ def mlp_chain_sigmoid(x, blocks, head, *extras):
 
 def head_ok(h, lin, extras):
     K = lin.in_features
-    return (h.is_cuda and h.dim() == 2 and h.dtype == torch.float32 and lin.out_features == 1 and 1 <= K <= 1024 and
+    return (h.is_cuda and h.dim() == 2 and h.dtype == torch.float32 and lin.out_features == 1 and 1 <= K <= _lib.H.RH_HEAD_MAX_K and
             len(extras) <= 2 and h.shape[0] > 0 and all(e.numel() == h.shape[0] for e in extras))
 
 
@@ -1989,7 +1986,7 @@ class _L2NormFn(torch.autograd.Function):
 
 def l2_normalize_ok(x):
     return x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] > 0 and x.shape[1] % 4 == 0 and \
-        4 <= x.shape[1] <= 4096
+        _lib.H.RH_L2NORM_MIN_D <= x.shape[1] <= _lib.H.RH_L2NORM_MAX_D
 
 
 def l2_normalize(x, eps=1e-12):
@@ -2032,7 +2029,7 @@ class _CrossEntropyFn(torch.autograd.Function):
 def cross_entropy_ok(criterion, logits, target):
     return (type(criterion) is torch.nn.CrossEntropyLoss and criterion.reduction == "mean" and criterion.weight is None and
             criterion.label_smoothing == 0.0 and criterion.ignore_index == -100 and logits.is_cuda and
-            logits.dtype == torch.float32 and logits.dim() == 2 and 1 <= logits.shape[1] <= 1024 and logits.shape[0] > 0 and
+            logits.dtype == torch.float32 and logits.dim() == 2 and 1 <= logits.shape[1] <= _lib.H.RH_CE_MAX_C and logits.shape[0] > 0 and
             (target is None or (target.dtype == torch.int64 and target.shape == (logits.shape[0],) and target.is_cuda)))
 
 
@@ -2097,7 +2094,7 @@ class _BnDiceFn(torch.autograd.Function):
 
 
 def bn_dice_ok(h, bn, dice_mod):
-    return (h.is_cuda and h.dim() == 2 and h.dtype == torch.float32 and h.shape[1] <= 512 and h.shape[0] > 1 and
+    return (h.is_cuda and h.dim() == 2 and h.dtype == torch.float32 and h.shape[1] <= _lib.H.RH_BN_DICE_MAX_C and h.shape[0] > 1 and
             bn.affine and bn.track_running_stats and bn.momentum is not None)
 
 
@@ -2175,7 +2172,7 @@ class _BnDiceHeadFn(torch.autograd.Function):
 
 
 def bn_dice_head_ok(h_cols, bn, dice_mod, lin):
-    return (type(lin) is torch.nn.Linear and lin.out_features == 1 and lin.in_features == h_cols and h_cols <= 512 and
+    return (type(lin) is torch.nn.Linear and lin.out_features == 1 and lin.in_features == h_cols and h_cols <= _lib.H.RH_BN_DICE_MAX_C and
             lin.weight.dtype == torch.float32 and FUSE_DICE_HEAD)
 
 
@@ -2333,7 +2330,7 @@ def din_att_pool(weight, history):
 
 def din_dim_ok(d):
     q = d // 4
-    return d % 4 == 0 and 1 <= q <= 32 and (q & (q - 1)) == 0
+    return d % 4 == 0 and 4 <= d <= _lib.H.RH_DIN_ATT_MAX_D and (q & (q - 1)) == 0
 
 
 # --------------------------------------------------------------------------------------------
@@ -2403,14 +2400,11 @@ class _CrossV2LayerFn(torch.autograd.Function):
         return (g_x0 if ctx.needs_input_grad[0] else None), g_x, g_w, g_b
 
 
-CROSS_V2_MAX_B, CROSS_V2_MAX_D = 16384, 1024  # limits of rh_cross_v2_fwd / rh_cross_v2_dgrad (enforced there: csrc/gemm.hip)
-
-
 def cross_v2_shape_ok(x, weight):
     """THE predicate of the fused CrossNetV2 layer (ops.cross_v2_layer_ok and torch.ops.rechub_hip.cross_net_v2 share it):
     contiguous f32 x (B, d) and W (d, d) within the entry points' limits."""
     return (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and weight.dtype == torch.float32 and
-            1 <= x.shape[0] <= CROSS_V2_MAX_B and 1 <= x.shape[1] <= CROSS_V2_MAX_D and
+            1 <= x.shape[0] <= _lib.H.RH_CROSS_V2_MAX_M and 1 <= x.shape[1] <= _lib.H.RH_CROSS_V2_MAX_D and
             tuple(weight.shape[-2:]) == (x.shape[1], x.shape[1]))
 
 
@@ -2537,7 +2531,7 @@ class _CrossMoeFn(torch.autograd.Function):
         slabV, slabU, gC = [], [], []
         # The two weight gradients of a layer (g_UTb = g_Y^T wp, g_VgT = g_PG^T x_l) feed nothing but the final unpack: they
         # are collected and run as grouped launches of <= 8 problems after the loop (round 4: 2 L launches of ~16.5 us -> 1)
-        group = WGRAD_GROUP and B < 32768
+        group = WGRAD_GROUP and B < _lib.H.RH_WGRAD_LONG_MIN_B
         problems = []
         own_G = False
         for l in reversed(range(L)):
@@ -2662,7 +2656,7 @@ class _AugruFn(torch.autograd.Function):
 
 def augru_ok(xw, D):
     return (xw.is_cuda and xw.dtype == torch.float32 and xw.dim() == 3 and xw.shape[1] >= 1 and
-            D in (4, 8, 16, 32) and xw.shape[2] == 3 * D)
+            4 <= D <= _lib.H.RH_AUGRU_MAX_D and D & (D - 1) == 0 and xw.shape[2] == 3 * D)
 
 
 def augru(xw, attn, U, state_bias=None):
@@ -2736,7 +2730,7 @@ class _InbatchLogitsFn(torch.autograd.Function):
 
 def inbatch_logits_ok(u, v):
     return (u.is_cuda and v.is_cuda and u.dtype == torch.float32 and v.dtype == torch.float32 and u.dim() == 2 and
-            v.dim() == 2 and u.shape[1] == v.shape[1] and 1 <= u.shape[1] <= 1024 and u.shape[0] >= 1)
+            v.dim() == 2 and u.shape[1] == v.shape[1] and 1 <= u.shape[1] <= _lib.H.RH_INBATCH_MAX_D and u.shape[0] >= 1)
 
 
 def inbatch_logits(u, v, neg, row0=0):
@@ -2925,8 +2919,9 @@ class _ListwiseFn(torch.autograd.Function):
 
 def listwise_ok(u, pos, neg):
     return (u.is_cuda and u.dtype == pos.dtype == neg.dtype == torch.float32 and u.dim() == 3 and pos.dim() == 2 and
-            neg.dim() == 3 and 1 <= u.shape[1] <= 16 and 1 <= u.shape[2] <= 64 and pos.shape == (u.shape[0], u.shape[2])
-            and neg.shape[0] == u.shape[0] and neg.shape[2] == u.shape[2] and neg.shape[1] < 1024)
+            neg.dim() == 3 and 1 <= u.shape[1] <= _lib.H.RH_LISTWISE_MAX_I and 1 <= u.shape[2] <= _lib.H.RH_LISTWISE_MAX_D and
+            pos.shape == (u.shape[0], u.shape[2])
+            and neg.shape[0] == u.shape[0] and neg.shape[2] == u.shape[2] and neg.shape[1] <= _lib.H.RH_LISTWISE_MAX_K)
 
 
 def listwise_logits(u, pos, neg, temperature=1.0):
@@ -2935,7 +2930,8 @@ def listwise_logits(u, pos, neg, temperature=1.0):
     require_hip(u, pos, neg)
     if not listwise_ok(u, pos, neg):
         raise RuntimeError(f"torch_rechub_amd: list-wise scoring of user {tuple(u.shape)}, items {tuple(pos.shape)} / "
-                           f"{tuple(neg.shape)} has no HIP kernel (I <= 16, D <= 64, K < 1024, float32)")
+                           f"{tuple(neg.shape)} has no HIP kernel (I <= {_lib.H.RH_LISTWISE_MAX_I}, D <= {_lib.H.RH_LISTWISE_MAX_D}, "
+                           f"K <= {_lib.H.RH_LISTWISE_MAX_K}, float32)")
     return _ListwiseFn.apply(u, pos, neg, float(temperature))
 
 
@@ -3025,7 +3021,8 @@ def _sine_check(what, tensors, mask, S, E, T, K):
     if not sine_supported(S, E, T, K):
         from .models.matching._listwise import no_kernel
         raise no_kernel(f"{what} at seq_max_len {S}, embedding_dim {E}, num_concept {T}, num_intention {K} "
-                        "(S <= 64, E <= 128, T <= 64, K <= min(T, 8))")
+                        f"(S <= {_lib.H.RH_SINE_MAX_S}, E <= {_lib.H.RH_SINE_MAX_E}, T <= {_lib.H.RH_SINE_MAX_T}, "
+                        f"K <= min(T, {_lib.H.RH_SINE_MAX_K}))")
 
 
 def sine_interests(X, Y, a1, a2, mask, C):
@@ -3056,7 +3053,8 @@ def sine_aggregate(xhat, a3, mask, phi, temperature):
 # --------------------------------------------------------------------------------------------
 # RQ-VAE's residual quantizer (csrc/rq.hip)
 def rq_supported(E, sizes):
-    """Whether csrc/rq.hip takes rows of width E against codebooks of these sizes (E <= 128, sizes <= 1024, <= 8 levels)."""
+    """Whether csrc/rq.hip takes rows of width E against codebooks of these sizes (E <= RH_RQ_MAX_E, sizes <= RH_RQ_MAX_CODES, <= RH_RQ_MAX_L
+    levels)."""
     sizes = [int(v) for v in sizes]
     arr = _int_array(sizes)
     return bool(_lib.query("rh_rq_supported", int(E), len(sizes), ctypes.cast(arr, ctypes.c_void_p)))
@@ -3072,7 +3070,7 @@ def _rq_check(x, codebooks):
     if not rq_supported(int(x.shape[1]), sizes):
         from .models.matching._listwise import no_kernel
         raise no_kernel(f"the residual quantizer at e_dim {int(x.shape[1])} with codebook sizes {sizes} "
-                        "(e_dim <= 128, sizes <= 1024, at most 8 levels)")
+                        f"(e_dim <= {_lib.H.RH_RQ_MAX_E}, sizes <= {_lib.H.RH_RQ_MAX_CODES}, at most {_lib.H.RH_RQ_MAX_L} levels)")
     return sizes
 
 
@@ -3241,10 +3239,13 @@ def hstu_attention(proj, pos_w, ts_w, n_heads, dqk, dv, max_seq_len, time_diffs=
     B, L, W = (int(v) for v in proj.shape)
     if W != 2 * n_heads * (dqk + dv):
         raise RuntimeError(f"torch_rechub_amd: HSTU projection width {W} != 2 * {n_heads} * ({dqk} + {dv})")
-    if not (1 <= L <= min(int(max_seq_len), 1024) and 1 <= dqk <= 64 and 1 <= dv <= 64 and num_time_buckets <= 1023):
+    if not (1 <= L <= min(int(max_seq_len), _lib.H.RH_HSTU_MAX_L) and 1 <= dqk <= _lib.H.RH_HSTU_MAX_DH and
+            1 <= dv <= _lib.H.RH_HSTU_MAX_DH and
+            num_time_buckets <= _lib.H.RH_HSTU_MAX_BUCKETS):
         raise RuntimeError(f"torch_rechub_amd: HSTU attention with L={L}, dqk={dqk}, dv={dv}, "
-                           f"num_time_buckets={num_time_buckets} has no HIP kernel (L <= min(max_seq_len, 1024), "
-                           "dqk, dv <= 64, num_time_buckets <= 1023)")
+                           f"num_time_buckets={num_time_buckets} has no HIP kernel (L <= min(max_seq_len, "
+                           f"{_lib.H.RH_HSTU_MAX_L}), dqk, dv <= {_lib.H.RH_HSTU_MAX_DH}, "
+                           f"num_time_buckets <= {_lib.H.RH_HSTU_MAX_BUCKETS})")
     if time_bucket_fn not in ("sqrt", "log") or time_bucket_unit not in ("minutes", "seconds"):
         raise ValueError(f"Unsupported time bucketing {time_bucket_fn!r} / {time_bucket_unit!r}")
     td = None if time_diffs is None else time_diffs.to(torch.int64).contiguous()
@@ -3385,11 +3386,12 @@ def softmax_attention(q, k, v, n_heads, max_seq_len, bias_table=None, dropout_p=
     H = int(n_heads)
     dh = W // H
     nb = int(bias_table.shape[0]) if bias_table is not None else 0
-    if not (1 <= L <= min(int(max_seq_len), 1024) and 1 <= dh <= 128) or (bias_table is not None and (
+    if not (1 <= L <= min(int(max_seq_len), _lib.H.RH_ATTN_MAX_L) and 1 <= dh <= _lib.H.RH_ATTN_MAX_DH) or (bias_table is not None and (
             nb < 1 or bias_table.dim() != 2 or bias_table.shape[1] != H)):
         raise RuntimeError(f"torch_rechub_amd: softmax attention with L={L}, head width {dh}, bias table "
                            f"{None if bias_table is None else tuple(bias_table.shape)} has no HIP kernel "
-                           "(1 <= L <= min(max_seq_len, 1024), 1 <= head width <= 128, table (num_buckets >= 1, H))")
+                           f"(1 <= L <= min(max_seq_len, {_lib.H.RH_ATTN_MAX_L}), 1 <= head width <= {_lib.H.RH_ATTN_MAX_DH}, table "
+                           "(num_buckets >= 1, H))")
     p = float(dropout_p) if training else 0.0
     if not 0.0 <= p < 1.0:
         raise RuntimeError(f"torch_rechub_amd: attention dropout p={p} has no HIP kernel (0 <= p < 1)")
@@ -3441,19 +3443,19 @@ def gru_layers_ok(gru_mod, x, batch_first=None):
     bf = gru_mod.batch_first if batch_first is None else batch_first
     return (isinstance(gru_mod, torch.nn.GRU) and not gru_mod.bidirectional and x.dim() == 3 and x.is_cuda and
             x.dtype == torch.float32 and gru_mod.input_size == x.shape[-1] and gru_mod.proj_size == 0 and
-            1 <= gru_mod.hidden_size <= _lib.call("rh_gru_max_hidden") and x.shape[1 if bf else 0] >= 1)
+            1 <= gru_mod.hidden_size <= _lib.H.RH_GRU_MAX_H and x.shape[1 if bf else 0] >= 1)
 
 
 def gru_layers(gru_mod, x, batch_first=None):
     """(output, h_n) of a multi-layer ``nn.GRU`` from the zero state, as the module returns them (``batch_first`` either way,
     with or without bias; ``batch_first`` given: the layout of ``x`` and of the output instead of the module's): per layer the input halves of all steps are one ops.linear product and the recurrence one launch
-    each way (csrc/session.hip).  1 <= hidden_size <= 128; inter-layer dropout is not supported in training."""
+    each way (csrc/session.hip).  1 <= hidden_size <= RH_GRU_MAX_H; inter-layer dropout is not supported in training."""
     require_hip(x)
     bf = gru_mod.batch_first if batch_first is None else batch_first
     if not gru_layers_ok(gru_mod, x, bf):
         raise RuntimeError(f"torch_rechub_amd: nn.GRU(input {gru_mod.input_size}, hidden {gru_mod.hidden_size}, "
                            f"bidirectional={gru_mod.bidirectional}) on {tuple(x.shape)} has no HIP kernel "
-                           f"(float32, unidirectional, 1 <= hidden_size <= {_lib.call('rh_gru_max_hidden')})")
+                           f"(float32, unidirectional, 1 <= hidden_size <= {_lib.H.RH_GRU_MAX_H})")
     if gru_mod.dropout > 0 and gru_mod.training and gru_mod.num_layers > 1:
         raise RuntimeError("torch_rechub_amd: nn.GRU inter-layer dropout has no HIP kernel")
     h = x if bf else x.transpose(0, 1)
@@ -3515,9 +3517,10 @@ def additive_attention_pool(P, r, w0, mask, X, add=None, floor=False):
             w0.numel() != P.shape[2] or mask.shape != P.shape[:2] or (add is not None and add.shape != (X.shape[0], X.shape[2])):
         raise RuntimeError(f"torch_rechub_amd: attention pooling shapes P {tuple(P.shape)}, r {tuple(r.shape)}, "
                            f"w0 {tuple(w0.shape)}, mask {tuple(mask.shape)}, X {tuple(X.shape)} do not agree")
-    if not (1 <= P.shape[1] <= 1024 and 1 <= P.shape[2] <= 4096 and 1 <= X.shape[2] <= 4096):
+    if not (1 <= P.shape[1] <= _lib.H.RH_ATTN_POOL_MAX_L and 1 <= P.shape[2] <= _lib.H.RH_ATTN_POOL_MAX_W and
+            1 <= X.shape[2] <= _lib.H.RH_ATTN_POOL_MAX_W):
         raise RuntimeError(f"torch_rechub_amd: attention pooling with L={P.shape[1]}, H={P.shape[2]}, Dx={X.shape[2]} has "
-                           "no HIP kernel (1 <= L <= 1024, 1 <= H, Dx <= 4096)")
+                           f"no HIP kernel (1 <= L <= {_lib.H.RH_ATTN_POOL_MAX_L}, 1 <= H, Dx <= {_lib.H.RH_ATTN_POOL_MAX_W})")
     if any(t.dtype != torch.float32 for t in (P, r, w0, X) + (() if add is None else (add,))):
         raise RuntimeError("torch_rechub_amd: attention pooling runs in float32 only")
     m = mask.to(torch.float32).contiguous()
@@ -3621,7 +3624,8 @@ def session_lengths(seq, check_full=False):
 # Exact top-K item retrieval (csrc/topk.hip)
 # --------------------------------------------------------------------------------------------
 def topk_supported(D, K, S=0):
-    """Whether csrc/topk.hip takes width D, K results and S exclusions per query (D <= 1024, K <= 256, S <= 1024)."""
+    """Whether csrc/topk.hip takes width D, K results and S exclusions per query (D <= RH_TOPK_MAX_D, K <= RH_TOPK_MAX_K,
+    S <= RH_TOPK_MAX_S)."""
     return bool(_lib.query("rh_topk_supported", int(D), int(K), int(S)))
 
 
@@ -3678,7 +3682,7 @@ def topk_items(q, table, k, bias=None, exclude=None, invalid=None, nsplit=None):
         if V < 1 or not topk_supported(D, k, S):
             from .models.matching._listwise import no_kernel
             raise no_kernel(f"top-k retrieval at D={D}, k={k}, {S} exclusions per query, V={V} "
-                            "(1 <= D <= 1024, 1 <= k <= 256, S <= 1024, V >= 1)")
+                            f"(1 <= D <= {_lib.H.RH_TOPK_MAX_D}, 1 <= k <= {_lib.H.RH_TOPK_MAX_K}, S <= {_lib.H.RH_TOPK_MAX_S}, V >= 1)")
 
     q, ldq, bias, exclude, S, ids, scores = _scan_inputs("topk_items", "table", q, table, k, bias, exclude, refuse)
     (M, D), V, k = q.shape, int(table.shape[0]), int(k)
@@ -3689,8 +3693,8 @@ def topk_items(q, table, k, bias=None, exclude=None, invalid=None, nsplit=None):
     if nsplit is None:
         nsplit, _ = topk_plan(M, V, k)
     nsplit = int(nsplit)
-    if not 1 <= nsplit <= min(V, 1024):
-        raise ValueError(f"topk_items: nsplit={nsplit} outside [1, min(V, 1024)]")
+    if not 1 <= nsplit <= min(V, _lib.H.RH_TOPK_MAX_SPLIT):
+        raise ValueError(f"topk_items: nsplit={nsplit} outside [1, min(V, {_lib.H.RH_TOPK_MAX_SPLIT})]")
     if M == 0:
         return ids, scores
     work = torch.empty((8 * M * nsplit * k,), dtype=torch.uint8, device=q.device)
@@ -3703,8 +3707,8 @@ def topk_items(q, table, k, bias=None, exclude=None, invalid=None, nsplit=None):
 # Inverted-file index: the list scan and the k-means update (csrc/ivf.hip)
 # --------------------------------------------------------------------------------------------
 def ivf_supported(D, K, S=0, nprobe=1):
-    """Whether csrc/ivf.hip takes width D, K results, S exclusions per query and nprobe lists per query (D <= 1024,
-    K <= 256, S <= 1024, nprobe <= 256)."""
+    """Whether csrc/ivf.hip takes width D, K results, S exclusions per query and nprobe lists per query (the limits of
+    ops.topk_supported and nprobe <= RH_IVF_MAX_NPROBE)."""
     return bool(_lib.query("rh_ivf_supported", int(D), int(K), int(S), int(nprobe)))
 
 
@@ -3739,7 +3743,8 @@ def ivf_scan(q, table_sorted, row_ids, list_offsets, probe, k, bias=None, exclud
         if V < 1 or M * nprobe >= 2 ** 31 - 64 * (nlists + 2) or not ivf_supported(D, k, S, nprobe):
             from .models.matching._listwise import no_kernel
             raise no_kernel(f"the inverted-file scan at D={D}, k={k}, {S} exclusions per query, nprobe={nprobe}, V={V} "
-                            "(1 <= D <= 1024, 1 <= k <= 256, S <= 1024, 1 <= nprobe <= 256, V >= 1, M nprobe < 2^31)")
+                            f"(1 <= D <= {_lib.H.RH_TOPK_MAX_D}, 1 <= k <= {_lib.H.RH_TOPK_MAX_K}, S <= {_lib.H.RH_TOPK_MAX_S}, "
+                            f"1 <= nprobe <= {_lib.H.RH_IVF_MAX_NPROBE}, V >= 1, M nprobe < 2^31)")
 
     q, ldq, bias, exclude, S, ids, scores = _scan_inputs("ivf_scan", "table_sorted", q, table_sorted, k, bias, exclude,
                                                          refuse)
@@ -3794,16 +3799,13 @@ def ivf_list_mean(x_sorted, list_offsets, previous):
 # --------------------------------------------------------------------------------------------
 # SASRec: the transformer block around ops.softmax_attention, fused per row tile (csrc/sasrec.hip)
 # --------------------------------------------------------------------------------------------
-_SASREC_MAX_D = 128
-
-
 def _sasrec_check(what, D, *tensors):
     """Before anything is allocated or launched: float32 tensors and a width the kernels take."""
     if any(t is not None and t.dtype != torch.float32 for t in tensors):
         raise ValueError(f"torch_rechub_amd: {what} takes float32 tensors")
-    if not 1 <= int(D) <= _SASREC_MAX_D:
+    if not 1 <= int(D) <= _lib.H.RH_SASREC_MAX_D:
         from .models.matching._listwise import no_kernel
-        raise no_kernel(f"{what} at width {int(D)} (1 <= D <= {_SASREC_MAX_D})")
+        raise no_kernel(f"{what} at width {int(D)} (1 <= D <= {_lib.H.RH_SASREC_MAX_D})")
 
 
 def _sasrec_ntiles(M, D):
@@ -4067,7 +4069,7 @@ class _LayerNormFn(torch.autograd.Function):
 
 
 def layer_norm(x, weight, bias, eps=1e-5):
-    """F.layer_norm(x, (D,), weight, bias, eps) over the last axis of a float32 (..., D) tensor, D <= 128: two-pass
+    """F.layer_norm(x, (D,), weight, bias, eps) over the last axis of a float32 (..., D) tensor, D <= RH_SASREC_MAX_D: two-pass
     variance, so an all-zero row gives exactly ``bias``; the weight and bias gradients are summed in a fixed order."""
     require_hip(x, weight, bias)
     D = int(x.shape[-1])
@@ -4132,7 +4134,7 @@ class _BandLogitsFn(torch.autograd.Function):
 def _f32_rows(*tensors):
     first = tensors[0]
     return all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape == first.shape for t in tensors) and \
-        first.shape[0] >= 1 and 1 <= first.shape[1] <= 1024
+        first.shape[0] >= 1 and 1 <= first.shape[1] <= _lib.H.RH_TWOTOWER_MAX_D
 
 
 def band_logits_ok(u, v, w, n_neg):
@@ -4224,8 +4226,9 @@ class _SenetFn(torch.autograd.Function):
 
 
 def senet_ok(x, w1, w2):
-    return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[0] >= 1 and 1 <= x.shape[1] <= 64 and
-            1 <= x.shape[2] <= 256 and w1.is_cuda and w2.is_cuda and w1.dtype == torch.float32 and
+    return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[0] >= 1 and
+            1 <= x.shape[1] <= _lib.H.RH_SENET_MAX_F and 1 <= x.shape[2] <= _lib.H.RH_SENET_MAX_D and
+            w1.is_cuda and w2.is_cuda and w1.dtype == torch.float32 and
             w2.dtype == torch.float32 and w1.dim() == 2 and w1.shape[1] == x.shape[1] and 1 <= w1.shape[0] <= x.shape[1] and
             tuple(w2.shape) == (x.shape[1], w1.shape[0]))
 
@@ -4370,7 +4373,7 @@ def t5_attention(q, k, v, n_heads, key_mask=None, causal=False, bias_table=None,
         k, v = k.contiguous(), v.contiguous()
     mask = None if key_mask is None else (key_mask != 0).to(torch.uint8).contiguous()
     bucket = None
-    if bias_table is not None and 1 <= Lq <= 1024 and 1 <= Lk <= 1024:
+    if bias_table is not None and 1 <= Lq <= _lib.H.RH_ATTN_MAX_L and 1 <= Lk <= _lib.H.RH_ATTN_MAX_L:
         bucket = t5_relative_buckets(Lq, Lk, bidirectional, nb, max_distance, device=q.device)
     cfg = (H, dh, 1 if causal else 0, nb, p)
     # (shapes outside the kernel's range are refused by the entry point itself, before any launch)
@@ -4416,15 +4419,15 @@ class _AddRmsNormFn(torch.autograd.Function):
 
 def add_rms_norm(h, delta, weight, eps=1e-6):
     """(h_new, y): h_new = h + delta (``delta`` None: h itself), y = h_new * rsqrt(mean(h_new^2, -1) + eps) * weight --
-    T5LayerNorm behind the residual add of the sub-layer before it, in one pass.  float32 (..., D), D <= 1024; the weight
+    T5LayerNorm behind the residual add of the sub-layer before it, in one pass.  float32 (..., D), D <= RH_RMS_NORM_MAX_D; the weight
     gradient is summed in a fixed order."""
     require_hip(h, delta, weight)
     D = int(h.shape[-1])
     if h.dtype != torch.float32 or weight.dtype != torch.float32 or (delta is not None and delta.dtype != torch.float32):
         raise RuntimeError("torch_rechub_amd: add_rms_norm runs in float32 only")
-    if not 1 <= D <= 1024 or tuple(weight.shape) != (D,) or (delta is not None and delta.shape != h.shape):
+    if not 1 <= D <= _lib.H.RH_RMS_NORM_MAX_D or tuple(weight.shape) != (D,) or (delta is not None and delta.shape != h.shape):
         raise RuntimeError(f"torch_rechub_amd: add_rms_norm of h {tuple(h.shape)}, weight {tuple(weight.shape)} has no HIP "
-                           "kernel (1 <= D <= 1024, weight (D,), delta like h)")
+                           f"kernel (1 <= D <= {_lib.H.RH_RMS_NORM_MAX_D}, weight (D,), delta like h)")
     hn, y = _AddRmsNormFn.apply(h.reshape(-1, D).contiguous(), None if delta is None else delta.reshape(-1, D).contiguous(),
                                 weight.contiguous(), float(eps))
     return (h if delta is None else hn.view(h.shape)), y.view(h.shape)
@@ -4450,8 +4453,8 @@ def beam_step(logits, running, node, trie):
         raise ValueError(f"beam_step: {int(logits.shape[0])} logits rows for B K = {B} x {K} beams")
     if not (logits.device == running.device == node.device == trie.child_off.device):
         raise ValueError("beam_step: logits, running, node and the trie must be on one device")
-    if not 1 <= K <= 64 or V < 1:
-        raise ValueError(f"beam_step: K={K}, V={V} unsupported (1 <= K <= 64, V >= 1)")
+    if not 1 <= K <= _lib.H.RH_BEAM_MAX_K or V < 1:
+        raise ValueError(f"beam_step: K={K}, V={V} unsupported (1 <= K <= {_lib.H.RH_BEAM_MAX_K}, V >= 1)")
     if trie.max_token >= V:
         raise ValueError(f"beam_step: the trie holds token {trie.max_token}, outside the vocabulary V={V}")
     logits = logits.detach()
@@ -4473,7 +4476,6 @@ def beam_step(logits, running, node, trie):
 # --------------------------------------------------------------------------------------------
 # CIN: one Compressed Interaction Network layer (csrc/cin.hip)
 # --------------------------------------------------------------------------------------------
-CIN_LIMITS = {"D": 128, "F": 64, "Hp": 256, "Ho": 512}  # the ranges of include/rechub_hip.h (rh_cin_*)
 
 
 def _cin_views(x0, h):
@@ -4534,14 +4536,14 @@ class _CinLayerFn(torch.autograd.Function):
 
 
 def cin_layer_ok(x0, h, weight, bias):
-    """True when the HIP kernels take this layer: float32 HIP tensors inside the ranges of rh_cin_* (CIN_LIMITS)."""
+    """True when the HIP kernels take this layer: float32 HIP tensors inside the ranges of rh_cin_* (RH_CIN_MAX_*)."""
     ts = (x0, h, weight, bias)
     if not all(t.is_cuda and t.dtype == torch.float32 for t in ts) or x0.dim() != 3 or h.dim() != 3 or weight.dim() != 3:
         return False
     (B, F, D), Hp, Ho = x0.shape, h.shape[1], weight.shape[0]
-    L = CIN_LIMITS
     return (h.shape[0] == B and h.shape[2] == D and tuple(weight.shape) == (Ho, F * Hp, 1) and tuple(bias.shape) == (Ho,) and
-            1 <= D <= L["D"] and 1 <= F <= L["F"] and 1 <= Hp <= L["Hp"] and 1 <= Ho <= L["Ho"])
+            1 <= D <= _lib.H.RH_CIN_MAX_D and 1 <= F <= _lib.H.RH_CIN_MAX_F and 1 <= Hp <= _lib.H.RH_CIN_MAX_HP and
+            1 <= Ho <= _lib.H.RH_CIN_MAX_HO)
 
 
 def cin_layer(x0, h, weight, bias):
@@ -4565,7 +4567,6 @@ def cin_layer(x0, h, weight, bias):
 # Evaluation metrics (csrc/metric.hip): exact AUC / GAUC, log loss, top-K list metrics
 # --------------------------------------------------------------------------------------------
 _LABEL_DTYPES = {torch.float32: 0, torch.float64: 1, torch.int64: 2, torch.uint8: 3, torch.bool: 3}
-_RANK_MAX_K, _RANK_MAX_CUTOFFS = 256, 8
 _rank_tables = {}
 _PLAN_OUT = (ctypes.c_int, ctypes.c_int, ctypes.c_int64)  # what the metric kernels' plans answer with
 
@@ -4719,8 +4720,8 @@ def rank_metrics(pred_ids, truth, cutoffs, per_user=False):
     float64 = mrr, recall, precision, ndcg summed over users, ``per_user`` (M, n_k, 5) float64 = hit, mrr, recall,
     precision, ndcg or None.  No autograd; current stream."""
     cutoffs = [int(k) for k in cutoffs]
-    if len(cutoffs) > _RANK_MAX_CUTOFFS:  # the newer list metrics answer this with "no HIP kernel"; here it stays a ValueError
-        raise ValueError(f"torch_rechub_amd: rank_metrics takes 1 to {_RANK_MAX_CUTOFFS} cut-offs, got {cutoffs}")
+    if len(cutoffs) > _lib.H.RH_RANK_MAX_CUTOFFS:  # the newer list metrics answer this with "no HIP kernel"; here it stays a ValueError
+        raise ValueError(f"torch_rechub_amd: rank_metrics takes 1 to {_lib.H.RH_RANK_MAX_CUTOFFS} cut-offs, got {cutoffs}")
     pred_ids, ld, M, K, cuts, n_k = _list_inputs("rank_metrics", pred_ids, cutoffs)
     if isinstance(truth, (tuple, list)) and len(truth) == 2 and all(torch.is_tensor(t) for t in truth):
         off, ids = truth
@@ -4750,7 +4751,6 @@ def rank_metrics(pred_ids, truth, cutoffs, per_user=False):
 
 
 # beyond-accuracy metrics (rh_ild, rh_coverage, rh_novelty): intra-list diversity, catalogue coverage, novelty
-_ILD_MAX_D = 1024
 _POP_DTYPES = {torch.float32: 0, torch.float64: 1}
 
 
@@ -4779,15 +4779,15 @@ def _list_inputs(what, pred_ids, cutoffs, *more):
     M, K = (int(v) for v in pred_ids.shape)
     if M == 0 or K == 0:
         raise ValueError(f"torch_rechub_amd: {what} of an empty input")
-    if K > _RANK_MAX_K:
+    if K > _lib.H.RH_RANK_MAX_K:
         from .models.matching._listwise import no_kernel
-        raise no_kernel(f"{what} over K={K} recommendations (1 <= K <= {_RANK_MAX_K})")
+        raise no_kernel(f"{what} over K={K} recommendations (1 <= K <= {_lib.H.RH_RANK_MAX_K})")
     cutoffs = [int(k) for k in cutoffs]
     if not cutoffs or any(not 1 <= k <= K for k in cutoffs):
         raise ValueError(f"torch_rechub_amd: {what} takes cut-offs within [1, K={K}], got {cutoffs}")
-    if len(cutoffs) > _RANK_MAX_CUTOFFS:
+    if len(cutoffs) > _lib.H.RH_RANK_MAX_CUTOFFS:
         from .models.matching._listwise import no_kernel
-        raise no_kernel(f"{what} at {len(cutoffs)} cut-offs (1 to {_RANK_MAX_CUTOFFS})")
+        raise no_kernel(f"{what} at {len(cutoffs)} cut-offs (1 to {_lib.H.RH_RANK_MAX_CUTOFFS})")
     pred_ids = pred_ids.detach()
     if pred_ids.stride(1) != 1 or (M > 1 and pred_ids.stride(0) < K):
         pred_ids = pred_ids.contiguous()
@@ -4809,9 +4809,9 @@ def ild(pred_ids, table, cutoffs, per_user=False):
     V, D = (int(v) for v in table.shape)
     if V == 0 or D == 0:
         raise ValueError("torch_rechub_amd: ild of an empty embedding table")
-    if D > _ILD_MAX_D:
+    if D > _lib.H.RH_ILD_MAX_D:
         from .models.matching._listwise import no_kernel
-        raise no_kernel(f"intra-list diversity over embeddings of width {D} (1 <= D <= {_ILD_MAX_D})")
+        raise no_kernel(f"intra-list diversity over embeddings of width {D} (1 <= D <= {_lib.H.RH_ILD_MAX_D})")
     table = table.detach()
     if table.stride(1) != 1 or (V > 1 and table.stride(0) < D):
         table = table.contiguous()

@@ -35,7 +35,7 @@ LOOK_DEPTH = 2  # step-ahead form: batches beyond the next one whose lookups in 
 
 class TableAdam(torch.optim.Adam):
 
-    RING = 1024  # per-step (A, E) history for the lazy replay; lazy_k must be < RING
+    RING = _lib.H.RH_ADAM_MAX_RING  # per-step (A, E) history for the lazy replay; lazy_k must be < RING
     _rider = None  # weight-gradient group the coming end-of-step launch carries (_ride_wgrad)
     _dp_tail_head = None  # strict head at the END of the step's graph (replicated tables under data parallelism): what _lazy_step launches
 
@@ -169,7 +169,7 @@ class TableAdam(torch.optim.Adam):
         """Step the dense parameters with ONE rh_adam_small launch reading the packed gradient bucket."""
         if [id(p) for p in bucket.params] != [id(p) for p in self._others if p.requires_grad]:
             raise ValueError("TableAdam.attach_bucket: the bucket must hold exactly the non-table parameters, in order")
-        if not bucket.params or len(bucket.params) > 128:
+        if not bucket.params or len(bucket.params) > _lib.H.RH_ADAM_MAX_TENSORS:
             return
         self._bucket = bucket
         dev = bucket.flat.device
@@ -208,7 +208,7 @@ class TableAdam(torch.optim.Adam):
             self._t_hyper[:5].copy_(torch.tensor(host, dtype=torch.float64))
             self._t_hyper_host = host
 
-    MAX_TENSORS = 128  # kMaxTensors of csrc/optim.hip: tensors per multi-tensor launch
+    MAX_TENSORS = _lib.H.RH_ADAM_MAX_TENSORS  # tensors per multi-tensor launch
 
     def _desc(self):
         """[(device descriptor, n tensors, host numel array)] -- one entry per launch of <= MAX_TENSORS tables."""
