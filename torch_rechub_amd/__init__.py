@@ -5,7 +5,9 @@ project name cannot be imported).
 
 Layout (mirrors only what the hot path needs from the reference package):
   csrc/        hand-written HIP kernels + the C ABI (include/rechub_hip.h) -> librechub_hip.so
-  _lib.py      ctypes binding; ops.py: autograd functions over raw pointers + the current HIP stream
+  _lib.py      ctypes binding; ops.py: autograd functions over raw pointers + the current HIP stream (the CTR core, and
+               every op by name); _families/<name>.py: the stateless leaf families, one per csrc/<name>.hip; _opcore.py: the
+               pointer / stream helpers they share with ops.py
   basic/       features, initializers, activation, layers, loss_func, callback   (reference basic/*)
   models/ranking/  DeepFM, WideDeep, DCN, DCNv2, DIN, DIEN, BST, AFM, AutoInt, EDCN, FiBiNet   (reference models/ranking/*)
   models/matching/ DSSM; models/multi_task/ SharedBottom, ESMM, MMOE, PLE, AITM

@@ -4,6 +4,16 @@ Each op hands raw device pointers + the current HIP stream to ``librechub_hip.so
 PyTorch is only the allocator / stream / autograd plumbing here.  There is no CPU path: tensors that
 are not on a HIP device raise ``RuntimeError``.
 
+This module holds the CTR core and everything with module-level state: the fused embedding and its persistent
+gradient buffers, the MLP chain, head and losses, deferred gradients and step fusion, DIN, the cross networks,
+AUGRU, the in-batch sampler, the shard helpers, the kernel error word, and the A/B switches the tests flip as
+attributes of this module.  The pointer / stream helpers and the dropout counter come from ``_opcore``.  The
+stateless retrieval, sequence and metric families live in ``_families``, one module per ``csrc/<name>.hip``
+(interest, sine, rq, hstu, hllm, session, topk, ivf, sasrec, twotower, t5attn, beam, cin, metric), and are
+re-exported at the end of this file: every op is still called as ``ops.<name>``.  The few functions of those
+families that call the core (``err_flag``, ``check_errors``, ``linear``, ``linear_wgrad``) stay here, just
+above the re-exports.
+
 Gradient convention for embedding tables (replaces ``embedding_dense_backward`` + ``model.zero_grad``,
 reference trainers/ctr_trainer.py:97-98): every table owns ONE persistent dense gradient buffer
 (``grad_buffer(weight)``), zero outside the rows touched since the last optimizer step.  The fused
@@ -11,38 +21,14 @@ backward scatter-adds into it and publishes it as ``weight.grad``; ``FusedDenseA
 touched rows inside its own pass.  A stock ``torch.optim`` optimizer sees an ordinary dense ``.grad``.
 """
 import ctypes
-import math
 import os
 from collections import OrderedDict
 
 import torch
 
 from . import _lib
-
-_NULL = ctypes.c_void_p(0)
-
-
-_empty_stub = {}
-
-
-def _p(t):
-    """Device pointer of a tensor for the C ABI.  An EMPTY tensor has a null data_ptr(); the entry points check their
-    pointers before they look at the sizes (and then return at once for B = 0), so empties are passed as a pointer to
-    a small per-device stub allocation."""
-    if t is None:
-        return _NULL
-    if t.numel() == 0:
-        stub = _empty_stub.get(t.device)
-        if stub is None:
-            stub = torch.zeros(64, dtype=torch.float32, device=t.device)
-            _empty_stub[t.device] = stub
-        return ctypes.c_void_p(stub.data_ptr())
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
+from ._opcore import (_NULL, _attn_view_ok, _dropout_rng, _empty_stub, _int_array, _p, _ptr_array, _rng_state,  # noqa: F401
+                      _stream, require_hip)
 
 _BRANCH_STREAMS = {}
 
@@ -70,15 +56,6 @@ def run_beside(fn_main, fn_side, side_inputs=()):
         if torch.is_tensor(t):
             t.record_stream(cur)
     return a, b
-
-
-def require_hip(*tensors):
-    """Fail loudly for anything that is not a HIP tensor (there is no CPU fallback)."""
-    for t in tensors:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError("torch_rechub_amd: this op runs only on a HIP device (MI355X); got a "
-                               f"{t.device} tensor. There is no CPU fallback by design.")
-    _lib.load()
 
 
 # --------------------------------------------------------------------------------------------
@@ -944,18 +921,6 @@ def cross_network(x, W, Bv):
 
 
 # --------------------------------------------------------------------------------------------
-_rng_state = {}
-
-
-def _dropout_rng(device):
-    """Device-resident (seed, call counter) of the fused dropout; seeded from torch's generator on first use."""
-    st = _rng_state.get(device)
-    if st is None:
-        st = torch.tensor([torch.initial_seed() & 0x7FFFFFFFFFFFFFFF, 0, 0, 0], dtype=torch.int64).to(device)
-        _rng_state[device] = st
-    return st
-
-
 class _BnReluDropoutFn(torch.autograd.Function):
     """y = dropout(relu(batch_norm(h))) for one MLP hidden layer (training mode); see csrc/mlp.hip.
     ``stats`` / ``stats_ctr``: per-slab (sum, M2) of h and the dropout counter drawn by the GEMM that produced h
@@ -2456,16 +2421,6 @@ def cross_mix_epilogue(x0, xl, uv, gate, bias):
 
 
 # --------------------------------------------------------------------------------------------
-def _ptr_array(tensors):
-    import ctypes
-    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-
-
-def _int_array(values):
-    import ctypes
-    return (ctypes.c_int * len(values))(*values)
-
-
 def cross_moe_ok(x, L, E, d, r):
     return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] >= 1 and x.stride(1) == 1 and
             _lib.call("rh_cross_moe_supported", L, E, d, r) == 1)
@@ -2788,473 +2743,10 @@ def shard_localize(idx, desc, world, rank, out=None):
 
 
 # --------------------------------------------------------------------------------------------
-# multi-interest user towers and list-wise scoring (csrc/interest.hip)
-class _CapsuleFn(torch.autograd.Function):
-    """CapsuleNetwork routing (reference basic/layers.py:657-712).  Types 0 / 1: x = the Linear's output U (B, L, Iu*D);
-    type 2: x = the history E (B, L, D) and w the (1, L, I*D, D) weight.  Gradient through the last iteration only."""
-
-    @staticmethod
-    def forward(ctx, x, w, mask, init, kind, I, D, iters):
-        B, L = int(mask.shape[0]), int(mask.shape[1])
-        x = x.contiguous()
-        w = w.contiguous() if w is not None else None
-        dev = x.device
-        cap = torch.empty((B, I, D), dtype=torch.float32, device=dev)
-        sw = torch.empty((B, I, L), dtype=torch.float32, device=dev)
-        s = torch.empty((B, I, D), dtype=torch.float32, device=dev)
-        U, E = (None, x) if kind == 2 else (x, None)
-        _lib.call("rh_capsule_fwd", _p(U), _p(E), _p(w), _p(mask), _p(init), B, L, I, D, kind, iters, _p(cap), _p(sw), _p(s),
-                  _stream())
-        ctx.dims = (B, L, I, D, kind)
-        ctx.save_for_backward(x, w, sw, s)
-        return cap
-
-    @staticmethod
-    def backward(ctx, g):
-        x, w, sw, s = ctx.saved_tensors
-        B, L, I, D, kind = ctx.dims
-        g = g.contiguous()
-        dev = g.device
-        if kind != 2:
-            g_u = torch.empty(x.shape, dtype=torch.float32, device=dev)
-            _lib.call("rh_capsule_bwd", _p(g), _p(s), _p(sw), _NULL, B, L, I, D, kind, _p(g_u), _NULL, _NULL, _stream())
-            return g_u, None, None, None, None, None, None, None
-        g_e = torch.empty((B, L, D), dtype=torch.float32, device=dev)
-        g_s = torch.empty((B, I, D), dtype=torch.float32, device=dev)
-        _lib.call("rh_capsule_bwd", _p(g), _p(s), _p(sw), _p(w), B, L, I, D, 2, _NULL, _p(g_e), _p(g_s), _stream())
-        g_w = None
-        if ctx.needs_input_grad[1]:
-            g_w = torch.empty(w.shape, dtype=torch.float32, device=dev)
-            if B == 0:
-                g_w.zero_()
-            else:
-                nch = _lib.call("rh_capsule_wgrad_nchunks", B)
-                part = torch.empty((nch, L * I * D * D), dtype=torch.float32, device=dev)
-                _lib.call("rh_capsule_wgrad", _p(g_s), _p(sw), _p(x), B, L, I, D, _p(part), _stream())
-                _lib.call("rh_colsum", _p(part), nch, L * I * D * D, _p(g_w), _NULL, 0, _NULL, _stream())
-        return g_e, g_w, None, None, None, None, None, None
-
-
-def capsule_supported(L, I, D, kind):
-    return bool(_lib.call("rh_capsule_supported", int(L), int(I), int(D), int(kind)))
-
-
-def capsule_routing(x, w, mask, init, kind, interest_num, embed_dim, routing_times):
-    """(B, I, D) interest capsules; ``mask`` (B, L) int32 (nonzero = kept), ``init`` (B, I, L) initial logits or None."""
-    require_hip(x, w, mask, init)
-    return _CapsuleFn.apply(x, w, mask, init, int(kind), int(interest_num), int(embed_dim), int(routing_times))
-
-
-class _SaPoolFn(torch.autograd.Function):
-    """MultiInterestSA after A = tanh(E W1) W2: softmax over L of A + -1e9 (1 - mask), then A^T E (layers.py:601-608)."""
-
-    @staticmethod
-    def forward(ctx, A, E, mask):
-        A, E = A.contiguous(), E.contiguous()
-        B, L, I = (int(v) for v in A.shape)
-        D = int(E.shape[2])
-        P = torch.empty((B, L, I), dtype=torch.float32, device=A.device)
-        out = torch.empty((B, I, D), dtype=torch.float32, device=A.device)
-        _lib.call("rh_sa_pool_fwd", _p(A), _p(E), _p(mask), B, L, I, D, _p(P), _p(out), _stream())
-        ctx.save_for_backward(P, E)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        P, E = ctx.saved_tensors
-        B, L, I = (int(v) for v in P.shape)
-        D = int(E.shape[2])
-        g = g.contiguous()
-        gA = torch.empty((B, L, I), dtype=torch.float32, device=g.device)
-        gE = torch.empty((B, L, D), dtype=torch.float32, device=g.device)
-        _lib.call("rh_sa_pool_bwd", _p(P), _p(E), _p(g), B, L, I, D, _p(gA), _p(gE), _stream())
-        return gA, gE, None
-
-
-def sa_supported(L, I, D):
-    return bool(_lib.call("rh_sa_supported", int(L), int(I), int(D)))
-
-
-def sa_pool(A, E, mask=None):
-    """(B, I, D) = softmax_L(A + -1e9 (1 - mask))^T E for A (B, L, I), E (B, L, D), mask (B, L) int32 or None."""
-    require_hip(A, E, mask)
-    return _SaPoolFn.apply(A, E, mask)
-
-
-class _ListwiseFn(torch.autograd.Function):
-    """(B, 1 + K) logits of the list-wise retrieval models: normalised item rows, best interest by the positive."""
-
-    @staticmethod
-    def forward(ctx, u, pos, neg, temperature):
-        u, neg = u.contiguous(), neg.contiguous()
-        if pos.stride(1) != 1:
-            pos = pos.contiguous()
-        B, I, D = (int(v) for v in u.shape)
-        K = int(neg.shape[1])
-        dev = u.device
-        logits = torch.empty((B, 1 + K), dtype=torch.float32, device=dev)
-        best = torch.empty((B,), dtype=torch.int32, device=dev)
-        nrm = torch.empty((B, 1 + K), dtype=torch.float32, device=dev)
-        _lib.call("rh_listwise_fwd", _p(u), _p(pos), pos.stride(0), _p(neg), B, I, D, K, float(temperature), _p(logits),
-                  _p(best), _p(nrm), _stream())
-        ctx.temperature = float(temperature)
-        ctx.save_for_backward(u, pos, neg, best, nrm)
-        ctx.mark_non_differentiable(best)
-        return logits, best
-
-    @staticmethod
-    def backward(ctx, g, _unused):
-        u, pos, neg, best, nrm = ctx.saved_tensors
-        B, I, D = (int(v) for v in u.shape)
-        K = int(neg.shape[1])
-        g = g.contiguous()
-        dev = g.device
-        g_u = torch.empty((B, I, D), dtype=torch.float32, device=dev)
-        g_pos = torch.empty((B, D), dtype=torch.float32, device=dev)
-        g_neg = torch.empty((B, K, D), dtype=torch.float32, device=dev)
-        _lib.call("rh_listwise_bwd", _p(u), _p(pos), pos.stride(0), _p(neg), _p(best), _p(nrm), _p(g), B, I, D, K,
-                  ctx.temperature, _p(g_u), _p(g_pos), _p(g_neg), _stream())
-        return g_u, g_pos, g_neg, None
-
-
-def listwise_ok(u, pos, neg):
-    return (u.is_cuda and u.dtype == pos.dtype == neg.dtype == torch.float32 and u.dim() == 3 and pos.dim() == 2 and
-            neg.dim() == 3 and 1 <= u.shape[1] <= _lib.H.RH_LISTWISE_MAX_I and 1 <= u.shape[2] <= _lib.H.RH_LISTWISE_MAX_D and
-            pos.shape == (u.shape[0], u.shape[2])
-            and neg.shape[0] == u.shape[0] and neg.shape[2] == u.shape[2] and neg.shape[1] <= _lib.H.RH_LISTWISE_MAX_K)
-
-
-def listwise_logits(u, pos, neg, temperature=1.0):
-    """(logits (B, 1 + K), best (B,) int32): logits = u_best . normalize([pos, neg]) / temperature, u (B, I, D) the
-    normalised user vectors, pos (B, D) / neg (B, K, D) the raw item rows; best = first argmax_i u_i . normalize(pos)."""
-    require_hip(u, pos, neg)
-    if not listwise_ok(u, pos, neg):
-        raise RuntimeError(f"torch_rechub_amd: list-wise scoring of user {tuple(u.shape)}, items {tuple(pos.shape)} / "
-                           f"{tuple(neg.shape)} has no HIP kernel (I <= {_lib.H.RH_LISTWISE_MAX_I}, D <= {_lib.H.RH_LISTWISE_MAX_D}, "
-                           f"K <= {_lib.H.RH_LISTWISE_MAX_K}, float32)")
-    return _ListwiseFn.apply(u, pos, neg, float(temperature))
-
-
+# What the sequence families need of the core above and therefore keep here: the streaming cross-entropy heads and
+# session_lengths report through err_flag / check_errors (csrc/stream_ce.hip, csrc/session.hip), the general GRU and
+# SASRec's attention-input and feed-forward stages run on linear / linear_wgrad (csrc/session.hip, csrc/sasrec.hip).
 # --------------------------------------------------------------------------------------------
-# SINE's sparse-interest chain (csrc/sine.hip)
-class _SineInterestFn(torch.autograd.Function):
-    """sine.py:94-118 between the w_1 / w_k1 / w_3 products and h_3: (phi (B, K, E), xhat (B, S, E), idx (B, K) int32)."""
-
-    @staticmethod
-    def forward(ctx, X, Y, a1, a2, mask, C):
-        X, Y, a1, a2, C = X.contiguous(), Y.contiguous(), a1.contiguous(), a2.contiguous(), C.contiguous()
-        B, S, E = (int(v) for v in X.shape)
-        K, T = int(a2.shape[2]), int(C.shape[0])
-        dev = X.device
-        idx = torch.empty((B, K), dtype=torch.int32, device=dev)
-        phi = torch.empty((B, K, E), dtype=torch.float32, device=dev)
-        xhat = torch.empty((B, S, E), dtype=torch.float32, device=dev)
-        P1 = torch.empty((B, S), dtype=torch.float32, device=dev)
-        P2 = torch.empty((B, K, S), dtype=torch.float32, device=dev)
-        PU = torch.empty((B, K, S), dtype=torch.float32, device=dev)
-        _lib.call("rh_sine_interest_fwd", _p(X), _p(Y), _p(a1), _p(a2), _p(mask), _p(C), B, S, E, T, K, _p(idx), _p(phi),
-                  _p(xhat), _p(P1), _p(P2), _p(PU), _stream())
-        ctx.save_for_backward(X, Y, C, mask, idx, P1, P2, PU)
-        ctx.mark_non_differentiable(idx)
-        return phi, xhat, idx
-
-    @staticmethod
-    def backward(ctx, g_phi, g_xhat, _unused):
-        X, Y, C, mask, idx, P1, P2, PU = ctx.saved_tensors
-        B, S, E = (int(v) for v in X.shape)
-        K, T = int(idx.shape[1]), int(C.shape[0])
-        dev = X.device
-        g_phi, g_xhat = g_phi.contiguous(), g_xhat.contiguous()  # (autograd materialises an unused output's as zeros)
-        g_X = torch.empty((B, S, E), dtype=torch.float32, device=dev)
-        g_Y = torch.empty((B, S, E), dtype=torch.float32, device=dev)
-        g_a1 = torch.empty((B, S), dtype=torch.float32, device=dev)
-        g_a2 = torch.empty((B, S, K), dtype=torch.float32, device=dev)
-        g_C = torch.empty((T, E), dtype=torch.float32, device=dev)
-        if B == 0:
-            g_C.zero_()
-        else:
-            nch = _lib.query("rh_sine_nchunks", B)
-            rows = torch.empty((B, K, E), dtype=torch.float32, device=dev)
-            part = torch.empty((nch, T * E), dtype=torch.float32, device=dev)
-            _lib.call("rh_sine_interest_bwd", _p(X), _p(Y), _p(C), _p(idx), _p(P1), _p(P2), _p(PU), _p(g_phi), _p(g_xhat), B,
-                      S, E, T, K, _p(g_X), _p(g_Y), _p(g_a1), _p(g_a2), _p(rows), _p(part), _stream())
-            _lib.call("rh_colsum", _p(part), nch, T * E, _p(g_C), _NULL, 0, _NULL, _stream())
-        return g_X, g_Y, g_a1, g_a2, None, g_C
-
-
-class _SineAggregateFn(torch.autograd.Function):
-    """sine.py:122-128 after h_3 w_5: v (B, E).  The backward recomputes the chain from the inputs (in fp64, csrc/sine.hip)."""
-
-    @staticmethod
-    def forward(ctx, xhat, a3, mask, phi, inv_t):
-        xhat, a3, phi = xhat.contiguous(), a3.contiguous(), phi.contiguous()
-        B, S, E = (int(v) for v in xhat.shape)
-        K = int(phi.shape[1])
-        v = torch.empty((B, E), dtype=torch.float32, device=xhat.device)
-        _lib.call("rh_sine_aggregate_fwd", _p(xhat), _p(a3), _p(mask), _p(phi), inv_t, B, S, E, K, _p(v), _stream())
-        ctx.inv_t = inv_t
-        ctx.save_for_backward(xhat, a3, mask, phi)
-        return v
-
-    @staticmethod
-    def backward(ctx, g_v):
-        xhat, a3, mask, phi = ctx.saved_tensors
-        B, S, E = (int(v) for v in xhat.shape)
-        K = int(phi.shape[1])
-        dev = xhat.device
-        g_v = g_v.contiguous()
-        g_xhat = torch.empty((B, S, E), dtype=torch.float32, device=dev)
-        g_a3 = torch.empty((B, S), dtype=torch.float32, device=dev)
-        g_phi = torch.empty((B, K, E), dtype=torch.float32, device=dev)
-        _lib.call("rh_sine_aggregate_bwd", _p(xhat), _p(a3), _p(mask), _p(phi), _p(g_v), ctx.inv_t, B, S, E, K, _p(g_xhat),
-                  _p(g_a3), _p(g_phi), _stream())
-        return g_xhat, g_a3, None, g_phi, None
-
-
-def sine_supported(S, E, T, K):
-    return bool(_lib.query("rh_sine_supported", int(S), int(E), int(T), int(K)))
-
-
-def _sine_check(what, tensors, mask, S, E, T, K):
-    if any(t.dtype != torch.float32 for t in tensors) or mask.dtype != torch.int32 or not mask.is_contiguous():
-        raise ValueError(f"torch_rechub_amd: {what} takes float32 tensors and a contiguous int32 mask")
-    if not sine_supported(S, E, T, K):
-        from .models.matching._listwise import no_kernel
-        raise no_kernel(f"{what} at seq_max_len {S}, embedding_dim {E}, num_concept {T}, num_intention {K} "
-                        f"(S <= {_lib.H.RH_SINE_MAX_S}, E <= {_lib.H.RH_SINE_MAX_E}, T <= {_lib.H.RH_SINE_MAX_T}, "
-                        f"K <= min(T, {_lib.H.RH_SINE_MAX_K}))")
-
-
-def sine_interests(X, Y, a1, a2, mask, C):
-    """(phi (B, K, E), xhat (B, S, E), idx (B, K) int32) of SINE's sparse-interest extraction (sine.py:94-118) from
-    X = x_u and Y = X w_3 (B, S, E), a1 (B, S) = tanh(X w_1) w_2, a2 (B, S, K) = tanh(X w_k1) w_k2, mask (B, S) int32
-    (1 = kept) and the concept table C (T, E).  idx are the chosen concepts in descending score order."""
-    require_hip(X, Y, a1, a2, mask, C)
-    B, S, E = (int(v) for v in X.shape)
-    if Y.shape != X.shape or a1.shape != (B, S) or a2.dim() != 3 or a2.shape[:2] != (B, S) or mask.shape != (B, S) or \
-            C.dim() != 2 or C.shape[1] != E:
-        raise ValueError("sine_interests: X, Y (B, S, E), a1 (B, S), a2 (B, S, K), mask (B, S), C (T, E) expected")
-    _sine_check("SINE's interest extraction", (X, Y, a1, a2, C), mask, S, E, int(C.shape[0]), int(a2.shape[2]))
-    return _SineInterestFn.apply(X, Y, a1, a2, mask, C)
-
-
-def sine_aggregate(xhat, a3, mask, phi, temperature):
-    """v (B, E) of SINE's interest aggregation (sine.py:122-128) from xhat (B, S, E), a3 (B, S) = tanh(xhat w_4) w_5,
-    mask (B, S) int32 and phi (B, K, E)."""
-    require_hip(xhat, a3, mask, phi)
-    B, S, E = (int(v) for v in xhat.shape)
-    if a3.shape != (B, S) or mask.shape != (B, S) or phi.dim() != 3 or phi.shape[0] != B or phi.shape[2] != E:
-        raise ValueError("sine_aggregate: xhat (B, S, E), a3 (B, S), mask (B, S), phi (B, K, E) expected")
-    K = int(phi.shape[1])
-    _sine_check("SINE's interest aggregation", (xhat, a3, phi), mask, S, E, max(K, 1), K)
-    return _SineAggregateFn.apply(xhat, a3, mask, phi, 1.0 / float(temperature))
-
-
-# --------------------------------------------------------------------------------------------
-# RQ-VAE's residual quantizer (csrc/rq.hip)
-def rq_supported(E, sizes):
-    """Whether csrc/rq.hip takes rows of width E against codebooks of these sizes (E <= RH_RQ_MAX_E, sizes <= RH_RQ_MAX_CODES, <= RH_RQ_MAX_L
-    levels)."""
-    sizes = [int(v) for v in sizes]
-    arr = _int_array(sizes)
-    return bool(_lib.query("rh_rq_supported", int(E), len(sizes), ctypes.cast(arr, ctypes.c_void_p)))
-
-
-def _rq_check(x, codebooks):
-    require_hip(x, *codebooks)
-    if x.dim() != 2 or not codebooks or any(c.dim() != 2 or c.shape[1] != x.shape[1] for c in codebooks):
-        raise ValueError("residual quantizer: rows (N, E) and codebooks (n_e, E) expected")
-    if x.dtype != torch.float32 or any(c.dtype != torch.float32 for c in codebooks):
-        raise ValueError("torch_rechub_amd: the residual quantizer takes float32 tensors")
-    sizes = [int(c.shape[0]) for c in codebooks]
-    if not rq_supported(int(x.shape[1]), sizes):
-        from .models.matching._listwise import no_kernel
-        raise no_kernel(f"the residual quantizer at e_dim {int(x.shape[1])} with codebook sizes {sizes} "
-                        f"(e_dim <= {_lib.H.RH_RQ_MAX_E}, sizes <= {_lib.H.RH_RQ_MAX_CODES}, at most {_lib.H.RH_RQ_MAX_L} levels)")
-    return sizes
-
-
-def rq_forward(r_in, codebooks, l0=0, l1=None, given=0, idx=None, sse=None):
-    """The levels [l0, l1) of the residual quantizer on r_in (N, E), the residual entering level l0: (idx (N, L) int32,
-    r_out (N, E), x_q = r_in - r_out, sse (L,)).  Level l takes its index from ``idx`` instead of searching it when bit l of
-    ``given`` is set.  ``idx`` and ``sse`` of an earlier call are continued in place.  No autograd."""
-    codebooks = [c.detach().contiguous() for c in codebooks]
-    r_in = r_in.detach().contiguous()
-    sizes = _rq_check(r_in, codebooks)
-    N, E = (int(v) for v in r_in.shape)
-    L = len(sizes)
-    l1 = L if l1 is None else int(l1)
-    if not 0 <= l0 < l1 <= L:
-        raise ValueError(f"residual quantizer: level range [{l0}, {l1}) of {L}")
-    dev = r_in.device
-    whole = l0 == 0 and l1 == L  # every element of idx and sse is written by this call
-    if idx is None:
-        if given:
-            raise ValueError("residual quantizer: given levels need their indices")
-        idx = (torch.empty if whole and N else torch.zeros)((N, L), dtype=torch.int32, device=dev)
-    if sse is None:
-        sse = (torch.empty if whole and N else torch.zeros)((L,), dtype=torch.float32, device=dev)
-    r_out = torch.empty((N, E), dtype=torch.float32, device=dev)
-    x_q = torch.empty((N, E), dtype=torch.float32, device=dev)
-    if N:
-        blocks, _ = _lib.query("rh_rq_nchunks", N, out=(ctypes.c_int, ctypes.c_int))
-        part = torch.empty((blocks, l1 - l0), dtype=torch.float32, device=dev)
-        _lib.call("rh_rq_fwd", _p(r_in), ctypes.cast(_ptr_array(codebooks), ctypes.c_void_p),
-                  ctypes.cast(_int_array(sizes), ctypes.c_void_p), N, E, L, int(l0), l1, int(given), _p(idx), _p(r_out),
-                  _p(x_q), _p(part), _p(sse), _stream())
-    return idx, r_out, x_q, sse
-
-
-def _sinkhorn_level(r, C, epsilon, iters):
-    """Index of every row at a Sinkhorn level, as torch ops on the device (rqvae.py:248-258)."""
-    from .models.generative.rqvae import VectorQuantizer, sinkhorn_algorithm
-    d = torch.sum(r**2, dim=1, keepdim=True) + torch.sum(C**2, dim=1, keepdim=True).t() - 2 * torch.matmul(r, C.t())
-    d = VectorQuantizer.center_distance_for_constraint(d).double()
-    Q = sinkhorn_algorithm(d, epsilon, iters)
-    if torch.isnan(Q).any() or torch.isinf(Q).any():
-        print("Sinkhorn Algorithm returns nan/inf values.")
-    return torch.argmax(Q, dim=-1).to(torch.int32)
-
-
-class _ResidualQuantizeFn(torch.autograd.Function):
-    """(x_q (N, E), loss (), idx (N, L) int64) of rqvae.py:382-398 on x (N, E); sk = ((level, epsilon, iterations), ...)."""
-
-    @staticmethod
-    def forward(ctx, x, beta, sk, *codebooks):
-        x = x.contiguous()
-        cbs = [c.detach().contiguous() for c in codebooks]
-        N, E = (int(v) for v in x.shape)
-        L = len(cbs)
-        idx, sse, r, l0, given, x_q = None, None, x, 0, 0, None
-        for level, eps, iters in sk:  # the cold path: the levels before a Sinkhorn level, then its index as torch ops
-            if level > l0:
-                idx, r, _, sse = rq_forward(r, cbs, l0, level, given, idx, sse)
-            if idx is None:
-                idx = torch.zeros((N, L), dtype=torch.int32, device=x.device)
-            idx[:, level] = _sinkhorn_level(r, cbs[level], eps, iters)
-            l0, given = level, given | (1 << level)
-        idx, r, x_q, sse = rq_forward(r, cbs, l0, L, given, idx, sse)
-        if l0 > 0:
-            x_q = x - r
-        loss = sse.sum() * ((1.0 + beta) / (float(N) * E * L)) if N else sse.sum() * float("nan")
-        ctx.beta = beta
-        ctx.save_for_backward(x, idx, *cbs)
-        out_idx = idx.to(torch.int64)
-        ctx.mark_non_differentiable(out_idx)
-        return x_q, loss, out_idx
-
-    @staticmethod
-    def backward(ctx, g_xq, g_loss, _unused):
-        x, idx, *cbs = ctx.saved_tensors
-        N, E = (int(v) for v in x.shape)
-        sizes = [int(c.shape[0]) for c in cbs]
-        dev = x.device
-        total = sum(sizes) * E
-        g_x = torch.empty((N, E), dtype=torch.float32, device=dev)
-        g_C = torch.empty((total,), dtype=torch.float32, device=dev)
-        if N == 0:
-            g_C.zero_()
-        else:
-            _, nch = _lib.query("rh_rq_nchunks", N, out=(ctypes.c_int, ctypes.c_int))
-            part = torch.empty((nch, total), dtype=torch.float32, device=dev)
-            g_loss, g_xq = g_loss.to(torch.float32).contiguous(), g_xq.contiguous()
-            _lib.call("rh_rq_bwd", _p(x), ctypes.cast(_ptr_array(cbs), ctypes.c_void_p),
-                      ctypes.cast(_int_array(sizes), ctypes.c_void_p), _p(idx), _p(g_xq), _p(g_loss),
-                      float(ctx.beta), N, E, len(cbs), _p(g_x), _p(part), _p(g_C), _stream())
-        grads, off = [], 0
-        for n in sizes:
-            grads.append(g_C[off:off + n * E].view(n, E))
-            off += n * E
-        return (g_x, None, None, *grads)
-
-
-def residual_quantize(x, codebooks, beta, sk_epsilons=None, sk_iters=100, use_sk=True):
-    """(x_q, loss, indices) of the RQ-VAE's residual quantizer (rqvae.py:241-274 per level, :382-398 across levels) on x
-    (..., E) and the codebooks [(n_e, E), ...]: x_q = x + (sum of the chosen codes - x).detach(), loss = the mean over
-    levels of codebook_loss + beta commitment_loss, indices int64 of shape x.shape[:-1] + (L,).  A level with ``use_sk`` and
-    ``sk_epsilons[l] > 0`` takes its index from the Sinkhorn assignment (torch ops on the device; ``sk_iters`` an int or one
-    per level); every other level, the distances, arg-min, gathers, losses and the backward are csrc/rq.hip."""
-    codebooks = list(codebooks)
-    if not codebooks:
-        raise ValueError("residual_quantize: at least one codebook expected")
-    flat = x.reshape(-1, x.shape[-1])
-    _rq_check(flat, codebooks)
-    L = len(codebooks)
-    eps = [0.0] * L if sk_epsilons is None else [float(e) for e in sk_epsilons]
-    if len(eps) != L:
-        raise ValueError(f"residual_quantize: {len(eps)} sk_epsilons for {L} codebooks")
-    iters = [int(sk_iters)] * L if isinstance(sk_iters, int) else [int(v) for v in sk_iters]
-    sk = tuple((l, eps[l], iters[l]) for l in range(L) if use_sk and eps[l] > 0)
-    x_q, loss, idx = _ResidualQuantizeFn.apply(flat, float(beta), sk, *codebooks)
-    return x_q.view(x.shape), loss, idx.view(tuple(x.shape[:-1]) + (L,))
-
-
-# --------------------------------------------------------------------------------------------
-# HSTU: pointwise relative-bias attention (csrc/hstu.hip) and the next-token head (csrc/stream_ce.hip)
-# --------------------------------------------------------------------------------------------
-class _HstuAttnFn(torch.autograd.Function):
-    """(B, L, H dv) = (silu(alpha q k^T + rab) / N, causal and key-padding masked) v, q / k / v read from proj."""
-
-    @staticmethod
-    def forward(ctx, proj, pos_w, ts_w, td, kmask, cfg):
-        proj = proj.contiguous()
-        B, L, ld = (int(v) for v in proj.shape)
-        H, dqk, dv, N, nb, fn_log, minutes, divisor, alpha = cfg
-        out = torch.empty((B, L, H * dv), dtype=torch.float32, device=proj.device)
-        _lib.call("rh_hstu_attn_fwd", _p(proj), ld, B, L, H, dqk, dv, _p(td), _p(kmask), _p(pos_w), _p(ts_w), N, nb,
-                  fn_log, minutes, divisor, alpha, _p(out), _stream())
-        ctx.cfg = cfg
-        ctx.save_for_backward(proj, pos_w, ts_w, td, kmask)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        proj, pos_w, ts_w, td, kmask = ctx.saved_tensors
-        B, L, ld = (int(v) for v in proj.shape)
-        H, dqk, dv, N, nb, fn_log, minutes, divisor, alpha = ctx.cfg
-        g = g.contiguous()
-        dev = g.device
-        g_proj = torch.zeros((B, L, ld), dtype=torch.float32, device=dev)  # the u columns stay zero
-        if B == 0:
-            return g_proj, torch.zeros_like(pos_w), torch.zeros_like(ts_w), None, None, None
-        nparts = _lib.call("rh_hstu_attn_nparts", B, L, H)
-        pos_part = torch.empty((nparts, L), dtype=torch.float32, device=dev)
-        ts_part = torch.empty((nparts, nb + 1), dtype=torch.float32, device=dev) if td is not None else None
-        g_pos = torch.empty_like(pos_w)
-        g_ts = torch.empty_like(ts_w)
-        _lib.call("rh_hstu_attn_bwd", _p(proj), ld, B, L, H, dqk, dv, _p(td), _p(kmask), _p(pos_w), _p(ts_w), N, nb,
-                  fn_log, minutes, divisor, alpha, _p(g), _p(g_proj), _p(pos_part), _p(ts_part), _p(g_pos), _p(g_ts),
-                  _stream())
-        return g_proj, g_pos, g_ts, None, None, None
-
-
-def hstu_attention(proj, pos_w, ts_w, n_heads, dqk, dv, max_seq_len, time_diffs=None, padding_mask=None,
-                   num_time_buckets=128, time_bucket_fn="sqrt", time_bucket_divisor=1.0, time_bucket_unit="minutes"):
-    """HSTU attention output (B, L, H dv) from ``proj`` (B, L, 2 H (dqk + dv)) = silu(proj1(LN(x))) laid out [q | k | u | v],
-    the rab tables pos_w (2 N - 1, H) / ts_w (nb + 1, H), time_diffs (B, L) int64 seconds or None (position-only bias) and
-    padding_mask (B, L) bool (True = valid key) or None."""
-    require_hip(proj, pos_w, ts_w, time_diffs, padding_mask)
-    if proj.dtype != torch.float32 or pos_w.dtype != torch.float32 or ts_w.dtype != torch.float32:
-        raise RuntimeError("torch_rechub_amd: HSTU attention runs in float32 only")
-    B, L, W = (int(v) for v in proj.shape)
-    if W != 2 * n_heads * (dqk + dv):
-        raise RuntimeError(f"torch_rechub_amd: HSTU projection width {W} != 2 * {n_heads} * ({dqk} + {dv})")
-    if not (1 <= L <= min(int(max_seq_len), _lib.H.RH_HSTU_MAX_L) and 1 <= dqk <= _lib.H.RH_HSTU_MAX_DH and
-            1 <= dv <= _lib.H.RH_HSTU_MAX_DH and
-            num_time_buckets <= _lib.H.RH_HSTU_MAX_BUCKETS):
-        raise RuntimeError(f"torch_rechub_amd: HSTU attention with L={L}, dqk={dqk}, dv={dv}, "
-                           f"num_time_buckets={num_time_buckets} has no HIP kernel (L <= min(max_seq_len, "
-                           f"{_lib.H.RH_HSTU_MAX_L}), dqk, dv <= {_lib.H.RH_HSTU_MAX_DH}, "
-                           f"num_time_buckets <= {_lib.H.RH_HSTU_MAX_BUCKETS})")
-    if time_bucket_fn not in ("sqrt", "log") or time_bucket_unit not in ("minutes", "seconds"):
-        raise ValueError(f"Unsupported time bucketing {time_bucket_fn!r} / {time_bucket_unit!r}")
-    td = None if time_diffs is None else time_diffs.to(torch.int64).contiguous()
-    km = None if padding_mask is None else padding_mask.to(torch.int32).contiguous()
-    cfg = (int(n_heads), int(dqk), int(dv), int(max_seq_len), int(num_time_buckets), int(time_bucket_fn == "log"),
-           int(time_bucket_unit == "minutes"), float(time_bucket_divisor), 1.0 / math.sqrt(dqk))
-    return _HstuAttnFn.apply(proj, pos_w.contiguous(), ts_w.contiguous(), td, km, cfg)
-
-
 def _head_fwd_workspaces(M, V, dev):
     """part, zlab, lse, wrow, loss of the streaming cross entropy's forward over M rows and V items."""
     nsplit = _lib.call("rh_hstu_head_nsplit", M, V)
@@ -3322,90 +2814,6 @@ def next_token_loss(h, weight, bias, labels, temperature=1.0, nce_temperature=No
                                   float(nce_temperature) if nce else 1.0, nce)
 
 
-# --------------------------------------------------------------------------------------------
-# HLLM: causal softmax attention with the bucketed relative-position bias and dropout (csrc/hllm.hip)
-# --------------------------------------------------------------------------------------------
-class _SoftmaxAttnFn(torch.autograd.Function):
-    """(B, L, H dh) = dropout(softmax_j(scale q k^T + bias, causal)) v; keeps the rows' log-sum-exp, never the weights."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, bias, cfg):
-        H, dh, N, nb, scale, p = cfg
-        B, L = int(q.shape[0]), int(q.shape[1])
-        ld = int(q.stride(1))
-        dev = q.device
-        out = torch.empty((B, L, H * dh), dtype=torch.float32, device=dev)
-        lse = torch.empty((B, H, L), dtype=torch.float32, device=dev)
-        rng = _dropout_rng(dev) if p > 0 else None
-        ctr = torch.empty(1, dtype=torch.int64, device=dev) if p > 0 else None
-        _lib.call("rh_softmax_attn_fwd", _p(q), _p(k), _p(v), ld, B, L, H, dh, _p(bias), N, nb, scale, p, _p(rng), _p(ctr),
-                  _p(out), _p(lse), _stream())
-        ctx.cfg = cfg
-        ctx.save_for_backward(q, k, v, bias, out, lse, rng, ctr)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        q, k, v, bias, out, lse, rng, ctr = ctx.saved_tensors
-        H, dh, N, nb, scale, p = ctx.cfg
-        B, L = int(q.shape[0]), int(q.shape[1])
-        dev = q.device
-        g = g.contiguous()
-        g_qkv = torch.empty((3, B, L, H * dh), dtype=torch.float32, device=dev)
-        g_bias = torch.empty_like(bias) if bias is not None else None
-        if B == 0:
-            return g_qkv[0], g_qkv[1], g_qkv[2], None if bias is None else torch.zeros_like(bias), None
-        delta = torch.empty((B, H, L), dtype=torch.float32, device=dev)
-        part = None
-        if bias is not None:
-            part = torch.empty((_lib.call("rh_softmax_attn_nparts", B, L, H), L), dtype=torch.float32, device=dev)
-        _lib.call("rh_softmax_attn_bwd", _p(q), _p(k), _p(v), int(q.stride(1)), B, L, H, dh, _p(bias), N, nb, scale, p,
-                  _p(rng), _p(ctr), _p(out), _p(lse), _p(g), _p(delta), _p(g_qkv[0]), _p(g_qkv[1]), _p(g_qkv[2]), H * dh,
-                  _p(part), _p(g_bias), _stream())
-        return g_qkv[0], g_qkv[1], g_qkv[2], g_bias, None
-
-
-def _attn_view_ok(t, B, L, W):
-    """(B, L, W) with unit column stride and rows B L apart by one stride (a contiguous tensor or a column block of one)."""
-    return t.stride(2) == 1 and t.stride(1) >= W and (B <= 1 or t.stride(0) == L * t.stride(1))
-
-
-def softmax_attention(q, k, v, n_heads, max_seq_len, bias_table=None, dropout_p=0.0, training=True, scale=None):
-    """Causal multi-head softmax attention (B, L, H dh) of q, k, v (B, L, H dh): three contiguous projections, or three
-    column blocks of one (B, L, 3 H dh) product (fed without a copy when they share the row stride).  ``bias_table``
-    (num_buckets, H): RelPosBias's table, added as table[min(|i - j|, max_seq_len) * (num_buckets - 1) // max_seq_len, h].
-    Dropout with probability ``dropout_p`` on the attention weights when ``training``.  No padding mask."""
-    require_hip(q, k, v, bias_table)
-    if q.dim() != 3 or q.shape != k.shape or q.shape != v.shape or q.shape[2] % n_heads != 0:
-        raise RuntimeError(f"torch_rechub_amd: softmax attention of q {tuple(q.shape)}, k {tuple(k.shape)}, "
-                           f"v {tuple(v.shape)} with {n_heads} heads unsupported (three (B, L, H dh) tensors)")
-    if q.dtype != torch.float32 or k.dtype != torch.float32 or v.dtype != torch.float32 or (
-            bias_table is not None and bias_table.dtype != torch.float32):
-        raise RuntimeError("torch_rechub_amd: softmax attention runs in float32 only")
-    B, L, W = (int(x) for x in q.shape)
-    H = int(n_heads)
-    dh = W // H
-    nb = int(bias_table.shape[0]) if bias_table is not None else 0
-    if not (1 <= L <= min(int(max_seq_len), _lib.H.RH_ATTN_MAX_L) and 1 <= dh <= _lib.H.RH_ATTN_MAX_DH) or (bias_table is not None and (
-            nb < 1 or bias_table.dim() != 2 or bias_table.shape[1] != H)):
-        raise RuntimeError(f"torch_rechub_amd: softmax attention with L={L}, head width {dh}, bias table "
-                           f"{None if bias_table is None else tuple(bias_table.shape)} has no HIP kernel "
-                           f"(1 <= L <= min(max_seq_len, {_lib.H.RH_ATTN_MAX_L}), 1 <= head width <= {_lib.H.RH_ATTN_MAX_DH}, table "
-                           "(num_buckets >= 1, H))")
-    p = float(dropout_p) if training else 0.0
-    if not 0.0 <= p < 1.0:
-        raise RuntimeError(f"torch_rechub_amd: attention dropout p={p} has no HIP kernel (0 <= p < 1)")
-    if not (_attn_view_ok(q, B, L, W) and _attn_view_ok(k, B, L, W) and _attn_view_ok(v, B, L, W) and
-            q.stride(1) == k.stride(1) == v.stride(1)):
-        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-    cfg = (H, dh, int(max_seq_len), nb, float(dh**-0.5 if scale is None else scale), p)
-    return _SoftmaxAttnFn.apply(q, k, v, None if bias_table is None else bias_table.contiguous(), cfg)
-
-
-# --------------------------------------------------------------------------------------------
-# Session-based retrieval: general GRU, additive attention pooling, full-catalogue cross entropy
-# (csrc/session.hip, csrc/stream_ce.hip)
-# --------------------------------------------------------------------------------------------
 class _GruLayerFn(torch.autograd.Function):
     """h_all (B, T, H) of one nn.GRU layer from the zero state; xw (B, T, 3H) = x W_ih^T (+ b_ih), rows r | z | n."""
 
@@ -3473,61 +2881,6 @@ def gru_layers(gru_mod, x, batch_first=None):
     return (h if bf else h.transpose(0, 1)), h_n
 
 
-class _AttnPoolFn(torch.autograd.Function):
-    """out (B, Dx) = sum_l a_l X_l (+ add), a = exp(w0 . sigmoid(P + r)) mask / den (csrc/session.hip)."""
-
-    @staticmethod
-    def forward(ctx, P, r, w0, mask, X, add, floor_):
-        B, L, H = (int(v) for v in P.shape)
-        Dx = int(X.shape[2])
-        dev = P.device
-        out = torch.empty((B, Dx), dtype=torch.float32, device=dev)
-        e = torch.empty((B, L), dtype=torch.float32, device=dev)
-        sums = torch.empty((B, 2), dtype=torch.float32, device=dev)
-        _lib.call("rh_attn_pool_fwd", _p(P), _p(r), _p(w0), _p(mask), _p(X), _p(add), B, L, H, Dx, int(floor_), _p(out), _p(e),
-                  _p(sums), _stream())
-        ctx.floor_ = int(floor_)
-        ctx.has_add = add is not None
-        ctx.save_for_backward(P, r, w0, X, e, sums)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        P, r, w0, X, e, sums = ctx.saved_tensors
-        B, L, H = (int(v) for v in P.shape)
-        Dx = int(X.shape[2])
-        dev = P.device
-        g = g.contiguous()
-        dP = torch.empty_like(P)
-        dr = torch.empty((B, H), dtype=torch.float32, device=dev)
-        dw0_part = torch.empty((B, H), dtype=torch.float32, device=dev)
-        dw0 = torch.empty((H,), dtype=torch.float32, device=dev)
-        dX = torch.empty_like(X)
-        _lib.call("rh_attn_pool_bwd", _p(P), _p(r), _p(w0), _p(X), _p(e), _p(sums), _p(g), B, L, H, Dx, ctx.floor_, _p(dP),
-                  _p(dr), _p(dw0_part), _p(dw0), _p(dX), _stream())
-        return dP, dr, dw0.view(w0.shape), None, dX, (g if ctx.has_add else None), None
-
-
-def additive_attention_pool(P, r, w0, mask, X, add=None, floor=False):
-    """Additive attention pooling of NARM / STAMP: s_l = sum_h w0_h sigmoid(P_lh + r_h), a_l = exp(s_l) mask_l / den,
-    out (B, Dx) = sum_l a_l X_l (+ add).  den = sum_l exp(s_l) mask_l, or max(that, 1e-12) with ``floor`` (F.normalize(p=1)).
-    P (B, L, H), r (B, H), w0 (H,) or (H, 1), mask (B, L) (bool / 0-1), X (B, L, Dx), add (B, Dx) or None."""
-    require_hip(P, r, w0, mask, X, add)
-    if P.dim() != 3 or X.dim() != 3 or P.shape[:2] != X.shape[:2] or r.shape != (P.shape[0], P.shape[2]) or \
-            w0.numel() != P.shape[2] or mask.shape != P.shape[:2] or (add is not None and add.shape != (X.shape[0], X.shape[2])):
-        raise RuntimeError(f"torch_rechub_amd: attention pooling shapes P {tuple(P.shape)}, r {tuple(r.shape)}, "
-                           f"w0 {tuple(w0.shape)}, mask {tuple(mask.shape)}, X {tuple(X.shape)} do not agree")
-    if not (1 <= P.shape[1] <= _lib.H.RH_ATTN_POOL_MAX_L and 1 <= P.shape[2] <= _lib.H.RH_ATTN_POOL_MAX_W and
-            1 <= X.shape[2] <= _lib.H.RH_ATTN_POOL_MAX_W):
-        raise RuntimeError(f"torch_rechub_amd: attention pooling with L={P.shape[1]}, H={P.shape[2]}, Dx={X.shape[2]} has "
-                           f"no HIP kernel (1 <= L <= {_lib.H.RH_ATTN_POOL_MAX_L}, 1 <= H, Dx <= {_lib.H.RH_ATTN_POOL_MAX_W})")
-    if any(t.dtype != torch.float32 for t in (P, r, w0, X) + (() if add is None else (add,))):
-        raise RuntimeError("torch_rechub_amd: attention pooling runs in float32 only")
-    m = mask.to(torch.float32).contiguous()
-    return _AttnPoolFn.apply(P.contiguous(), r.contiguous(), w0.contiguous(), m, X.contiguous(),
-                             None if add is None else add.contiguous(), bool(floor))
-
-
 class _CatalogueCEFn(torch.autograd.Function):
     """Mean nn.CrossEntropyLoss of u E^T against labels without the (B, V) logits."""
 
@@ -3573,39 +2926,6 @@ def catalogue_cross_entropy(u, weight, labels):
     return _CatalogueCEFn.apply(u, weight, labels.to(torch.int64).contiguous())
 
 
-class _DropoutFn(torch.autograd.Function):
-
-    @staticmethod
-    def forward(ctx, x, p):
-        x = x.contiguous()
-        y = torch.empty_like(x)
-        rng = _dropout_rng(x.device)
-        ctr = torch.empty(1, dtype=torch.int64, device=x.device)
-        _lib.call("rh_session_dropout_fwd", _p(x), x.numel(), float(p), _p(rng), _p(ctr), _p(y), _stream())
-        ctx.p = float(p)
-        ctx.save_for_backward(rng, ctr)
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        rng, ctr = ctx.saved_tensors
-        g = g.contiguous()
-        dx = torch.empty_like(g)
-        _lib.call("rh_session_dropout_bwd", _p(g), g.numel(), ctx.p, _p(rng), _p(ctr), _p(dx), _stream())
-        return dx, None
-
-
-def dropout(x, p, training=True):
-    """nn.Dropout(p) with the project's counter-hash mask (the fused MLP dropout's stream): identity at p = 0 or in eval;
-    the mask is recomputed in the backward, never stored."""
-    if not training or p == 0:
-        return x
-    require_hip(x)
-    if not (0 < p < 1) or x.dtype != torch.float32:
-        raise RuntimeError(f"torch_rechub_amd: dropout p={p} on {x.dtype} has no HIP kernel (0 <= p < 1, float32)")
-    return _DropoutFn.apply(x, p)
-
-
 def session_lengths(seq, check_full=False):
     """(B,) int64 number of non-zero ids per row of a (B, L) id matrix, one launch.  A row without items (and, with
     ``check_full``, a batch whose longest row is shorter than L) sets the device error word: outside a hipGraph capture this
@@ -3618,270 +2938,6 @@ def session_lengths(seq, check_full=False):
     if not torch.cuda.is_current_stream_capturing():
         check_errors(seq.device)
     return counts
-
-
-# --------------------------------------------------------------------------------------------
-# Exact top-K item retrieval (csrc/topk.hip)
-# --------------------------------------------------------------------------------------------
-def topk_supported(D, K, S=0):
-    """Whether csrc/topk.hip takes width D, K results and S exclusions per query (D <= RH_TOPK_MAX_D, K <= RH_TOPK_MAX_K,
-    S <= RH_TOPK_MAX_S)."""
-    return bool(_lib.query("rh_topk_supported", int(D), int(K), int(S)))
-
-
-def topk_plan(M, V, K):
-    """(nsplit, workspace_bytes): the default number of item ranges for M queries over V items and the size of the
-    partial lists for it (8 M nsplit K bytes)."""
-    return _lib.query("rh_topk_plan", int(M), int(V), int(K), out=(ctypes.c_int, ctypes.c_int64))
-
-
-def _scan_inputs(what, tname, q, table, k, bias, exclude, refuse):
-    """What ``topk_items`` and ``ivf_scan`` check and prepare alike: q (M, D) and the table (V, D; ``tname`` in the
-    messages) float32, the table contiguous, bias (V,) float32, exclude (M, S).  ``refuse(M, D, V, k, S)`` makes the
-    caller's own checks and raises where there is no kernel, before anything is allocated.  Returns q with unit column
-    stride and its row stride, bias and exclude as the kernels read them, S and the empty (ids, scores) (M, k)."""
-    if q.dim() != 2 or table.dim() != 2 or q.shape[1] != table.shape[1]:
-        raise ValueError(f"{what}: q (M, D) and {tname} (V, D) expected")
-    if q.dtype != torch.float32 or table.dtype != torch.float32 or (bias is not None and bias.dtype != torch.float32):
-        raise ValueError(f"torch_rechub_amd: {what} takes float32 tensors")
-    if not table.is_contiguous():
-        raise ValueError(f"{what}: the table must be contiguous")
-    M, D = (int(v) for v in q.shape)
-    V, k = int(table.shape[0]), int(k)
-    if exclude is not None and (exclude.dim() != 2 or exclude.shape[0] != M):
-        raise ValueError(f"{what}: exclude (M, S) expected")
-    S = 0 if exclude is None else int(exclude.shape[1])
-    if bias is not None and tuple(bias.shape) != (V,):
-        raise ValueError(f"{what}: bias (V,) expected")
-    refuse(M, D, V, k, S)
-    q = q.detach()
-    if M > 0 and (q.stride(1) != 1 or q.stride(0) < D):
-        q = q.contiguous()
-    ldq = int(q.stride(0)) if M > 1 else D
-    if bias is not None:
-        bias = bias.detach().contiguous()
-    if S > 0:
-        exclude = exclude.to(torch.int64).contiguous()
-    ids = torch.empty((M, k), dtype=torch.int64, device=q.device)
-    scores = torch.empty((M, k), dtype=torch.float32, device=q.device)
-    return q, ldq, bias, exclude, S, ids, scores
-
-
-def topk_items(q, table, k, bias=None, exclude=None, invalid=None, nsplit=None):
-    """(ids (M, k) int64, scores (M, k) float32): the k best items of ``table`` (V, D) for every row of ``q`` (M, D) by
-    q_i . x_j (+ bias[j]), best first, exact ties to the lower id; the (M, V) scores are never formed.  ``exclude`` (M, S)
-    int64: ids that may not be returned to query i (entries outside [0, V) are ignored: pad with -1, or pass a 0-padded
-    history to drop id 0 with it); ``invalid``: ids dropped for every query.  With fewer than k candidates the tail is
-    id -1, score -inf.  ``nsplit`` forces the number of item ranges (the result does not depend on it).  No autograd;
-    runs on the current stream."""
-    if invalid is not None and not torch.is_tensor(invalid):
-        invalid = torch.as_tensor(list(invalid), dtype=torch.int64, device=q.device)
-    require_hip(q, table, bias, exclude, invalid)
-
-    def refuse(M, D, V, k, S):
-        if V < 1 or not topk_supported(D, k, S):
-            from .models.matching._listwise import no_kernel
-            raise no_kernel(f"top-k retrieval at D={D}, k={k}, {S} exclusions per query, V={V} "
-                            f"(1 <= D <= {_lib.H.RH_TOPK_MAX_D}, 1 <= k <= {_lib.H.RH_TOPK_MAX_K}, S <= {_lib.H.RH_TOPK_MAX_S}, V >= 1)")
-
-    q, ldq, bias, exclude, S, ids, scores = _scan_inputs("topk_items", "table", q, table, k, bias, exclude, refuse)
-    (M, D), V, k = q.shape, int(table.shape[0]), int(k)
-    n_inv = 0
-    if invalid is not None:
-        invalid = invalid.to(torch.int64).reshape(-1).contiguous()
-        n_inv = int(invalid.numel())
-    if nsplit is None:
-        nsplit, _ = topk_plan(M, V, k)
-    nsplit = int(nsplit)
-    if not 1 <= nsplit <= min(V, _lib.H.RH_TOPK_MAX_SPLIT):
-        raise ValueError(f"topk_items: nsplit={nsplit} outside [1, min(V, {_lib.H.RH_TOPK_MAX_SPLIT})]")
-    if M == 0:
-        return ids, scores
-    work = torch.empty((8 * M * nsplit * k,), dtype=torch.uint8, device=q.device)
-    _lib.call("rh_topk_fwd", _p(q), ldq, _p(table.detach()), _p(bias), _p(exclude) if S > 0 else _NULL, S,
-              _p(invalid) if n_inv > 0 else _NULL, n_inv, M, D, V, k, nsplit, _p(work), _p(ids), _p(scores), _stream())
-    return ids, scores
-
-
-# --------------------------------------------------------------------------------------------
-# Inverted-file index: the list scan and the k-means update (csrc/ivf.hip)
-# --------------------------------------------------------------------------------------------
-def ivf_supported(D, K, S=0, nprobe=1):
-    """Whether csrc/ivf.hip takes width D, K results, S exclusions per query and nprobe lists per query (the limits of
-    ops.topk_supported and nprobe <= RH_IVF_MAX_NPROBE)."""
-    return bool(_lib.query("rh_ivf_supported", int(D), int(K), int(S), int(nprobe)))
-
-
-def ivf_plan(M, nlists, nprobe, K):
-    """(rows_per_tile, grid, workspace_bytes) of ``ivf_scan``: the (query, slot) pairs one workgroup takes, the fixed grid
-    bound ceil(M nprobe / rows_per_tile) + nlists + 1, and 8 M nprobe K bytes of partial lists + 4 M nprobe of pair
-    indices + 8 (nlists + 2) of group and tile offsets."""
-    return _lib.query("rh_ivf_plan", int(M), int(nlists), int(nprobe), int(K),
-                      out=(ctypes.c_int, ctypes.c_int64, ctypes.c_int64))
-
-
-def ivf_scan(q, table_sorted, row_ids, list_offsets, probe, k, bias=None, exclude=None):
-    """(ids (M, k) int64, scores (M, k) float32): the k best rows for every row of ``q`` (M, D) by q_i . x_j (+ bias[j])
-    among the lists it probes, best first, exact ties to the lower id; ``topk_items`` restricted to a union of lists.
-    ``table_sorted`` (V, D) holds the table's rows grouped by list, ``bias`` (V,) alike, ``row_ids`` (V,) int32 the original
-    id of every grouped row (ascending inside each list: a stable sort by list gives that), ``list_offsets`` (nlists + 1,)
-    int32 the lists' offsets.  ``probe`` (M, nprobe) int32: the lists of each query, distinct per row; an entry outside
-    [0, nlists) (-1) is no list.  ``exclude`` (M, S) int64: original ids that may not be returned to query i (anything
-    else is padding).  The returned ids are original ids; with fewer than k candidates the tail is id -1, score -inf.
-    With every list probed the result is ``topk_items``' on the un-grouped table, bit for bit.  The pairs are grouped by
-    list with a stable ``torch.sort``; nothing synchronises with the host.  No autograd; runs on the current stream."""
-    require_hip(q, table_sorted, row_ids, list_offsets, probe, bias, exclude)
-
-    def refuse(M, D, V, k, S):
-        if row_ids.dtype != torch.int32 or list_offsets.dtype != torch.int32 or probe.dtype != torch.int32:
-            raise ValueError("ivf_scan: row_ids, list_offsets and probe are int32 tensors")
-        if tuple(row_ids.shape) != (V,) or list_offsets.dim() != 1 or list_offsets.shape[0] < 2:
-            raise ValueError("ivf_scan: row_ids (V,) and list_offsets (nlists + 1,) expected")
-        if probe.dim() != 2 or probe.shape[0] != M:
-            raise ValueError("ivf_scan: probe (M, nprobe) expected")
-        nlists, nprobe = int(list_offsets.shape[0]) - 1, int(probe.shape[1])
-        if V < 1 or M * nprobe >= 2 ** 31 - 64 * (nlists + 2) or not ivf_supported(D, k, S, nprobe):
-            from .models.matching._listwise import no_kernel
-            raise no_kernel(f"the inverted-file scan at D={D}, k={k}, {S} exclusions per query, nprobe={nprobe}, V={V} "
-                            f"(1 <= D <= {_lib.H.RH_TOPK_MAX_D}, 1 <= k <= {_lib.H.RH_TOPK_MAX_K}, S <= {_lib.H.RH_TOPK_MAX_S}, "
-                            f"1 <= nprobe <= {_lib.H.RH_IVF_MAX_NPROBE}, V >= 1, M nprobe < 2^31)")
-
-    q, ldq, bias, exclude, S, ids, scores = _scan_inputs("ivf_scan", "table_sorted", q, table_sorted, k, bias, exclude,
-                                                         refuse)
-    (M, D), V, k, dev = q.shape, int(table_sorted.shape[0]), int(k), q.device
-    nlists, nprobe = int(list_offsets.shape[0]) - 1, int(probe.shape[1])
-    if M == 0:
-        return ids, scores
-    table_sorted, row_ids, list_offsets = table_sorted.detach(), row_ids.contiguous(), list_offsets.contiguous()
-    rb = ivf_plan(M, nlists, nprobe, k)[0]
-    # the pairs grouped by list: group 0 = no list, group l + 1 = list l (a stable sort: reproducible pair order)
-    key = torch.where((probe >= 0) & (probe < nlists), probe + 1, torch.zeros_like(probe)).reshape(-1)
-    key, order = torch.sort(key, stable=True)
-    pair = order.to(torch.int32)
-    del order
-    bounds = torch.arange(nlists + 2, dtype=torch.int32, device=dev)
-    pair_off = torch.searchsorted(key, bounds, out_int32=True)
-    del key, bounds
-    tile_off = torch.zeros_like(pair_off)
-    tile_off[1:] = torch.cumsum((pair_off[1:] - pair_off[:-1] + (rb - 1)) // rb, 0)
-    part = torch.empty((8 * M * nprobe * k,), dtype=torch.uint8, device=dev)
-    _lib.call("rh_ivf_scan", _p(q), ldq, _p(table_sorted), _p(bias), _p(row_ids), _p(list_offsets), nlists, _p(pair),
-              _p(pair_off), _p(tile_off), _p(exclude) if S > 0 else _NULL, S, M, D, V, k, nprobe, _p(part), _p(ids),
-              _p(scores), _stream())
-    return ids, scores
-
-
-def ivf_list_mean(x_sorted, list_offsets, previous):
-    """(nlists, D) float32: row l = the mean of the rows [list_offsets[l], list_offsets[l + 1]) of ``x_sorted`` (V, D),
-    summed in a fixed order (two runs give the same bits) and divided once; an empty list keeps ``previous[l]``.  The
-    update step of k-means over rows grouped by list.  No autograd; runs on the current stream."""
-    require_hip(x_sorted, list_offsets, previous)
-    if x_sorted.dim() != 2 or previous.dim() != 2 or previous.shape[1] != x_sorted.shape[1] or previous.shape[0] < 1 or \
-            x_sorted.shape[1] < 1:
-        raise ValueError("ivf_list_mean: x_sorted (V, D) and previous (nlists, D) expected")
-    if x_sorted.dtype != torch.float32 or previous.dtype != torch.float32:
-        raise ValueError("torch_rechub_amd: ivf_list_mean takes float32 tensors")
-    nlists = int(previous.shape[0])
-    if list_offsets.dtype != torch.int32 or tuple(list_offsets.shape) != (nlists + 1,):
-        raise ValueError("ivf_list_mean: list_offsets (nlists + 1,) int32 expected")
-    if not x_sorted.is_contiguous():
-        raise ValueError("ivf_list_mean: the rows must be contiguous")
-    V, D = (int(v) for v in x_sorted.shape)
-    if V >= 2 ** 31:
-        from .models.matching._listwise import no_kernel
-        raise no_kernel(f"the list mean over V={V} rows (V < 2^31)")
-    previous, list_offsets = previous.detach().contiguous(), list_offsets.contiguous()
-    out = torch.empty_like(previous)
-    _lib.call("rh_ivf_list_mean", _p(x_sorted.detach()), _p(list_offsets), _p(previous), V, D, nlists, _p(out), _stream())
-    return out
-
-
-# --------------------------------------------------------------------------------------------
-# SASRec: the transformer block around ops.softmax_attention, fused per row tile (csrc/sasrec.hip)
-# --------------------------------------------------------------------------------------------
-def _sasrec_check(what, D, *tensors):
-    """Before anything is allocated or launched: float32 tensors and a width the kernels take."""
-    if any(t is not None and t.dtype != torch.float32 for t in tensors):
-        raise ValueError(f"torch_rechub_amd: {what} takes float32 tensors")
-    if not 1 <= int(D) <= _lib.H.RH_SASREC_MAX_D:
-        from .models.matching._listwise import no_kernel
-        raise no_kernel(f"{what} at width {int(D)} (1 <= D <= {_lib.H.RH_SASREC_MAX_D})")
-
-
-def _sasrec_ntiles(M, D):
-    return _lib.query("rh_sasrec_ntiles", int(M), int(D))
-
-
-def _ln_param_grads(part, D):
-    """(g_gamma, g_beta) (D,) from the per-workgroup partials (n, 2, D), summed in a fixed order."""
-    out = torch.empty((2 * D,), dtype=torch.float32, device=part.device)
-    _lib.call("rh_colsum", _p(part), int(part.shape[0]), 2 * D, _p(out), _NULL, 0, _NULL, _stream())
-    return out[:D], out[D:]
-
-
-def _sample_view(t, B, L, D):
-    """A (B, L, D) tensor as the kernels read it: unit column stride, rows and samples one stride apart each (a slice of
-    the (B, 3, L, >= D) gather, or a contiguous tensor) -> (tensor, sample stride, row stride)."""
-    if not (t.stride(2) == 1 and t.stride(1) >= D and t.stride(0) >= L * t.stride(1)):
-        t = t.contiguous()
-    return t, int(t.stride(0)), int(t.stride(1))
-
-
-class _SasrecInputFn(torch.autograd.Function):
-    """x0 (B, L, D) = m dropout(e sqrt(D) + P[l]), m = seq != 0."""
-
-    @staticmethod
-    def forward(ctx, seq, e, P, p):
-        B, L, D = (int(v) for v in e.shape)
-        dev = e.device
-        e, ebs, ers = _sample_view(e, B, L, D)
-        x0 = torch.empty((B, L, D), dtype=torch.float32, device=dev)
-        rng = _dropout_rng(dev) if p > 0 else None
-        ctr = torch.empty(1, dtype=torch.int64, device=dev) if p > 0 else None
-        scale = float(torch.tensor(float(D)**0.5, dtype=torch.float32))
-        _lib.call("rh_sasrec_input_fwd", _p(seq), _p(e), ebs, ers, _p(P), B, L, D, int(P.shape[0]), scale, p, _p(rng), _p(ctr),
-                  _p(x0), _stream())
-        ctx.cfg = (B, L, D, int(P.shape[0]), scale, p)
-        ctx.save_for_backward(seq, rng, ctr)
-        return x0
-
-    @staticmethod
-    def backward(ctx, g):
-        seq, rng, ctr = ctx.saved_tensors
-        B, L, D, max_len, scale, p = ctx.cfg
-        g = g.contiguous()
-        g_e = torch.empty((B, L, D), dtype=torch.float32, device=g.device)
-        g_P = torch.empty((max_len, D), dtype=torch.float32, device=g.device)
-        _lib.call("rh_sasrec_input_bwd", _p(seq), _p(g), B, L, D, max_len, scale, p, _p(rng), _p(ctr), _p(g_e), _p(g_P),
-                  _stream())
-        return None, g_e, g_P, None
-
-
-def _seq_ids(seq, B, L):
-    if seq.dim() != 2 or tuple(seq.shape) != (B, L):
-        raise ValueError(f"torch_rechub_amd: the history ids must be (B, L) = ({B}, {L}), got {tuple(seq.shape)}")
-    return seq.to(torch.int64).contiguous()
-
-
-def _drop_p(p, training):
-    p = float(p) if training else 0.0
-    if not 0.0 <= p < 1.0:
-        raise RuntimeError(f"torch_rechub_amd: dropout p={p} has no HIP kernel (0 <= p < 1)")
-    return p
-
-
-def sasrec_input(seq, e, P, dropout_p=0.0, training=True):
-    """SASRec's input stage x0 (B, L, D) = m dropout(e sqrt(D) + P[:L]) from the history ids seq (B, L) (0 = pad, m = seq
-    != 0), their gathered rows e (B, L, D) (a slice of the (B, 3, L, D) gather is read in place) and the position table P
-    (max_len, D), L <= max_len."""
-    require_hip(seq, e, P)
-    if e.dim() != 3 or P.dim() != 2 or P.shape[1] != e.shape[2]:
-        raise ValueError("sasrec_input: e (B, L, D) and P (max_len, D) expected")
-    B, L, D = (int(v) for v in e.shape)
-    _sasrec_check("SASRec's input stage", D, e, P)
-    if L > P.shape[0]:
-        raise IndexError("index out of range in self")  # the reference's position lookup fails with this error
-    return _SasrecInputFn.apply(_seq_ids(seq, B, L), e, P.contiguous(), _drop_p(dropout_p, training))
 
 
 class _SasrecAttnInFn(torch.autograd.Function):
@@ -4000,867 +3056,30 @@ def sasrec_ffn(attn, Q, seq, out_proj_weight, out_proj_bias, ln_weight, ln_bias,
     return out.view(B, L, D)
 
 
-class _SasrecHeadFn(torch.autograd.Function):
-    """(pos_logits, neg_logits) (B, L) = LN(x) . pos_e, LN(x) . neg_e."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, pos_e, neg_e, eps):
-        B, L, D = (int(v) for v in x.shape)
-        dev = x.device
-        pos_e, pbs, prs = _sample_view(pos_e, B, L, D)
-        neg_e, nbs, nrs = _sample_view(neg_e, B, L, D)
-        if prs != nrs:
-            pos_e, pbs, prs = pos_e.contiguous(), L * D, D
-            neg_e, nbs, nrs = neg_e.contiguous(), L * D, D
-        pos = torch.empty((B, L), dtype=torch.float32, device=dev)
-        neg = torch.empty((B, L), dtype=torch.float32, device=dev)
-        stats = torch.empty((B * L, 2), dtype=torch.float32, device=dev)
-        _lib.call("rh_sasrec_head_fwd", _p(x), _p(gamma), _p(beta), eps, _p(pos_e), pbs, _p(neg_e), nbs, prs, B, L, D, _NULL,
-                  _p(pos), _p(neg), _p(stats), _stream())
-        ctx.strides = (pbs, nbs, prs)
-        ctx.save_for_backward(x, gamma, beta, pos_e, neg_e, stats)
-        return pos, neg
-
-    @staticmethod
-    def backward(ctx, g_pos, g_neg):
-        x, gamma, beta, pos_e, neg_e, stats = ctx.saved_tensors
-        B, L, D = (int(v) for v in x.shape)
-        dev = x.device
-        g_pos, g_neg = g_pos.contiguous(), g_neg.contiguous()
-        g_x, g_pe, g_ne = (torch.empty((B, L, D), dtype=torch.float32, device=dev) for _ in range(3))
-        if B * L == 0:
-            z = torch.zeros((D,), dtype=torch.float32, device=dev)
-            return g_x, z, z.clone(), g_pe, g_ne, None
-        part = torch.empty((-(-B * L // 64), 2, D), dtype=torch.float32, device=dev)
-        _lib.call("rh_sasrec_head_bwd", _p(x), _p(gamma), _p(beta), _p(stats), _p(pos_e), ctx.strides[0], _p(neg_e),
-                  ctx.strides[1], ctx.strides[2], _NULL, _p(g_pos), _p(g_neg), B, L, D, _p(g_x), _p(g_pe), _p(g_ne), _p(part), _stream())
-        g_gamma, g_beta = _ln_param_grads(part, D)
-        return g_x, g_gamma, g_beta, g_pe, g_ne, None
-
-
-class _LayerNormFn(torch.autograd.Function):
-    """LayerNorm over the last axis of (M, D) (the head kernels without their products)."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, eps):
-        M, D = (int(v) for v in x.shape)
-        s = torch.empty((M, D), dtype=torch.float32, device=x.device)
-        stats = torch.empty((M, 2), dtype=torch.float32, device=x.device)
-        _lib.call("rh_sasrec_head_fwd", _p(x), _p(gamma), _p(beta), eps, _NULL, 0, _NULL, 0, 0, M, 1, D, _p(s), _NULL, _NULL,
-                  _p(stats), _stream())
-        ctx.save_for_backward(x, gamma, beta, stats)
-        return s
-
-    @staticmethod
-    def backward(ctx, g):
-        x, gamma, beta, stats = ctx.saved_tensors
-        M, D = (int(v) for v in x.shape)
-        dev = x.device
-        g = g.contiguous()
-        g_x = torch.empty((M, D), dtype=torch.float32, device=dev)
-        if M == 0:
-            z = torch.zeros((D,), dtype=torch.float32, device=dev)
-            return g_x, z, z.clone(), None
-        part = torch.empty((-(-M // 64), 2, D), dtype=torch.float32, device=dev)
-        _lib.call("rh_sasrec_head_bwd", _p(x), _p(gamma), _p(beta), _p(stats), _NULL, 0, _NULL, 0, 0, _p(g), _NULL, _NULL, M, 1,
-                  D, _p(g_x), _NULL, _NULL, _p(part), _stream())
-        g_gamma, g_beta = _ln_param_grads(part, D)
-        return g_x, g_gamma, g_beta, None
-
-
-def layer_norm(x, weight, bias, eps=1e-5):
-    """F.layer_norm(x, (D,), weight, bias, eps) over the last axis of a float32 (..., D) tensor, D <= RH_SASREC_MAX_D: two-pass
-    variance, so an all-zero row gives exactly ``bias``; the weight and bias gradients are summed in a fixed order."""
-    require_hip(x, weight, bias)
-    D = int(x.shape[-1])
-    _sasrec_check("LayerNorm", D, x, weight, bias)
-    if tuple(weight.shape) != (D,) or tuple(bias.shape) != (D,):
-        raise ValueError("layer_norm: weight and bias (D,) expected")
-    out = _LayerNormFn.apply(x.reshape(-1, D).contiguous(), weight.contiguous(), bias.contiguous(), float(eps))
-    return out.view(x.shape)
-
-
-def sasrec_head(x, ln_weight, ln_bias, pos_e, neg_e, eps=1e-8):
-    """SASRec's training head: (pos_logits, neg_logits) (B, L) = sum_d LayerNorm(x) pos_e, sum_d LayerNorm(x) neg_e for x,
-    pos_e, neg_e (B, L, D); pos_e / neg_e may be slices of the (B, 3, L, D) gather (read in place)."""
-    require_hip(x, ln_weight, ln_bias, pos_e, neg_e)
-    if x.dim() != 3 or pos_e.shape != x.shape or neg_e.shape != x.shape:
-        raise ValueError("sasrec_head: x, pos_e, neg_e (B, L, D) expected")
-    D = int(x.shape[2])
-    _sasrec_check("SASRec's final LayerNorm + logits", D, x, ln_weight, ln_bias, pos_e, neg_e)
-    if tuple(ln_weight.shape) != (D,) or tuple(ln_bias.shape) != (D,):
-        raise ValueError("sasrec_head: LayerNorm weight and bias (D,) expected")
-    return _SasrecHeadFn.apply(x.contiguous(), ln_weight.contiguous(), ln_bias.contiguous(), pos_e, neg_e, float(eps))
-
-
 # --------------------------------------------------------------------------------------------
-# two-tower score tails and the SENET field gate (csrc/twotower.hip)
+# The stateless leaf families (_families/<name>.py drives csrc/<name>.hip), under the names they have always had here.
+# Callers say ops.<name>, so a test that replaces ops.<name> is seen by the models.  Private names come along because the
+# functions above use some of them and the module's surface stays what it was.
 # --------------------------------------------------------------------------------------------
-def _rows(t):
-    """A float32 (B, D) tensor whose rows are contiguous (any row stride), as the row-strided entry points read it."""
-    return t if t.stride(1) == 1 and t.stride(0) >= t.shape[1] else t.contiguous()
-
-
-class _BandLogitsFn(torch.autograd.Function):
-    """YoutubeSBC's (B, 1 + n_neg) scores straight from the tower outputs: no (B, B) tensor; the item gradient is a gather."""
-
-    @staticmethod
-    def forward(ctx, u, v, w, K1, temperature, eps):
-        require_hip(u, v, w)
-        u, v, w = _rows(u), _rows(v), w.contiguous()
-        B, D = u.shape
-        dev = u.device
-        logits = torch.empty((B, K1), dtype=torch.float32, device=dev)
-        norms = torch.empty((2, B), dtype=torch.float32, device=dev)
-        _lib.call("rh_band_logits_fwd", _p(u), u.stride(0), _p(v), v.stride(0), _p(w), B, D, K1, temperature, eps, _p(logits),
-                  _p(norms[0]), _p(norms[1]), _stream())
-        ctx.save_for_backward(u, v, norms)
-        ctx.cfg = (K1, temperature, eps)
-        return logits
-
-    @staticmethod
-    def backward(ctx, g):
-        u, v, norms = ctx.saved_tensors
-        K1, temperature, eps = ctx.cfg
-        B, D = u.shape
-        g = g.contiguous()
-        g_u = torch.empty((B, D), dtype=torch.float32, device=u.device)
-        g_v = torch.empty((B, D), dtype=torch.float32, device=u.device)
-        _lib.call("rh_band_logits_bwd", _p(u), u.stride(0), _p(v), v.stride(0), _p(norms[0]), _p(norms[1]), _p(g), B, D, K1,
-                  temperature, eps, _p(g_u), _p(g_v), _stream())
-        return g_u, g_v, None, None, None, None
-
-
-def _f32_rows(*tensors):
-    first = tensors[0]
-    return all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape == first.shape for t in tensors) and \
-        first.shape[0] >= 1 and 1 <= first.shape[1] <= _lib.H.RH_TWOTOWER_MAX_D
-
-
-def band_logits_ok(u, v, w, n_neg):
-    return (_f32_rows(u, v) and w.is_cuda and w.dtype == torch.float32 and tuple(w.shape) == (u.shape[0],) and
-            0 <= int(n_neg) < u.shape[0])
-
-
-def band_logits(u, v, w, n_neg, temperature=1.0, eps=1e-8):
-    """logits[i, k] = (cosine_similarity(u_i, v_j, eps) - log w_j) / temperature with j = (i + k) mod B, k = 0..n_neg:
-    ``((torch.cosine_similarity(u.unsqueeze(1), v, dim=2) - torch.log(w))[index0, index1] / temperature).view(B, -1)`` for
-    YoutubeSBC's band ``index1 = (i + k) mod B``.  ``w`` gets no gradient (it is a DenseFeature input)."""
-    return _BandLogitsFn.apply(u, v, w, int(n_neg) + 1, float(temperature), float(eps))
-
-
-class _PairCosineFn(torch.autograd.Function):
-    """(sum(n(hu) n(hp)), sum(n(hu) n(hn))), n = F.normalize(., p=2, dim=1, eps): one launch each way."""
-
-    @staticmethod
-    def forward(ctx, hu, hp, hn, eps):
-        require_hip(hu, hp, hn)
-        hu, hp, hn = _rows(hu), _rows(hp), _rows(hn)
-        B, D = hu.shape
-        dev = hu.device
-        score = torch.empty((2, B), dtype=torch.float32, device=dev)
-        nrm = torch.empty((3, B), dtype=torch.float32, device=dev)
-        _lib.call("rh_pair_cosine_fwd", _p(hu), hu.stride(0), _p(hp), hp.stride(0), _p(hn), hn.stride(0), B, D, eps,
-                  _p(score[0]), _p(score[1]), _p(nrm), _stream())
-        ctx.save_for_backward(hu, hp, hn, nrm)
-        ctx.eps = eps
-        return score[0], score[1]
-
-    @staticmethod
-    def backward(ctx, g_pos, g_neg):
-        hu, hp, hn, nrm = ctx.saved_tensors
-        B, D = hu.shape
-        g_pos, g_neg = g_pos.contiguous(), g_neg.contiguous()
-        grads = torch.empty((3, B, D), dtype=torch.float32, device=hu.device)
-        _lib.call("rh_pair_cosine_bwd", _p(hu), hu.stride(0), _p(hp), hp.stride(0), _p(hn), hn.stride(0), _p(nrm), _p(g_pos),
-                  _p(g_neg), B, D, ctx.eps, _p(grads[0]), _p(grads[1]), _p(grads[2]), _stream())
-        return grads[0], grads[1], grads[2], None
-
-
-def pair_cosine_scores_ok(hu, hp, hn):
-    return _f32_rows(hu, hp, hn)
-
-
-def pair_cosine_scores(hu, hp, hn, eps=1e-12):
-    """(pos, neg) (B,) each: the cosine of every user row with its positive and its negative item row, from the RAW tower
-    outputs -- ``(F.normalize(hu) * F.normalize(hp)).sum(1), (F.normalize(hu) * F.normalize(hn)).sum(1)``."""
-    return _PairCosineFn.apply(hu, hp, hn, float(eps))
-
-
-class _SenetFn(torch.autograd.Function):
-    """SENETLayer.forward over the (B, F, D) field block; the weight gradients through per-workgroup partials + rh_colsum."""
-
-    @staticmethod
-    def forward(ctx, x, w1, w2):
-        require_hip(x, w1, w2)
-        B, F, D = x.shape
-        if x.stride(2) != 1 or x.stride(1) != D or x.stride(0) < F * D:
-            x = x.contiguous()
-        w1, w2 = w1.contiguous(), w2.contiguous()
-        R = w1.shape[0]
-        dev = x.device
-        y = torch.empty((B, F, D), dtype=torch.float32, device=dev)
-        z = torch.empty((B, F), dtype=torch.float32, device=dev)
-        h = torch.empty((B, R), dtype=torch.float32, device=dev)
-        a = torch.empty((B, F), dtype=torch.float32, device=dev)
-        _lib.call("rh_senet_fwd", _p(x), x.stride(0), _p(w1), _p(w2), B, F, R, D, _p(y), _p(z), _p(h), _p(a), _stream())
-        ctx.save_for_backward(x, w1, w2, z, h, a)
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        x, w1, w2, z, h, a = ctx.saved_tensors
-        B, F, D = x.shape
-        R = w1.shape[0]
-        dev = x.device
-        if g.stride(2) != 1 or g.stride(1) != D or g.stride(0) < F * D:
-            g = g.contiguous()
-        g_x = torch.empty((B, F, D), dtype=torch.float32, device=dev)
-        nb = _lib.query("rh_twotower_nblocks", B)
-        partial = torch.empty((nb, 2 * R * F), dtype=torch.float32, device=dev)
-        _lib.call("rh_senet_bwd", _p(x), x.stride(0), _p(w1), _p(w2), _p(z), _p(h), _p(a), _p(g), g.stride(0), B, F, R, D,
-                  _p(g_x), _p(partial), _stream())
-        g_w = torch.empty((2, R * F), dtype=torch.float32, device=dev)
-        _lib.call("rh_colsum", _p(partial), nb, 2 * R * F, _p(g_w), _NULL, 0, _NULL, _stream())
-        return g_x, g_w[0].view(R, F), g_w[1].view(F, R)
-
-
-def senet_ok(x, w1, w2):
-    return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[0] >= 1 and
-            1 <= x.shape[1] <= _lib.H.RH_SENET_MAX_F and 1 <= x.shape[2] <= _lib.H.RH_SENET_MAX_D and
-            w1.is_cuda and w2.is_cuda and w1.dtype == torch.float32 and
-            w2.dtype == torch.float32 and w1.dim() == 2 and w1.shape[1] == x.shape[1] and 1 <= w1.shape[0] <= x.shape[1] and
-            tuple(w2.shape) == (x.shape[1], w1.shape[0]))
-
-
-def senet(x, w1, w2):
-    """``x * relu(relu(x.mean(-1) @ w1.T) @ w2.T).unsqueeze(-1)`` for x (B, F, D) -- a view of the fused gather's (B, F D)
-    output is read in place --, w1 (R, F), w2 (F, R): SENETLayer.forward as one launch each way."""
-    return _SenetFn.apply(x, w1, w2)
-
-
-# --------------------------------------------------------------------------------------------
-# TIGER / T5: masked, biased, rectangular softmax attention and the residual RMS norm (csrc/t5attn.hip)
-# --------------------------------------------------------------------------------------------
-_t5_bucket_cache = {}
-
-
-def _t5_bucket_of(rel, bidirectional, num_buckets, max_distance):
-    """T5Attention._relative_position_bucket's rule, in its own order of operations (int64 positions, float32 logarithm,
-    truncation to int64) on the CPU, so a bucket boundary falls where the reference's falls."""
-    rel = rel.to(torch.int64)
-    buckets = torch.zeros_like(rel)
-    nb = int(num_buckets)
-    if nb == 1:  # one bucket holds every distance (the reference's rule divides by zero here)
-        return buckets
-    if nb // (4 if bidirectional else 2) == 0:
-        raise ValueError(f"t5_relative_buckets: num_buckets={nb} leaves no exact bucket (the reference's rule divides by "
-                         "zero): 1, or at least 4 bidirectional / 2 one-sided")
-    if bidirectional:
-        nb //= 2
-        buckets = buckets + (rel > 0).to(torch.int64) * nb
-        rel = rel.abs()
-    else:
-        rel = -torch.minimum(rel, torch.zeros_like(rel))
-    max_exact = nb // 2
-    small = rel < max_exact
-    with torch.no_grad():
-        big = max_exact + (torch.log(rel.to(torch.float32) / max_exact) / math.log(max_distance / max_exact) *
-                           (nb - max_exact)).to(torch.int64)
-    big = torch.minimum(big, torch.full_like(big, nb - 1))
-    return buckets + torch.where(small, rel, big)
-
-
-def t5_relative_buckets(Lq, Lk, bidirectional, num_buckets, max_distance, device=None):
-    """The int32 table of T5's relative-position buckets for Lq queries against Lk keys: entry (j - i) + (Lq - 1) is the
-    bucket of key j seen from query i.  Built once per (Lq, Lk, bidirectional, num_buckets, max_distance) on the host and
-    cached (per device when ``device`` is given)."""
-    key = (int(Lq), int(Lk), bool(bidirectional), int(num_buckets), int(max_distance))
-    table = _t5_bucket_cache.get(key)
-    if table is None:
-        rel = torch.arange(-(key[0] - 1), key[1], dtype=torch.int64)
-        table = _t5_bucket_of(rel, key[2], key[3], key[4]).to(torch.int32).contiguous()
-        if int(table.min()) < 0 or int(table.max()) >= key[3]:  # the kernel indexes the bias table with it
-            raise ValueError(f"t5_relative_buckets{key}: a bucket outside [0, num_buckets)")
-        _t5_bucket_cache[key] = table
-    if device is None or torch.device(device).type == "cpu":
-        return table
-    dkey = key + (str(device),)
-    dev_table = _t5_bucket_cache.get(dkey)
-    if dev_table is None:
-        dev_table = _t5_bucket_cache[dkey] = table.to(device)
-    return dev_table
-
-
-class _T5AttnFn(torch.autograd.Function):
-    """(B, Lq, H dh) = dropout(softmax_j(q k^T + bias, mask)) v; keeps the rows' log-sum-exp, never the weights."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, bias, mask, bucket, cfg):
-        H, dh, causal, nb, p = cfg
-        B, Lq, Lk = int(q.shape[0]), int(q.shape[1]), int(k.shape[1])
-        dev = q.device
-        out = torch.empty((B, Lq, H * dh), dtype=torch.float32, device=dev)
-        lse = torch.empty((B, H, Lq), dtype=torch.float32, device=dev)
-        rng = _dropout_rng(dev) if p > 0 else None
-        ctr = torch.empty(1, dtype=torch.int64, device=dev) if p > 0 else None
-        _lib.call("rh_t5_attn_fwd", _p(q), int(q.stride(1)), _p(k), _p(v), int(k.stride(1)), B, Lq, Lk, H, dh, _p(mask),
-                  causal, _p(bias), _p(bucket), nb, p, _p(rng), _p(ctr), _p(out), _p(lse), _stream())
-        ctx.cfg = cfg
-        ctx.save_for_backward(q, k, v, bias, mask, bucket, out, lse, rng, ctr)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        q, k, v, bias, mask, bucket, out, lse, rng, ctr = ctx.saved_tensors
-        H, dh, causal, nb, p = ctx.cfg
-        B, Lq, Lk = int(q.shape[0]), int(q.shape[1]), int(k.shape[1])
-        dev = q.device
-        g = g.contiguous()
-        W = H * dh
-        g_q = torch.empty((B, Lq, W), dtype=torch.float32, device=dev)
-        if k.stride(1) >= 2 * W:  # column blocks of a fused product: its gradient's blocks, side by side
-            g_kv = torch.empty((B, Lk, 2 * W), dtype=torch.float32, device=dev)
-            g_k, g_v = g_kv[:, :, :W], g_kv[:, :, W:]
-        else:
-            g_kv = torch.empty((2, B, Lk, W), dtype=torch.float32, device=dev)
-            g_k, g_v = g_kv[0], g_kv[1]
-        g_bias = torch.empty_like(bias) if bias is not None else None
-        if B == 0:
-            return g_q, g_k, g_v, None if bias is None else torch.zeros_like(bias), None, None, None
-        delta = torch.empty((B, H, Lq), dtype=torch.float32, device=dev)
-        part = None
-        if bias is not None:
-            part = torch.empty((_lib.query("rh_t5_attn_nparts", B, Lq, H), Lq + Lk - 1), dtype=torch.float32, device=dev)
-        _lib.call("rh_t5_attn_bwd", _p(q), int(q.stride(1)), _p(k), _p(v), int(k.stride(1)), B, Lq, Lk, H, dh, _p(mask),
-                  causal, _p(bias), _p(bucket), nb, p, _p(rng), _p(ctr), _p(out), _p(lse), _p(g), _p(delta), _p(g_q), W,
-                  _p(g_k), _p(g_v), int(g_k.stride(1)), _p(part), _p(g_bias), _stream())
-        return g_q, g_k, g_v, g_bias, None, None, None
-
-
-def t5_attention(q, k, v, n_heads, key_mask=None, causal=False, bias_table=None, bidirectional=True, max_distance=128,
-                 dropout_p=0.0, training=True):
-    """T5's multi-head attention (B, Lq, H dh) of q (B, Lq, H dh) against k, v (B, Lk, H dh), with no scale on q . k:
-    separate projections, or column blocks of one fused QKV / KV product (read in place when k and v share a row stride).
-    ``key_mask`` (B, Lk), non-zero = attend; a row with no key left weighs all Lk keys equally, as the reference's additive
-    mask does.  ``causal`` excludes j > i and needs Lq == Lk.  ``bias_table`` (num_buckets, H): the stack's
-    relative_attention_bias weight, added by T5's bucket rule (``bidirectional``, ``max_distance``).  Dropout with
-    probability ``dropout_p`` on the weights when ``training``."""
-    require_hip(q, k, v, key_mask, bias_table)
-    if (q.dim() != 3 or k.dim() != 3 or k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[2] != k.shape[2] or
-            q.shape[2] % n_heads != 0):
-        raise RuntimeError(f"torch_rechub_amd: T5 attention of q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} "
-                           f"with {n_heads} heads unsupported (q (B, Lq, H dh), k and v (B, Lk, H dh))")
-    if q.dtype != torch.float32 or k.dtype != torch.float32 or v.dtype != torch.float32 or (
-            bias_table is not None and bias_table.dtype != torch.float32):
-        raise RuntimeError("torch_rechub_amd: T5 attention runs in float32 only")
-    B, Lq, W = (int(x) for x in q.shape)
-    Lk = int(k.shape[1])
-    H = int(n_heads)
-    dh = W // H
-    nb = int(bias_table.shape[0]) if bias_table is not None else 0
-    if bias_table is not None and (bias_table.dim() != 2 or nb < 1 or bias_table.shape[1] != H):
-        raise RuntimeError(f"torch_rechub_amd: T5 attention bias table {tuple(bias_table.shape)} unsupported "
-                           "((num_buckets >= 1, H))")
-    if key_mask is not None and tuple(key_mask.shape) != (B, Lk):
-        raise RuntimeError(f"torch_rechub_amd: T5 attention key mask {tuple(key_mask.shape)} is not (B, Lk) = ({B}, {Lk})")
-    p = float(dropout_p) if training else 0.0
-    if not 0.0 <= p < 1.0:
-        raise RuntimeError(f"torch_rechub_amd: attention dropout p={p} has no HIP kernel (0 <= p < 1)")
-    if not _attn_view_ok(q, B, Lq, W):
-        q = q.contiguous()
-    if not (_attn_view_ok(k, B, Lk, W) and _attn_view_ok(v, B, Lk, W) and k.stride(1) == v.stride(1)):
-        k, v = k.contiguous(), v.contiguous()
-    mask = None if key_mask is None else (key_mask != 0).to(torch.uint8).contiguous()
-    bucket = None
-    if bias_table is not None and 1 <= Lq <= _lib.H.RH_ATTN_MAX_L and 1 <= Lk <= _lib.H.RH_ATTN_MAX_L:
-        bucket = t5_relative_buckets(Lq, Lk, bidirectional, nb, max_distance, device=q.device)
-    cfg = (H, dh, 1 if causal else 0, nb, p)
-    # (shapes outside the kernel's range are refused by the entry point itself, before any launch)
-    return _T5AttnFn.apply(q, k, v, None if bias_table is None else bias_table.contiguous(), mask, bucket, cfg)
-
-
-class _AddRmsNormFn(torch.autograd.Function):
-    """(h + delta, RMSNorm(h + delta) * w) over the rows of (M, D); g_w through per-workgroup partials and rh_colsum."""
-
-    @staticmethod
-    def forward(ctx, h, delta, w, eps):
-        M, D = (int(x) for x in h.shape)
-        dev = h.device
-        y = torch.empty((M, D), dtype=torch.float32, device=dev)
-        rstd = torch.empty((M,), dtype=torch.float32, device=dev)
-        hn = torch.empty((M, D), dtype=torch.float32, device=dev) if delta is not None else None
-        _lib.call("rh_add_rms_norm_fwd", _p(h), _p(delta), _p(w), eps, M, D, _p(hn), _p(y), _p(rstd), _stream())
-        ctx.has_delta = delta is not None
-        ctx.save_for_backward(h if hn is None else hn, w, rstd)
-        if hn is None:  # no sum was formed: the caller keeps h; a placeholder stands in the output tuple
-            hn = torch.empty((0,), dtype=torch.float32, device=dev)
-            ctx.mark_non_differentiable(hn)
-        return hn, y
-
-    @staticmethod
-    def backward(ctx, g_hn, g_y):
-        hn, w, rstd = ctx.saved_tensors
-        M, D = (int(x) for x in hn.shape)
-        dev = hn.device
-        if g_y is None:
-            return g_hn, (g_hn if ctx.has_delta else None), torch.zeros_like(w), None
-        g_y = g_y.contiguous()
-        g_hn = g_hn.contiguous() if (ctx.has_delta and g_hn is not None) else None  # (else: the placeholder's)
-        g_h = torch.empty((M, D), dtype=torch.float32, device=dev)
-        g_w = torch.zeros((D,), dtype=torch.float32, device=dev)
-        if M > 0:
-            n = _lib.query("rh_add_rms_norm_nparts", M)
-            part = torch.empty((n, D), dtype=torch.float32, device=dev)
-            _lib.call("rh_add_rms_norm_bwd", _p(hn), _p(w), _p(rstd), _p(g_y), _p(g_hn), M, D, _p(g_h), _p(part), _stream())
-            _lib.call("rh_colsum", _p(part), n, D, _p(g_w), _NULL, 0, _NULL, _stream())
-        return g_h, (g_h if ctx.has_delta else None), g_w, None
-
-
-def add_rms_norm(h, delta, weight, eps=1e-6):
-    """(h_new, y): h_new = h + delta (``delta`` None: h itself), y = h_new * rsqrt(mean(h_new^2, -1) + eps) * weight --
-    T5LayerNorm behind the residual add of the sub-layer before it, in one pass.  float32 (..., D), D <= RH_RMS_NORM_MAX_D; the weight
-    gradient is summed in a fixed order."""
-    require_hip(h, delta, weight)
-    D = int(h.shape[-1])
-    if h.dtype != torch.float32 or weight.dtype != torch.float32 or (delta is not None and delta.dtype != torch.float32):
-        raise RuntimeError("torch_rechub_amd: add_rms_norm runs in float32 only")
-    if not 1 <= D <= _lib.H.RH_RMS_NORM_MAX_D or tuple(weight.shape) != (D,) or (delta is not None and delta.shape != h.shape):
-        raise RuntimeError(f"torch_rechub_amd: add_rms_norm of h {tuple(h.shape)}, weight {tuple(weight.shape)} has no HIP "
-                           f"kernel (1 <= D <= {_lib.H.RH_RMS_NORM_MAX_D}, weight (D,), delta like h)")
-    hn, y = _AddRmsNormFn.apply(h.reshape(-1, D).contiguous(), None if delta is None else delta.reshape(-1, D).contiguous(),
-                                weight.contiguous(), float(eps))
-    return (h if delta is None else hn.view(h.shape)), y.view(h.shape)
-
-
-def beam_step(logits, running, node, trie):
-    """One step of the constrained beam search (csrc/beam.hip): ``logits`` (B K, V) float32 the beams' next-token logits
-    (rows may be strided: the ``[:, -1, :]`` view of a decoder output is read in place), ``running`` (B, K) float32 their
-    scores, ``node`` (B, K) int32 their nodes in ``trie`` (a ``utils.data.DeviceTrie`` on the same device), -1 = dead beam.
-    Returns ``(running, parent, token, node, short)``: per query the K best continuations running + log_softmax(logits)[tok]
-    over the children of the beams' nodes, by (score descending, beam ascending, token ascending) -- (B, K) float32 and
-    three (B, K) int32 -- and ``short`` (B,) int32, 1 where fewer than K continuations exist (the unused slots are -inf,
-    -1, -1, -1).  No autograd; no host synchronisation; runs on the current stream."""
-    require_hip(logits, running, node, trie.child_off)
-    if logits.dim() != 2 or running.dim() != 2 or tuple(node.shape) != tuple(running.shape):
-        raise ValueError(f"beam_step: logits {tuple(logits.shape)}, running {tuple(running.shape)}, node {tuple(node.shape)}: "
-                         "(B K, V), (B, K) and (B, K) expected")
-    if logits.dtype != torch.float32 or running.dtype != torch.float32 or node.dtype != torch.int32:
-        raise ValueError("beam_step: float32 logits and running and int32 node expected")
-    B, K = (int(v) for v in running.shape)
-    V = int(logits.shape[1])
-    if int(logits.shape[0]) != B * K:
-        raise ValueError(f"beam_step: {int(logits.shape[0])} logits rows for B K = {B} x {K} beams")
-    if not (logits.device == running.device == node.device == trie.child_off.device):
-        raise ValueError("beam_step: logits, running, node and the trie must be on one device")
-    if not 1 <= K <= _lib.H.RH_BEAM_MAX_K or V < 1:
-        raise ValueError(f"beam_step: K={K}, V={V} unsupported (1 <= K <= {_lib.H.RH_BEAM_MAX_K}, V >= 1)")
-    if trie.max_token >= V:
-        raise ValueError(f"beam_step: the trie holds token {trie.max_token}, outside the vocabulary V={V}")
-    logits = logits.detach()
-    if B * K > 0 and (logits.stride(1) != 1 or (B * K > 1 and logits.stride(0) < V)):
-        logits = logits.contiguous()
-    ld = int(logits.stride(0)) if B * K > 1 else V
-    running, node = running.detach().contiguous(), node.contiguous()
-    dev = logits.device
-    out_run = torch.empty((B, K), dtype=torch.float32, device=dev)
-    parent, tok, child = (torch.empty((B, K), dtype=torch.int32, device=dev) for _ in range(3))
-    short = torch.empty((B,), dtype=torch.int32, device=dev)
-    if B > 0:
-        _lib.call("rh_beam_step", _p(logits), ld, _p(running), _p(node), _p(trie.child_off), _p(trie.child_tok),
-                  _p(trie.child_node), int(trie.n_nodes), B, K, V, _p(out_run), _p(parent), _p(tok), _p(child), _p(short),
-                  _stream())
-    return out_run, parent, tok, child, short
-
-
-# --------------------------------------------------------------------------------------------
-# CIN: one Compressed Interaction Network layer (csrc/cin.hip)
-# --------------------------------------------------------------------------------------------
-
-
-def _cin_views(x0, h):
-    """(x0, sample stride, field stride, h, sample stride) as the kernels read them: d contiguous, x0's fields at least D
-    apart, a sample of h contiguous.  Anything else is copied here."""
-    D = int(x0.shape[2])
-    if (x0.stride(2) != 1 and D > 1) or (x0.shape[1] > 1 and x0.stride(1) < D):
-        x0 = x0.contiguous()
-    if (h.stride(2) != 1 and D > 1) or (h.shape[1] > 1 and h.stride(1) != D):
-        h = h.contiguous()
-    xf = int(x0.stride(1)) if x0.shape[1] > 1 else D
-    return x0, int(x0.stride(0)), max(xf, D), h, int(h.stride(0))
-
-
-class _CinLayerFn(torch.autograd.Function):
-    """relu(conv1d(x0 (x) h)) of one CIN layer; the (B, F Hp, D) product exists only in registers, both ways."""
-
-    @staticmethod
-    def forward(ctx, x0, h, weight, bias):
-        B, F, D = (int(s) for s in x0.shape)
-        Hp, Ho = int(h.shape[1]), int(weight.shape[0])
-        x0, xs, xf, h, hs = _cin_views(x0, h)
-        weight, bias = weight.contiguous(), bias.contiguous()  # (Ho, F Hp, 1): read as (Ho, F Hp)
-        y = torch.empty((B, Ho, D), dtype=torch.float32, device=x0.device)
-        _lib.call("rh_cin_fwd", _p(x0), xs, xf, _p(h), hs, _p(weight), _p(bias), B, D, F, Hp, Ho, _p(y), _stream())
-        ctx.save_for_backward(x0, h, weight, y)
-        ctx.strides = (xs, xf, hs)
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        x0, h, weight, y = ctx.saved_tensors
-        xs, xf, hs = ctx.strides
-        B, F, D = (int(s) for s in x0.shape)
-        Hp, Ho = int(h.shape[1]), int(weight.shape[0])
-        K = F * Hp
-        dev = x0.device
-        g = g.contiguous()
-        need_x0, need_h, need_w, need_b = ctx.needs_input_grad
-        g_x0 = torch.empty((B, F, D), dtype=torch.float32, device=dev) if need_x0 else None
-        g_h = torch.empty((B, Hp, D), dtype=torch.float32, device=dev) if need_h else None
-        if need_x0 or need_h:
-            _lib.call("rh_cin_bwd", _p(x0), xs, xf, _p(h), hs, _p(weight), _p(y), _p(g), B, D, F, Hp, Ho, _p(g_x0), _p(g_h),
-                      _stream())
-        g_w = g_b = None
-        if need_w or need_b:
-            if B == 0:  # nothing is launched: the parameter gradients are exact zeros
-                both = torch.zeros((Ho * K + Ho,), dtype=torch.float32, device=dev)
-            else:
-                nch = _lib.query("rh_cin_wgrad_chunks", B, D, F, Hp, Ho)
-                part = torch.empty((nch, Ho * K + Ho), dtype=torch.float32, device=dev)
-                _lib.call("rh_cin_wgrad", _p(x0), xs, xf, _p(h), hs, _p(y), _p(g), B, D, F, Hp, Ho, _p(part), _stream())
-                both = torch.empty((Ho * K + Ho,), dtype=torch.float32, device=dev)
-                _lib.call("rh_colsum", _p(part), nch, Ho * K + Ho, _p(both), _NULL, 0, _NULL, _stream())
-            g_w = both[:Ho * K].view(Ho, K, 1) if need_w else None
-            g_b = both[Ho * K:] if need_b else None
-        return g_x0, g_h, g_w, g_b
-
-
-def cin_layer_ok(x0, h, weight, bias):
-    """True when the HIP kernels take this layer: float32 HIP tensors inside the ranges of rh_cin_* (RH_CIN_MAX_*)."""
-    ts = (x0, h, weight, bias)
-    if not all(t.is_cuda and t.dtype == torch.float32 for t in ts) or x0.dim() != 3 or h.dim() != 3 or weight.dim() != 3:
-        return False
-    (B, F, D), Hp, Ho = x0.shape, h.shape[1], weight.shape[0]
-    return (h.shape[0] == B and h.shape[2] == D and tuple(weight.shape) == (Ho, F * Hp, 1) and tuple(bias.shape) == (Ho,) and
-            1 <= D <= _lib.H.RH_CIN_MAX_D and 1 <= F <= _lib.H.RH_CIN_MAX_F and 1 <= Hp <= _lib.H.RH_CIN_MAX_HP and
-            1 <= Ho <= _lib.H.RH_CIN_MAX_HO)
-
-
-def cin_layer(x0, h, weight, bias):
-    """``relu(conv1d((x0.unsqueeze(2) * h.unsqueeze(1)).view(B, F * Hp, D), weight, bias))`` for x0 (B, F, D), h (B, Hp, D),
-    weight (Ho, F * Hp, 1) -- the Conv1d parameter, used in place --, bias (Ho,): one CIN layer as one MFMA GEMM launch
-    (csrc/cin.hip) whose operand is formed from x0 and h in registers.  x0 may be a strided view (the sparse block of the
-    fused gather's output) and h the second half of the previous layer's output; the backward is deterministic.  Shapes
-    outside the kernel's ranges are refused by the entry points, before any launch."""
-    require_hip(x0, h, weight, bias)
-    if any(t.dtype != torch.float32 for t in (x0, h, weight, bias)):
-        raise RuntimeError("torch_rechub_amd: cin_layer runs in float32 only")
-    if (x0.dim() != 3 or h.dim() != 3 or h.shape[0] != x0.shape[0] or h.shape[2] != x0.shape[2] or
-            tuple(weight.shape) != (weight.shape[0], x0.shape[1] * h.shape[1], 1) or tuple(bias.shape) != (weight.shape[0],)):
-        raise RuntimeError(f"torch_rechub_amd: cin_layer of x0 {tuple(x0.shape)}, h {tuple(h.shape)}, weight "
-                           f"{tuple(weight.shape)}, bias {tuple(bias.shape)}: need x0 (B, F, D), h (B, Hp, D), weight "
-                           "(Ho, F * Hp, 1), bias (Ho,)")
-    return _CinLayerFn.apply(x0, h, weight, bias)
-
-
-# --------------------------------------------------------------------------------------------
-# Evaluation metrics (csrc/metric.hip): exact AUC / GAUC, log loss, top-K list metrics
-# --------------------------------------------------------------------------------------------
-_LABEL_DTYPES = {torch.float32: 0, torch.float64: 1, torch.int64: 2, torch.uint8: 3, torch.bool: 3}
-_rank_tables = {}
-_PLAN_OUT = (ctypes.c_int, ctypes.c_int, ctypes.c_int64)  # what the metric kernels' plans answer with
-
-
-def auc_plan(n):
-    """(chunk, max_grid, workspace_bytes) of rh_auc_groups over n samples: the sorted elements a workgroup takes per trip,
-    the grid cap (more chunks than that are further trips) and the scratch size."""
-    return _lib.query("rh_auc_plan", int(n), out=_PLAN_OUT)
-
-
-def _metric_inputs(what, pred, label, *more):
-    """The guards of the pointwise metrics, before anything is allocated or launched.  -> (pred 1-D, possibly strided;
-    label 1-D contiguous; n)."""
-    require_hip(pred, label, *more)
-    if pred.dtype != torch.float32:
-        raise ValueError(f"torch_rechub_amd: {what} takes float32 predictions, got {pred.dtype}")
-    if label.dtype not in _LABEL_DTYPES:
-        raise ValueError(f"torch_rechub_amd: {what} takes float32, float64, int64, uint8 or bool labels, got {label.dtype}")
-    if pred.numel() != label.numel() or any(t.numel() != pred.numel() for t in more):
-        raise ValueError(f"torch_rechub_amd: {what}: {[tuple(t.shape) for t in (pred, label) + more]} do not agree")
-    n = int(pred.numel())
-    if n == 0:
-        raise ValueError(f"torch_rechub_amd: {what} of an empty input")
-    if n >= 2 ** 31:
-        raise ValueError(f"torch_rechub_amd: {what} takes fewer than 2**31 samples, got {n}")
-    pred = pred.detach()
-    if pred.dim() != 1:
-        pred = pred.reshape(-1)
-    return pred, label.detach().reshape(-1).contiguous(), n
-
-
-def _auc_groups(pred, label, g, G, n):
-    dev = pred.device
-    ps = int(pred.stride(0)) if n > 1 else 1
-    keys = torch.empty((n,), dtype=torch.int64, device=dev)
-    _lib.call("rh_auc_keys", _p(pred), ps, _p(g), n, _p(keys), _stream())
-    order = torch.sort(keys).indices  # the permutation is plumbing: the counting below is the metric
-    del keys
-    work = torch.empty((auc_plan(n)[2],), dtype=torch.uint8, device=dev)
-    out = torch.empty((3, G), dtype=torch.int64, device=dev)
-    bad = torch.empty((2,), dtype=torch.int64, device=dev)
-    _lib.call("rh_auc_groups", _p(pred), ps, _p(label), _LABEL_DTYPES[label.dtype], _p(g), _p(order), n, G, _p(work), _p(out),
-              _p(bad), _stream())
-    nonfinite, badlabel = bad.tolist()
-    if nonfinite:
-        raise ValueError(f"torch_rechub_amd: {nonfinite} predictions are NaN or infinite")
-    if badlabel:
-        raise ValueError(f"torch_rechub_amd: {badlabel} labels are neither 0 nor 1")
-    return out
-
-
-def auc_groups(pred, label, group=None):
-    """(P, N, U2), int64 tensors of length G: per group the positives, the negatives and the rank statistic
-    U2 = sum over positives of 2 #{negatives below} + #{negatives tied}, so that AUC_g = U2 / (2 P N) exactly.  ``group``:
-    dense int64 ids in [0, G) with G = max + 1, or None for one group.  Ties are equal VALUES (-0.0 == +0.0, distinct
-    denormals distinct).  NaN / infinite predictions and labels other than 0 / 1 raise ValueError.  No autograd; current
-    stream."""
-    more = () if group is None else (group,)
-    pred, label, n = _metric_inputs("auc_groups", pred, label, *more)
-    G, g = 1, None
-    if group is not None:
-        if group.dtype != torch.int64:
-            raise ValueError(f"torch_rechub_amd: auc_groups takes int64 group ids, got {group.dtype}")
-        g = group.detach().reshape(-1).contiguous()
-        lo, hi = int(g.min()), int(g.max())
-        if lo < 0 or hi >= 2 ** 31 - 1:
-            raise ValueError(f"torch_rechub_amd: auc_groups takes dense group ids in [0, G), G < 2**31; got [{lo}, {hi}]")
-        G = hi + 1
-    out = _auc_groups(pred, label, g, G, n)
-    return out[0], out[1], out[2]
-
-
-def auc(pred, label):
-    """roc_auc_score(label, pred) as a Python float: the exact rational U2 / (2 P N), correctly rounded."""
-    P, N, U2 = (int(t) for t in auc_groups(pred, label))
-    if P == 0 or N == 0:
-        raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
-    return U2 / (2 * P * N)
-
-
-def gauc(pred, label, users, weights=None):
-    """sum_u w_u AUC_u / sum_u w_u over the distinct values u of ``users`` (any int64 tensor); w_u = the samples of u, or
-    ``weights[u]`` (a 1-D tensor indexed by user id).  nan when a user holds one class only."""
-    pred, label, n = _metric_inputs("gauc", pred, label, users)
-    if users.dtype != torch.int64:
-        raise ValueError(f"torch_rechub_amd: gauc takes int64 user ids, got {users.dtype}")
-    if weights is not None:
-        require_hip(weights)
-        if weights.dim() != 1:
-            raise ValueError("torch_rechub_amd: gauc takes a 1-D weight tensor indexed by user id")
-    uniq, g = torch.unique(users.detach().reshape(-1), return_inverse=True)
-    G = int(uniq.numel())
-    w = None
-    if weights is not None:
-        if int(uniq[0]) < 0 or int(uniq[-1]) >= weights.numel():
-            raise ValueError("torch_rechub_amd: gauc: a user id lies outside the weight tensor")
-        w = weights.detach()[uniq].to(torch.float64).contiguous()
-    stats = _auc_groups(pred, label, g.contiguous(), G, n)
-    dev = pred.device
-    partial = torch.empty((3072,), dtype=torch.float64, device=dev)
-    result = torch.empty((2,), dtype=torch.float64, device=dev)
-    single = torch.empty((1,), dtype=torch.int64, device=dev)
-    _lib.call("rh_gauc_reduce", _p(stats), _p(w), G, _p(partial), _p(result), _p(single), _stream())
-    if int(single):
-        return float("nan")
-    num, den = result.tolist()
-    return num / den
-
-
-def log_loss(pred, label):
-    """-mean(y log p + (1 - y) log(1 - p)) as a Python float; p is widened to double before the logarithms."""
-    pred, label, n = _metric_inputs("log_loss", pred, label)
-    dev = pred.device
-    partial = torch.empty((1024,), dtype=torch.float64, device=dev)
-    result = torch.empty((1,), dtype=torch.float64, device=dev)
-    _lib.call("rh_log_loss", _p(pred), int(pred.stride(0)) if n > 1 else 1, _p(label), _LABEL_DTYPES[label.dtype], n,
-              _p(partial), _p(result), _stream())
-    return float(result)
-
-
-def rank_metrics_plan(M):
-    """(stage, users_per_workgroup, max_grid, partial_doubles) of rh_rank_metrics over M users."""
-    return _lib.query("rh_rank_metrics_plan", int(M), out=(ctypes.c_int,) + _PLAN_OUT)
-
-
-def rank_gain_tables(K):
-    """(gain (K,), ideal (K + 1,)) as float64 numpy arrays: gain[j] = 1 / log2(j + 2) position by position, ideal its
-    sequential prefix sums from 0 -- the operands and the order of additions of the host loop."""
-    import numpy as np
-    gain = np.array([1. / np.log2(j + 2) for j in range(K)], dtype=np.float64)
-    ideal = np.zeros(K + 1, dtype=np.float64)
-    for j in range(K):
-        ideal[j + 1] = ideal[j] + gain[j]
-    return gain, ideal
-
-
-def pack_truth(truth, device):
-    """A list of id lists as the CSR pair (offsets (M + 1,), ids) of int64 tensors on ``device``: packed once, on the host."""
-    import numpy as np
-    lens = np.fromiter((len(t) for t in truth), dtype=np.int64, count=len(truth))
-    off = np.zeros(len(truth) + 1, dtype=np.int64)
-    np.cumsum(lens, out=off[1:])
-    ids = np.fromiter((i for t in truth for i in t), dtype=np.int64, count=int(off[-1]))
-    return torch.from_numpy(off).to(device), torch.from_numpy(ids).to(device)
-
-
-def rank_metrics(pred_ids, truth, cutoffs, per_user=False):
-    """The raw sums behind the top-K list metrics.  ``pred_ids`` (M, K) int64 (what ``topk_items`` returns; a strided
-    ``ids[:, :k]`` view is read in place), ``truth`` an (offsets, ids) pair of int64 device tensors or a row-aligned list of
-    id lists, ``cutoffs`` at most 8 ints in [1, K].  -> dict: ``hits`` (n_k,) int64, ``gts`` (1,) int64, ``sums`` (n_k, 4)
-    float64 = mrr, recall, precision, ndcg summed over users, ``per_user`` (M, n_k, 5) float64 = hit, mrr, recall,
-    precision, ndcg or None.  No autograd; current stream."""
-    cutoffs = [int(k) for k in cutoffs]
-    if len(cutoffs) > _lib.H.RH_RANK_MAX_CUTOFFS:  # the newer list metrics answer this with "no HIP kernel"; here it stays a ValueError
-        raise ValueError(f"torch_rechub_amd: rank_metrics takes 1 to {_lib.H.RH_RANK_MAX_CUTOFFS} cut-offs, got {cutoffs}")
-    pred_ids, ld, M, K, cuts, n_k = _list_inputs("rank_metrics", pred_ids, cutoffs)
-    if isinstance(truth, (tuple, list)) and len(truth) == 2 and all(torch.is_tensor(t) for t in truth):
-        off, ids = truth
-        require_hip(off, ids)
-        if off.dtype != torch.int64 or ids.dtype != torch.int64 or off.dim() != 1 or ids.dim() != 1:
-            raise ValueError("torch_rechub_amd: rank_metrics takes int64 1-D truth offsets and ids")
-        off, ids = off.contiguous(), ids.contiguous()
-    else:
-        if len(truth) != M:
-            raise ValueError(f"torch_rechub_amd: rank_metrics: {len(truth)} truth lists for {M} users")
-        off, ids = pack_truth(truth, pred_ids.device)
-    if off.numel() != M + 1:
-        raise ValueError(f"torch_rechub_amd: rank_metrics: {off.numel()} truth offsets for {M} users (M + 1 expected)")
-    dev = pred_ids.device
-    tables = _rank_tables.get((K, dev))
-    if tables is None:
-        tables = _rank_tables[(K, dev)] = tuple(torch.from_numpy(t).to(dev) for t in rank_gain_tables(K))
-    partial = torch.empty((rank_metrics_plan(M)[3],), dtype=torch.float64, device=dev)
-    hits = torch.empty((n_k,), dtype=torch.int64, device=dev)
-    gts = torch.empty((1,), dtype=torch.int64, device=dev)
-    sums = torch.empty((n_k, 4), dtype=torch.float64, device=dev)
-    users = torch.empty((M, n_k, 5), dtype=torch.float64, device=dev) if per_user else None
-    _lib.call("rh_rank_metrics", _p(pred_ids), ld, M, K, _p(off), _p(ids), int(ids.numel()),
-              ctypes.c_void_p(ctypes.addressof(cuts)), n_k, _p(tables[0]), _p(tables[1]), _p(partial), _p(hits), _p(gts),
-              _p(sums), _p(users), _stream())
-    return {"hits": hits, "gts": gts, "sums": sums, "per_user": users}
-
-
-# beyond-accuracy metrics (rh_ild, rh_coverage, rh_novelty): intra-list diversity, catalogue coverage, novelty
-_POP_DTYPES = {torch.float32: 0, torch.float64: 1}
-
-
-def ild_plan(M):
-    """(users_per_workgroup, max_grid, partial_doubles) of rh_ild over M users."""
-    return _lib.query("rh_ild_plan", int(M), out=_PLAN_OUT)
-
-
-def novelty_plan(M):
-    """(users_per_workgroup, max_grid, partial_doubles) of rh_novelty over M users."""
-    return _lib.query("rh_novelty_plan", int(M), out=_PLAN_OUT)
-
-
-def coverage_plan(n_slots):
-    """(rows_per_workgroup, max_grid, workspace_bytes) of rh_coverage over n_slots item slots: the rows a workgroup marks
-    per trip, the grid cap of both passes (the counting pass takes 256 slots per workgroup and trip) and the scratch size."""
-    return _lib.query("rh_coverage_plan", int(n_slots), out=_PLAN_OUT)
-
-
-def _list_inputs(what, pred_ids, cutoffs, *more):
-    """The guards the list metrics share, before anything is allocated or launched.  -> (pred_ids readable in place, ld, M,
-    K, the cut-offs as a C array, n_k)."""
-    require_hip(pred_ids, *more)
-    if pred_ids.dim() != 2 or pred_ids.dtype != torch.int64:
-        raise ValueError(f"torch_rechub_amd: {what} takes an (M, K) int64 id tensor")
-    M, K = (int(v) for v in pred_ids.shape)
-    if M == 0 or K == 0:
-        raise ValueError(f"torch_rechub_amd: {what} of an empty input")
-    if K > _lib.H.RH_RANK_MAX_K:
-        from .models.matching._listwise import no_kernel
-        raise no_kernel(f"{what} over K={K} recommendations (1 <= K <= {_lib.H.RH_RANK_MAX_K})")
-    cutoffs = [int(k) for k in cutoffs]
-    if not cutoffs or any(not 1 <= k <= K for k in cutoffs):
-        raise ValueError(f"torch_rechub_amd: {what} takes cut-offs within [1, K={K}], got {cutoffs}")
-    if len(cutoffs) > _lib.H.RH_RANK_MAX_CUTOFFS:
-        from .models.matching._listwise import no_kernel
-        raise no_kernel(f"{what} at {len(cutoffs)} cut-offs (1 to {_lib.H.RH_RANK_MAX_CUTOFFS})")
-    pred_ids = pred_ids.detach()
-    if pred_ids.stride(1) != 1 or (M > 1 and pred_ids.stride(0) < K):
-        pred_ids = pred_ids.contiguous()
-    ld = int(pred_ids.stride(0)) if M > 1 else K
-    return pred_ids, ld, M, K, (ctypes.c_int * len(cutoffs))(*cutoffs), len(cutoffs)
-
-
-def ild(pred_ids, table, cutoffs, per_user=False):
-    """The raw sums behind intra-list diversity.  ``pred_ids`` (M, K) int64 (what ``topk_items`` returns; a strided
-    ``ids[:, :k]`` view is read in place; an id below 0 is an absent position), ``table`` (V, D) float32, read in place
-    under a row stride, ``cutoffs`` at most 8 ints in [1, K].  Per user and cut-off k the mean over the pairs i < j of
-    1 - cos(e_i, e_j) among the first k entries with 0 <= id < V (norms clamped at 1e-10, in double), for users with at
-    least two such entries -- the reference run on the rows with the negative entries removed.  -> dict: ``sums`` (n_k,)
-    float64 over the users, ``counts`` (n_k,) int64 = the users that contributed, ``per_user`` (M, n_k) float64 (nan where
-    the user was left out) or None.  O(k D) per user; no (M, K, D) gather.  No autograd; current stream."""
-    pred_ids, ld, M, K, cuts, n_k = _list_inputs("ild", pred_ids, cutoffs, table)
-    if table.dim() != 2 or table.dtype != torch.float32:
-        raise ValueError("torch_rechub_amd: ild takes a (V, D) float32 embedding table")
-    V, D = (int(v) for v in table.shape)
-    if V == 0 or D == 0:
-        raise ValueError("torch_rechub_amd: ild of an empty embedding table")
-    if D > _lib.H.RH_ILD_MAX_D:
-        from .models.matching._listwise import no_kernel
-        raise no_kernel(f"intra-list diversity over embeddings of width {D} (1 <= D <= {_lib.H.RH_ILD_MAX_D})")
-    table = table.detach()
-    if table.stride(1) != 1 or (V > 1 and table.stride(0) < D):
-        table = table.contiguous()
-    lt = int(table.stride(0)) if V > 1 else D
-    dev = pred_ids.device
-    partial = torch.empty((ild_plan(M)[2],), dtype=torch.float64, device=dev)
-    sums = torch.empty((n_k,), dtype=torch.float64, device=dev)
-    counts = torch.empty((n_k,), dtype=torch.int64, device=dev)
-    users = torch.empty((M, n_k), dtype=torch.float64, device=dev) if per_user else None
-    _lib.call("rh_ild", _p(pred_ids), ld, M, K, _p(table), lt, V, D, ctypes.c_void_p(ctypes.addressof(cuts)), n_k,
-              _p(partial), _p(sums), _p(counts), _p(users), _stream())
-    return {"sums": sums, "counts": counts, "per_user": users}
-
-
-def coverage(pred_ids, n_slots, cutoffs):
-    """The distinct ids in [0, n_slots) among ``pred_ids[:, :k]`` for every cut-off, in one pass: -> dict ``counts`` (n_k,)
-    int64.  Ids outside [0, n_slots) -- the -1 padding among them -- are ignored.  Exact.  No autograd; current stream."""
-    pred_ids, ld, M, K, cuts, n_k = _list_inputs("coverage", pred_ids, cutoffs)
-    n_slots = int(n_slots)
-    if n_slots < 1:
-        raise ValueError(f"torch_rechub_amd: coverage takes n_slots >= 1, got {n_slots}")
-    if n_slots >= 2 ** 31:
-        from .models.matching._listwise import no_kernel
-        raise no_kernel(f"coverage over {n_slots} item slots (fewer than 2**31)")
-    dev = pred_ids.device
-    first = torch.empty((coverage_plan(n_slots)[2] // 4,), dtype=torch.int32, device=dev)
-    counts = torch.empty((n_k,), dtype=torch.int64, device=dev)
-    _lib.call("rh_coverage", _p(pred_ids), ld, M, K, n_slots, ctypes.c_void_p(ctypes.addressof(cuts)), n_k, _p(first),
-              _p(counts), _stream())
-    return {"counts": counts}
-
-
-def novelty(pred_ids, popularity, cutoffs, per_user=False):
-    """The raw sums behind novelty.  ``popularity`` (V,) float32 or float64, indexed by item id.  An id >= 0 adds
-    -log2(max(p, 1e-10)) in double, p = 1e-10 for an id >= V; an id below 0 is an absent position.  Per user and cut-off k
-    the mean over the present positions among the first k; a user with none is left out -- the reference run on the rows
-    with the negative entries removed.  -> dict like ``ild``'s.  No autograd; current stream."""
-    pred_ids, ld, M, K, cuts, n_k = _list_inputs("novelty", pred_ids, cutoffs, popularity)
-    if popularity.dim() != 1 or popularity.dtype not in _POP_DTYPES:
-        raise ValueError("torch_rechub_amd: novelty takes a 1-D float32 or float64 popularity tensor indexed by item id")
-    V = int(popularity.numel())
-    if V == 0:
-        raise ValueError("torch_rechub_amd: novelty of an empty popularity tensor")
-    popularity = popularity.detach().contiguous()
-    dev = pred_ids.device
-    partial = torch.empty((novelty_plan(M)[2],), dtype=torch.float64, device=dev)
-    sums = torch.empty((n_k,), dtype=torch.float64, device=dev)
-    counts = torch.empty((n_k,), dtype=torch.int64, device=dev)
-    users = torch.empty((M, n_k), dtype=torch.float64, device=dev) if per_user else None
-    _lib.call("rh_novelty", _p(pred_ids), ld, M, K, _p(popularity), _POP_DTYPES[popularity.dtype], V,
-              ctypes.c_void_p(ctypes.addressof(cuts)), n_k, _p(partial), _p(sums), _p(counts), _p(users), _stream())
-    return {"sums": sums, "counts": counts, "per_user": users}
+from ._families.interest import (_CapsuleFn, capsule_supported, capsule_routing, _SaPoolFn, sa_supported, sa_pool,
+                                 _ListwiseFn, listwise_ok, listwise_logits)
+from ._families.sine import (_SineInterestFn, _SineAggregateFn, sine_supported, _sine_check, sine_interests,
+                             sine_aggregate)
+from ._families.rq import rq_supported, _rq_check, rq_forward, _sinkhorn_level, _ResidualQuantizeFn, residual_quantize
+from ._families.hstu import _HstuAttnFn, hstu_attention
+from ._families.hllm import _SoftmaxAttnFn, softmax_attention
+from ._families.session import _AttnPoolFn, additive_attention_pool, _DropoutFn, dropout
+from ._families.topk import topk_supported, topk_plan, _scan_inputs, topk_items
+from ._families.ivf import ivf_supported, ivf_plan, ivf_scan, ivf_list_mean
+from ._families.sasrec import (_sasrec_check, _sasrec_ntiles, _ln_param_grads, _sample_view, _SasrecInputFn, _seq_ids,
+                               _drop_p, sasrec_input, _SasrecHeadFn, _LayerNormFn, layer_norm, sasrec_head)
+from ._families.twotower import (_rows, _BandLogitsFn, _f32_rows, band_logits_ok, band_logits, _PairCosineFn,
+                                 pair_cosine_scores_ok, pair_cosine_scores, _SenetFn, senet_ok, senet)
+from ._families.t5attn import (_t5_bucket_cache, _t5_bucket_of, t5_relative_buckets, _T5AttnFn, t5_attention,
+                               _AddRmsNormFn, add_rms_norm)
+from ._families.beam import beam_step
+from ._families.cin import _cin_views, _CinLayerFn, cin_layer_ok, cin_layer
+from ._families.metric import (_LABEL_DTYPES, _rank_tables, _PLAN_OUT, auc_plan, _metric_inputs, _auc_groups,
+                               auc_groups, auc, gauc, log_loss, rank_metrics_plan, rank_gain_tables, pack_truth,
+                               rank_metrics, _POP_DTYPES, ild_plan, novelty_plan, coverage_plan, _list_inputs, ild,
+                               coverage, novelty)
