@@ -1392,6 +1392,32 @@ int rh_cin_bwd(const float* x0, int64_t x0_sample_stride, int64_t x0_field_strid
 int rh_cin_wgrad(const float* x0, int64_t x0_sample_stride, int64_t x0_field_stride, const float* h, int64_t h_sample_stride,
                  const float* y, const float* g_y, int B, int D, int F, int Hp, int Ho, float* partial, void* stream);
 
+/* AutoInt's interacting layer (csrc/interact.hip): multi-head self-attention over the F fields of a sample, a projected
+ * residual and a ReLU, one launch each way.  fp32, the 64-row tile on v_mfma_f32_32x32x2_f32; a tile holds 64 / F whole
+ * samples, projections included, so neither the (B F, 4 D) projections nor the (B, H, F, F) scores ever exist in HBM.
+ * x, y, g_y, g_x (B, F, D) contiguous; w_q, w_k, w_v, w_res (D, D) = the nn.Linear weights, read in place; w_res may be
+ * null (no residual).  Head h owns columns [h D / H, (h + 1) D / H).
+ * rh_interact_fwd: y = relu(concat_h softmax(scale Q_h K_h^T) V_h + x w_res^T) with Q = x w_q^T, K = x w_k^T, V = x w_v^T;
+ *   lse (B, H, F) = the row log-sum-exp of the scaled scores, all that is kept for backward besides y.
+ * rh_interact_bwd: recomputes Q, K, V and P = exp(scale S - lse) from x; gO = g_y where y > 0, else 0 -> g_x (or null: not
+ *   computed) and part (*nblocks of rh_interact_plan, 4 D D) = per-workgroup sums [g_w_q | g_w_k | g_w_v | g_w_res] over the
+ *   workgroup's tiles in ascending order, every element written (the g_w_res block exact zeros when w_res is null); the
+ *   gradients are rh_colsum of it.  part may be null (not computed), not both.  No atomics: two runs give the same bits.
+ * rh_interact_plan answers through HOST ints: *ntiles = ceil(B / floor(64 / F)), *nblocks = the backward's launch grid
+ *   (<= 256 persistent workgroups, one per CU) = the rows of part.
+ * B >= 0, 1 <= F <= RH_CIN_MAX_F (the fields of a (B, F, D) block), 1 <= D <= RH_SA_MAX_D (the self-attention width: the
+ * 4 D D weight-gradient sums stay in accumulator registers, 64 per lane at D = 64), H >= 1, else RH_E_UNSUPPORTED; D % H != 0
+ * is RH_E_BADARG; all before any launch.  The two limits are the existing macros of the same quantities: this family
+ * defines none.  B = 0 returns at once.  LDS: forward 4 (320 (D|1) + 4160) bytes (99840 at D = 64), backward
+ * 4 (320 (D|1) + 8320) bytes (116480 at D = 64).
+ * replaces: torch_rechub/basic/layers.py:1006-1044 (InteractingLayer.forward) and its autograd. */
+int rh_interact_plan(int B, int F, int D, int H, int* ntiles, int* nblocks);
+int rh_interact_fwd(const float* x, const float* w_q, const float* w_k, const float* w_v, const float* w_res, float scale, int B,
+                    int F, int D, int H, float* y, float* lse, void* stream);
+int rh_interact_bwd(const float* x, const float* w_q, const float* w_k, const float* w_v, const float* w_res, float scale,
+                    const float* y, const float* lse, const float* g_y, int B, int F, int D, int H, float* g_x, float* part,
+                    void* stream);
+
 /* ---- evaluation metrics (csrc/metric.hip) ---------------------------------------------------------------------------
  * Exact AUC / GAUC.  pred: n float32 values with element stride pred_stride; label: n contiguous values of label_dtype
  * (0 float32, 1 float64, 2 int64, 3 uint8 / bool), 1 = positive, 0 = negative; g: n dense group ids in [0, G) or null

@@ -736,7 +736,10 @@ class BiLinearInteractionLayer(nn.Module):
 
 class InteractingLayer(nn.Module):
     """AutoInt's multi-head self-attention over the fields with a projected residual and a ReLU
-    (reference layers.py:973-1044); W_Q / W_K / W_V / W_Res are applied as one product over their concatenation."""
+    (reference layers.py:973-1044).  float32 HIP tensors inside the kernel's ranges (``ops.interacting_layer_ok``) run as
+    one launch each way (``ops.interacting_layer``, csrc/interact.hip) whenever dropout is inactive (``dropout == 0`` or eval
+    mode).  Attention dropout in training is outside the kernel and, like CPU tensors, keeps the torch formulation
+    (``forward_torch``), where W_Q / W_K / W_V / W_Res are applied as one product over their concatenation."""
 
     def __init__(self, embed_dim, num_heads=2, dropout=0.0, residual=True):
         super().__init__()
@@ -753,6 +756,13 @@ class InteractingLayer(nn.Module):
         self.dropout = nn.Dropout(dropout) if dropout > 0 else None
 
     def forward(self, x):
+        w_res = self.W_Res.weight if self.W_Res is not None else None
+        if (self.dropout is None or not self.training) and ops.interacting_layer_ok(
+                x, self.W_Q.weight, self.W_K.weight, self.W_V.weight, w_res, self.num_heads):
+            return ops.interacting_layer(x, self.W_Q.weight, self.W_K.weight, self.W_V.weight, w_res, self.num_heads)
+        return self.forward_torch(x)
+
+    def forward_torch(self, x):
         B, Fn, D = x.shape
         H, Dh = self.num_heads, self.head_dim
         ws = [self.W_Q.weight, self.W_K.weight, self.W_V.weight] + ([self.W_Res.weight] if self.W_Res is not None else [])

@@ -921,6 +921,85 @@ def cross_network(x, W, Bv):
 
 
 # --------------------------------------------------------------------------------------------
+class _InteractFn(torch.autograd.Function):
+    """AutoInt's interacting layer (csrc/interact.hip): y and the (B, H, F) row log-sum-exp are all that is kept."""
+
+    @staticmethod
+    def forward(ctx, x, w_q, w_k, w_v, w_res, num_heads):
+        B, F, D = (int(s) for s in x.shape)
+        x = x.contiguous()
+        ws = [w.contiguous() if w is not None else None for w in (w_q, w_k, w_v, w_res)]
+        scale = float(max(D // max(num_heads, 1), 1)) ** -0.5  # (a bad num_heads is refused by the entry point)
+        y = torch.empty((B, F, D), dtype=torch.float32, device=x.device)
+        lse = torch.empty((B, num_heads, F), dtype=torch.float32, device=x.device)
+        _lib.call("rh_interact_fwd", _p(x), *[_p(w) for w in ws], scale, B, F, D, num_heads, _p(y), _p(lse), _stream())
+        ctx.save_for_backward(x, y, lse, *ws[:3 if w_res is None else 4])
+        ctx.heads, ctx.scale = num_heads, scale
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, y, lse, *ws = ctx.saved_tensors
+        ws = ws + [None] * (4 - len(ws))
+        B, F, D = (int(s) for s in x.shape)
+        H, dev = ctx.heads, x.device
+        g = g.contiguous()
+        need_x, need_w = ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:5])
+        g_x = torch.empty((B, F, D), dtype=torch.float32, device=dev) if need_x else None
+        g_w = part = None
+        if need_w:
+            if B == 0:  # nothing is launched: the parameter gradients are exact zeros
+                g_w = torch.zeros((4, D, D), dtype=torch.float32, device=dev)
+            else:
+                _, nblocks = _lib.query("rh_interact_plan", B, F, D, H, out=(ctypes.c_int, ctypes.c_int))
+                part = torch.empty((nblocks, 4 * D * D), dtype=torch.float32, device=dev)
+                g_w = torch.empty((4, D, D), dtype=torch.float32, device=dev)
+        if B > 0 and (need_x or need_w):
+            _lib.call("rh_interact_bwd", _p(x), *[_p(w) for w in ws], ctx.scale, _p(y), _p(lse), _p(g), B, F, D, H, _p(g_x),
+                      _p(part), _stream())
+            if need_w:
+                _lib.call("rh_colsum", _p(part), part.shape[0], 4 * D * D, _p(g_w), _NULL, 0, _NULL, _stream())
+        return (g_x,) + tuple(g_w[i] if need_w and ctx.needs_input_grad[1 + i] and ws[i] is not None else None
+                              for i in range(4)) + (None,)
+
+
+def _interact_form(x, w_q, w_k, w_v, w_res):
+    """None, or why these are not the layer's tensors: x (B, F, D) and three or four (D, D) weights, all float32 on x's
+    device."""
+    ws = [w for w in (w_q, w_k, w_v, w_res) if w is not None]
+    if w_q is None or w_k is None or w_v is None or x.dim() != 3 or any(tuple(w.shape) != (x.shape[2],) * 2 for w in ws):
+        return f"of x {tuple(x.shape)} and weights {[tuple(w.shape) for w in ws]}: need x (B, F, D) and (D, D) weights"
+    if any(t.dtype != torch.float32 for t in [x] + ws):
+        return "runs in float32 only"
+    if any(w.device != x.device for w in ws):
+        return f"needs the weights on x's device {x.device}"
+    return None
+
+
+def interacting_layer_ok(x, w_q, w_k, w_v, w_res, num_heads):
+    """True when the HIP kernels take this layer: float32 HIP tensors on one device inside the ranges of rh_interact_* (F
+    up to RH_CIN_MAX_F, D up to RH_SA_MAX_D, D a multiple of num_heads); ``w_res`` may be None."""
+    if not x.is_cuda or _interact_form(x, w_q, w_k, w_v, w_res) is not None:
+        return False
+    F, D = int(x.shape[1]), int(x.shape[2])
+    return 1 <= F <= _lib.H.RH_CIN_MAX_F and 1 <= D <= _lib.H.RH_SA_MAX_D and num_heads >= 1 and D % num_heads == 0
+
+
+def interacting_layer(x, w_q, w_k, w_v, w_res, num_heads):
+    """``relu(concat_h softmax(Q_h K_h^T / sqrt(dh)) V_h + x w_res^T)`` for x (B, F, D) with Q, K, V = x w^T: AutoInt's
+    interacting layer as one launch each way (csrc/interact.hip).  The weights are the (D, D) nn.Linear parameters, used
+    in place; ``w_res`` None is the layer without the residual.  Nothing of size (B, H, F, F) or (B F, 4 D) is allocated;
+    the backward is deterministic (and differentiable once).  Shapes outside the kernel's ranges are refused by the entry
+    points, before any launch."""
+    require_hip(x, w_q, w_k, w_v, w_res)
+    why = _interact_form(x, w_q, w_k, w_v, w_res)
+    if why is not None:
+        raise RuntimeError(f"torch_rechub_amd: interacting_layer {why}")
+    return _InteractFn.apply(x, w_q, w_k, w_v, w_res, int(num_heads))
+
+
+# --------------------------------------------------------------------------------------------
 class _BnReluDropoutFn(torch.autograd.Function):
     """y = dropout(relu(batch_norm(h))) for one MLP hidden layer (training mode); see csrc/mlp.hip.
     ``stats`` / ``stats_ctr``: per-slab (sum, M2) of h and the dropout counter drawn by the GEMM that produced h
