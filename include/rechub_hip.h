@@ -1237,6 +1237,54 @@ int rh_sasrec_head_bwd(const float* x, const float* gamma, const float* beta, co
                        const float* g_pos, const float* g_neg, int B, int L, int D, float* g_x, float* g_pos_e, float* g_neg_e, float* part,
                        void* stream);
 
+/* ---- encoder block: what follows the attention in a post-norm transformer encoder layer (csrc/encoder.hip) -----------
+ * fp32.  M rows of width D, hidden width F; w1 (F, D), b1 (F,), w2 (D, F), b2 (D,), wo (D, D), bo (D,) as nn.Linear holds
+ * them.  attn (M, D) contiguous: the heads' output before out_proj; x (M, D) with row stride ldx >= D: the sub-layer input
+ * (the last position of every sample of a (B, L, D) tensor: ldx = L D).
+ *   y1 = x + drop_o(attn Wo^T + bo)              x1  = LN1(y1)
+ *   u  = x1 W1^T + b1  (M, F)                    a   = drop_h(leaky(u, slope)),  leaky(u) = u > 0 ? u : slope u
+ *   y2 = x1 + drop_f(a W2^T + b2)                out = LN2(y2)
+ * LayerNorm as for SASRec above (two passes, rstd = 1 / sqrt(var + eps)); stats1, stats2 (M, 2) = the rows' (mean, rstd).
+ * u and a never reach HBM: a workgroup owns a row tile and walks F in chunks, both products of a chunk on
+ * v_mfma_f32_32x32x2_f32, the (rows, D) accumulator of a W2^T in registers across the chunks.  Saved for the backward:
+ * y1, y2, stats1, stats2 -- nothing of size M F; the backward recomputes x1, u and a.
+ * Limits: 1 <= D <= RH_SASREC_MAX_D (the row tile is SASRec's), any M >= 1, F >= 1 with no cap of its own (the chunk loop
+ * needs none; (2 RH_SASREC_MAX_D + 1) F must fit an int, the row length of wpart), else RH_E_UNSUPPORTED before any launch;
+ * M = 0 returns at once.  No atomics: a backward run twice gives the same bits.
+ * Dropout as for SASRec: rh_drop_hash, kept when hash >= p 2^32, scale 1 / (1 - p), recomputed in the backward;
+ * rh_enc_block_fwd draws ONE counter value, returns it in saved_ctr (1,) and advances the device counter; p = 0 computes no
+ * hash and takes null rng / saved_ctr.  Element index (64-bit) ranges of that counter:
+ *   drop_o [0, M D): row D + c;   drop_h [M D, M D + M F): M D + row F + j;   drop_f the next M D: M D + M F + row D + c.
+ *
+ * rh_enc_block_fwd: ONE launch (the counter's advance is a one-thread launch behind it).
+ * rh_enc_block_bwd_rows: g_out (M, D) -> g_x = g_y1 and g_attn = drop_o(g_y1) Wo (M, D); emits g_f = drop_f(g_y2) and
+ *   g_o = drop_o(g_y1) (M, D): g_f feeds rh_enc_block_bwd_weights, (g_o, attn) are the operands of rh_linear_wgrad for
+ *   Wo / bo.  part (*ntiles, 5, D) = per-tile [g_gamma2 | g_beta2 | g_gamma1 | g_beta1 | g_b2], summed by rh_colsum.
+ * rh_enc_block_bwd_weights: one workgroup per (F chunk, row split) walks its split's row tiles in ascending order,
+ *   recomputes its chunk of u, a, g_a = g_f W2, g_u = g_a leaky'(u) drop_h (leaky'(0) = slope) and keeps the chunk of
+ *   g_W1 = g_u^T x1, g_b1 and g_W2 = g_f^T a in registers.  wpart (*nsplits, (2 D + 1) F) = per-split
+ *   [g_W1 (F, D) | g_W2 (D, F) | g_b1 (F,)], every element written, summed by rh_colsum.
+ * rh_enc_nsplits answers through HOST ints, like rh_sasrec_ntiles: *ntiles = the row tiles (64 rows at D <= 64, else 32),
+ *   *nsplits = the row splits of the weight kernel: chunks x splits aims at one workgroup per CU, so wpart does not grow
+ *   with M; no split is empty, the last may be short.
+ * replaces: nn.TransformerEncoderLayer.forward behind its self-attention (out_proj of nn.MultiheadAttention, dropout1,
+ *           norm1, linear1, LeakyReLU, dropout, linear2, dropout2, norm2) as torch_rechub/models/ranking/bst.py:47-48,79
+ *           builds and calls it, and its autograd, whose saved activations are three (M, F) tensors. */
+int rh_enc_nsplits(int M, int D, int F, int* ntiles, int* nsplits);
+int rh_enc_block_fwd(const float* attn, const float* x, int64_t ldx, const float* wo, const float* bo, const float* gamma1,
+                     const float* beta1, float eps1, const float* w1, const float* b1, const float* w2, const float* b2,
+                     const float* gamma2, const float* beta2, float eps2, float slope, int M, int D, int F, float p_drop,
+                     int64_t* rng, int64_t* saved_ctr, float* y1, float* y2, float* stats1, float* stats2, float* out,
+                     void* stream);
+int rh_enc_block_bwd_rows(const float* wo, const float* gamma1, const float* beta1, const float* w1, const float* b1,
+                          const float* w2, const float* gamma2, const float* y1, const float* y2, const float* stats1,
+                          const float* stats2, const float* g_out, float slope, int M, int D, int F, float p_drop,
+                          const int64_t* rng, const int64_t* saved_ctr, float* g_f, float* g_o, float* g_x, float* g_attn,
+                          float* part, void* stream);
+int rh_enc_block_bwd_weights(const float* gamma1, const float* beta1, const float* w1, const float* b1, const float* w2,
+                             const float* y1, const float* stats1, const float* g_f, float slope, int M, int D, int F,
+                             float p_drop, const int64_t* rng, const int64_t* saved_ctr, float* wpart, void* stream);
+
 /* ---- row-sharded tables (one shard per rank) -----------------------------------------------------------------------
  * Global row g of a table lives on rank g % world as local row g / world.  rh_shard_localize rewrites an index matrix
  * idx (n_rows, F) (int64 / int32, contiguous: the all-gathered indices of the global batch) for this rank's shards:

@@ -2,7 +2,8 @@
 """Train-step throughput of the secondary BASELINE.json configs on ONE GPU (eager + hipGraph):
   dcn / dcnv2 : configs[2] shape (Criteo tables, 13 dense + 26 sparse, 3 cross layers)          [C3 runs it data-parallel]
   din         : configs[3] shape (2 history fields x L=100 + 2 targets + user_id, D=16, attention MLP [256,128] Dice)
-  dien / bst  : the same tables and histories through DIEN (GRU + AUGRU recurrences, auxiliary loss) / BST (1 encoder layer)
+  dien / bst  : the same tables and histories through DIEN (GRU + AUGRU recurrences, auxiliary loss) / BST (1 encoder layer:
+                the target-only path of ops.encoder_layer); bst2: two layers, so the first runs on all B (L + 1) rows
   dssm        : configs[4] shape (100 M-item + 10 M-user tables, history L=50 mean-pooled, towers [256,128,64] prelu,
                 in-batch negatives)
   deepffm / fatdeepffm : the Criteo example's DeepFFM / FAT-DeepFFM (examples/ranking/run_criteo.py:77-80: 26 sparse fields,
@@ -58,7 +59,7 @@ def build(name, dev, B, scale):
         x = {f.name: torch.randint(0, v, (B,), device=dev, generator=g) for f, v in zip(sparse, vocabs)}
         x.update({f.name: torch.rand(B, device=dev, generator=g) for f in dense})
         trainer = CTRTrainer(model, device=str(dev), show_progress=False)
-    elif name in ("din", "dien", "bst"):
+    elif name in ("din", "dien", "bst", "bst2"):
         nu, ni, nc, L = int(200000 * scale) + 10, int(63001 * scale) + 10, 801, 100
         feats = [SparseFeature("user_id", nu, 16)]
         hist = [SequenceFeature("hist_item", ni, 16, pooling="concat", shared_with="target_item", padding_idx=0),
@@ -75,7 +76,8 @@ def build(name, dev, B, scale):
                 model = DIEN(feats, hist, neg, tgt, mlp_params={"dims": [256, 128], "dropout": 0.2})
             else:
                 from torch_rechub_amd.models.ranking import BST
-                model = BST(feats, hist, tgt, mlp_params=mlp, nhead=4, dropout=0.2, num_layers=1, max_seq_len=L + 1)
+                model = BST(feats, hist, tgt, mlp_params=mlp, nhead=4, dropout=0.2, num_layers=2 if name == "bst2" else 1,
+                            max_seq_len=L + 1)
         lens = torch.randint(1, L + 1, (B,), device=dev, generator=g)
         pad = torch.arange(L, device=dev)[None, :] >= lens[:, None]
         x = {"user_id": torch.randint(0, nu, (B,), device=dev, generator=g),

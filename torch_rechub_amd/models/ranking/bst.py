@@ -5,11 +5,15 @@ absolute positional table added, ``nn.TransformerEncoder`` under a key-padding m
 history features are padding there; the target never is), the target position's output joined with the target and
 profile embeddings for the MLP.  Attribute / checkpoint names are the reference's (``embedding``, ``pos_embedding``,
 ``transformer_layers``, ``mlp``).  Here every lookup is a HIP gather (plain features: one fused launch; histories: the
-gather + concat kernel), the encoder is the library's, the MLP the fused BatchNorm path.
+gather + concat kernel), the MLP the fused BatchNorm path.  ``transformer_layers`` holds the encoder's parameters; its
+layers run on ``ops.encoder_layer`` (in-projection, masked attention, then the fused post-norm block of csrc/encoder.hip whose
+2048-wide feed-forward hidden never reaches HBM), the last one for the target position alone.  A layer the kernels do not
+take (item_dim > 128, or one the user has changed) sends the whole encoder down the library's path.
 """
 import torch
 from torch import nn
 
+from ... import ops
 from ...basic.layers import MLP, EmbeddingLayer
 
 
@@ -56,6 +60,15 @@ class BST(nn.Module):
             raise ValueError(f"sequence length {T + 1} exceeds max_seq_len {self.max_seq_len}")
         seq = seq + self.pos_embedding.weight[:T + 1]
         key_padding = torch.cat([self._padding_steps(x), torch.zeros((B, 1), dtype=torch.bool, device=seq.device)], dim=1)
-        encoded = self.transformer_layers(seq, src_key_padding_mask=key_padding)
-        mlp_in = torch.cat([encoded[:, -1, :], target.flatten(start_dim=1), profile], dim=1)
+        layers = list(self.transformer_layers.layers)
+        if self.transformer_layers.norm is None and all(ops.encoder_layer_ok(seq, layer) for layer in layers):
+            # Only the target position's output is read below, and everything in a layer but its attention is row-wise:
+            # the last layer runs its query, out-projection, LayerNorms and feed-forward on that row alone.
+            keep = ~key_padding
+            for layer in layers[:-1]:
+                seq = ops.encoder_layer(seq, layer, keep)
+            last = ops.encoder_layer(seq, layers[-1], keep, last_only=True)
+        else:  # wider than the kernels take, or a layer the user has changed: the library's encoder
+            last = self.transformer_layers(seq, src_key_padding_mask=key_padding)[:, -1, :]
+        mlp_in = torch.cat([last, target.flatten(start_dim=1), profile], dim=1)
         return torch.sigmoid(self.mlp(mlp_in).squeeze(1))

@@ -21,6 +21,7 @@ backward scatter-adds into it and publishes it as ``weight.grad``; ``FusedDenseA
 touched rows inside its own pass.  A stock ``torch.optim`` optimizer sees an ordinary dense ``.grad``.
 """
 import ctypes
+import math
 import os
 from collections import OrderedDict
 
@@ -3133,6 +3134,168 @@ def sasrec_ffn(attn, Q, seq, out_proj_weight, out_proj_bias, ln_weight, ln_bias,
                              ln_bias.contiguous(), w1.contiguous(), b1.contiguous(), w2.contiguous(), b2.contiguous(),
                              float(eps), _drop_p(dropout_p, training))
     return out.view(B, L, D)
+
+
+# --------------------------------------------------------------------------------------------
+# The post-norm encoder block with a wide feed-forward (csrc/encoder.hip).  Like SASRec's two stages above it ends in
+# linear_wgrad, so it lives here and not in a leaf family.
+class _EncoderBlockFn(torch.autograd.Function):
+    """out = LN2(x1 + drop_f(W2 drop_h(leaky(W1 x1 + b1)) + b2)), x1 = LN1(x + drop_o(attn Wo^T + bo)); keeps y1, y2 and the
+    LayerNorms' statistics, never the (M, F) hidden: the two backward launches recompute it chunk by chunk."""
+
+    @staticmethod
+    def forward(ctx, attn, x, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2, cfg):
+        eps1, eps2, slope, p = cfg
+        M, D = (int(v) for v in attn.shape)
+        F = int(w1.shape[0])
+        dev = attn.device
+        y1, y2, out = (torch.empty((M, D), dtype=torch.float32, device=dev) for _ in range(3))
+        st1, st2 = (torch.empty((M, 2), dtype=torch.float32, device=dev) for _ in range(2))
+        rng = _dropout_rng(dev) if p > 0 else None
+        ctr = torch.empty(1, dtype=torch.int64, device=dev) if p > 0 else None
+        _lib.call("rh_enc_block_fwd", _p(attn), _p(x), int(x.stride(0)) if M > 1 else D, _p(wo), _p(bo), _p(g1), _p(be1), eps1,
+                  _p(w1), _p(b1), _p(w2), _p(b2), _p(g2), _p(be2), eps2, slope, M, D, F, p, _p(rng), _p(ctr), _p(y1), _p(y2),
+                  _p(st1), _p(st2), _p(out), _stream())
+        ctx.cfg = cfg
+        ctx.save_for_backward(attn, wo, g1, be1, w1, b1, w2, g2, y1, y2, st1, st2, rng, ctr)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        attn, wo, g1, be1, w1, b1, w2, g2, y1, y2, st1, st2, rng, ctr = ctx.saved_tensors
+        _, _, slope, p = ctx.cfg
+        M, D = (int(v) for v in attn.shape)
+        F = int(w1.shape[0])
+        dev = attn.device
+        g = g.contiguous()
+        g_f, g_o, g_x, g_attn = (torch.empty((M, D), dtype=torch.float32, device=dev) for _ in range(4))
+        g_wo = torch.empty((D, D), dtype=torch.float32, device=dev)
+        g_bo = torch.empty((D,), dtype=torch.float32, device=dev)
+        vec = torch.empty((5 * D,), dtype=torch.float32, device=dev)  # g_gamma2 | g_beta2 | g_gamma1 | g_beta1 | g_b2
+        wsum = torch.empty(((2 * D + 1) * F,), dtype=torch.float32, device=dev)  # g_W1 | g_W2 | g_b1
+        if M == 0:
+            vec.zero_(), wsum.zero_()
+        else:
+            ntiles, nsplits = _lib.query("rh_enc_nsplits", M, D, F, out=(ctypes.c_int, ctypes.c_int))
+            part = torch.empty((ntiles, 5 * D), dtype=torch.float32, device=dev)
+            wpart = torch.empty((nsplits, (2 * D + 1) * F), dtype=torch.float32, device=dev)
+            _lib.call("rh_enc_block_bwd_rows", _p(wo), _p(g1), _p(be1), _p(w1), _p(b1), _p(w2), _p(g2), _p(y1), _p(y2), _p(st1),
+                      _p(st2), _p(g), slope, M, D, F, p, _p(rng), _p(ctr), _p(g_f), _p(g_o), _p(g_x), _p(g_attn), _p(part),
+                      _stream())
+            _lib.call("rh_enc_block_bwd_weights", _p(g1), _p(be1), _p(w1), _p(b1), _p(w2), _p(y1), _p(st1), _p(g_f), slope, M,
+                      D, F, p, _p(rng), _p(ctr), _p(wpart), _stream())
+            _lib.call("rh_colsum", _p(part), ntiles, 5 * D, _p(vec), _NULL, 0, _NULL, _stream())
+            _lib.call("rh_colsum", _p(wpart), nsplits, (2 * D + 1) * F, _p(wsum), _NULL, 0, _NULL, _stream())
+        linear_wgrad(g_o, attn, out=(g_wo, g_bo))
+        g_g2, g_be2, g_g1, g_be1, g_b2 = vec.split(D)
+        g_w1, g_w2, g_b1 = wsum.split([F * D, F * D, F])
+        return (g_attn, g_x, g_wo, g_bo, g_g1, g_be1, g_w1.view(F, D), g_b1, g_w2.view(D, F), g_b2, g_g2, g_be2, None)
+
+
+def _ln_params(ln, D):
+    """(weight, bias, eps) of an nn.LayerNorm over (D,), or of a (weight, bias[, eps]) tuple."""
+    if isinstance(ln, torch.nn.LayerNorm):
+        return ln.weight, ln.bias, ln.eps
+    return ln[0], ln[1], (ln[2] if len(ln) > 2 else 1e-5)
+
+
+def encoder_block_ok(attn, x, out_proj_w, out_proj_b, ln1, w1, b1, w2, b2, ln2):
+    """Whether ops.encoder_block takes these: float32 HIP tensors, attn and x (..., D) alike, 1 <= D <= RH_SASREC_MAX_D (the
+    kernels' row tile is SASRec's), w1 (F, D) and w2 (D, F) with F >= 1, affine LayerNorms."""
+    g1, be1, _ = _ln_params(ln1, 0)
+    g2, be2, _ = _ln_params(ln2, 0)
+    tensors = (attn, x, out_proj_w, out_proj_b, g1, be1, w1, b1, w2, b2, g2, be2)
+    if any(t is None or not t.is_cuda or t.dtype != torch.float32 for t in tensors):
+        return False
+    D = int(attn.shape[-1])
+    F = int(w1.shape[0]) if w1.dim() == 2 else 0
+    return (attn.shape == x.shape and 1 <= D <= _lib.H.RH_SASREC_MAX_D and
+            1 <= F <= (2**31 - 1) // (2 * _lib.H.RH_SASREC_MAX_D + 1) and tuple(w1.shape) == (F, D) and
+            tuple(w2.shape) == (D, F) and tuple(out_proj_w.shape) == (D, D) and tuple(b1.shape) == (F,) and
+            all(tuple(v.shape) == (D,) for v in (out_proj_b, g1, be1, b2, g2, be2)))
+
+
+def encoder_block(attn, x, out_proj_w, out_proj_b, ln1, w1, b1, w2, b2, ln2, slope=0.01, dropout_p=0.0, training=True):
+    """What follows the attention in a post-norm transformer encoder layer, for attn (the heads' output before out_proj) and
+    x (the layer's input), both (..., D):  x1 = LN1(x + drop(attn Wo^T + bo)),  out = LN2(x1 + drop(W2 drop(leaky(W1 x1 +
+    b1)) + b2)).  ln1 / ln2: nn.LayerNorm modules or (weight, bias[, eps]).  The (rows, F) hidden is never written: one
+    launch forward, two backward that recompute it.  A 2-D x may have any row stride (the last position of every sample of
+    a (B, L, D) tensor is read in place).  One dropout probability for the three sites; a missing kernel is an error."""
+    require_hip(attn, x, out_proj_w, out_proj_b, w1, b1, w2, b2)
+    if not encoder_block_ok(attn, x, out_proj_w, out_proj_b, ln1, w1, b1, w2, b2, ln2):
+        from .models.matching._listwise import no_kernel
+        raise no_kernel(f"the encoder block of attn {tuple(attn.shape)}, x {tuple(x.shape)}, w1 {tuple(w1.shape)}, w2 "
+                        f"{tuple(w2.shape)} (float32, 1 <= D <= {_lib.H.RH_SASREC_MAX_D}, w1 (F, D), w2 (D, F))")
+    D = int(attn.shape[-1])
+    g1, be1, eps1 = _ln_params(ln1, D)
+    g2, be2, eps2 = _ln_params(ln2, D)
+    if not (x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= D):
+        x = x.reshape(-1, D).contiguous()
+    cfg = (float(eps1), float(eps2), float(slope), _drop_p(dropout_p, training))
+    out = _EncoderBlockFn.apply(attn.reshape(-1, D).contiguous(), x, out_proj_w.contiguous(), out_proj_b.contiguous(),
+                                g1.contiguous(), be1.contiguous(), w1.contiguous(), b1.contiguous(), w2.contiguous(),
+                                b2.contiguous(), g2.contiguous(), be2.contiguous(), cfg)
+    return out if out.shape == attn.shape else out.view(attn.shape)
+
+
+def encoder_layer_ok(x, layer):
+    """Whether ops.encoder_layer runs ``layer`` (an nn.TransformerEncoderLayer) on x (B, L, D): post-norm, batch_first, a
+    LeakyReLU feed-forward, a fused in-projection with bias, one dropout probability, shapes the kernels take."""
+    nn = torch.nn
+    att = getattr(layer, "self_attn", None)
+    if not (isinstance(layer, nn.TransformerEncoderLayer) and isinstance(att, nn.MultiheadAttention) and x.dim() == 3):
+        return False
+    if (layer.norm_first or not att.batch_first or not isinstance(layer.activation, nn.LeakyReLU) or
+            att.in_proj_weight is None or att.in_proj_bias is None or att.bias_k is not None or att.add_zero_attn or
+            not isinstance(layer.norm1, nn.LayerNorm) or not isinstance(layer.norm2, nn.LayerNorm)):
+        return False
+    if len({float(att.dropout), layer.dropout.p, layer.dropout1.p, layer.dropout2.p}) != 1 or not 0.0 <= layer.dropout.p < 1.0:
+        return False
+    B, L, D = (int(v) for v in x.shape)
+    if not (1 <= L <= _lib.H.RH_ATTN_MAX_L and D == att.embed_dim and D // att.num_heads <= _lib.H.RH_ATTN_MAX_DH and
+            att.in_proj_weight.is_cuda and att.in_proj_weight.dtype == torch.float32 and att.in_proj_bias.is_cuda):
+        return False
+    return encoder_block_ok(x, x, att.out_proj.weight, att.out_proj.bias, layer.norm1, layer.linear1.weight,
+                            layer.linear1.bias, layer.linear2.weight, layer.linear2.bias, layer.norm2)
+
+
+def encoder_layer(x, layer, key_mask=None, last_only=False):
+    """One post-norm nn.TransformerEncoderLayer's forward on x (B, L, D) with the module's parameters: the in-projection
+    through ops.linear, ops.t5_attention on the Q, K, V column blocks of that product (read in place; 1 / sqrt(dh) is folded
+    into the Q rows of the projection weight and bias, as torch scales q before q . k), ops.encoder_block for the rest.
+    ``key_mask`` (B, L): non-zero = attend.  ``last_only``: the layer's output at the last position alone, (B, D) -- only that
+    row gets a query, an out-projection, LayerNorms and a feed-forward; every row is still a key and a value.
+
+    A row whose keys are all masked is where the two attention paths part: torch's -inf mask gives nan, t5_attention's
+    largest-negative-finite mask gives equal weights.  BST never masks the target's key, so it cannot get there."""
+    if not encoder_layer_ok(x, layer):
+        from .models.matching._listwise import no_kernel
+        raise no_kernel(f"this encoder layer on x {tuple(x.shape)} (post-norm, batch_first, LeakyReLU, fused in-projection, "
+                        "one dropout probability)")
+    att = layer.self_attn
+    B, L, D = (int(v) for v in x.shape)
+    H = att.num_heads
+    x = x.contiguous()
+    rows = x.view(B * L, D)
+    scale = torch.ones((3 * D,), dtype=torch.float32, device=x.device)
+    scale[:D] = 1.0 / math.sqrt(D // H)
+    w = att.in_proj_weight * scale[:, None]
+    b = att.in_proj_bias * scale
+    p, training = layer.dropout.p, layer.training
+    if last_only:
+        last = x[:, -1]  # (B, D), rows L D apart
+        q = linear(last, w[:D], b[:D]).view(B, 1, D)
+        kv = linear(rows, w[D:], b[D:]).view(B, L, 2 * D)
+        attn = t5_attention(q, kv[:, :, :D], kv[:, :, D:], H, key_mask=key_mask, dropout_p=p, training=training)
+        attn, res = attn.view(B, D), last
+    else:
+        qkv = linear(rows, w, b).view(B, L, 3 * D)
+        attn = t5_attention(qkv[:, :, :D], qkv[:, :, D:2 * D], qkv[:, :, 2 * D:], H, key_mask=key_mask, dropout_p=p,
+                            training=training)
+        res = x
+    return encoder_block(attn, res, att.out_proj.weight, att.out_proj.bias, layer.norm1, layer.linear1.weight,
+                         layer.linear1.bias, layer.linear2.weight, layer.linear2.bias, layer.norm2,
+                         slope=layer.activation.negative_slope, dropout_p=p, training=training)
 
 
 # --------------------------------------------------------------------------------------------
