@@ -1466,6 +1466,39 @@ int rh_interact_bwd(const float* x, const float* w_q, const float* w_k, const fl
                     const float* y, const float* lse, const float* g_y, int B, int F, int D, int H, float* g_x, float* part,
                     void* stream);
 
+/* FiBiNET's bilinear interaction (csrc/bilinear.hip): out[b, p, :] = (W x_i) * x_j for the P = F (F - 1) / 2 field pairs
+ * p = (i, j), i < j, in itertools.combinations order, and with a gate the same on the gated fields a_f x_f, computed as
+ * a_i a_j times the raw value.  fp32, v_mfma_f32_32x32x2_f32 over 32-wide blocks of the flat column c = j D + d.
+ * x (B, F, D): sample stride x_stride >= F D, the (F, D) block contiguous.  w (NW, D, D) = the stacked nn.Linear weights
+ * w[n][o][k]; kind 0 "field_all" (NW = 1), 1 "field_each" (NW = F, the left field's), 2 "field_interaction" (NW = P).
+ * gate (B, F) contiguous or null.  out, g_out: (B, P, D) without a gate, (B, 2 P, D) = [raw | gated] with one, contiguous.
+ * rh_bilinear_fwd: out.  Nothing is kept for backward.
+ * rh_bilinear_bwd: recomputes U_i = x_i W^T per left field -> g_x (B, F, D) contiguous and g_gate (B, F); either may be
+ *   null (not computed), not both; g_gate needs a gate.  workspace: *bwd_floats of rh_bilinear_plan = S B (F D + F)
+ *   floats, S = *bwd_slices = ceil(F D / 128) <= 8: per-slice partials, every element read was written, added in slice
+ *   order by a second launch.
+ * rh_bilinear_wgrad: part (*wgrad_splits, NW D D) = per-row-split sums of g_w, every element written (g_w = rh_colsum
+ *   of it).  *wgrad_floats = *wgrad_splits NW D D <= (1024 + NW) D D floats; *wgrad_splits <= 256, each split
+ *   *wgrad_tiles 64-row tiles (the last one fewer).
+ * rh_bilinear_plan answers through HOST pointers; *fwd_units = 32-row tiles x left-field groups (<= 8 groups of about
+ *   equal pair count while the tiles alone are fewer than 512), *fwd_grid = min(*fwd_units, 1024) persistent workgroups.
+ * No atomics: two runs give the same bits.  B >= 0, 2 <= F <= RH_CIN_MAX_F, 1 <= D <= RH_SA_MAX_D,
+ * F D <= RH_TWOTOWER_MAX_D (the width of a sample's flattened row), else RH_E_UNSUPPORTED; kind outside 0 .. 2 or
+ * x_stride < F D is RH_E_BADARG; all before any launch.  The limits are the existing macros of the same quantities: this
+ * family defines none.  B = 0 returns at once.  LDS: forward 4 (32 (F D | 1) + 32 (F | 1)) bytes (139520 at the limits:
+ * the x tile always fits), backward 4 (192 (D | 1) + 8256) bytes plus 4 (128 (F | 1) + 8256) with a gate (124672 at
+ * D = 64, F = 16), wgrad 16384.
+ * replaces: torch_rechub/basic/layers.py:557-565 (BiLinearInteractionLayer.forward), called twice and concatenated by
+ *           FiBiNet.forward (models/ranking/fibinet.py), and its autograd. */
+int rh_bilinear_plan(int B, int F, int D, int kind, int* fwd_units, int* fwd_grid, int* bwd_slices, int* wgrad_splits,
+                     int* wgrad_tiles, int64_t* bwd_floats, int64_t* wgrad_floats);
+int rh_bilinear_fwd(const float* x, int64_t x_stride, const float* w, const float* gate, int B, int F, int D, int kind,
+                    float* out, void* stream);
+int rh_bilinear_bwd(const float* x, int64_t x_stride, const float* w, const float* gate, const float* g_out, int B, int F,
+                    int D, int kind, float* g_x, float* g_gate, float* workspace, void* stream);
+int rh_bilinear_wgrad(const float* x, int64_t x_stride, const float* gate, const float* g_out, int B, int F, int D, int kind,
+                      float* part, void* stream);
+
 /* ---- evaluation metrics (csrc/metric.hip) ---------------------------------------------------------------------------
  * Exact AUC / GAUC.  pred: n float32 values with element stride pred_stride; label: n contiguous values of label_dtype
  * (0 float32, 1 float64, 2 int64, 3 uint8 / bool), 1 = positive, 0 = negative; g: n dense group ids in [0, G) or null

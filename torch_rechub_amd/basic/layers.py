@@ -707,7 +707,10 @@ class SENETLayer(nn.Module):
 class BiLinearInteractionLayer(nn.Module):
     """(W v_i) * v_j for every field pair i < j (reference layers.py:532-565); W shared ("field_all"), one per left
     field ("field_each") or one per pair ("field_interaction").  Same parameters as the reference (``bilinear_layer`` is a
-    Linear or a ModuleList of Linear(D, D, bias=False)); evaluated as one batched product over the pairs."""
+    Linear or a ModuleList of Linear(D, D, bias=False)).  ``forward(x, gate)`` with a (B, F) gate returns the pairs of x
+    followed by the pairs of ``gate[..., None] * x``: (B, 2 P, D).  float32 HIP tensors inside the kernel's ranges
+    (``ops.bilinear_interaction_ok``) run on the fused kernels of csrc/bilinear.hip; CPU tensors and other shapes keep
+    the torch formulation (``forward_torch``): one batched product over the pairs."""
 
     def __init__(self, input_dim, num_fields, bilinear_type="field_interaction"):
         super().__init__()
@@ -724,7 +727,21 @@ class BiLinearInteractionLayer(nn.Module):
         else:
             raise NotImplementedError()
 
-    def forward(self, x):
+    def stacked_weight(self):
+        """(1 | F | P, D_out, D_in): the Linear weights in the order of their index."""
+        if self.bilinear_type == "field_all":
+            return self.bilinear_layer.weight.unsqueeze(0)
+        return torch.stack([lin.weight for lin in self.bilinear_layer])
+
+    def forward(self, x, gate=None):
+        w = self.stacked_weight()
+        if ops.bilinear_interaction_ok(x, w, self.bilinear_type, gate):
+            return ops.bilinear_interaction(x, w, self.bilinear_type, gate)
+        return self.forward_torch(x, gate)
+
+    def forward_torch(self, x, gate=None):
+        if gate is not None:
+            return torch.cat([self.forward_torch(x), self.forward_torch(x * gate.unsqueeze(-1))], dim=1)
         left, right = x[:, self._left], x[:, self._right]  # (B, P, D)
         if self.bilinear_type == "field_all":
             return self.bilinear_layer(left) * right

@@ -3,7 +3,8 @@
 Reference forward: gather (B, F, D) -> SENETLayer -> BiLinearInteractionLayer on the raw and on the gated embeddings
 -> concat -> MLP -> sigmoid.  Same constructor, attribute names and state_dict keys (``senet_layer.mlp.{0,2}.weight``,
 ``bilinear_interaction.bilinear_layer[.k].weight``, ``mlp.mlp.*``); the gather is the fused HIP launch, the MLP the
-fused BatchNorm / head path, and the F (F - 1) / 2 per-pair Linear calls of the reference run as ONE batched product.
+fused BatchNorm / head path, and the F (F - 1) / 2 per-pair Linear calls of the reference, on the raw and on the gated
+fields, run as ONE fused kernel call (csrc/bilinear.hip) that takes the SENET gate as a (B, F) operand.
 """
 import torch
 
@@ -26,6 +27,6 @@ class FiBiNet(torch.nn.Module):
 
     def forward(self, x):
         embed_x = self.embedding(x, self.features)
-        embed_senet = self.senet_layer(embed_x)
-        both = torch.cat([self.bilinear_interaction(embed_x), self.bilinear_interaction(embed_senet)], dim=1)
+        gate = self.senet_layer.mlp(embed_x.mean(dim=-1))  # (B, F): SENETLayer.forward is x * gate[..., None]
+        both = self.bilinear_interaction(embed_x, gate)  # [raw pairs | pairs of the gated fields], one call
         return self.mlp.sigmoid_head(both.flatten(start_dim=1))

@@ -1001,6 +1001,103 @@ def interacting_layer(x, w_q, w_k, w_v, w_res, num_heads):
 
 
 # --------------------------------------------------------------------------------------------
+BILINEAR_KINDS = ("field_all", "field_each", "field_interaction")
+_BILINEAR_PLAN = (ctypes.c_int,) * 5 + (ctypes.c_int64,) * 2
+
+
+def _x_rows(x):
+    """x (B, F, D) as the kernels read it: the (F, D) block contiguous, any sample stride (a view is read in place)."""
+    B, F, D = x.shape
+    if x.stride(2) == 1 and x.stride(1) == D and (B <= 1 or x.stride(0) >= F * D):
+        return x, (x.stride(0) if B > 1 else F * D)
+    return x.contiguous(), F * D
+
+
+class _BilinearFn(torch.autograd.Function):
+    """FiBiNET's bilinear interaction (csrc/bilinear.hip): x, w and the gate are all that is kept."""
+
+    @staticmethod
+    def forward(ctx, x, w, gate, kind):
+        B, F, D = (int(s) for s in x.shape)
+        x, xs = _x_rows(x)
+        w = w.contiguous()
+        gate = gate.contiguous() if gate is not None else None
+        P = F * (F - 1) // 2
+        out = torch.empty((B, P if gate is None else 2 * P, D), dtype=torch.float32, device=x.device)
+        _lib.call("rh_bilinear_fwd", _p(x), xs, _p(w), _p(gate), B, F, D, kind, _p(out), _stream())
+        ctx.save_for_backward(x, w, gate)
+        ctx.kind, ctx.xs = kind, xs
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, w, gate = ctx.saved_tensors
+        B, F, D = (int(s) for s in x.shape)
+        kind, xs, dev = ctx.kind, ctx.xs, x.device
+        need_x, need_w, need_gate = ctx.needs_input_grad[:3]
+        need_gate = need_gate and gate is not None
+        g = g.contiguous()
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        g_x = new(B, F, D) if need_x else None
+        g_gate = new(B, F) if need_gate else None
+        g_w = (torch.zeros if B == 0 else torch.empty)(tuple(w.shape), dtype=torch.float32, device=dev) if need_w else None
+        if B > 0 and (need_x or need_w or need_gate):
+            plan = _lib.query("rh_bilinear_plan", B, F, D, kind, out=_BILINEAR_PLAN)
+            if need_x or need_gate:
+                _lib.call("rh_bilinear_bwd", _p(x), xs, _p(w), _p(gate), _p(g), B, F, D, kind, _p(g_x), _p(g_gate),
+                          _p(new(plan[5])), _stream())
+            if need_w:
+                part = new(plan[3], w.numel())
+                _lib.call("rh_bilinear_wgrad", _p(x), xs, _p(gate), _p(g), B, F, D, kind, _p(part), _stream())
+                _lib.call("rh_colsum", _p(part), plan[3], w.numel(), _p(g_w), _NULL, 0, _NULL, _stream())
+        return g_x, g_w, g_gate, None
+
+
+def _bilinear_form(x, w, kind, gate):
+    """None, or why these are not the layer's tensors: x (B, F, D), w (NW, D, D) with NW = 1, F or F (F - 1) / 2 by kind,
+    gate None or (B, F), all float32 on x's device."""
+    if kind not in BILINEAR_KINDS:
+        return f"kind {kind!r}: need one of {BILINEAR_KINDS}"
+    if x.dim() != 3:
+        return f"of x {tuple(x.shape)}: need (B, F, D)"
+    B, F, D = (int(s) for s in x.shape)
+    nw = (1, F, F * (F - 1) // 2)[BILINEAR_KINDS.index(kind)]
+    if tuple(w.shape) != (nw, D, D) or (gate is not None and tuple(gate.shape) != (B, F)):
+        return (f"of x {tuple(x.shape)}, w {tuple(w.shape)} and gate {None if gate is None else tuple(gate.shape)}: need w "
+                f"({nw}, {D}, {D}) and a gate (B, F)")
+    ts = [x, w] + ([gate] if gate is not None else [])
+    if any(t.dtype != torch.float32 for t in ts):
+        return "runs in float32 only"
+    if any(t.device != x.device for t in ts):
+        return f"needs w and the gate on x's device {x.device}"
+    return None
+
+
+def bilinear_interaction_ok(x, w, kind, gate=None):
+    """True when the HIP kernels take this layer: float32 HIP tensors on one device inside the ranges of rh_bilinear_* (2 <= F
+    <= RH_CIN_MAX_F, D <= RH_SA_MAX_D, F D <= RH_TWOTOWER_MAX_D)."""
+    if not x.is_cuda or _bilinear_form(x, w, kind, gate) is not None:
+        return False
+    F, D = int(x.shape[1]), int(x.shape[2])
+    return 2 <= F <= _lib.H.RH_CIN_MAX_F and 1 <= D <= _lib.H.RH_SA_MAX_D and F * D <= _lib.H.RH_TWOTOWER_MAX_D
+
+
+def bilinear_interaction(x, w, kind, gate=None):
+    """``(W x_i) * x_j`` for every field pair i < j of x (B, F, D), in ``itertools.combinations`` order: (B, P, D).  ``w``
+    (NW, D, D) are the stacked nn.Linear weights of ``kind`` "field_all" (NW = 1), "field_each" (F) or "field_interaction"
+    (P).  With ``gate`` (B, F) the result is (B, 2 P, D): the raw pairs, then the pairs of the gated fields
+    ``gate[..., None] * x`` -- the raw value times gate_i gate_j.  Nothing else of that size is allocated and nothing is
+    kept for backward, which recomputes W x_i and is deterministic (and differentiable once).  Shapes outside the kernel's
+    ranges are refused by the entry points, before any launch."""
+    require_hip(x, w, gate)
+    why = _bilinear_form(x, w, kind, gate)
+    if why is not None:
+        raise RuntimeError(f"torch_rechub_amd: bilinear_interaction {why}")
+    return _BilinearFn.apply(x, w, gate, BILINEAR_KINDS.index(kind))
+
+
+# --------------------------------------------------------------------------------------------
 class _BnReluDropoutFn(torch.autograd.Function):
     """y = dropout(relu(batch_norm(h))) for one MLP hidden layer (training mode); see csrc/mlp.hip.
     ``stats`` / ``stats_ctr``: per-slab (sum, M2) of h and the dropout counter drawn by the GEMM that produced h
