@@ -1499,6 +1499,61 @@ int rh_bilinear_bwd(const float* x, int64_t x_stride, const float* w, const floa
 int rh_bilinear_wgrad(const float* x, int64_t x_stride, const float* gate, const float* g_out, int B, int F, int D, int kind,
                       float* part, void* stream);
 
+/* Expert banks of MMOE and PLE's CGC levels (csrc/experts.hip): G groups -- expert stacks of [Linear, BatchNorm1d, ReLU,
+ * Dropout] and softmax gates (Linear, BatchNorm1d, Softmax) -- over the same M rows.  A bank layer is ONE wide (M, C) buffer,
+ * C = sum N_g, group g in the column block that starts at col0_g = N_0 + ... + N_{g-1}; every entry point is one launch
+ * for all groups (rh_experts_bn_bwd: two).  fp32, v_mfma_f32_32x32x2_f32 in the two GEMMs, no atomics: two runs give the
+ * same bits.  Arrays of G (S, n_out) entries are HOST arrays; the descriptors travel by value in the kernel arguments.
+ * rh_experts_fwd: z[:, block g] = x_g W_g^T + b_g; x_g (M, K_g) with row stride ldx_g, w_g (N_g, K_g) contiguous, bias_g
+ *   (N_g,) or null.  Consecutive groups with the same (x, ldx, K) share 32-wide column tiles.  stats (ceil(M / R), 2, C),
+ *   R = rh_gemm_chain_stats_rows(M): per slab and wide column the sum and M2 about the slab mean, as rh_linear_fwd's.
+ * rh_experts_bn_fwd: training: Chan's combination of the slabs in slab order -> stat (5, C) = mean, rstd, gamma, beta, kind;
+ *   running_mean / running_var of every group updated as nn.BatchNorm1d does (biased batch variance for the
+ *   normalisation, unbiased into running_var), *batches[g] += 1 where not null, and the layer's dropout counter drawn:
+ *   saved_ctr[0] = rng[1]++.  Eval: stat from the running statistics, nothing updated.  kind[g]: 1 expert, 0 gate.
+ * rh_experts_act_fwd: a = dropout(relu(bn(z))) over the wide buffer (0 in gate columns); an element's dropout index is its
+ *   position r C + c in the wide buffer.
+ * rh_experts_mix_fwd: out_o (M, H) contiguous = sum_e softmax(bn(zg[:, gate_col_o : + n_sel_o]))[e] *
+ *   dropout(relu(bn(ze[:, sel_col[o * 32 + e] : + H]))); zg / statg (row width Cg): the layer that holds the gates, ze / state
+ *   (Ce): the experts' last layer (the same buffer for a one-layer bank).  sel_col: n_out rows of 32 ints.
+ * rh_experts_mix_bwd: from g_out_o, recomputing activations and softmax: the gradient w.r.t. every BatchNorm output -- ge in
+ *   the n_exp expert blocks exp_col (summed over the outputs in output order, ReLU and mask applied), gg in the gate blocks
+ *   (softmax backward) -- and partg / parte (ceil(M / 16), 2, C): per 16-row slab (sum g, sum g xhat).
+ * rh_experts_act_bwd: hidden layer: g (the dgrad's output) *= mask, ReLU, in place, expert columns only, + its slab sums.
+ * rh_experts_bn_bwd: dgb (2, C) = (dgamma, dbeta) = the slab sums added in slab order; g -> the gradient w.r.t. z, in place.
+ * rh_experts_dgrad: stream s: gx_s (M, K) row stride ldgx_s = sum over the groups g_begin_s <= g < g_end_s (all of the same
+ *   K) of gz[:, block g] W_g, the sum carried in the accumulator in group order.  gz (M, C) contiguous.
+ * rh_experts_limits / rh_experts_supported / rh_experts_blocks answer through HOST pointers: the limits (groups per launch
+ *   32, K_g and N_g and H 1024, experts per gate 32, outputs 8 -- held once, in experts.hip), whether a bank is inside them,
+ *   and the capped grids (row tiles of the GEMMs, 16-row chunks of the other passes; more rows: further trips).
+ * Outside the limits: RH_E_UNSUPPORTED before any launch; M = 0 returns at once.
+ * replaces: the expert / gate loops, torch.stack and gate products of torch_rechub/models/multi_task/mmoe.py:47-58 and
+ *           ple.py:94-116, and their autograd. */
+int rh_experts_limits(int* max_groups, int* max_width, int* max_sel, int* max_out);
+int rh_experts_supported(int G, const int* K, const int* N, int n_out, int max_sel, int H, int* ok);
+int rh_experts_blocks(int M, int* gemm_row_blocks, int* gemm_rows, int* chunk_blocks, int* chunk_rows);
+int rh_experts_fwd(int G, const float* const* x, const int64_t* ldx, const float* const* w, const float* const* bias,
+                   const int* K, const int* N, int M, float* z, float* stats, void* stream);
+int rh_experts_dgrad(int S, float* const* gx, const int64_t* ldgx, const int* g_begin, const int* g_end, int G,
+                     const float* const* w, const int* K, const int* N, const float* gz, int M, void* stream);
+int rh_experts_bn_fwd(int G, const int* N, const int* kind, const float* const* gamma, const float* const* beta,
+                      float* const* running_mean, float* const* running_var, int64_t* const* batches, const float* momentum,
+                      const float* eps, int M, const float* stats, int training, int64_t* rng, int64_t* saved_ctr, float* stat,
+                      void* stream);
+int rh_experts_act_fwd(const float* z, const float* stat, int M, int C, float p_drop, const int64_t* rng, const int64_t* ctr,
+                       float* a, void* stream);
+int rh_experts_mix_fwd(int n_out, const int* gate_col, const int* n_sel, const int* sel_col, int H, const float* zg,
+                       const float* statg, int Cg, const float* ze, const float* state, int Ce, int M, float p_drop,
+                       const int64_t* rng, const int64_t* ctr, float* const* out, void* stream);
+int rh_experts_mix_bwd(int n_out, const int* gate_col, const int* n_sel, const int* sel_col, int H, int n_exp,
+                       const int* exp_col, const float* zg, const float* statg, int Cg, const float* ze, const float* state,
+                       int Ce, int M, float p_drop, const int64_t* rng, const int64_t* ctr, float* const* g_out, float* gg,
+                       float* partg, float* ge, float* parte, void* stream);
+int rh_experts_act_bwd(const float* z, const float* stat, int M, int C, float p_drop, const int64_t* rng, const int64_t* ctr,
+                       float* g, float* partial, void* stream);
+int rh_experts_bn_bwd(const float* z, const float* stat, int M, int C, const float* partial, float* g, float* dgb,
+                      void* stream);
+
 /* ---- evaluation metrics (csrc/metric.hip) ---------------------------------------------------------------------------
  * Exact AUC / GAUC.  pred: n float32 values with element stride pred_stride; label: n contiguous values of label_dtype
  * (0 float32, 1 float64, 2 int64, 3 uint8 / bool), 1 = positive, 0 = negative; g: n dense group ids in [0, G) or null

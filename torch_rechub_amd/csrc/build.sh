@@ -7,7 +7,7 @@ INC=../../include
 FLAGS="--offload-arch=gfx950 -mcode-object-version=5 -munsafe-fp-atomics -O3 -std=c++17 -fPIC -I$INC -I. -Wall -Wno-unused-function"
 mkdir -p _build
 pids=()
-for src in api.cpp embed.hip cross.hip optim.hip data.hip match.hip fm.hip seqpool.hip mlp.hip din.hip dinmlp.hip crossmix.hip moe.hip linear.hip gemm.hip shard.hip augru.hip ffm.hip interest.hip sine.hip sasrec.hip rq.hip hstu.hip stream_ce.hip session.hip hllm.hip topk.hip ivf.hip twotower.hip t5attn.hip cin.hip metric.hip beam.hip interact.hip encoder.hip bilinear.hip; do
+for src in api.cpp embed.hip cross.hip optim.hip data.hip match.hip fm.hip seqpool.hip mlp.hip din.hip dinmlp.hip crossmix.hip moe.hip linear.hip gemm.hip shard.hip augru.hip ffm.hip interest.hip sine.hip sasrec.hip rq.hip hstu.hip stream_ce.hip session.hip hllm.hip topk.hip ivf.hip twotower.hip t5attn.hip cin.hip metric.hip beam.hip interact.hip encoder.hip bilinear.hip experts.hip; do
   [ -f "$src" ] || continue
   obj="_build/${src%.*}.o"
   stale=0
@@ -20,8 +20,8 @@ for src in api.cpp embed.hip cross.hip optim.hip data.hip match.hip fm.hip seqpo
   # kernel was written, not the cure of an observed failure: the kernel was never run built otherwise, and neither build's
   # ISA holds a v_pk_* instruction (272 MFMAs either way; only register allocation differs).  The host pass
   # prints "not a recognized feature" for it.  The older files, whose v_pk_*_f32 are measured and tested, keep the plain flags.
-  # encoder.hip and bilinear.hip, written after it, are built the same way for the same reason.
-  [ "$src" = interact.hip ] || [ "$src" = encoder.hip ] || [ "$src" = bilinear.hip ] && extra="-Xclang -target-feature -Xclang -packed-fp32-ops"
+  # encoder.hip, bilinear.hip and experts.hip, written after it, are built the same way for the same reason.
+  [ "$src" = interact.hip ] || [ "$src" = encoder.hip ] || [ "$src" = bilinear.hip ] || [ "$src" = experts.hip ] && extra="-Xclang -target-feature -Xclang -packed-fp32-ops"
   if [ $stale = 1 ]; then
     ( $HIPCC $FLAGS $extra -x hip -c "$src" -o "$obj" ) &
     pids+=($!)

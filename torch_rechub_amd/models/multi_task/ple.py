@@ -7,6 +7,7 @@ gates_specific, gate_shared}``, ``towers``, ``predict_layers``) are the referenc
 import torch
 from torch import nn
 
+from ... import ops
 from ...basic.layers import MLP, EmbeddingLayer
 from ._common import gate_mix, run_heads, softmax_gate, task_heads
 
@@ -50,8 +51,19 @@ class CGC(nn.Module):
             self.gate_shared = softmax_gate(width, self.n_expert_all)
 
     def forward(self, x_list):
-        k = self.n_expert_specific
-        own = [self.experts_specific[t * k + e](x_list[t]) for t in range(self.n_task) for e in range(k)]
+        k, T, n_own = self.n_expert_specific, self.n_task, self.n_task * self.n_expert_specific
+        shared_ix = list(range(n_own, self.n_expert_all))
+        gates, gate_stream_of = list(self.gates_specific), list(range(T))
+        selections = [list(range(t * k, (t + 1) * k)) + shared_ix for t in range(T)]
+        if self.cur_level < self.n_level:
+            gates, gate_stream_of = gates + [self.gate_shared], gate_stream_of + [T]
+            selections = selections + [list(range(self.n_expert_all))]
+        bank = (list(x_list), list(self.experts_specific) + list(self.experts_shared),
+                [t for t in range(T) for _ in range(k)] + [T] * self.n_expert_shared, gates, gate_stream_of, selections)
+        if ops.expert_bank_ok(*bank):
+            # the level's experts and gates as groups of ONE grouped GEMM per layer, its mixtures as one launch
+            return ops.expert_bank(*bank)
+        own =[self.experts_specific[t * k + e](x_list[t]) for t in range(self.n_task) for e in range(k)]
         shared = [expert(x_list[-1]) for expert in self.experts_shared]
         outs = []
         for t, gate in enumerate(self.gates_specific):

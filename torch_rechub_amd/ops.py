@@ -3396,6 +3396,340 @@ def encoder_layer(x, layer, key_mask=None, last_only=False):
 
 
 # --------------------------------------------------------------------------------------------
+# Expert banks of the multi-task models: MMOE's and CGC's expert MLPs, softmax gates and gated mixtures (csrc/experts.hip)
+_SEL_STRIDE = 32  # row length of the sel_col table of rh_experts_mix_* (its limit on experts per gate)
+
+
+def _host_array(ctype, values):
+    """(c_void_p to a host array of ``ctype``, the array to keep alive)."""
+    a = (ctype * len(values))(*values)
+    return ctypes.cast(a, ctypes.c_void_p), a
+
+
+def _host_ptrs(tensors):
+    return _host_array(ctypes.c_void_p, [0 if t is None else t.data_ptr() for t in tensors])
+
+
+def expert_bank_limits():
+    """(groups per launch, K_g / N_g / H, experts per gate, outputs per bank) of rh_experts_*."""
+    return _lib.query("rh_experts_limits", out=(ctypes.c_int,) * 4)
+
+
+def _expert_blocks(mlp):
+    """[(Linear, BatchNorm1d, Dropout)] of an expert MLP that is nothing but [Linear, BatchNorm1d, ReLU, Dropout] groups."""
+    mods = list(getattr(mlp, "mlp", ()))
+    if not mods or len(mods) % 4:
+        return None
+    out = []
+    for i in range(0, len(mods), 4):
+        lin, bn, act, drop = mods[i:i + 4]
+        if not (type(lin) is torch.nn.Linear and type(bn) is torch.nn.BatchNorm1d and type(act) is torch.nn.ReLU and type(drop) is torch.nn.Dropout):
+            return None
+        out.append((lin, bn, drop))
+    return out
+
+
+def _gate_block(mlp):
+    """(Linear, BatchNorm1d) of a gate spelled Linear -> BatchNorm1d -> Softmax(dim=1) -> Dropout(0)."""
+    mods = list(getattr(mlp, "mlp", ()))
+    if len(mods) != 4:
+        return None
+    lin, bn, act, drop = mods
+    if not (type(lin) is torch.nn.Linear and type(bn) is torch.nn.BatchNorm1d and type(act) is torch.nn.Softmax and act.dim == 1 and
+            type(drop) is torch.nn.Dropout and (drop.p == 0 or not drop.training)):
+        return None
+    return lin, bn
+
+
+def _bank_bn_ok(bn):
+    return bn.affine and bn.track_running_stats and bn.momentum is not None and bn.weight.dtype == torch.float32
+
+
+class _BankPlan(object):
+    """The bank as the kernels see it.  Groups are ordered by input stream (a stream's experts, then its gates), so that the
+    groups of a stream are consecutive: they share forward column tiles and their input gradients are one product."""
+
+    def __init__(self, streams, experts, stream_of, gates, gate_stream_of, selections):
+        # the same rows given as several streams (PLE's first level) are one stream
+        uniq, self.stream_ix = [], []
+        for s in streams:
+            key = (s.data_ptr(), tuple(s.shape), tuple(s.stride()))
+            for i, u in enumerate(uniq):
+                if u[0] == key:
+                    self.stream_ix.append(i)
+                    break
+            else:
+                self.stream_ix.append(len(uniq))
+                uniq.append((key, s))
+        self.streams = [u[1] for u in uniq]
+        blocks = [_expert_blocks(e) for e in experts]
+        gblocks = [_gate_block(g) for g in gates]
+        self.depth = len(blocks[0])
+        order = []  # layer 0: ("e", i) / ("g", t)
+        for s in range(len(self.streams)):
+            order += [("e", i) for i in range(len(experts)) if self.stream_ix[stream_of[i]] == s]
+            order += [("g", t) for t in range(len(gates)) if self.stream_ix[gate_stream_of[t]] == s]
+        self.layers = []  # per layer: list of (Linear, BatchNorm1d, kind, source)
+        for l in range(self.depth):
+            groups = []
+            for what, i in order:
+                if what == "e":
+                    groups.append((blocks[i][l][0], blocks[i][l][1], 1, i))
+                elif l == 0:
+                    groups.append((gblocks[i][0], gblocks[i][1], 0, i))
+            self.layers.append(groups)
+        self.expert_ix = [i for what, i in order if what == "e"]  # expert order inside every layer
+        self.p_drop = [float(blocks[0][l][2].p) if blocks[0][l][2].training else 0.0 for l in range(self.depth)]
+        self.training = bool(blocks[0][0][1].training)
+        self.col0 = []
+        for groups in self.layers:
+            c, cols = 0, []
+            for lin, _, _, _ in groups:
+                cols.append(c)
+                c += lin.out_features
+            self.col0.append(cols + [c])
+        self.expert_col = []  # per layer: expert i -> first column
+        for l, groups in enumerate(self.layers):
+            self.expert_col.append({src: self.col0[l][j] for j, (_, _, kind, src) in enumerate(groups) if kind == 1})
+        self.gate_col = {src: self.col0[0][j] for j, (_, _, kind, src) in enumerate(self.layers[0]) if kind == 0}
+        self.stream_groups = []  # per unique stream: [begin, end) in layer 0's order
+        j = 0
+        for s in range(len(self.streams)):
+            n = sum(1 for what, i in order
+                    if self.stream_ix[(stream_of[i] if what == "e" else gate_stream_of[i])] == s)
+            self.stream_groups.append((j, j + n))
+            j += n
+        self.selections = [list(sel) for sel in selections]
+        self.H = blocks[0][-1][0].out_features
+        self.M = int(self.streams[0].shape[0])
+
+    def params(self):
+        out = []
+        for groups in self.layers:
+            for lin, bn, _, _ in groups:
+                out += [lin.weight, lin.bias, bn.weight, bn.bias]
+        return out
+
+
+def _mix_tables(plan):
+    L = plan.depth - 1
+    gate_col = [plan.gate_col[o] for o in range(len(plan.selections))]
+    n_sel = [len(sel) for sel in plan.selections]
+    sel_col = []
+    for sel in plan.selections:
+        row = [plan.expert_col[L][i] for i in sel]
+        sel_col += row + [0] * (_SEL_STRIDE - len(row))
+    return gate_col, n_sel, sel_col
+
+
+class _ExpertBankFn(torch.autograd.Function):
+    """All mixed outputs of a bank.  Kept for backward: the streams, per layer the wide z, stat and dropout counter, and the
+    hidden layers' activations; the (M, E, H) stack and the gate weights never exist."""
+
+    @staticmethod
+    def forward(ctx, plan, *tensors):
+        ns = len(plan.streams)
+        streams = tensors[:ns]
+        M, dev = plan.M, streams[0].device
+        rng = _dropout_rng(dev)
+        R = _lib.call("rh_gemm_chain_stats_rows", M)
+        zs, stats_, ctrs, acts = [], [], [], []
+        prev = None
+        for l, groups in enumerate(plan.layers):
+            C = plan.col0[l][-1]
+            if l == 0:
+                xs = []
+                for j in range(len(groups)):
+                    s = next(i for i, (b, e) in enumerate(plan.stream_groups) if b <= j < e)
+                    xs.append(streams[s])
+                xp = [x.data_ptr() for x in xs]
+                ldx = [int(x.stride(0)) for x in xs]
+            else:
+                xp = [prev.data_ptr() + 4 * plan.expert_col[l - 1][src] for _, _, _, src in groups]
+                ldx = [plan.col0[l - 1][-1]] * len(groups)
+            z = torch.empty((M, C), dtype=torch.float32, device=dev)
+            slabs = torch.empty((-(-M // R), 2, C), dtype=torch.float32, device=dev)
+            a_x, k0 = _host_array(ctypes.c_void_p, xp)
+            a_ld, k1 = _host_array(ctypes.c_int64, ldx)
+            a_w, k2 = _host_ptrs([g[0].weight for g in groups])
+            a_b, k3 = _host_ptrs([g[0].bias for g in groups])
+            a_K, k4 = _host_array(ctypes.c_int, [g[0].in_features for g in groups])
+            a_N, k5 = _host_array(ctypes.c_int, [g[0].out_features for g in groups])
+            _lib.call("rh_experts_fwd", len(groups), a_x, a_ld, a_w, a_b, a_K, a_N, M, _p(z), _p(slabs), _stream())
+            stat = torch.empty((5, C), dtype=torch.float32, device=dev)
+            ctr = torch.empty(1, dtype=torch.int64, device=dev)
+            a_kind, k6 = _host_array(ctypes.c_int, [g[2] for g in groups])
+            a_ga, k7 = _host_ptrs([g[1].weight for g in groups])
+            a_be, k8 = _host_ptrs([g[1].bias for g in groups])
+            a_rm, k9 = _host_ptrs([g[1].running_mean for g in groups])
+            a_rv, k10 = _host_ptrs([g[1].running_var for g in groups])
+            a_nb, k11 = _host_ptrs([g[1].num_batches_tracked for g in groups])
+            a_mo, k12 = _host_array(ctypes.c_float, [float(g[1].momentum) for g in groups])
+            a_ep, k13 = _host_array(ctypes.c_float, [float(g[1].eps) for g in groups])
+            _lib.call("rh_experts_bn_fwd", len(groups), a_N, a_kind, a_ga, a_be, a_rm, a_rv, a_nb, a_mo, a_ep, M, _p(slabs),
+                      1 if plan.training else 0, _p(rng), _p(ctr), _p(stat), _stream())
+            zs.append(z), stats_.append(stat), ctrs.append(ctr)
+            if l < plan.depth - 1:
+                prev = torch.empty((M, C), dtype=torch.float32, device=dev)
+                _lib.call("rh_experts_act_fwd", _p(z), _p(stat), M, C, plan.p_drop[l], _p(rng), _p(ctr), _p(prev), _stream())
+                acts.append(prev)
+        outs = [torch.empty((M, plan.H), dtype=torch.float32, device=dev) for _ in plan.selections]
+        gate_col, n_sel, sel_col = _mix_tables(plan)
+        a_gc, k0 = _host_array(ctypes.c_int, gate_col)
+        a_ns, k1 = _host_array(ctypes.c_int, n_sel)
+        a_sc, k2 = _host_array(ctypes.c_int, sel_col)
+        a_out, k3 = _host_ptrs(outs)
+        L = plan.depth - 1
+        _lib.call("rh_experts_mix_fwd", len(outs), a_gc, a_ns, a_sc, plan.H, _p(zs[0]), _p(stats_[0]), plan.col0[0][-1],
+                  _p(zs[L]), _p(stats_[L]), plan.col0[L][-1], M, plan.p_drop[L], _p(rng), _p(ctrs[L]), a_out, _stream())
+        ctx.plan = plan
+        ctx.save_for_backward(*streams, *zs, *stats_, *ctrs, *acts)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *g_outs):
+        plan = ctx.plan
+        ns, D = len(plan.streams), plan.depth
+        saved = ctx.saved_tensors
+        streams = saved[:ns]
+        zs, stats_, ctrs = saved[ns:ns + D], saved[ns + D:ns + 2 * D], saved[ns + 2 * D:ns + 3 * D]
+        acts = saved[ns + 3 * D:]
+        M, dev, L = plan.M, streams[0].device, D - 1
+        rng = _dropout_rng(dev)
+        nchunk = -(-M // 16)
+        g_outs = [torch.zeros((M, plan.H), dtype=torch.float32, device=dev) if g is None else g.contiguous() for g in g_outs]
+        gbuf = [torch.empty((M, plan.col0[l][-1]), dtype=torch.float32, device=dev) for l in range(D)]
+        part = [torch.empty((nchunk, 2, plan.col0[l][-1]), dtype=torch.float32, device=dev) for l in range(D)]
+        gate_col, n_sel, sel_col = _mix_tables(plan)
+        a_gc, k0 = _host_array(ctypes.c_int, gate_col)
+        a_ns, k1 = _host_array(ctypes.c_int, n_sel)
+        a_sc, k2 = _host_array(ctypes.c_int, sel_col)
+        a_ec, k3 = _host_array(ctypes.c_int, [plan.expert_col[L][i] for i in plan.expert_ix])
+        a_go, k4 = _host_ptrs(g_outs)
+        _lib.call("rh_experts_mix_bwd", len(g_outs), a_gc, a_ns, a_sc, plan.H, len(plan.expert_ix), a_ec, _p(zs[0]),
+                  _p(stats_[0]), plan.col0[0][-1], _p(zs[L]), _p(stats_[L]), plan.col0[L][-1], M, plan.p_drop[L], _p(rng),
+                  _p(ctrs[L]), a_go, _p(gbuf[0]), _p(part[0]), _p(gbuf[L]), _p(part[L]), _stream())
+        grads = {}  # id(param) -> gradient
+        g_streams = [None] * ns
+        for l in reversed(range(D)):
+            groups, C = plan.layers[l], plan.col0[l][-1]
+            if l < L:
+                _lib.call("rh_experts_act_bwd", _p(zs[l]), _p(stats_[l]), M, C, plan.p_drop[l], _p(rng), _p(ctrs[l]),
+                          _p(gbuf[l]), _p(part[l]), _stream())
+            dgb = torch.empty((2, C), dtype=torch.float32, device=dev)
+            _lib.call("rh_experts_bn_bwd", _p(zs[l]), _p(stats_[l]), M, C, _p(part[l]), _p(gbuf[l]), _p(dgb), _stream())
+            a_w, k5 = _host_ptrs([g[0].weight for g in groups])
+            a_K, k6 = _host_array(ctypes.c_int, [g[0].in_features for g in groups])
+            a_N, k7 = _host_array(ctypes.c_int, [g[0].out_features for g in groups])
+            if l > 0:
+                Cp = plan.col0[l - 1][-1]
+                gx = [gbuf[l - 1].data_ptr() + 4 * plan.expert_col[l - 1][src] for _, _, _, src in groups]
+                ldg = [Cp] * len(groups)
+                begin, end = list(range(len(groups))), list(range(1, len(groups) + 1))
+            else:
+                need = [s for s in range(ns) if ctx.needs_input_grad[1 + s]]
+                for s in need:
+                    g_streams[s] = torch.empty((M, streams[s].shape[1]), dtype=torch.float32, device=dev)
+                gx = [g_streams[s].data_ptr() for s in need]
+                ldg = [int(g_streams[s].stride(0)) for s in need]
+                begin, end = [plan.stream_groups[s][0] for s in need], [plan.stream_groups[s][1] for s in need]
+            if gx:
+                a_gx, k8 = _host_array(ctypes.c_void_p, gx)
+                a_ld, k9 = _host_array(ctypes.c_int64, ldg)
+                a_b, k10 = _host_array(ctypes.c_int, begin)
+                a_e, k11 = _host_array(ctypes.c_int, end)
+                _lib.call("rh_experts_dgrad", len(gx), a_gx, a_ld, a_b, a_e, len(groups), a_w, a_K, a_N, _p(gbuf[l]), M,
+                          _stream())
+            # weight and bias gradients: the existing split-batch kernel on column-block views of the wide buffers
+            for j, (lin, bn, _, src) in enumerate(groups):
+                c0, N = plan.col0[l][j], lin.out_features
+                if l == 0:
+                    x = streams[next(i for i, (b, e) in enumerate(plan.stream_groups) if b <= j < e)]
+                else:
+                    x = acts[l - 1][:, plan.expert_col[l - 1][src]:plan.expert_col[l - 1][src] + lin.in_features]
+                dW, db = linear_wgrad(gbuf[l][:, c0:c0 + N], x, want_bias=lin.bias is not None, weight=lin.weight,
+                                          bias=lin.bias)
+                grads[id(lin.weight)], grads[id(lin.bias)] = dW, db
+                grads[id(bn.weight)], grads[id(bn.bias)] = dgb[0, c0:c0 + N], dgb[1, c0:c0 + N]
+        out = [None] + g_streams
+        for p in plan.params():
+            out.append(None if p is None else grads.get(id(p)))
+        return tuple(out)
+
+
+def expert_bank_layout(streams, experts, stream_of, gates, gate_stream_of, selections):
+    """[(C, {expert index: first column})] per bank layer: where each expert's column block lies in the layer's wide buffer.
+    Element (r, c) of a block that starts at column c0 of a C-wide layer takes dropout index r C + c0 + c, and layer l of
+    the bank's n-th call since the counter stood at c takes dropout counter c + n depth + l."""
+    plan = _BankPlan(streams, experts, stream_of, gates, gate_stream_of, selections)
+    return [(plan.col0[l][-1], dict(plan.expert_col[l])) for l in range(plan.depth)]
+
+
+def expert_bank_ok(streams, experts, stream_of, gates, gate_stream_of, selections):
+    """True when csrc/experts.hip takes this bank: float32 HIP streams of the same row count, experts that are same-depth
+    [Linear, BatchNorm1d, ReLU, Dropout] stacks of one output width and one dropout rate per layer, gates spelled Linear ->
+    BatchNorm1d -> Softmax(dim=1) -> Dropout(0) over exactly their selection, BatchNorms the fused MLP path takes too, and
+    every size inside rh_experts_limits."""
+    if not streams or not experts or not gates or len(gates) != len(selections):
+        return False
+    M = streams[0].shape[0] if streams[0].dim() == 2 else -1
+    for s in streams:
+        if not (s.is_cuda and s.dtype == torch.float32 and s.dim() == 2 and s.shape[0] == M and s.stride(1) == 1 and
+                s.shape[1] >= 1):
+            return False
+    blocks = [_expert_blocks(e) for e in experts]
+    gblocks = [_gate_block(g) for g in gates]
+    if any(b is None for b in blocks) or any(g is None for g in gblocks) or len({len(b) for b in blocks}) != 1:
+        return False
+    bns = [bn for b in blocks for _, bn, _ in b] + [bn for _, bn in gblocks]
+    training = bns[0].training
+    if not all(_bank_bn_ok(bn) and bn.training == training and bn.weight.is_cuda for bn in bns):
+        return False
+    if training and M < 2:
+        return False
+    if not training and torch.is_grad_enabled():
+        return False  # (eval-mode BatchNorm has no fused backward: MLP._bn_ok refuses it as well)
+    for l in range(len(blocks[0])):
+        ps = {float(b[l][2].p) if b[l][2].training else 0.0 for b in blocks}
+        if len(ps) != 1 or not 0.0 <= next(iter(ps)) < 1.0:
+            return False
+    if len({b[-1][0].out_features for b in blocks}) != 1:
+        return False
+    for b, s in zip(blocks, stream_of):
+        if b[0][0].in_features != streams[s].shape[1]:
+            return False
+    for (lin, _), s, sel in zip(gblocks, gate_stream_of, selections):
+        if lin.in_features != streams[s].shape[1] or lin.out_features != len(sel) or len(set(sel)) != len(sel):
+            return False
+    max_g, max_w, max_sel, max_out = expert_bank_limits()
+    widths = [lin for b in blocks for lin, _, _ in b] + [lin for lin, _ in gblocks]
+    if any(lin.weight.dtype != torch.float32 or not lin.weight.is_contiguous() for lin in widths):
+        return False
+    G = len(experts) + len(gates)
+    if G > max_g or len(selections) > max_out or max(len(s) for s in selections) > max_sel:
+        return False
+    if any(not 1 <= v <= max_w for lin in widths for v in (lin.in_features, lin.out_features)):
+        return False
+    first = [b[0][0] for b in blocks] + [lin for lin, _ in gblocks]  # the widest launch: the first layer's, with the gates
+    K, k0 = _host_array(ctypes.c_int, [lin.in_features for lin in first])
+    N, k1 = _host_array(ctypes.c_int, [lin.out_features for lin in first])
+    return bool(_lib.query("rh_experts_supported", G, K, N, len(selections), max(len(s) for s in selections),
+                           blocks[0][-1][0].out_features))
+
+
+def expert_bank(streams, experts, stream_of, gates, gate_stream_of, selections):
+    """The mixed outputs of an expert bank: ``[sum_e gates[o](streams[gate_stream_of[o]])[:, e] *
+    experts[selections[o][e]](streams[stream_of[selections[o][e]]]) for o in range(len(gates))]`` with ``experts`` / ``gates``
+    the MLP modules themselves (their parameters are used in place and their running statistics updated), as ONE autograd node
+    on the grouped kernels of csrc/experts.hip: one GEMM launch per bank layer for all experts and gates, one mixture launch
+    for all outputs, and a backward without atomics.  Check ``expert_bank_ok`` first."""
+    if not expert_bank_ok(streams, experts, stream_of, gates, gate_stream_of, selections):
+        raise RuntimeError("torch_rechub_amd: expert_bank does not take this bank (see expert_bank_ok)")
+    plan = _BankPlan(streams, experts, stream_of, gates, gate_stream_of, selections)
+    return list(_ExpertBankFn.apply(plan, *plan.streams, *plan.params()))
+
+
+# --------------------------------------------------------------------------------------------
 # The stateless leaf families (_families/<name>.py drives csrc/<name>.hip), under the names they have always had here.
 # Callers say ops.<name>, so a test that replaces ops.<name> is seen by the models.  Private names come along because the
 # functions above use some of them and the module's surface stays what it was.
