@@ -1133,6 +1133,29 @@ int rh_ivf_scan(const float* q, int64_t ldq, const float* xs, const float* bias_
 int rh_ivf_list_mean(const float* xs, const int32_t* list_off, const float* previous, int V, int D, int nlists,
                      float* centroids, void* stream);
 
+/* ---- fp16 / bf16 item tables for the two scans (csrc/topk_half.hip) --------------------------------------------------
+ * rh_topk_fwd and rh_ivf_scan over a table x / xs (V, D) of type T = fp16 (is_bf16 = 0) or bf16 (is_bf16 = 1), contiguous:
+ * half the bytes per item (a flag beside the untyped pointer, as idx_is_i64 of rh_seq_pool_fwd).  Every other argument, the limits, the order, the tie rule, exclude, invalid and
+ * the (-1, -inf) tail are those of the fp32 entry points; rh_topk_plan and rh_ivf_plan size the workspaces.
+ *   score[i][j] = sum_k T(q[i][k]) x[j][k] (+ bias[j])
+ * q stays fp32 in memory and is rounded to T, to nearest even, as it is loaded (the value of q.to(T); a q outside fp16's
+ * range becomes +-inf); a product of two T values is exact in fp32; the sum is fp32 from zero over k in ascending steps
+ * of 16 (v_mfma_f32_32x32x16_f16 / _bf16, zero-padded; the order inside one instruction is the hardware's); bias (fp32)
+ * is one fp32 add at the end.  A score depends on q_i, x_j and D only: every nsplit gives the same bits, and with every
+ * list probed rh_ivf_scan_half equals rh_topk_half_fwd bit for bit.  No atomics.  NaN is out of scope; what the matrix
+ * instruction does with fp16 subnormals is not verified.
+ * Another is_bf16 than 0 / 1: RH_E_UNSUPPORTED (rh_topk_half_supported answers 0 through its HOST pointer).
+ * replaces: the useFloat16 store of the faiss GPU flat index behind FaissBuilder (torch_rechub/serving/faiss.py) and the
+ *           FP16 inference path of torch_rechub/utils/quantization.py for the item table. */
+int rh_topk_half_supported(int D, int K, int S, int is_bf16, int* supported);
+int rh_topk_half_fwd(const float* q, int64_t ldq, const void* x, int is_bf16, const float* bias, const int64_t* exclude, int S,
+                     const int64_t* invalid, int n_inv, int M, int D, int V, int K, int nsplit, void* workspace,
+                     int64_t* ids, float* scores, void* stream);
+int rh_ivf_scan_half(const float* q, int64_t ldq, const void* xs, int is_bf16, const float* bias_s, const int32_t* row_id,
+                     const int32_t* list_off, int nlists, const int32_t* pair, const int32_t* pair_off,
+                     const int32_t* tile_off, const int64_t* exclude, int S, int M, int D, int V, int K, int nprobe,
+                     void* partials, int64_t* ids, float* scores, void* stream);
+
 /* ---- session-based retrieval (csrc/session.hip) ---------------------------------------------------------------------
  * GRU recurrence of nn.GRU (gate order r, z, n) from the zero state: xw (B, T, 3H) = x W_ih^T (+ b_ih) for every step,
  * w_hh (3H, H) = weight_hh, b_hh (3H,) or null.  1 <= H <= RH_GRU_MAX_H, else RH_E_UNSUPPORTED.

@@ -9,7 +9,10 @@ synchronise), warm-up first; min and max of the windows are printed beside it.  
 ids (the exact answer) that the IVF answer holds.  A setting the kernel refuses (nprobe above its limit of 256) is reported
 as refused.  Build time is one wall-clock build (k-means of 10 rounds, final assignment, grouping) after a warm-up build of
 a small index; peak memory is torch.cuda.max_memory_allocated above what was allocated before.  The lines are also
-written to ``--out`` (default profiles/ivf_bench.txt); one JSON line at the end."""
+written to ``--out`` (default profiles/ivf_bench.txt); one JSON line at the end.
+
+``--dtype float16`` (or bfloat16) measures the same IVF index with its table stored in that type (csrc/topk_half.hip,
+same centroids: k-means trains on the fp32 rows) in the same alternation, and prints half / fp32 per row."""
 import argparse
 import json
 import statistics
@@ -64,7 +67,9 @@ def mixture(n, centres, g):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="profiles/ivf_bench.txt")
+    ap.add_argument("--dtype", default="float32", choices=("float32", "float16", "bfloat16"))
     args = ap.parse_args()
+    T = getattr(torch, args.dtype)
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
     centres = 4.0 * torch.randn(NLISTS, D, generator=g, device=dev)
@@ -94,6 +99,10 @@ def main():
         say(f"build (10 rounds of k-means + final assignment + grouping): {build_s:.3f} s, peak memory {build_peak / 2**20:.1f} MiB "
             f"above the {V * D * 4 / 2**20:.0f} MiB table; rows per list min {sizes.min():.0f}, mean {sizes.mean():.0f}, "
             f"max {sizes.max():.0f}, empty lists {int((sizes == 0).sum())}")
+        half = None
+        if T != torch.float32:
+            half = type(ivf)(x, ivf.centroids, "L2", dev, 1, T)
+            say(f"{args.dtype} index over the same centroids: grouped table {half._search.numel() * 2 / 2**20:.0f} MiB")
         for K in KS:
             (want, _), flat_peak = peak_bytes(lambda: flat.query(q, K))
             for nprobe in NPROBES:
@@ -108,8 +117,16 @@ def main():
                 recall = float(hit.sum()) / float((want >= 0).sum())
                 same = bool(torch.equal(got, want))
                 iters = 10 if nprobe <= 32 else 3
-                w = windows_ms({"ivf": lambda: ivf.query(q, K, nprobe=nprobe), "flat": lambda: flat.query(q, K)}, iters)
+                fns = {"ivf": lambda: ivf.query(q, K, nprobe=nprobe), "flat": lambda: flat.query(q, K)}
+                if half is not None:
+                    fns[args.dtype] = lambda: half.query(q, K, nprobe=nprobe)
+                w = windows_ms(fns, iters)
                 res = {n + "_ms": statistics.median(ts) for n, ts in w.items()}
+                if half is not None:
+                    h = w[args.dtype]
+                    res["half_over_ivf"] = res[args.dtype + "_ms"] / res["ivf_ms"]
+                    say(f"{what}: {args.dtype} ivf {res[args.dtype + '_ms']:9.3f} ms ({min(h):.3f} - {max(h):.3f}), "
+                        f"{args.dtype} / fp32 ivf = {res['half_over_ivf']:.3f}")
                 res.update(flat_over_ivf=res["flat_ms"] / res["ivf_ms"], recall=recall, ids_equal_flat=same,
                            ivf_peak_bytes=ivf_peak, flat_peak_bytes=flat_peak)
                 say(f"{what}: ivf {res['ivf_ms']:9.3f} ms ({min(w['ivf']):.3f} - {max(w['ivf']):.3f}), flat {res['flat_ms']:9.3f} ms "

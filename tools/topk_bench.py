@@ -9,7 +9,12 @@ kernel gets the same thing as ``invalid=[0]``.  Each figure is the median over R
 two device events (a window ends in a synchronise), warm-up first; min and max of the windows are printed beside it.  Peak
 memory is torch.cuda.max_memory_allocated above what was allocated before one call.  The share of rows whose id lists are
 identical on the two paths is printed (their fp32 scores differ in the last bits, so near-ties may swap).  One JSON line
-at the end."""
+at the end.
+
+``--dtype float32,float16,bfloat16`` adds the scan over the table stored in each half type (csrc/topk_half.hip; the table is
+the fp32 one rounded, converted before the timing) to the same alternation, and prints half / fp32 and the share of rows
+whose ids equal the fp32 kernel's.  ``--out`` also writes the lines to a file."""
+import argparse
 import json
 import statistics
 import sys
@@ -55,9 +60,19 @@ def peak_bytes(fn):
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--dtype", default="float32", help="comma-separated table types; float32 is always measured")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    halves = [getattr(torch, n) for n in args.dtype.split(",") if n != "float32"]
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
-    result = {}
+    result, lines = {}, []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+
     for name, M, D, V, K, iters in SHAPES:
         q = torch.randn(M, D, device=dev)
         x = torch.randn(V, D, device=dev)
@@ -74,21 +89,34 @@ def main():
         ids, _ = fused()
         ref = eager().indices
         same = float((ids == ref).all(dim=1).float().mean())
-        w = windows_ms({"kernel": fused, "eager": eager}, iters)
+        fns = {"kernel": fused, "eager": eager}
+        for T in halves:
+            fns[str(T)[6:]] = lambda xt=x.to(T): ops.topk_items(q, xt, K, invalid=invalid)
+        w = windows_ms(fns, iters)
         what = f"{name} (M {M}, D {D}, V {V}, K {K})"
         res = {}
         for n, ts in w.items():
             res[n + "_ms"] = statistics.median(ts)
-            print(f"{what}: {n:7s} {res[n + '_ms']:9.3f} ms  (min {min(ts):.3f}, max {max(ts):.3f})")
+            say(f"{what}: {n:7s} {res[n + '_ms']:9.3f} ms  (min {min(ts):.3f}, max {max(ts):.3f})")
         res["eager_over_kernel"] = res["eager_ms"] / res["kernel_ms"]
         res["kernel_peak_bytes"], res["eager_peak_bytes"] = peak_bytes(fused), peak_bytes(eager)
+        for T in halves:
+            n = str(T)[6:]
+            res[n + "_over_kernel"] = res[n + "_ms"] / res["kernel_ms"]
+            res[n + "_peak_bytes"] = peak_bytes(fns[n])
+            same_T = float((fns[n]()[0] == ids).all(dim=1).float().mean())
+            say(f"{what}: {n} / fp32 kernel = {res[n + '_over_kernel']:.3f}; peak memory {res[n + '_peak_bytes'] / 2**20:.1f} MiB "
+                  f"above the {V * D * 2 / 2**20:.0f} MiB table; rows with the fp32 kernel's ids {same_T:.4f}")
         res["nsplit"] = ops.topk_plan(M, V, K)[0]
         res["rows_with_identical_ids"] = same
-        print(f"{what}: eager / kernel = {res['eager_over_kernel']:.2f}x; peak memory kernel {res['kernel_peak_bytes'] / 2**20:.1f} MiB, "
+        say(f"{what}: eager / kernel = {res['eager_over_kernel']:.2f}x; peak memory kernel {res['kernel_peak_bytes'] / 2**20:.1f} MiB, "
               f"eager {res['eager_peak_bytes'] / 2**20:.1f} MiB; nsplit {res['nsplit']}; rows with identical ids {same:.4f}")
         result[f"{name}_M{M}_V{V}_K{K}"] = res
-        del q, x, mask, ids, ref
-    print(json.dumps(result))
+        del q, x, mask, ids, ref, fns
+    say(json.dumps(result))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
 
 
 if __name__ == "__main__":

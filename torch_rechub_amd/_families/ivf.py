@@ -5,7 +5,7 @@ import torch
 
 from .. import _lib
 from .._opcore import _NULL, _p, _stream, require_hip
-from .topk import _scan_inputs
+from .topk import HALF_TABLES, _scan_inputs, _table_dtype
 
 
 def ivf_supported(D, K, S=0, nprobe=1):
@@ -22,7 +22,7 @@ def ivf_plan(M, nlists, nprobe, K):
                       out=(ctypes.c_int, ctypes.c_int64, ctypes.c_int64))
 
 
-def ivf_scan(q, table_sorted, row_ids, list_offsets, probe, k, bias=None, exclude=None):
+def ivf_scan(q, table_sorted, row_ids, list_offsets, probe, k, bias=None, exclude=None, dtype=torch.float32):
     """(ids (M, k) int64, scores (M, k) float32): the k best rows for every row of ``q`` (M, D) by q_i . x_j (+ bias[j])
     among the lists it probes, best first, exact ties to the lower id; ``topk_items`` restricted to a union of lists.
     ``table_sorted`` (V, D) holds the table's rows grouped by list, ``bias`` (V,) alike, ``row_ids`` (V,) int32 the original
@@ -30,8 +30,13 @@ def ivf_scan(q, table_sorted, row_ids, list_offsets, probe, k, bias=None, exclud
     int32 the lists' offsets.  ``probe`` (M, nprobe) int32: the lists of each query, distinct per row; an entry outside
     [0, nlists) (-1) is no list.  ``exclude`` (M, S) int64: original ids that may not be returned to query i (anything
     else is padding).  The returned ids are original ids; with fewer than k candidates the tail is id -1, score -inf.
-    With every list probed the result is ``topk_items``' on the un-grouped table, bit for bit.  The pairs are grouped by
+    With every list probed the result is ``topk_items``' on the un-grouped table, bit for bit.  ``dtype``: the type
+    ``table_sorted`` is stored in, float32 unless the caller names torch.float16 or torch.bfloat16 (with the score
+    ``topk_items`` gives such a table); a table of any other type than the one named is refused.  The pairs are grouped by
     list with a stable ``torch.sort``; nothing synchronises with the host.  No autograd; runs on the current stream."""
+    _table_dtype("ivf_scan", "table_sorted", table_sorted)
+    if table_sorted.dtype != dtype:
+        raise ValueError(f"torch_rechub_amd: ivf_scan was told dtype={dtype} and given a {table_sorted.dtype} table_sorted")
     require_hip(q, table_sorted, row_ids, list_offsets, probe, bias, exclude)
 
     def refuse(M, D, V, k, S):
@@ -67,9 +72,12 @@ def ivf_scan(q, table_sorted, row_ids, list_offsets, probe, k, bias=None, exclud
     tile_off = torch.zeros_like(pair_off)
     tile_off[1:] = torch.cumsum((pair_off[1:] - pair_off[:-1] + (rb - 1)) // rb, 0)
     part = torch.empty((8 * M * nprobe * k,), dtype=torch.uint8, device=dev)
-    _lib.call("rh_ivf_scan", _p(q), ldq, _p(table_sorted), _p(bias), _p(row_ids), _p(list_offsets), nlists, _p(pair),
-              _p(pair_off), _p(tile_off), _p(exclude) if S > 0 else _NULL, S, M, D, V, k, nprobe, _p(part), _p(ids),
-              _p(scores), _stream())
+    tail = (_p(bias), _p(row_ids), _p(list_offsets), nlists, _p(pair), _p(pair_off), _p(tile_off),
+            _p(exclude) if S > 0 else _NULL, S, M, D, V, k, nprobe, _p(part), _p(ids), _p(scores), _stream())
+    if table_sorted.dtype == torch.float32:
+        _lib.call("rh_ivf_scan", _p(q), ldq, _p(table_sorted), *tail)
+    else:
+        _lib.call("rh_ivf_scan_half", _p(q), ldq, _p(table_sorted), HALF_TABLES[table_sorted.dtype], *tail)
     return ids, scores
 
 

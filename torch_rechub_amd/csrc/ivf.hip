@@ -17,68 +17,18 @@
 //
 // List mean (the update step of k-means): one workgroup per list; wavefront w adds the rows w, w + 4, ... of the list in
 // order, the four partial sums are added as (0 + 1) + (2 + 3) and divided by the count.  An empty list keeps `previous`.
-#include "topk_list.h"
+#include "topk_rules.h"
 
 namespace {
 
-constexpr int kIvfMaxProbe = RH_IVF_MAX_NPROBE;
-
-struct IvfArgs {
-  TopkScanArgs s;           // x, bias = the rows grouped by list; exclude = original ids; nlist = nprobe
-  const int32_t* row_id;    // (V,) original ids
-  const int32_t* list_off;  // (nlists + 1,)
-  const int32_t* pair;      // (M nprobe,) pair indices grouped by list
-  const int32_t* pair_off;  // (nlists + 2,)
-  const int32_t* tile_off;  // (nlists + 2,)
-  int nlists;
-};
-
 size_t ivf_lds_bytes(int K) { return topk_lds_bytes(K) + (size_t)kT * 4; }
-
-// tile row r holds the pair prs[r] = query nprobe + slot (-1: no row), whose list in the partials is the pair's; the id
-// of a grouped row is row_id's
-struct IvfRule {
-  const int* prs;  // [64] in LDS
-  const int32_t* row_id;
-  int nprobe, K;
-  static constexpr const int64_t* invalid = nullptr;
-  static constexpr int n_inv = 0;
-  __device__ __forceinline__ bool has_row(int r) const { return prs[r] >= 0; }
-  __device__ __forceinline__ int64_t query_row(int r) const { return prs[r] / nprobe; }
-  __device__ __forceinline__ int64_t id_of(int64_t c) const { return row_id[c]; }
-  __device__ __forceinline__ int64_t list_offset(int r) const { return (int64_t)prs[r] * K; }
-};
 
 __global__ __launch_bounds__(RH_BLOCK) void ivf_scan_kernel(const IvfArgs a) {
   extern __shared__ __align__(16) float lds[];
   const TopkScanArgs& s = a.s;
   int* prs = reinterpret_cast<int*>(lds + topk_lds_bytes(s.K) / sizeof(float));  // [64] pair index of the row, -1 = no row
-  const int tid = threadIdx.x, RB = s.RB;
-  const int b = blockIdx.x;
-  if (b >= a.tile_off[a.nlists + 1]) return;
-  int g = 0;  // the last group with tile_off[g] <= b: tile_off[g + 1] > b, so the group has the tile
-  for (int hi_g = a.nlists; g < hi_g;) {
-    const int mid = (g + hi_g + 1) / 2;
-    if (a.tile_off[mid] <= b) g = mid; else hi_g = mid - 1;
-  }
-  const int64_t p0 = (int64_t)a.pair_off[g] + (int64_t)(b - a.tile_off[g]) * RB, p1 = a.pair_off[g + 1];
-  const int64_t npair = (int64_t)s.M * s.nlist;
-  int64_t lo = 0, hi = 0;  // group 0: no list
-  if (g > 0) {
-    lo = a.list_off[g - 1];
-    hi = a.list_off[g];
-    if (lo < 0) lo = 0;
-    if (hi > s.V) hi = s.V;
-  }
-  if (tid < kT) {
-    int p = -1;
-    if (tid < RB && p0 >= 0 && p0 + tid < p1 && p0 + tid < npair) {
-      p = a.pair[p0 + tid];
-      if (p < 0 || p >= npair) p = -1;
-    }
-    prs[tid] = p;
-  }
-  __syncthreads();
+  int64_t lo, hi;
+  if (!ivf_tile(a, prs, lo, hi)) return;
   topk_scan_tiles(s, IvfRule{prs, a.row_id, s.nlist, s.K}, lo, hi, lds);
 }
 
@@ -116,10 +66,6 @@ __global__ __launch_bounds__(RH_BLOCK) void ivf_list_mean_kernel(const float* __
   }
 }
 
-bool ivf_shape_ok(int D, int K, int S, int nprobe) {
-  return topk_shape_ok(D, K, S) && nprobe >= 1 && nprobe <= kIvfMaxProbe;
-}
-
 }  // namespace
 
 extern "C" int rh_ivf_supported(int D, int K, int S, int nprobe, int* supported) {
@@ -147,25 +93,13 @@ extern "C" int rh_ivf_scan(const float* q, int64_t ldq, const float* xs, const f
                            const int32_t* list_off, int nlists, const int32_t* pair, const int32_t* pair_off,
                            const int32_t* tile_off, const int64_t* exclude, int S, int M, int D, int V, int K, int nprobe,
                            void* partials, int64_t* ids, float* scores, void* stream) {
-  RH_REQUIRE(ivf_shape_ok(D, K, S, nprobe), RH_E_UNSUPPORTED,
-             "rh_ivf_scan: D=%d K=%d S=%d nprobe=%d unsupported (1 <= D <= %d, 1 <= K <= %d, 0 <= S <= %d, "
-             "1 <= nprobe <= %d)", D, K, S, nprobe, kTopkMaxD, kTopkMaxK, kTopkMaxS, kIvfMaxProbe);
-  if (int rc = topk_scan_sizes("rh_ivf_scan", M, V, "nlists", nlists, nlists >= 1, ldq, D)) return rc;
-  const int RB = topk_rows(K);
-  const int64_t npair = (int64_t)M * nprobe, grid = (npair + RB - 1) / RB + nlists + 1;
-  RH_REQUIRE(grid < ((int64_t)1 << 31), RH_E_UNSUPPORTED, "rh_ivf_scan: M nprobe = %lld pairs are too many",
-             (long long)npair);
-  if (M == 0) return 0;
   IvfArgs a{};
-  if (int rc = topk_scan_args("rh_ivf_scan", &a.s, q, ldq, xs, bias_s, exclude, S, M, D, V, K, nprobe, partials, ids, scores))
+  bool go;
+  int64_t grid;
+  if (int rc = ivf_scan_args("rh_ivf_scan", &a, &go, &grid, q, ldq, xs, bias_s, row_id, list_off, nlists, pair, pair_off,
+                             tile_off, exclude, S, M, D, V, K, nprobe, partials, ids, scores))
     return rc;
-  RH_REQUIRE(row_id && list_off && pair && pair_off && tile_off, RH_E_BADARG, "rh_ivf_scan: null pointer");
-  a.row_id = row_id;
-  a.list_off = list_off;
-  a.pair = pair;
-  a.pair_off = pair_off;
-  a.tile_off = tile_off;
-  a.nlists = nlists;
+  if (!go) return 0;
   static RhLdsReserved reserved;
   if (int rc = rh_reserve_lds(reserved, ivf_scan_kernel, ivf_lds_bytes(128), "rh_ivf_scan")) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);

@@ -14,36 +14,17 @@
 // under a total order holds the global top K's members of that range, so the result does not depend on nsplit.
 // No atomics; every element of the partials is written (unused tail: -inf, -1).
 // The scan of one workgroup (topk_scan_tiles), its K-list (threshold, ballot, cooperative insert) and the merge of one row
-// live in topk_list.h, shared with ivf.hip: topk_scan_kernel only names its column range and, in FlatRule, its rows.
-#include "topk_list.h"
+// live in topk_list.h, shared with ivf.hip: topk_scan_kernel only names its column range and, in FlatRule, its rows
+// (topk_rules.h, which topk_half.hip runs under the half-table scan body).
+#include "topk_rules.h"
 
 namespace {
 
-struct TopkArgs {
-  TopkScanArgs s;          // nlist = nsplit
-  const int64_t* invalid;  // (n_inv,) or null
-  int n_inv;
-};
-
-// tile row r is query row r0 + r where r < rows, a column's id is its index, range `split` is the query's list `split`
-struct FlatRule {
-  int64_t r0;
-  int rows, nsplit, split, K;
-  const int64_t* invalid;
-  int n_inv;
-  __device__ __forceinline__ bool has_row(int r) const { return r < rows; }
-  __device__ __forceinline__ int64_t query_row(int r) const { return r0 + r; }
-  __device__ __forceinline__ int64_t id_of(int64_t c) const { return c; }
-  __device__ __forceinline__ int64_t list_offset(int r) const { return ((r0 + r) * nsplit + split) * K; }
-};
-
 __global__ __launch_bounds__(RH_BLOCK) void topk_scan_kernel(const TopkArgs a) {
   extern __shared__ __align__(16) float lds[];
-  const TopkScanArgs& s = a.s;
-  const int split = blockIdx.y;
-  const int64_t r0 = (int64_t)blockIdx.x * s.RB;
-  const FlatRule rule{r0, (int)(s.M - r0 < s.RB ? s.M - r0 : s.RB), s.nlist, split, s.K, a.invalid, a.n_inv};
-  topk_scan_tiles(s, rule, (int64_t)s.V * split / s.nlist, (int64_t)s.V * (split + 1) / s.nlist, lds);
+  int64_t lo, hi;
+  const FlatRule rule = topk_flat_rule(a, lo, hi);
+  topk_scan_tiles(a.s, rule, lo, hi, lds);
 }
 
 // one wavefront per row
@@ -87,19 +68,12 @@ extern "C" int rh_topk_plan(int M, int V, int K, int* nsplit, int64_t* workspace
 extern "C" int rh_topk_fwd(const float* q, int64_t ldq, const float* x, const float* bias, const int64_t* exclude, int S,
                            const int64_t* invalid, int n_inv, int M, int D, int V, int K, int nsplit, void* workspace,
                            int64_t* ids, float* scores, void* stream) {
-  RH_REQUIRE(topk_shape_ok(D, K, S), RH_E_UNSUPPORTED,
-             "rh_topk_fwd: D=%d K=%d S=%d unsupported (1 <= D <= %d, 1 <= K <= %d, 0 <= S <= %d)", D, K, S, kTopkMaxD,
-             kTopkMaxK, kTopkMaxS);
-  if (int rc = topk_scan_sizes("rh_topk_fwd", M, V, "n_inv", n_inv, n_inv >= 0, ldq, D)) return rc;
-  RH_REQUIRE(nsplit >= 1 && nsplit <= kTopkMaxSplit && nsplit <= V, RH_E_BADARG,
-             "rh_topk_fwd: nsplit=%d outside [1, min(V, %d)]", nsplit, kTopkMaxSplit);
-  if (M == 0) return 0;
   TopkArgs a{};
-  if (int rc = topk_scan_args("rh_topk_fwd", &a.s, q, ldq, x, bias, exclude, S, M, D, V, K, nsplit, workspace, ids, scores))
+  bool go;
+  if (int rc = topk_flat_args("rh_topk_fwd", &a, &go, q, ldq, x, bias, exclude, S, invalid, n_inv, M, D, V, K, nsplit,
+                              workspace, ids, scores))
     return rc;
-  RH_REQUIRE(n_inv == 0 || invalid, RH_E_BADARG, "rh_topk_fwd: null pointer");
-  a.invalid = invalid;
-  a.n_inv = n_inv;
+  if (!go) return 0;
   static RhLdsReserved reserved;
   if (int rc = rh_reserve_lds(reserved, topk_scan_kernel, topk_lds_bytes(128), "rh_topk_fwd")) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);

@@ -41,7 +41,7 @@ inline bool topk_shape_ok(int D, int K, int S) {
 struct TopkScanArgs {
   const float* q;          // (M, D), row stride ldq
   int64_t ldq;
-  const float* x;          // (V, D) contiguous
+  const float* x;          // (V, D) contiguous; the half scans (topk_half_tile.h) read it as their table type
   const float* bias;       // (V,) or null
   const int64_t* exclude;  // (M, S) or null
   int S, M, D, V, K;
@@ -62,12 +62,12 @@ inline int topk_scan_sizes(const char* who, int M, int V, const char* count, int
 }
 
 // For M > 0: the null pointers, the arguments and the split of the workspace into scores and ids.
-inline int topk_scan_args(const char* who, TopkScanArgs* a, const float* q, int64_t ldq, const float* x, const float* bias,
+inline int topk_scan_args(const char* who, TopkScanArgs* a, const float* q, int64_t ldq, const void* x, const float* bias,
                           const int64_t* exclude, int S, int M, int D, int V, int K, int nlist, void* workspace,
                           int64_t* ids, float* scores) {
   RH_REQUIRE(q && x && workspace && ids && scores && (S == 0 || exclude), RH_E_BADARG, "%s: null pointer", who);
   float* part_s = static_cast<float*>(workspace);
-  *a = TopkScanArgs{q, ldq, x, bias, exclude, S, M, D, V, K, nlist, topk_rows(K), part_s,
+  *a = TopkScanArgs{q, ldq, static_cast<const float*>(x), bias, exclude, S, M, D, V, K, nlist, topk_rows(K), part_s,
                     reinterpret_cast<int32_t*>(part_s + (int64_t)M * nlist * K), ids, scores};
   return 0;
 }

@@ -11,6 +11,14 @@ A query with fewer than ``top_k`` candidates gets id -1 and value +inf (-inf for
 ``HipIvfIndexer`` is the inverted-file index over the same three metrics (``HipBuilder(index_type="IVF")``): k-means
 centroids trained on the device, every row in the list of its nearest centroid, a query scanning only its ``nprobe``
 nearest lists on ``ops.ivf_scan`` (csrc/ivf.hip) -- approximate only in which rows it looks at.
+
+``dtype=torch.float16`` or ``torch.bfloat16`` stores the table in that type T (csrc/topk_half.hip): half the bytes per
+item.  The kernel rounds the queries to T and adds exact products in float32, so on data that T holds exactly (small
+integers) the answers are the float32 index's.  "IP" searches the rounded table; "L2" takes -|x|^2 from the rounded table
+(formed in float64) and rounds the queries to T before doubling them (doubling is exact, so the kernel does not round a
+second time) and returns |T(q)|^2 minus the score; "angular" normalises in float32 and then rounds both sides, so its
+unit vectors are only approximately unit and its distances approximate (about 2^-11 relative for float16, 2^-8 for
+bfloat16).  An index file keeps the stored type.
 """
 import contextlib
 
@@ -21,6 +29,19 @@ from .base import BaseBuilder, BaseIndexer
 METRICS = ("L2", "IP", "angular")
 
 
+DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
+def _check_dtype(dtype, table=None):
+    """The storage type: ``dtype``, or for None the table's own where that is a half type (an index file keeps its
+    type) and float32 otherwise."""
+    if dtype is None:
+        dtype = table.dtype if table is not None and table.dtype in DTYPES[1:] else torch.float32
+    if dtype not in DTYPES:
+        raise ValueError(f"dtype must be one of {DTYPES}, got {dtype!r}")
+    return dtype
+
+
 def _check_metric(metric):
     if metric not in METRICS:
         raise ValueError(f"metric must be one of {METRICS}, got {metric!r}")
@@ -28,11 +49,12 @@ def _check_metric(metric):
 
 
 def save_index(file_path, metric, table):
-    """Write an index file: the metric name and the float32 table, one ``torch.save``."""
+    """Write an index file: the metric name and the table (float32, or the half type it is stored in), one
+    ``torch.save``."""
     _check_metric(metric)
     if table.dim() != 2:
         raise ValueError("an index holds a 2D (n, d) table")
-    torch.save({"metric": metric, "table": table.detach().to("cpu", torch.float32).contiguous()}, file_path)
+    torch.save({"metric": metric, "table": table.detach().to("cpu", _check_dtype(None, table)).contiguous()}, file_path)
 
 
 def load_index(file_path):
@@ -48,16 +70,26 @@ def _unit_rows(x):
     return torch.where(n > 0, x / n.clamp_min(torch.finfo(torch.float32).tiny), torch.zeros_like(x))
 
 
-def _metric_query(metric, dev, embeddings, exclude, bias, search):
+def _neg_sq_norms(table):
+    """-|x|^2 of every row, float32; of a half table: formed in float64 from the stored values."""
+    if table.dtype == torch.float32:
+        return -(table * table).sum(dim=1)
+    return -(table.double() ** 2).sum(dim=1).float()
+
+
+def _metric_query(metric, dev, embeddings, exclude, bias, search, dtype=torch.float32):
     """``query`` of both indexers: ``search(q, bias, exclude) -> (ids, scores)`` is the inner-product search on the device
     ``dev``, given the queries as the metric has them ranked (2 q with the index's ``bias`` = -|x|^2 for "L2", unit rows
-    for "angular"); the scores become the metric's values and everything returns to the queries' device."""
+    for "angular"); the scores become the metric's values and everything returns to the queries' device.  ``dtype``: the
+    table's type; for a half type "L2" rounds the queries to it first, so that 2 q is a value the kernel keeps."""
     if embeddings.dim() != 2:
         raise ValueError("query takes a 2D (n, d) tensor")
     q = embeddings.detach().to(dev, torch.float32)
     if exclude is not None:
         exclude = exclude.to(dev)
     if metric == "L2":
+        if dtype != torch.float32:
+            q = q.to(dtype).float()
         qn = (q * q).sum(dim=1, keepdim=True)
         ids, s = search(q * 2.0, bias, exclude)
         val = (qn - s).clamp_min(0.0)
@@ -72,23 +104,25 @@ def _metric_query(metric, dev, embeddings, exclude, bias, search):
 
 
 class HipIndexer(BaseIndexer):
-    """``table`` (n, d) on the device, searched exactly."""
+    """``table`` (n, d) on the device, searched exactly.  ``dtype``: the type it is stored and searched in (float32,
+    float16 or bfloat16; None: a half table keeps its type, anything else becomes float32)."""
 
-    def __init__(self, table, metric="L2", device=None):
+    def __init__(self, table, metric="L2", device=None, dtype=None):
         from .. import ops
         self.metric = _check_metric(metric)
         if table.dim() != 2:
             raise ValueError("an index holds a 2D (n, d) table")
+        self.dtype = _check_dtype(dtype, table)
         device = torch.device("cuda" if device is None else device)
         self._ops = ops
-        self._table = table.detach().to(device, torch.float32).contiguous()
+        self._table = table.detach().to(device, self.dtype).contiguous()
         ops.require_hip(self._table)
         self._bias = None
         self._search = self._table
         if metric == "L2":
-            self._bias = -(self._table * self._table).sum(dim=1)
+            self._bias = _neg_sq_norms(self._table)
         elif metric == "angular":
-            self._search = _unit_rows(self._table)
+            self._search = _unit_rows(self._table.float()).to(self.dtype)
 
     def __len__(self):
         return int(self._table.shape[0])
@@ -99,7 +133,7 @@ class HipIndexer(BaseIndexer):
         def search(q, bias, exclude):
             return self._ops.topk_items(q, self._search, top_k, bias=bias, exclude=exclude)
 
-        return _metric_query(self.metric, self._table.device, embeddings, exclude, self._bias, search)
+        return _metric_query(self.metric, self._table.device, embeddings, exclude, self._bias, search, self.dtype)
 
     def save(self, file_path):
         save_index(file_path, self.metric, self._table)
@@ -135,16 +169,20 @@ class HipIvfIndexer(BaseIndexer):
     """``table`` (n, d) on the device behind an inverted file: every row belongs to the list of its nearest centroid
     (L2; for "angular" between unit vectors), a query scans the ``nprobe`` lists whose centroids are nearest to it (for
     "IP": whose centroids have the largest inner product with it) on ``ops.ivf_scan``.  Among the probed rows the answer
-    is exact and means what ``HipIndexer`` returns; with ``nprobe == nlists`` it is ``HipIndexer``'s answer bit for bit."""
+    is exact and means what ``HipIndexer`` returns; with ``nprobe == nlists`` it is ``HipIndexer``'s answer bit for bit.
+    ``dtype`` as ``HipIndexer``'s: only the table is stored in it; the rows are assigned to their lists from the stored
+    (rounded) values, through a float32 copy that is dropped again, and the centroids and the choice of the probed lists
+    stay float32."""
 
-    def __init__(self, table, centroids, metric="L2", device=None, nprobe=1):
+    def __init__(self, table, centroids, metric="L2", device=None, nprobe=1, dtype=None):
         from .. import ops
         self.metric = _check_metric(metric)
         if table.dim() != 2 or centroids.dim() != 2 or centroids.shape[1] != table.shape[1]:
             raise ValueError("an IVF index holds a 2D (n, d) table and (nlists, d) centroids")
+        self.dtype = _check_dtype(dtype, table)
         device = torch.device("cuda" if device is None else device)
         self._ops = ops
-        self._table = table.detach().to(device, torch.float32).contiguous()
+        self._table = table.detach().to(device, self.dtype).contiguous()
         ops.require_hip(self._table)
         self.centroids = centroids.detach().to(device, torch.float32).contiguous()
         self.nlists = int(self.centroids.shape[0])
@@ -152,14 +190,14 @@ class HipIvfIndexer(BaseIndexer):
             raise ValueError(f"nlists={self.nlists} must lie in [1, {len(self)}] (the number of rows)")
         self.nprobe = self._clip(nprobe)
         self._cbias = -(self.centroids * self.centroids).sum(dim=1)
-        search, bias = self._table, None
+        search, bias = self._table.float(), None
         if metric == "L2":
-            bias = -(self._table * self._table).sum(dim=1)
+            bias = _neg_sq_norms(self._table)
         elif metric == "angular":
-            search = _unit_rows(self._table)
+            search = _unit_rows(search).to(self.dtype).float()
         order, self._list_off = _group(_assign(search, self.centroids, ops), self.nlists)
         self._row_id = order.to(torch.int32)
-        self._search = search[order].contiguous()
+        self._search = search[order].to(self.dtype).contiguous()
         self._bias = None if bias is None else bias[order].contiguous()
 
     def _clip(self, nprobe):
@@ -192,9 +230,9 @@ class HipIvfIndexer(BaseIndexer):
                 q2 = q if self.metric == "L2" else q * 2.0
                 probe = ops.topk_items(q2, self.centroids, nprobe, bias=self._cbias)[0]
             return ops.ivf_scan(q, self._search, self._row_id, self._list_off, probe.to(torch.int32), top_k, bias=bias,
-                                exclude=exclude)
+                                exclude=exclude, dtype=self.dtype)
 
-        return _metric_query(self.metric, self._table.device, embeddings, exclude, self._bias, search)
+        return _metric_query(self.metric, self._table.device, embeddings, exclude, self._bias, search, self.dtype)
 
     def save(self, file_path):
         """One ``torch.save`` dict: the metric, the table in its original row order, the centroids and ``nprobe``.
@@ -213,11 +251,13 @@ class HipBuilder(BaseBuilder):
     1, as faiss; clipped to ``nlists``).  The centroids come from ``niter`` rounds of k-means on the device, started from
     ``nlists`` distinct rows drawn by ``torch.Generator(seed)`` or from ``centroids`` (nlists, d); ``niter=0`` with
     ``centroids`` uses them as they are.  k-means minimises L2 for every metric ("angular": between the unit rows).
-    An index file carries its own metric and its own type."""
+    ``dtype``: the type the table is stored and searched in, float32, float16 or bfloat16 (see the module's head; k-means
+    always trains on the float32 embeddings).  An index file carries its own metric, its own type and its own dtype."""
 
     def __init__(self, metric="L2", device=None, *, index_type="Flat", nlists=100, nprobe=None, niter=10, seed=2022,
-                 centroids=None):
+                 centroids=None, dtype=torch.float32):
         self.metric = _check_metric(metric)
+        self.dtype = _check_dtype(dtype)
         self.device = device
         if index_type == "HNSW":
             raise NotImplementedError('index_type "HNSW" (graph search) is not built here; use "Flat" or "IVF"')
@@ -254,14 +294,15 @@ class HipBuilder(BaseBuilder):
         else:
             perm = torch.randperm(n, generator=torch.Generator().manual_seed(self.seed))[:self.nlists]
             start = x[perm.to(device)].contiguous()
-        return HipIvfIndexer(table, train_centroids(x, start, self.niter, ops), self.metric, device, self.nprobe)
+        return HipIvfIndexer(table, train_centroids(x, start, self.niter, ops), self.metric, device, self.nprobe,
+                             self.dtype)
 
     @contextlib.contextmanager
     def from_embeddings(self, embeddings):
         if self.index_type == "IVF":
             yield self._ivf(embeddings)
         else:
-            yield HipIndexer(embeddings, self.metric, self.device)
+            yield HipIndexer(embeddings, self.metric, self.device, self.dtype)
 
     @contextlib.contextmanager
     def from_index_file(self, index_file):
