@@ -1156,6 +1156,37 @@ int rh_ivf_scan_half(const float* q, int64_t ldq, const void* xs, int is_bf16, c
                      const int32_t* tile_off, const int64_t* exclude, int S, int M, int D, int V, int K, int nprobe,
                      void* partials, int64_t* ids, float* scores, void* stream);
 
+/* ---- int8 item tables (SQ8) for the two scans (csrc/topk_q8.hip) -----------------------------------------------------
+ * A quantised table is codes plus scales: xc / xc_s (V, D) int8 contiguous and xs / xs_s (V,) fp32, one scale per row; a
+ * quarter of the fp32 bytes per item.  The queries are quantised by the same rule, per call: qc (M, D) int8 with row
+ * stride ldqc, a multiple of 16 with a 16-byte aligned base (else RH_E_BADARG; what the bytes from D on hold does not
+ * matter), and qs (M,) fp32.
+ * rh_quantize_rows_q8 is that rule, for the table's rows and the queries' alike.  For each of the M rows of x (row stride
+ * ldx): m = max_k |x[k]|; m == 0: scale = 1 and every code 0; else scale = m / 127 and
+ *   code[k] = clamp(rint(x[k] / scale), -127, 127)
+ * with rint to nearest even and both divisions correctly rounded fp32 divisions (not a multiplication by a reciprocal):
+ * numpy float32 reproduces it bit for bit.  codes has row stride ldc >= D; its columns [D, ldc) are written as zeros.  One
+ * wavefront per row.  NaN and inf are out of scope.
+ *   score[i][j] = ((float)(sum_k qc[i][k] xc[j][k]) * qs[i]) * xs[j] (+ bias[j])
+ * The sum is i32 (v_mfma_i32_32x32x32_i8) and exact in any order; for D <= RH_TOPK_MAX_D it is below 2^24, so its
+ * conversion to fp32 is exact; then two fp32 multiplications and one fp32 addition in exactly that order, each rounded on
+ * its own (no FMA).  A score depends on q_i, x_j and D only: every nsplit gives the same bits, and with every list probed
+ * rh_ivf_scan_q8 equals rh_topk_q8_fwd bit for bit.  No atomics.  Every other argument, the limits, the order, the tie
+ * rule, exclude, invalid and the (-1, -inf) tail are those of the fp32 entry points; rh_topk_plan and rh_ivf_plan size
+ * the workspaces.  rh_topk_q8_supported answers through its HOST pointer.
+ * replaces: faiss's SQ8 scalar quantizer (`IndexScalarQuantizer` / `IVF{nlists},SQ8`) behind FaissBuilder
+ *           (torch_rechub/serving/faiss.py) and the INT8 mode of torch_rechub/utils/quantization.py for the item table.
+ *           Unlike faiss, which keeps the query in float, the query is quantised too. */
+int rh_quantize_rows_q8(const float* x, int64_t ldx, int M, int D, int8_t* codes, int64_t ldc, float* scale, void* stream);
+int rh_topk_q8_supported(int D, int K, int S, int* supported);
+int rh_topk_q8_fwd(const int8_t* qc, int64_t ldqc, const float* qs, const int8_t* xc, const float* xs, const float* bias,
+                   const int64_t* exclude, int S, const int64_t* invalid, int n_inv, int M, int D, int V, int K, int nsplit,
+                   void* workspace, int64_t* ids, float* scores, void* stream);
+int rh_ivf_scan_q8(const int8_t* qc, int64_t ldqc, const float* qs, const int8_t* xc_s, const float* xs_s,
+                   const float* bias_s, const int32_t* row_id, const int32_t* list_off, int nlists, const int32_t* pair,
+                   const int32_t* pair_off, const int32_t* tile_off, const int64_t* exclude, int S, int M, int D, int V,
+                   int K, int nprobe, void* partials, int64_t* ids, float* scores, void* stream);
+
 /* ---- session-based retrieval (csrc/session.hip) ---------------------------------------------------------------------
  * GRU recurrence of nn.GRU (gate order r, z, n) from the zero state: xw (B, T, 3H) = x W_ih^T (+ b_ih) for every step,
  * w_hh (3H, H) = weight_hh, b_hh (3H,) or null.  1 <= H <= RH_GRU_MAX_H, else RH_E_UNSUPPORTED.

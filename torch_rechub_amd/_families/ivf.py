@@ -1,11 +1,11 @@
-"""Inverted-file index: the list scan and the k-means update (csrc/ivf.hip)."""
+"""Inverted-file index: the list scan and the k-means update (csrc/ivf.hip; int8 tables: csrc/topk_q8.hip)."""
 import ctypes
 
 import torch
 
 from .. import _lib
 from .._opcore import _NULL, _p, _stream, require_hip
-from .topk import HALF_TABLES, _scan_inputs, _table_dtype
+from .topk import HALF_TABLES, _q8_scan_inputs, _q8_table, _quantize_rows, _scan_inputs, _table_dtype
 
 
 def ivf_supported(D, K, S=0, nprobe=1):
@@ -39,13 +39,43 @@ def ivf_scan(q, table_sorted, row_ids, list_offsets, probe, k, bias=None, exclud
         raise ValueError(f"torch_rechub_amd: ivf_scan was told dtype={dtype} and given a {table_sorted.dtype} table_sorted")
     require_hip(q, table_sorted, row_ids, list_offsets, probe, bias, exclude)
 
+    def launch(q, ldq, table, tail):
+        if table.dtype == torch.float32:
+            _lib.call("rh_ivf_scan", _p(q), ldq, _p(table), *tail)
+        else:
+            _lib.call("rh_ivf_scan_half", _p(q), ldq, _p(table), HALF_TABLES[table.dtype], *tail)
+
+    return _list_scan("ivf_scan", "table_sorted", _scan_inputs, launch, q, table_sorted, row_ids, list_offsets, probe, k, bias,
+                      exclude)
+
+
+def ivf_scan_int8(q, codes_sorted, scale_sorted, row_ids, list_offsets, probe, k, bias=None, exclude=None):
+    """``ivf_scan`` over a quantised table (csrc/topk_q8.hip): ``codes_sorted`` (V, D) int8 and ``scale_sorted`` (V,)
+    float32, the rows of ``ops.quantize_rows_int8`` grouped by list, with the score ``ops.topk_items_int8`` gives (``q``
+    float32, quantised per call by the same rule).  With every list probed the result is ``topk_items_int8``'s on the
+    un-grouped table, bit for bit.  No autograd; runs on the current stream."""
+    _q8_table("ivf_scan_int8", "codes_sorted", codes_sorted, scale_sorted)
+    require_hip(q, codes_sorted, scale_sorted, row_ids, list_offsets, probe, bias, exclude)
+
+    def launch(q, ldq, codes, tail):
+        ldqc = (int(q.shape[1]) + 15) // 16 * 16
+        qc, qs = _quantize_rows(q, ldqc)
+        _lib.call("rh_ivf_scan_q8", _p(qc), ldqc, _p(qs), _p(codes), _p(scale_sorted.detach().contiguous()), *tail)
+
+    return _list_scan("ivf_scan_int8", "codes_sorted", _q8_scan_inputs, launch, q, codes_sorted, row_ids, list_offsets, probe,
+                      k, bias, exclude)
+
+
+def _list_scan(what, tname, inputs, launch, q, table_sorted, row_ids, list_offsets, probe, k, bias, exclude):
+    """What the list-scan entry points share: the checks (``inputs`` = the ``_scan_inputs`` of the table's kind), the
+    pairs grouped by list, the partials; ``launch(q, ldq, table, tail)`` calls the kernel."""
     def refuse(M, D, V, k, S):
         if row_ids.dtype != torch.int32 or list_offsets.dtype != torch.int32 or probe.dtype != torch.int32:
-            raise ValueError("ivf_scan: row_ids, list_offsets and probe are int32 tensors")
+            raise ValueError(f"{what}: row_ids, list_offsets and probe are int32 tensors")
         if tuple(row_ids.shape) != (V,) or list_offsets.dim() != 1 or list_offsets.shape[0] < 2:
-            raise ValueError("ivf_scan: row_ids (V,) and list_offsets (nlists + 1,) expected")
+            raise ValueError(f"{what}: row_ids (V,) and list_offsets (nlists + 1,) expected")
         if probe.dim() != 2 or probe.shape[0] != M:
-            raise ValueError("ivf_scan: probe (M, nprobe) expected")
+            raise ValueError(f"{what}: probe (M, nprobe) expected")
         nlists, nprobe = int(list_offsets.shape[0]) - 1, int(probe.shape[1])
         if V < 1 or M * nprobe >= 2 ** 31 - 64 * (nlists + 2) or not ivf_supported(D, k, S, nprobe):
             from ..models.matching._listwise import no_kernel
@@ -53,8 +83,7 @@ def ivf_scan(q, table_sorted, row_ids, list_offsets, probe, k, bias=None, exclud
                             f"(1 <= D <= {_lib.H.RH_TOPK_MAX_D}, 1 <= k <= {_lib.H.RH_TOPK_MAX_K}, S <= {_lib.H.RH_TOPK_MAX_S}, "
                             f"1 <= nprobe <= {_lib.H.RH_IVF_MAX_NPROBE}, V >= 1, M nprobe < 2^31)")
 
-    q, ldq, bias, exclude, S, ids, scores = _scan_inputs("ivf_scan", "table_sorted", q, table_sorted, k, bias, exclude,
-                                                         refuse)
+    q, ldq, bias, exclude, S, ids, scores = inputs(what, tname, q, table_sorted, k, bias, exclude, refuse)
     (M, D), V, k, dev = q.shape, int(table_sorted.shape[0]), int(k), q.device
     nlists, nprobe = int(list_offsets.shape[0]) - 1, int(probe.shape[1])
     if M == 0:
@@ -72,12 +101,9 @@ def ivf_scan(q, table_sorted, row_ids, list_offsets, probe, k, bias=None, exclud
     tile_off = torch.zeros_like(pair_off)
     tile_off[1:] = torch.cumsum((pair_off[1:] - pair_off[:-1] + (rb - 1)) // rb, 0)
     part = torch.empty((8 * M * nprobe * k,), dtype=torch.uint8, device=dev)
-    tail = (_p(bias), _p(row_ids), _p(list_offsets), nlists, _p(pair), _p(pair_off), _p(tile_off),
-            _p(exclude) if S > 0 else _NULL, S, M, D, V, k, nprobe, _p(part), _p(ids), _p(scores), _stream())
-    if table_sorted.dtype == torch.float32:
-        _lib.call("rh_ivf_scan", _p(q), ldq, _p(table_sorted), *tail)
-    else:
-        _lib.call("rh_ivf_scan_half", _p(q), ldq, _p(table_sorted), HALF_TABLES[table_sorted.dtype], *tail)
+    launch(q, ldq, table_sorted, (_p(bias), _p(row_ids), _p(list_offsets), nlists, _p(pair), _p(pair_off), _p(tile_off),
+                                  _p(exclude) if S > 0 else _NULL, S, M, D, V, k, nprobe, _p(part), _p(ids), _p(scores),
+                                  _stream()))
     return ids, scores
 
 

@@ -1,4 +1,4 @@
-"""Exact top-K item retrieval (csrc/topk.hip; fp16 / bf16 tables: csrc/topk_half.hip)."""
+"""Exact top-K item retrieval (csrc/topk.hip; fp16 / bf16 tables: csrc/topk_half.hip; int8 tables: csrc/topk_q8.hip)."""
 import ctypes
 
 import torch
@@ -39,6 +39,11 @@ def _scan_inputs(what, tname, q, table, k, bias, exclude, refuse):
     _table_dtype(what, tname, table)
     if q.dtype not in (torch.float32, table.dtype) or (bias is not None and bias.dtype != torch.float32):
         raise ValueError(f"torch_rechub_amd: {what} takes float32 tensors (q may have the {tname}'s type)")
+    return _scan_prepare(what, q, table, k, bias, exclude, refuse)
+
+
+def _scan_prepare(what, q, table, k, bias, exclude, refuse):
+    """The part of ``_scan_inputs`` that does not ask for the table's type (the int8 entries check theirs themselves)."""
     if not table.is_contiguous():
         raise ValueError(f"{what}: the table must be contiguous")
     M, D = (int(v) for v in q.shape)
@@ -62,6 +67,39 @@ def _scan_inputs(what, tname, q, table, k, bias, exclude, refuse):
     return q, ldq, bias, exclude, S, ids, scores
 
 
+def _as_ids(invalid, device):
+    """``invalid`` as the kernels read it, (n_inv,) int64 contiguous, or None; the caller keeps it until it has launched."""
+    if invalid is None:
+        return None
+    if not torch.is_tensor(invalid):
+        invalid = torch.as_tensor(list(invalid), dtype=torch.int64, device=device)
+    return invalid.to(torch.int64).reshape(-1).contiguous()
+
+
+def _flat_refuse(M, D, V, k, S):
+    if V < 1 or not topk_supported(D, k, S):
+        from ..models.matching._listwise import no_kernel
+        raise no_kernel(f"top-k retrieval at D={D}, k={k}, {S} exclusions per query, V={V} "
+                        f"(1 <= D <= {_lib.H.RH_TOPK_MAX_D}, 1 <= k <= {_lib.H.RH_TOPK_MAX_K}, S <= {_lib.H.RH_TOPK_MAX_S}, V >= 1)")
+
+
+def _flat_tail(what, M, D, V, k, bias, exclude, S, invalid, nsplit, ids, scores):
+    """(tail, work): the arguments every flat entry point takes after its table, from ``bias`` on (nsplit checked or
+    planned), and the tensor of the partial lists, which the caller keeps until it has launched -- the tail holds only
+    its address; (None, None) for M = 0."""
+    n_inv = 0 if invalid is None else int(invalid.numel())
+    if nsplit is None:
+        nsplit, _ = topk_plan(M, V, k)
+    nsplit = int(nsplit)
+    if not 1 <= nsplit <= min(V, _lib.H.RH_TOPK_MAX_SPLIT):
+        raise ValueError(f"{what}: nsplit={nsplit} outside [1, min(V, {_lib.H.RH_TOPK_MAX_SPLIT})]")
+    if M == 0:
+        return None, None
+    work = torch.empty((8 * M * nsplit * k,), dtype=torch.uint8, device=ids.device)
+    return (_p(bias), _p(exclude) if S > 0 else _NULL, S, _p(invalid) if n_inv > 0 else _NULL, n_inv, M, D, V, k, nsplit,
+            _p(work), _p(ids), _p(scores), _stream()), work
+
+
 def topk_items(q, table, k, bias=None, exclude=None, invalid=None, nsplit=None):
     """(ids (M, k) int64, scores (M, k) float32): the k best items of ``table`` (V, D) for every row of ``q`` (M, D) by
     q_i . x_j (+ bias[j]), best first, exact ties to the lower id; the (M, V) scores are never formed.  ``exclude`` (M, S)
@@ -70,35 +108,83 @@ def topk_items(q, table, k, bias=None, exclude=None, invalid=None, nsplit=None):
     id -1, score -inf.  ``nsplit`` forces the number of item ranges (the result does not depend on it).  A float16 or
     bfloat16 ``table`` (half the bytes per item) scores sum_k T(q_ik) x_jk: q is rounded to the table's type T as
     ``q.to(T)`` does, the products are exact and the sum is float32.  No autograd; runs on the current stream."""
-    if invalid is not None and not torch.is_tensor(invalid):
-        invalid = torch.as_tensor(list(invalid), dtype=torch.int64, device=q.device)
+    invalid = _as_ids(invalid, q.device)
     _table_dtype("topk_items", "table", table)
     require_hip(q, table, bias, exclude, invalid)
-
-    def refuse(M, D, V, k, S):
-        if V < 1 or not topk_supported(D, k, S):
-            from ..models.matching._listwise import no_kernel
-            raise no_kernel(f"top-k retrieval at D={D}, k={k}, {S} exclusions per query, V={V} "
-                            f"(1 <= D <= {_lib.H.RH_TOPK_MAX_D}, 1 <= k <= {_lib.H.RH_TOPK_MAX_K}, S <= {_lib.H.RH_TOPK_MAX_S}, V >= 1)")
-
-    q, ldq, bias, exclude, S, ids, scores = _scan_inputs("topk_items", "table", q, table, k, bias, exclude, refuse)
+    q, ldq, bias, exclude, S, ids, scores = _scan_inputs("topk_items", "table", q, table, k, bias, exclude, _flat_refuse)
     (M, D), V, k = q.shape, int(table.shape[0]), int(k)
-    n_inv = 0
-    if invalid is not None:
-        invalid = invalid.to(torch.int64).reshape(-1).contiguous()
-        n_inv = int(invalid.numel())
-    if nsplit is None:
-        nsplit, _ = topk_plan(M, V, k)
-    nsplit = int(nsplit)
-    if not 1 <= nsplit <= min(V, _lib.H.RH_TOPK_MAX_SPLIT):
-        raise ValueError(f"topk_items: nsplit={nsplit} outside [1, min(V, {_lib.H.RH_TOPK_MAX_SPLIT})]")
-    if M == 0:
+    tail, work = _flat_tail("topk_items", M, D, V, k, bias, exclude, S, invalid, nsplit, ids, scores)
+    if tail is None:
         return ids, scores
-    work = torch.empty((8 * M * nsplit * k,), dtype=torch.uint8, device=q.device)
-    tail = (_p(bias), _p(exclude) if S > 0 else _NULL, S, _p(invalid) if n_inv > 0 else _NULL, n_inv, M, D, V, k, nsplit,
-            _p(work), _p(ids), _p(scores), _stream())
     if table.dtype == torch.float32:
         _lib.call("rh_topk_fwd", _p(q), ldq, _p(table.detach()), *tail)
     else:
         _lib.call("rh_topk_half_fwd", _p(q), ldq, _p(table.detach()), HALF_TABLES[table.dtype], *tail)
+    return ids, scores
+
+
+def _q8_table(what, cname, codes, scale):
+    """Refuses what is not a quantised table (host-side, made before anything else): ``codes`` (V, D) int8 and ``scale``
+    (V,) float32, as ``quantize_rows_int8`` returns them."""
+    if codes.dtype != torch.int8 or codes.dim() != 2:
+        raise ValueError(f"torch_rechub_amd: {what} takes (V, D) int8 {cname}, got {codes.dtype} {tuple(codes.shape)}")
+    if scale.dtype != torch.float32 or tuple(scale.shape) != (codes.shape[0],):
+        raise ValueError(f"torch_rechub_amd: {what} takes one float32 scale per row of {cname} (V,), got {scale.dtype} "
+                         f"{tuple(scale.shape)}")
+
+
+def _q8_scan_inputs(what, cname, q, codes, k, bias, exclude, refuse):
+    """``_scan_inputs`` for a quantised table: q (M, D) float32 and bias (V,) float32 only."""
+    if q.dim() != 2 or q.shape[1] != codes.shape[1]:
+        raise ValueError(f"{what}: q (M, D) and {cname} (V, D) expected")
+    if q.dtype != torch.float32 or (bias is not None and bias.dtype != torch.float32):
+        raise ValueError(f"torch_rechub_amd: {what} takes float32 q and bias")
+    return _scan_prepare(what, q, codes, k, bias, exclude, refuse)
+
+
+def _quantize_rows(x, ldc):
+    """``quantize_rows_int8`` of x (M, D) float32 with unit column stride into codes (M, ldc), zero from column D on."""
+    M, D = (int(v) for v in x.shape)
+    codes = torch.empty((M, ldc), dtype=torch.int8, device=x.device)
+    scale = torch.empty((M,), dtype=torch.float32, device=x.device)
+    if M > 0:
+        _lib.call("rh_quantize_rows_q8", _p(x), int(x.stride(0)) if M > 1 else D, M, D, _p(codes), ldc, _p(scale), _stream())
+    return codes, scale
+
+
+def quantize_rows_int8(x):
+    """(codes (M, D) int8, scale (M,) float32) of ``x`` (M, D) float32, one scale per row: with m = max_k |x_k|,
+    scale = m / 127 and code_k = clamp(rint(x_k / scale), -127, 127), rounding to nearest even, both divisions correctly
+    rounded float32 divisions (numpy float32 gives the same bits); a zero row has scale 1 and codes 0.  x_k is about
+    scale * code_k, off by at most scale / 2.  The one rule of the int8 index: it builds the table and quantises every
+    batch of queries.  NaN and inf are out of scope.  No autograd; runs on the current stream."""
+    if x.dim() != 2 or x.shape[1] < 1 or x.dtype != torch.float32:
+        raise ValueError(f"torch_rechub_amd: quantize_rows_int8 takes a float32 (M, D) tensor with D >= 1, got {x.dtype} "
+                         f"{tuple(x.shape)}")
+    require_hip(x)
+    x = x.detach()
+    if x.shape[0] > 0 and (x.stride(1) != 1 or x.stride(0) < x.shape[1]):
+        x = x.contiguous()
+    return _quantize_rows(x, int(x.shape[1]))
+
+
+def topk_items_int8(q, codes, scale, k, bias=None, exclude=None, invalid=None, nsplit=None):
+    """``topk_items`` over a quantised table (csrc/topk_q8.hip): ``codes`` (V, D) int8 contiguous and ``scale`` (V,)
+    float32 as ``quantize_rows_int8`` makes them, a quarter of the float32 bytes per item.  ``q`` (M, D) float32 is
+    quantised per call by the same rule (qc, qs), and
+      score[i][j] = ((float32)(sum_k qc_ik xc_jk) * qs_i) * scale_j (+ bias_j):
+    the integer sum is exact, the two multiplications and the addition are single float32 operations in that order, so
+    the answer is defined bit for bit and does not depend on ``nsplit``.  Order, ties, ``exclude``, ``invalid`` and the
+    (-1, -inf) tail are ``topk_items``'.  No autograd; runs on the current stream."""
+    invalid = _as_ids(invalid, q.device)
+    _q8_table("topk_items_int8", "codes", codes, scale)
+    require_hip(q, codes, scale, bias, exclude, invalid)
+    q, _, bias, exclude, S, ids, scores = _q8_scan_inputs("topk_items_int8", "codes", q, codes, k, bias, exclude, _flat_refuse)
+    (M, D), V, k = q.shape, int(codes.shape[0]), int(k)
+    tail, work = _flat_tail("topk_items_int8", M, D, V, k, bias, exclude, S, invalid, nsplit, ids, scores)
+    if tail is None:
+        return ids, scores
+    ldqc = (D + 15) // 16 * 16
+    qc, qs = _quantize_rows(q, ldqc)
+    _lib.call("rh_topk_q8_fwd", _p(qc), ldqc, _p(qs), _p(codes.detach()), _p(scale.detach().contiguous()), *tail)
     return ids, scores

@@ -105,19 +105,21 @@ class ExactIndex(object):
     252-296), on the streaming top-K kernel: ``ExactIndex().fit(item_embedding)`` then ``query(v, n)``, so that the
     examples' ``match_evaluation`` runs with one name changed.  ``metric``: "angular" (Annoy's default), "L2" or "IP".
     ``n_trees`` and ``search_k`` are accepted and ignored: there is no approximation to tune.  ``dtype``: the storage type
-    of ``serving.HipIndexer`` (None: float32; torch.float16 / torch.bfloat16 halve the table)."""
+    of ``serving.HipIndexer`` (None: float32; torch.float16 / torch.bfloat16 halve the table); ``quantizer="SQ8"``: its
+    int8 codes with a scale per row (a quarter of the table; approximate)."""
 
-    def __init__(self, metric="angular", n_trees=None, search_k=None, device=None, dtype=None):
-        from ..serving.hip import _check_metric
+    def __init__(self, metric="angular", n_trees=None, search_k=None, device=None, dtype=None, quantizer=None):
+        from ..serving.hip import _check_metric, _check_quantizer
         self._metric = _check_metric({"euclidean": "L2", "l2": "L2", "dot": "IP", "ip": "IP"}.get(metric, metric))
         self._device = device
         self._dtype = torch.float32 if dtype is None else dtype
+        self._quantizer = _check_quantizer(quantizer, self._dtype)
         self._indexer = None
 
     def fit(self, X):
         """Index the rows of ``X`` (n, d), a numpy array or a tensor."""
         from ..serving.hip import HipIndexer
-        self._indexer = HipIndexer(torch.as_tensor(X), self._metric, self._device, self._dtype)
+        self._indexer = HipIndexer(torch.as_tensor(X), self._metric, self._device, self._dtype, self._quantizer)
         return self
 
     def set_query_arguments(self, search_k=None):
