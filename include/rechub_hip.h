@@ -1187,6 +1187,38 @@ int rh_ivf_scan_q8(const int8_t* qc, int64_t ldqc, const float* qs, const int8_t
                    const int32_t* pair_off, const int32_t* tile_off, const int64_t* exclude, int S, int M, int D, int V,
                    int K, int nprobe, void* partials, int64_t* ids, float* scores, void* stream);
 
+/* ---- multi-interest top-K retrieval (csrc/topk_multi.hip) -----------------------------------------------------------
+ * q holds I vectors per user, one per interest (the mode="user" output of MIND, ComiRec-DR / -SA and SINE), and every
+ * user gets ONE K-list:
+ *   t(u,i,j)  = q[u,i,:] . x[j,:]        the score of rh_topk_fwd (rh_topk_half_fwd) for the row (u, i), bit for bit
+ *   t'(u,i,j) = t + qbias[u,i]           one fp32 addition; skipped when qbias is null
+ *   s(u,j)    = max_i t'(u,i,j)
+ *   score     = s + bias[j]              one fp32 addition after the fold; skipped when bias is null
+ * The top K of s(u, .) is the merged, de-duplicated union of the I per-interest top-K lists (an item of it reaches its
+ * maximum under some interest i*; K items ahead of it there would each have s at least their score under i*), so the
+ * lists of the interests are never formed.  q is read as M I rows (u I + i) of D fp32 with row stride ldq; qbias (M, I)
+ * fp32 or null, -inf = the interest is absent (its row of q is not read); a user with every interest absent has no
+ * candidates.  x (V, D) contiguous, fp32 (rh_topk_multi_fwd) or fp16 / bf16 (rh_topk_multi_half_fwd, is_bf16 = 0 / 1; q is
+ * rounded to the table's type as rh_topk_half_fwd rounds it, qbias and bias stay fp32).  exclude (M, S) int64 per USER.
+ * ids (M, K) int64 and scores (M, K) fp32.  The order (score descending, id ascending), the tie rule, exclude, invalid, the
+ * (-1, -inf) tail, the independence of nsplit and the absence of atomics are rh_topk_fwd's; an item appears at most once.
+ * With I = 1 and no qbias the result is rh_topk_fwd's bit for bit.  NaN is out of scope.
+ * A user takes Ip = the next power of two >= I rows of the 64-row tile, a workgroup min(64 / Ip, rows of rh_topk_fwd's
+ * tile at K) users; the fold over the interests happens in the accumulator registers.  workspace: 8 M nsplit K bytes (per
+ * user, not per interest); rh_topk_multi_plan applies rh_topk_plan's rule to that many row tiles.
+ * Limits: rh_topk_fwd's and 1 <= I <= RH_LISTWISE_MAX_I (16: the interests the models above can have), M I < 2^31, else
+ * RH_E_UNSUPPORTED; M = 0 returns at once.  rh_topk_multi_supported and rh_topk_multi_plan answer through HOST pointers.
+ * replaces: the multi-interest branch of match_evaluation in examples/matching/movielens_utils.py:24-39 (one Annoy query
+ *           per interest, then a pandas sort and drop_duplicates per user on the host). */
+int rh_topk_multi_supported(int D, int K, int S, int I, int* supported);
+int rh_topk_multi_plan(int M, int I, int V, int K, int* nsplit, int64_t* workspace_bytes);
+int rh_topk_multi_fwd(const float* q, int64_t ldq, int I, const float* qbias, const float* x, const float* bias,
+                      const int64_t* exclude, int S, const int64_t* invalid, int n_inv, int M, int D, int V, int K,
+                      int nsplit, void* workspace, int64_t* ids, float* scores, void* stream);
+int rh_topk_multi_half_fwd(const float* q, int64_t ldq, int I, const float* qbias, const void* x, int is_bf16,
+                           const float* bias, const int64_t* exclude, int S, const int64_t* invalid, int n_inv, int M, int D,
+                           int V, int K, int nsplit, void* workspace, int64_t* ids, float* scores, void* stream);
+
 /* ---- session-based retrieval (csrc/session.hip) ---------------------------------------------------------------------
  * GRU recurrence of nn.GRU (gate order r, z, n) from the zero state: xw (B, T, 3H) = x W_ih^T (+ b_ih) for every step,
  * w_hh (3H, H) = weight_hh, b_hh (3H,) or null.  1 <= H <= RH_GRU_MAX_H, else RH_E_UNSUPPORTED.

@@ -1,4 +1,5 @@
-"""Exact top-K item retrieval (csrc/topk.hip; fp16 / bf16 tables: csrc/topk_half.hip; int8 tables: csrc/topk_q8.hip)."""
+"""Exact top-K item retrieval (csrc/topk.hip; fp16 / bf16 tables: csrc/topk_half.hip; int8 tables: csrc/topk_q8.hip;
+(M, I, D) multi-interest queries, one list per user: csrc/topk_multi.hip)."""
 import ctypes
 
 import torch
@@ -120,6 +121,76 @@ def topk_items(q, table, k, bias=None, exclude=None, invalid=None, nsplit=None):
         _lib.call("rh_topk_fwd", _p(q), ldq, _p(table.detach()), *tail)
     else:
         _lib.call("rh_topk_half_fwd", _p(q), ldq, _p(table.detach()), HALF_TABLES[table.dtype], *tail)
+    return ids, scores
+
+
+def topk_multi_supported(D, K, S=0, I=1):
+    """Whether csrc/topk_multi.hip takes I interests per user at width D, K results and S exclusions per user
+    (``topk_supported`` and 1 <= I <= RH_LISTWISE_MAX_I)."""
+    return bool(_lib.query("rh_topk_multi_supported", int(D), int(K), int(S), int(I)))
+
+
+def topk_multi_plan(M, I, V, K):
+    """(nsplit, workspace_bytes) for M users of I interests: ``topk_plan``'s rule over the users' row tiles; the partial
+    lists are per user (8 M nsplit K bytes)."""
+    return _lib.query("rh_topk_multi_plan", int(M), int(I), int(V), int(K), out=(ctypes.c_int, ctypes.c_int64))
+
+
+def topk_items_multi(q, table, k, qbias=None, bias=None, exclude=None, invalid=None, nsplit=None):
+    """(ids (M, k) int64, scores (M, k) float32): for ``q`` (M, I, D), one vector per interest of a user, the k best items
+    of ``table`` (V, D) for every USER by max_i (q[u, i] . x_j + qbias[u, i]) + bias[j] -- the merged, de-duplicated union
+    of the I per-interest ``topk_items`` lists, formed in one scan with one list per user (csrc/topk_multi.hip).  ``qbias``
+    (M, I) float32: -inf marks an absent interest; a user without any interest gets the (-1, -inf) tail.  ``exclude`` (M, S)
+    is per user.  Order, ties (to the lower id), ``invalid``, the tail, ``nsplit`` and a float16 / bfloat16 ``table`` are
+    ``topk_items``'; with I = 1 and no ``qbias`` the result is ``topk_items(q[:, 0])`` bit for bit.  An int8 table is not
+    built.  No autograd; runs on the current stream."""
+    what = "topk_items_multi"
+    invalid = _as_ids(invalid, q.device)
+    if table.dtype == torch.int8:
+        raise ValueError(f"torch_rechub_amd: {what} over an int8 (SQ8) table is not built; use a float32, float16 or "
+                         "bfloat16 table")
+    _table_dtype(what, "table", table)
+    if q.dim() != 3 or table.dim() != 2 or q.shape[2] != table.shape[1]:
+        raise ValueError(f"{what}: q (M, I, D) and table (V, D) expected")
+    if q.dtype not in (torch.float32, table.dtype) or (bias is not None and bias.dtype != torch.float32):
+        raise ValueError(f"torch_rechub_amd: {what} takes float32 tensors (q may have the table's type)")
+    if not table.is_contiguous():
+        raise ValueError(f"{what}: the table must be contiguous")
+    (M, I, D), V, k = (int(v) for v in q.shape), int(table.shape[0]), int(k)
+    if qbias is not None and (tuple(qbias.shape) != (M, I) or qbias.dtype != torch.float32):
+        raise ValueError(f"{what}: qbias (M, I) float32 expected")
+    if exclude is not None and (exclude.dim() != 2 or exclude.shape[0] != M):
+        raise ValueError(f"{what}: exclude (M, S) expected, one row per user")
+    S = 0 if exclude is None else int(exclude.shape[1])
+    if bias is not None and tuple(bias.shape) != (V,):
+        raise ValueError(f"{what}: bias (V,) expected")
+    if V < 1 or not topk_multi_supported(D, k, S, I):
+        from ..models.matching._listwise import no_kernel
+        raise no_kernel(f"multi-interest top-k retrieval at I={I}, D={D}, k={k}, {S} exclusions per user, V={V} "
+                        f"(1 <= I <= {_lib.H.RH_LISTWISE_MAX_I}, 1 <= D <= {_lib.H.RH_TOPK_MAX_D}, 1 <= k <= "
+                        f"{_lib.H.RH_TOPK_MAX_K}, S <= {_lib.H.RH_TOPK_MAX_S}, V >= 1)")
+    require_hip(q, table, qbias, bias, exclude, invalid)
+    q = q.detach().float()
+    # one stride ldq from an interest row to the next, over users and interests alike; anything else is copied
+    ldq = int(q.stride(1)) if I > 1 else (int(q.stride(0)) if M > 1 else D)
+    if M > 0 and (q.stride(2) != 1 or ldq < D or (I > 1 and M > 1 and q.stride(0) != I * ldq)):
+        q, ldq = q.contiguous(), D
+    qbias = None if qbias is None else qbias.detach().contiguous()
+    bias = None if bias is None else bias.detach().contiguous()
+    if S > 0:
+        exclude = exclude.to(torch.int64).contiguous()
+    ids = torch.empty((M, k), dtype=torch.int64, device=q.device)
+    scores = torch.empty((M, k), dtype=torch.float32, device=q.device)
+    if nsplit is None:
+        nsplit, _ = topk_multi_plan(M, I, V, k)
+    # work, invalid and qbias stay alive in this frame until the launch: the argument tuple holds only their addresses
+    tail, work = _flat_tail(what, M, D, V, k, bias, exclude, S, invalid, nsplit, ids, scores)
+    if tail is None:
+        return ids, scores
+    if table.dtype == torch.float32:
+        _lib.call("rh_topk_multi_fwd", _p(q), ldq, I, _p(qbias), _p(table.detach()), *tail)
+    else:
+        _lib.call("rh_topk_multi_half_fwd", _p(q), ldq, I, _p(qbias), _p(table.detach()), HALF_TABLES[table.dtype], *tail)
     return ids, scores
 
 

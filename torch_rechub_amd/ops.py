@@ -3742,7 +3742,8 @@ from ._families.rq import rq_supported, _rq_check, rq_forward, _sinkhorn_level, 
 from ._families.hstu import _HstuAttnFn, hstu_attention
 from ._families.hllm import _SoftmaxAttnFn, softmax_attention
 from ._families.session import _AttnPoolFn, additive_attention_pool, _DropoutFn, dropout
-from ._families.topk import topk_supported, topk_plan, _scan_inputs, topk_items, quantize_rows_int8, topk_items_int8
+from ._families.topk import (topk_supported, topk_plan, _scan_inputs, topk_items, quantize_rows_int8, topk_items_int8,
+                             topk_multi_supported, topk_multi_plan, topk_items_multi)
 from ._families.ivf import ivf_supported, ivf_plan, ivf_scan, ivf_scan_int8, ivf_list_mean
 from ._families.sasrec import (_sasrec_check, _sasrec_ntiles, _ln_param_grads, _sample_view, _SasrecInputFn, _seq_ids,
                                _drop_p, sasrec_input, _SasrecHeadFn, _LayerNormFn, layer_norm, sasrec_head)

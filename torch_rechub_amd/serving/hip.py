@@ -30,6 +30,11 @@ searches the codes; "L2" takes -|x^|^2 of the dequantised rows x^ = scale * code
 2 q and returns |q|^2 minus the score, clamped at 0; "angular" normalises in float32 and then quantises, so its rows are
 only approximately unit and its distances approximate (by how much has not been measured).  An index file of
 a quantised index keeps the codes and the scales (for "angular": of the unit rows) under keys of their own.
+
+``HipIndexer.query`` also takes (n, I, d) queries, one vector per interest of a user (MIND, ComiRec, SINE): every user gets
+one list, each item once with its best value over the interests (``ops.topk_items_multi``, csrc/topk_multi.hip) -- the
+merged, de-duplicated per-interest lists of the reference's ``match_evaluation``.  Not built for ``quantizer="SQ8"`` nor for
+``HipIvfIndexer``: both raise.
 """
 import contextlib
 
@@ -142,6 +147,40 @@ def _metric_query(metric, dev, embeddings, exclude, bias, search, dtype=torch.fl
     return ids.to(embeddings.device), val.to(embeddings.device)
 
 
+def _metric_query_multi(metric, dev, embeddings, exclude, bias, search, dtype=torch.float32):
+    """``_metric_query`` for (n, I, d) embeddings, one vector per interest of a user: ``search(q, qbias, bias, exclude) ->
+    (ids, scores)`` is ``ops.topk_items_multi``, max_i (q_i . x + qbias_i) + bias per user.  "IP": q as given; "L2": 2 q_i
+    with qbias = -|q_i|^2 and the index's bias = -|x|^2, so the value max(-score, 0) is the smallest squared distance over
+    the interests; "angular": unit rows per interest.  A row holding a nan is an absent interest: it is zeroed and its
+    qbias is -inf.  qbias is always handed over (zeros for "IP" and "angular"), so that no host synchronisation has to ask
+    whether an interest is absent; adding 0 changes no value."""
+    q = embeddings.detach().to(dev, torch.float32)
+    if exclude is not None:
+        exclude = exclude.to(dev)
+    absent = torch.isnan(q).any(dim=2)
+    q = q.masked_fill(absent.unsqueeze(2), 0.0)
+    qbias = torch.zeros(q.shape[:2], dtype=torch.float32, device=dev)
+    if metric == "L2":
+        if dtype != torch.float32:
+            q = q.to(dtype).float()
+        qbias = -(q * q).sum(dim=2)
+        q = q * 2.0
+    elif metric == "angular":
+        q, bias = _unit_rows(q.reshape(-1, q.shape[2])).reshape(q.shape), None
+    else:
+        bias = None
+    ids, s = search(q, qbias.masked_fill(absent, float("-inf")), bias, exclude)
+    if metric == "L2":
+        val = (-s).clamp_min(0.0)
+    elif metric == "angular":
+        val = (2.0 - 2.0 * s).clamp_min(0.0).sqrt()
+    else:
+        val = s
+    if metric != "IP":
+        val = torch.where(ids < 0, torch.full_like(val, float("inf")), val)
+    return ids.to(embeddings.device), val.to(embeddings.device)
+
+
 class HipIndexer(BaseIndexer):
     """``table`` (n, d) on the device, searched exactly.  ``dtype``: the type it is stored and searched in (float32,
     float16 or bfloat16; None: a half table keeps its type, anything else becomes float32).  ``quantizer="SQ8"``: int8
@@ -187,7 +226,20 @@ class HipIndexer(BaseIndexer):
 
     def query(self, embeddings, top_k, *, exclude=None):
         """(ids (n, top_k) int64, values (n, top_k) float32) on the queries' device, best first.  ``exclude`` (n, S) int64:
-        per-query ids that are never returned (entries outside [0, len(index)) are padding)."""
+        per-query ids that are never returned (entries outside [0, len(index)) are padding).  3-D ``embeddings`` (n, I, d),
+        one vector per interest of a user (MIND, ComiRec, SINE): one merged list per user, every item once with its best
+        value over the interests (``ops.topk_items_multi``); a row of nan is an absent interest."""
+        if embeddings.dim() == 3:
+            if self.quantizer is not None:
+                raise ValueError(f"multi-interest (n, I, d) queries over a quantizer={self.quantizer!r} index are not built; "
+                                 "use a float32, float16 or bfloat16 index")
+
+            def search_multi(q, qbias, bias, exclude):
+                return self._ops.topk_items_multi(q, self._search, top_k, qbias=qbias, bias=bias, exclude=exclude)
+
+            return _metric_query_multi(self.metric, self._table.device, embeddings, exclude, self._bias, search_multi,
+                                       self.dtype)
+
         def search(q, bias, exclude):
             if self.quantizer is not None:
                 return self._ops.topk_items_int8(q, self._search, self._scale, top_k, bias=bias, exclude=exclude)
@@ -305,6 +357,8 @@ class HipIvfIndexer(BaseIndexer):
 
     def query(self, embeddings, top_k, *, exclude=None, nprobe=None):
         """As ``HipIndexer.query``, over the ``nprobe`` (default: the index's) nearest lists of every query."""
+        if embeddings.dim() == 3:
+            raise ValueError("multi-interest (n, I, d) queries over an IVF index are not built; use index_type=\"Flat\"")
         nprobe = self.nprobe if nprobe is None else self._clip(nprobe)
         ops = self._ops
 

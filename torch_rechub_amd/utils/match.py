@@ -127,11 +127,13 @@ class ExactIndex(object):
 
     def query(self, v, n):
         """1-D ``v``: (ids list, distances list) of the ``n`` nearest rows, as ``Annoy.query``.  2-D ``v`` (a batch
-        extension): the two (len(v), n) tensors of ``HipIndexer.query``."""
+        extension): the two (len(v), n) tensors of ``HipIndexer.query``.  3-D ``v`` (users, interests, d), the user
+        embedding of MIND, ComiRec and SINE: the same two tensors, one merged list per user -- what the examples'
+        ``match_evaluation`` builds per user from one query per interest, a sort and ``drop_duplicates``."""
         if self._indexer is None:
             raise RuntimeError("ExactIndex.query before fit")
         v = torch.as_tensor(v)
-        if v.dim() == 2:
+        if v.dim() in (2, 3):
             return self._indexer.query(v, n)
         if v.dim() != 1:
             raise ValueError("query takes a 1-D vector or a 2-D batch")
