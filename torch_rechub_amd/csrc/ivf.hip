@@ -21,6 +21,8 @@
 
 namespace {
 
+static_assert(kTopkMaxSplit >= kIvfMaxProbe, "one merge kernel holds the heads of either scan's lists");
+
 size_t ivf_lds_bytes(int K) { return topk_lds_bytes(K) + (size_t)kT * 4; }
 
 __global__ __launch_bounds__(RH_BLOCK) void ivf_scan_kernel(const IvfArgs a) {
@@ -30,15 +32,6 @@ __global__ __launch_bounds__(RH_BLOCK) void ivf_scan_kernel(const IvfArgs a) {
   int64_t lo, hi;
   if (!ivf_tile(a, prs, lo, hi)) return;
   topk_scan_tiles(s, IvfRule{prs, a.row_id, s.nlist, s.K}, lo, hi, lds);
-}
-
-// one wavefront per query: one list per slot
-__global__ __launch_bounds__(RH_WAVE) void ivf_merge_kernel(const IvfArgs a) {
-  __shared__ int hp[kIvfMaxProbe];
-  const int64_t row = blockIdx.x;
-  const TopkScanArgs& s = a.s;
-  topk_merge_row(s.part_s + row * s.nlist * s.K, s.part_i + row * s.nlist * s.K, s.nlist, s.K, s.ids + row * s.K,
-                 s.scores + row * s.K, hp, threadIdx.x);
 }
 
 __global__ __launch_bounds__(RH_BLOCK) void ivf_list_mean_kernel(const float* __restrict__ xs,
@@ -104,7 +97,7 @@ extern "C" int rh_ivf_scan(const float* q, int64_t ldq, const float* xs, const f
   if (int rc = rh_reserve_lds(reserved, ivf_scan_kernel, ivf_lds_bytes(128), "rh_ivf_scan")) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(ivf_scan_kernel, dim3((unsigned)grid), dim3(RH_BLOCK), ivf_lds_bytes(K), st, a);
-  hipLaunchKernelGGL(ivf_merge_kernel, dim3((unsigned)M), dim3(RH_WAVE), 0, st, a);
+  hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)M), dim3(RH_WAVE), 0, st, a.s);
   RH_LAUNCH_CHECK("rh_ivf_scan");
   return 0;
 }

@@ -27,27 +27,6 @@ __global__ __launch_bounds__(RH_BLOCK) void topk_scan_kernel(const TopkArgs a) {
   topk_scan_tiles(a.s, rule, lo, hi, lds);
 }
 
-// one wavefront per row
-__global__ __launch_bounds__(RH_WAVE) void topk_merge_kernel(const TopkArgs a) {
-  __shared__ int hp[kTopkMaxSplit];
-  const int64_t row = blockIdx.x;
-  const TopkScanArgs& s = a.s;
-  topk_merge_row(s.part_s + row * s.nlist * s.K, s.part_i + row * s.nlist * s.K, s.nlist, s.K, s.ids + row * s.K,
-                 s.scores + row * s.K, hp, threadIdx.x);
-}
-
-// default ranges: enough workgroups for one round over the chip's 256 compute units, ranges of at least 4096 columns (the
-// lists of a range cost about K (1 + ln(range / K)) insertions per row whatever its length, so short ranges only add work)
-int topk_default_split(int M, int V, int K) {
-  const int64_t nrt = ((int64_t)M + topk_rows(K) - 1) / topk_rows(K);
-  int64_t s = nrt > 0 ? (256 + nrt - 1) / nrt : 1;
-  const int64_t cap = V / 4096;
-  if (s > cap) s = cap;
-  if (s > kTopkMaxSplit) s = kTopkMaxSplit;
-  if (s < 1) s = 1;
-  return (int)s;
-}
-
 }  // namespace
 
 extern "C" int rh_topk_supported(int D, int K, int S, int* supported) {
@@ -60,7 +39,7 @@ extern "C" int rh_topk_plan(int M, int V, int K, int* nsplit, int64_t* workspace
   RH_REQUIRE(nsplit != nullptr && workspace_bytes != nullptr, RH_E_BADARG, "rh_topk_plan: null pointer");
   RH_REQUIRE(M >= 0 && V >= 1, RH_E_BADARG, "rh_topk_plan: M=%d V=%d (M >= 0, V >= 1)", M, V);
   RH_REQUIRE(K >= 1 && K <= kTopkMaxK, RH_E_UNSUPPORTED, "rh_topk_plan: K=%d unsupported (1 <= K <= %d)", K, kTopkMaxK);
-  *nsplit = topk_default_split(M, V, K);
+  *nsplit = topk_default_split(M, V, topk_rows(K));
   *workspace_bytes = (int64_t)M * *nsplit * K * 8;
   return 0;
 }
@@ -79,7 +58,7 @@ extern "C" int rh_topk_fwd(const float* q, int64_t ldq, const float* x, const fl
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int64_t nrt = ((int64_t)M + a.s.RB - 1) / a.s.RB;
   hipLaunchKernelGGL(topk_scan_kernel, dim3((unsigned)nrt, nsplit), dim3(RH_BLOCK), topk_lds_bytes(K), st, a);
-  hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)M), dim3(RH_WAVE), 0, st, a);
+  hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)M), dim3(RH_WAVE), 0, st, a.s);
   RH_LAUNCH_CHECK("rh_topk_fwd");
   return 0;
 }

@@ -12,8 +12,6 @@ namespace {
 
 static_assert(kTopkMaxSplit >= kIvfMaxProbe, "one merge kernel holds the heads of either scan's lists");
 
-size_t ivf_half_lds_bytes(int K) { return topk_half_lds_bytes(K) + (size_t)kT * 4; }
-
 // vec: bit 0 = 16-byte loads of the table are legal, bit 1 = of q
 template <typename T>
 __global__ __launch_bounds__(RH_BLOCK) void topk_half_scan_kernel(const TopkArgs a, int vec) {
@@ -31,20 +29,6 @@ __global__ __launch_bounds__(RH_BLOCK) void ivf_half_scan_kernel(const IvfArgs a
   int64_t lo, hi;
   if (!ivf_tile(a, prs, lo, hi)) return;
   topk_half_scan_tiles<T>(s, IvfRule{prs, a.row_id, s.nlist, s.K}, lo, hi, lds, (vec & 1) != 0, (vec & 2) != 0);
-}
-
-// one wavefront per query row: its s.nlist lists (ranges or slots) into ids / scores
-__global__ __launch_bounds__(RH_WAVE) void topk_half_merge_kernel(const TopkScanArgs s) {
-  __shared__ int hp[kTopkMaxSplit];
-  const int64_t row = blockIdx.x;
-  topk_merge_row(s.part_s + row * s.nlist * s.K, s.part_i + row * s.nlist * s.K, s.nlist, s.K, s.ids + row * s.K,
-                 s.scores + row * s.K, hp, threadIdx.x);
-}
-
-int vec_flags(const TopkScanArgs& s) {
-  const bool xvec = s.D % 8 == 0 && reinterpret_cast<uintptr_t>(s.x) % 16 == 0;
-  const bool qvec = s.ldq % 4 == 0 && reinterpret_cast<uintptr_t>(s.q) % 16 == 0;
-  return (xvec ? 1 : 0) | (qvec ? 2 : 0);
 }
 
 template <typename T>
@@ -89,7 +73,7 @@ extern "C" int rh_topk_half_fwd(const float* q, int64_t ldq, const void* x, int 
   if (!go) return 0;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (int rc = is_bf16 == 0 ? launch_flat<TableF16>(a, st) : launch_flat<TableBf16>(a, st)) return rc;
-  hipLaunchKernelGGL(topk_half_merge_kernel, dim3((unsigned)M), dim3(RH_WAVE), 0, st, a.s);
+  hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)M), dim3(RH_WAVE), 0, st, a.s);
   RH_LAUNCH_CHECK("rh_topk_half_fwd");
   return 0;
 }
@@ -109,7 +93,7 @@ extern "C" int rh_ivf_scan_half(const float* q, int64_t ldq, const void* xs, int
   if (!go) return 0;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (int rc = is_bf16 == 0 ? launch_ivf<TableF16>(a, grid, st) : launch_ivf<TableBf16>(a, grid, st)) return rc;
-  hipLaunchKernelGGL(topk_half_merge_kernel, dim3((unsigned)M), dim3(RH_WAVE), 0, st, a.s);
+  hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)M), dim3(RH_WAVE), 0, st, a.s);
   RH_LAUNCH_CHECK("rh_ivf_scan_half");
   return 0;
 }

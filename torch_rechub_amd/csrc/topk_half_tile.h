@@ -40,6 +40,16 @@ static_assert(kHScore >= kHBuf && kHScore % 16 == 0 && kHBuf % 16 == 0, "the sco
 __host__ __device__ inline size_t topk_half_lds_bytes(int K) {
   return (size_t)kHStage + (size_t)topk_rows(K) * K * 8 + (size_t)2 * kT * 4;
 }
+// with [64] ints behind them: the pair indices of a list-scan workgroup (IvfRule::prs)
+inline size_t ivf_half_lds_bytes(int K) { return topk_half_lds_bytes(K) + (size_t)kT * 4; }
+
+// the `vec` of a half-table scan kernel: bit 0 = 16-byte loads of the table are legal (a row is a multiple of 16 bytes,
+// the base aligned), bit 1 = of q
+inline int vec_flags(const TopkScanArgs& s) {
+  const bool xvec = s.D % 8 == 0 && reinterpret_cast<uintptr_t>(s.x) % 16 == 0;
+  const bool qvec = s.ldq % 4 == 0 && reinterpret_cast<uintptr_t>(s.q) % 16 == 0;
+  return (xvec ? 1 : 0) | (qvec ? 2 : 0);
+}
 
 // the two table types: the bits of T(f), round to nearest even (NaN is out of scope), and the MFMA over 16 k
 struct TableF16 {

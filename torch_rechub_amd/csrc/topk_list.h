@@ -273,3 +273,24 @@ static __device__ __forceinline__ void topk_merge_row(const float* ps, const int
     scores[e] = -INFINITY;
   }
 }
+
+// The merge kernel of every scan: one wavefront per row of ids / scores, its s.nlist lists (ranges or slots) of the partials
+static __global__ __launch_bounds__(RH_WAVE) void topk_merge_kernel(const TopkScanArgs s) {
+  __shared__ int hp[kTopkMaxSplit];
+  const int64_t row = blockIdx.x;
+  topk_merge_row(s.part_s + row * s.nlist * s.K, s.part_i + row * s.nlist * s.K, s.nlist, s.K, s.ids + row * s.K,
+                 s.scores + row * s.K, hp, threadIdx.x);
+}
+
+// default ranges of a flat scan with `rows` list rows per workgroup: enough workgroups for one round over the chip's 256
+// compute units, ranges of at least 4096 columns (the lists of a range cost about K (1 + ln(range / K)) insertions per row
+// whatever its length, so short ranges only add work)
+inline int topk_default_split(int M, int V, int rows) {
+  const int64_t nrt = ((int64_t)M + rows - 1) / rows;
+  int64_t s = nrt > 0 ? (256 + nrt - 1) / nrt : 1;
+  const int64_t cap = V / 4096;
+  if (s > cap) s = cap;
+  if (s > kTopkMaxSplit) s = kTopkMaxSplit;
+  if (s < 1) s = 1;
+  return (int)s;
+}

@@ -26,28 +26,7 @@ __global__ __launch_bounds__(RH_BLOCK, P::kWaves) void topk_multi_scan_kernel(co
   topk_multi_scan_tiles<P>(a, lds, vec);
 }
 
-// one wavefront per user
-__global__ __launch_bounds__(RH_WAVE) void topk_multi_merge_kernel(const TopkScanArgs s) {
-  __shared__ int hp[kTopkMaxSplit];
-  const int64_t row = blockIdx.x;
-  topk_merge_row(s.part_s + row * s.nlist * s.K, s.part_i + row * s.nlist * s.K, s.nlist, s.K, s.ids + row * s.K,
-                 s.scores + row * s.K, hp, threadIdx.x);
-}
-
 bool multi_shape_ok(int D, int K, int S, int I) { return topk_shape_ok(D, K, S) && I >= 1 && I <= kMultiMaxI; }
-
-// the flat scan's rule over ceil(M / U) row tiles: one round over the chip's 256 compute units, ranges of at least 4096
-// columns
-int multi_default_split(int M, int I, int V, int K) {
-  const int U = topk_multi_users(I, K);
-  const int64_t nrt = ((int64_t)M + U - 1) / U;
-  int64_t s = nrt > 0 ? (256 + nrt - 1) / nrt : 1;
-  const int64_t cap = V / 4096;
-  if (s > cap) s = cap;
-  if (s > kTopkMaxSplit) s = kTopkMaxSplit;
-  if (s < 1) s = 1;
-  return (int)s;
-}
 
 // Everything up to the launch, whatever the table's type.  *go = there is something to launch (M > 0).
 int multi_args(const char* who, TopkMultiArgs* a, bool* go, const float* q, int64_t ldq, int I, const float* qbias,
@@ -75,7 +54,7 @@ int launch(const TopkMultiArgs& a, int vec, const char* who, hipStream_t st) {
   const int64_t nrt = ((int64_t)s.M + s.RB - 1) / s.RB;
   hipLaunchKernelGGL(topk_multi_scan_kernel<P>, dim3((unsigned)nrt, s.nlist), dim3(RH_BLOCK), multi_lds_bytes<P>(s.RB, s.K),
                      st, a, vec);
-  hipLaunchKernelGGL(topk_multi_merge_kernel, dim3((unsigned)s.M), dim3(RH_WAVE), 0, st, s);
+  hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)s.M), dim3(RH_WAVE), 0, st, s);
   return 0;
 }
 
@@ -92,7 +71,7 @@ extern "C" int rh_topk_multi_plan(int M, int I, int V, int K, int* nsplit, int64
   RH_REQUIRE(M >= 0 && V >= 1, RH_E_BADARG, "rh_topk_multi_plan: M=%d V=%d (M >= 0, V >= 1)", M, V);
   RH_REQUIRE(K >= 1 && K <= kTopkMaxK && I >= 1 && I <= kMultiMaxI, RH_E_UNSUPPORTED,
              "rh_topk_multi_plan: K=%d I=%d unsupported (1 <= K <= %d, 1 <= I <= %d)", K, I, kTopkMaxK, kMultiMaxI);
-  *nsplit = multi_default_split(M, I, V, K);
+  *nsplit = topk_default_split(M, V, topk_multi_users(I, K));
   *workspace_bytes = (int64_t)M * *nsplit * K * 8;
   return 0;
 }
@@ -124,9 +103,7 @@ extern "C" int rh_topk_multi_half_fwd(const float* q, int64_t ldq, int I, const 
     return rc;
   if (!go) return 0;
   const TopkScanArgs& s = a.f.s;
-  const bool xvec = s.D % 8 == 0 && reinterpret_cast<uintptr_t>(s.x) % 16 == 0;
-  const bool qvec = s.ldq % 4 == 0 && reinterpret_cast<uintptr_t>(s.q) % 16 == 0;
-  const int vec = (xvec ? 1 : 0) | (qvec ? 2 : 0);
+  const int vec = vec_flags(s);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (int rc = is_bf16 == 0 ? launch<MultiTileHalf<TableF16>>(a, vec, "rh_topk_multi_half_fwd", st)
                             : launch<MultiTileHalf<TableBf16>>(a, vec, "rh_topk_multi_half_fwd", st))

@@ -63,8 +63,6 @@ __global__ __launch_bounds__(RH_BLOCK) void quantize_rows_q8_kernel(const float*
   }
 }
 
-size_t ivf_q8_lds_bytes(int K) { return topk_half_lds_bytes(K) + (size_t)kT * 4; }
-
 template <bool kOneChunk>
 __global__ __launch_bounds__(RH_BLOCK) void topk_q8_scan_kernel(const TopkArgs a, const Q8Scales sc, int xvec) {
   extern __shared__ __align__(16) float lds[];
@@ -81,14 +79,6 @@ __global__ __launch_bounds__(RH_BLOCK) void ivf_q8_scan_kernel(const IvfArgs a, 
   int64_t lo, hi;
   if (!ivf_tile(a, prs, lo, hi)) return;
   topk_q8_scan_tiles<kOneChunk>(s, sc, IvfRule{prs, a.row_id, s.nlist, s.K}, lo, hi, lds, xvec != 0);
-}
-
-// one wavefront per query row: its s.nlist lists (ranges or slots) into ids / scores
-__global__ __launch_bounds__(RH_WAVE) void topk_q8_merge_kernel(const TopkScanArgs s) {
-  __shared__ int hp[kTopkMaxSplit];
-  const int64_t row = blockIdx.x;
-  topk_merge_row(s.part_s + row * s.nlist * s.K, s.part_i + row * s.nlist * s.K, s.nlist, s.K, s.ids + row * s.K,
-                 s.scores + row * s.K, hp, threadIdx.x);
 }
 
 bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
@@ -118,8 +108,8 @@ int launch_flat(const TopkArgs& a, const Q8Scales& sc, hipStream_t st) {
 template <bool kOneChunk>
 int launch_ivf(const IvfArgs& a, const Q8Scales& sc, int64_t grid, hipStream_t st) {
   static RhLdsReserved reserved;
-  if (int rc = rh_reserve_lds(reserved, ivf_q8_scan_kernel<kOneChunk>, ivf_q8_lds_bytes(128), "rh_ivf_scan_q8")) return rc;
-  hipLaunchKernelGGL(ivf_q8_scan_kernel<kOneChunk>, dim3((unsigned)grid), dim3(RH_BLOCK), ivf_q8_lds_bytes(a.s.K), st, a, sc,
+  if (int rc = rh_reserve_lds(reserved, ivf_q8_scan_kernel<kOneChunk>, ivf_half_lds_bytes(128), "rh_ivf_scan_q8")) return rc;
+  hipLaunchKernelGGL(ivf_q8_scan_kernel<kOneChunk>, dim3((unsigned)grid), dim3(RH_BLOCK), ivf_half_lds_bytes(a.s.K), st, a, sc,
                      xvec_flag(a.s));
   return 0;
 }
@@ -160,7 +150,7 @@ extern "C" int rh_topk_q8_fwd(const int8_t* qc, int64_t ldqc, const float* qs, c
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const Q8Scales sc{qs, xs};
   if (int rc = D <= kQ8Chunk ? launch_flat<true>(a, sc, st) : launch_flat<false>(a, sc, st)) return rc;
-  hipLaunchKernelGGL(topk_q8_merge_kernel, dim3((unsigned)M), dim3(RH_WAVE), 0, st, a.s);
+  hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)M), dim3(RH_WAVE), 0, st, a.s);
   RH_LAUNCH_CHECK("rh_topk_q8_fwd");
   return 0;
 }
@@ -182,7 +172,7 @@ extern "C" int rh_ivf_scan_q8(const int8_t* qc, int64_t ldqc, const float* qs, c
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const Q8Scales sc{qs, xs_s};
   if (int rc = D <= kQ8Chunk ? launch_ivf<true>(a, sc, grid, st) : launch_ivf<false>(a, sc, grid, st)) return rc;
-  hipLaunchKernelGGL(topk_q8_merge_kernel, dim3((unsigned)M), dim3(RH_WAVE), 0, st, a.s);
+  hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)M), dim3(RH_WAVE), 0, st, a.s);
   RH_LAUNCH_CHECK("rh_ivf_scan_q8");
   return 0;
 }
