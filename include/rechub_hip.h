@@ -1053,6 +1053,18 @@ int rh_softmax_attn_bwd(const float* q, const float* k, const float* v, int64_t 
                         const float* bias, int N, int nb, float scale, float p_drop, const int64_t* rng,
                         const int64_t* saved_ctr, const float* out, const float* lse, const float* g_out, float* delta,
                         float* g_q, float* g_k, float* g_v, int64_t ldg, float* part, float* g_bias, void* stream);
+/* The same attention on fp16 (is_bf16 = 0) or bf16 (is_bf16 = 1) operands (csrc/softmax_attn_half_tile.h): q, k, v, out,
+ * g_out, g_q, g_k, g_v hold that type (ld, ldg in elements), the products run on the half-precision MFMA with f32 sums;
+ * bias, lse, delta, part and g_bias stay float, and the weights and dS are rounded to the type where they enter a product.
+ * The dropout mask of a (seed, counter) is the float kernels'.  Same limits, refusals and part size as above; 16-byte loads
+ * where dh % 8 == 0 and the bases and strides are 16-byte aligned, single elements otherwise. */
+int rh_softmax_attn_half_fwd(const void* q, const void* k, const void* v, int is_bf16, int64_t ld, int B, int L, int H, int dh,
+                             const float* bias, int N, int nb, float scale, float p_drop, int64_t* rng, int64_t* saved_ctr,
+                             void* out, float* lse, void* stream);
+int rh_softmax_attn_half_bwd(const void* q, const void* k, const void* v, int is_bf16, int64_t ld, int B, int L, int H, int dh,
+                             const float* bias, int N, int nb, float scale, float p_drop, const int64_t* rng,
+                             const int64_t* saved_ctr, const void* out, const float* lse, const void* g_out, float* delta,
+                             void* g_q, void* g_k, void* g_v, int64_t ldg, float* part, float* g_bias, void* stream);
 
 /* Full-catalogue cross entropy (csrc/stream_ce.hip: the same head, every column and row counted, no bias / temperature):
  * u (B, D), E (V, D), labels (B,) int64 in [0, V).  loss (1,) = mean over rows of lse(u E^T) - (u E^T)[label].

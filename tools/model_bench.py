@@ -549,8 +549,9 @@ HLLM = {"hllm": dict(B=64, L=200, V=3707, d_model=512, n_heads=8, n_layers=2),
         "hllm_large": dict(B=64, L=200, V=100000, d_model=2048, n_heads=16, n_layers=2)}
 
 
-def hllm_bench(name, dev, steps):
-    """ms/step of the HIP SeqTrainer step of HLLMModel and of a plain-PyTorch eager restatement of the reference's step."""
+def hllm_bench(name, dev, steps, attn_dtype=None):
+    """ms/step of the HIP SeqTrainer step of HLLMModel (``attn_dtype``: its attention in float16 / bfloat16) and of a
+    plain-PyTorch float32 eager restatement of the reference's step."""
     import re
 
     import torch.nn.functional as F
@@ -562,7 +563,8 @@ def hllm_bench(name, dev, steps):
     B, L, V = cfg.pop("B"), cfg.pop("L"), cfg.pop("V")
     torch.manual_seed(0)
     g = torch.Generator().manual_seed(0)
-    model = HLLMModel(torch.randn(V, cfg["d_model"], generator=g), V, max_seq_len=L, dropout=0.1, **cfg)
+    model = HLLMModel(torch.randn(V, cfg["d_model"], generator=g), V, max_seq_len=L, dropout=0.1,
+                      attn_dtype=attn_dtype, **cfg)
     trainer = SeqTrainer(model, device=str(dev), loss_type="nce", loss_params={"temperature": 1.0, "ignore_index": 0})
     model.train()
     lens = torch.randint(L // 4, L + 1, (B,), generator=g)
@@ -635,8 +637,8 @@ def hllm_bench(name, dev, steps):
         eager = float("nan")
         print(f"  [{name}] eager restatement does not fit")
     mem_eager = torch.cuda.max_memory_allocated() / 2**30
-    print(f"{name:10s} B={B} L={L} V={V}  HIP {hip:8.3f} ms/step (peak {mem_hip:.2f} GiB)   plain PyTorch eager "
-          f"{eager:8.3f} ms/step (peak {mem_eager:.2f} GiB)   speedup {eager / hip:.2f}x", flush=True)
+    print(f"{name:10s} B={B} L={L} V={V} attention {attn_dtype or torch.float32}  HIP {hip:8.3f} ms/step "
+          f"(peak {mem_hip:.2f} GiB)   plain PyTorch eager {eager:8.3f} ms/step (peak {mem_eager:.2f} GiB)   speedup {eager / hip:.2f}x", flush=True)
     for k, (us, n) in sorted(kernels.items(), key=lambda kv: -kv[1][0]):
         print(f"    {k:32s} {us:10.1f} us per step ({n} launches)", flush=True)
     print(f"    {'(all device work of the HIP step)':32s} {hip_total:10.1f} us per step", flush=True)
@@ -652,6 +654,8 @@ def main():
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--scale", type=float, default=1.0, help="vocabulary scale")
+    ap.add_argument("--attn-dtype", choices=["float32", "float16", "bfloat16"], default="float32",
+                    help="hllm / hllm_large: the type the attention kernel runs in")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     for name in a.models.split(","):
@@ -665,7 +669,7 @@ def main():
             torch.cuda.reset_peak_memory_stats()
             continue
         if name in HLLM:
-            hllm_bench(name, dev, a.steps)
+            hllm_bench(name, dev, a.steps, None if a.attn_dtype == "float32" else getattr(torch, a.attn_dtype))
             torch.cuda.reset_peak_memory_stats()
             continue
         trainer, x, y = build(name, dev, a.batch, a.scale)

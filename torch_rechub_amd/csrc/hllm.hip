@@ -11,7 +11,10 @@
 // length, the key tiles up to the diagonal and the query tiles from it down, the scale, the linear buckets evaluated in
 // place, diagonals indexed i - j -- and the entry points with their checks and launches.  No mask test, no key-tile scan
 // and no LDS beyond the tiles: the rule's Lds is empty.
-#include "softmax_attn_tile.h"
+//
+// fp16 / bf16 operands (rh_softmax_attn_half_*): the same rule on the tile body of softmax_attn_half_tile.h, whose products
+// run on the half-precision MFMA; scores, statistics and the bias table's gradient stay f32 (the numerics are stated there).
+#include "softmax_attn_half_tile.h"
 
 namespace {
 
@@ -116,5 +119,89 @@ extern "C" int rh_softmax_attn_bwd(const float* q, const float* k, const float* 
                        nqt);
   }
   RH_LAUNCH_CHECK("rh_softmax_attn_bwd");
+  return 0;
+}
+
+// ---- fp16 / bf16 operands ---------------------------------------------------------------------------------------------------
+namespace {
+
+const float* as_f(const void* p) { return static_cast<const float*>(p); }  // AttnArgs' element pointers carry T here
+float* as_f(void* p) { return static_cast<float*>(p); }
+
+template <class T>
+void half_fwd_launch(const AttnArgs& a, int vec, int nqt, hipStream_t st) {
+  hipLaunchKernelGGL((softmax_attn_half_fwd_kernel<T, HllmRule>), dim3(a.B * a.H, nqt), dim3(RH_BLOCK), 0, st, a, vec);
+}
+
+template <class T>
+void half_bwd_launch(const AttnArgs& a, int vec, int nqt, hipStream_t st) {
+  const int64_t n = (int64_t)a.B * a.H * a.Lq;
+  int grid = (int)((n + RH_BLOCK - 1) / RH_BLOCK);
+  if (grid > 4096) grid = 4096;
+  hipLaunchKernelGGL(softmax_attn_half_delta_kernel<T>, dim3(grid), dim3(RH_BLOCK), 0, st, a, vec);
+  hipLaunchKernelGGL((softmax_attn_half_dkv_kernel<T, HllmRule>), dim3(a.B * a.H, nqt), dim3(RH_BLOCK), 0, st, a, vec);
+  hipLaunchKernelGGL((softmax_attn_half_dq_kernel<T, HllmRule>), dim3(a.B * a.H, nqt), dim3(RH_BLOCK), 0, st, a, vec);
+}
+
+// bit 0: 16-byte loads of q, k, v; bit 1: of out / g_out (row stride H dh)
+int half_vec(const AttnArgs& a, const void* g_out, const void* out) {
+  const bool qkv = half_rows_vec(a.q, a.ldq, a.dh) && half_rows_vec(a.k, a.ldkv, a.dh) && half_rows_vec(a.v, a.ldkv, a.dh);
+  const int64_t ldo = (int64_t)a.H * a.dh;
+  return (qkv ? 1 : 0) | (half_rows_vec(g_out, ldo, a.dh) && half_rows_vec(out, ldo, a.dh) ? 2 : 0);
+}
+
+}  // namespace
+
+extern "C" int rh_softmax_attn_half_fwd(const void* q, const void* k, const void* v, int is_bf16, int64_t ld, int B, int L,
+                                        int H, int dh, const float* bias, int N, int nb, float scale, float p_drop,
+                                        int64_t* rng, int64_t* saved_ctr, void* out, float* lse, void* stream) {
+  RH_REQUIRE(is_bf16 == 0 || is_bf16 == 1, RH_E_UNSUPPORTED,
+             "rh_softmax_attn_half_fwd: is_bf16=%d is neither 0 (fp16) nor 1 (bf16)", is_bf16);
+  AttnArgs a = sattn_args(as_f(q), as_f(k), as_f(v), ld, B, L, H, dh, bias, N, nb, scale, p_drop, rng, saved_ctr, as_f(out), lse);
+  a.fwd = 1;
+  if (int rc = sattn_check("rh_softmax_attn_half_fwd", a)) return rc;
+  RH_REQUIRE(out && lse, RH_E_BADARG, "rh_softmax_attn_half_fwd: null output");
+  if (B == 0) return 0;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int nqt = (L + kT - 1) / kT, vec = half_vec(a, nullptr, nullptr);
+  if (is_bf16)
+    half_fwd_launch<TableBf16>(a, vec, nqt, st);
+  else
+    half_fwd_launch<TableF16>(a, vec, nqt, st);
+  if (p_drop > 0.f) hipLaunchKernelGGL(drop_advance_kernel, dim3(1), dim3(1), 0, st, rng);
+  RH_LAUNCH_CHECK("rh_softmax_attn_half_fwd");
+  return 0;
+}
+
+extern "C" int rh_softmax_attn_half_bwd(const void* q, const void* k, const void* v, int is_bf16, int64_t ld, int B, int L,
+                                        int H, int dh, const float* bias, int N, int nb, float scale, float p_drop,
+                                        const int64_t* rng, const int64_t* saved_ctr, const void* out, const float* lse,
+                                        const void* g_out, float* delta, void* g_q, void* g_k, void* g_v, int64_t ldg,
+                                        float* part, float* g_bias, void* stream) {
+  RH_REQUIRE(is_bf16 == 0 || is_bf16 == 1, RH_E_UNSUPPORTED,
+             "rh_softmax_attn_half_bwd: is_bf16=%d is neither 0 (fp16) nor 1 (bf16)", is_bf16);
+  AttnArgs a = sattn_args(as_f(q), as_f(k), as_f(v), ld, B, L, H, dh, bias, N, nb, scale, p_drop, rng, saved_ctr, as_f(out), lse);
+  attn_bwd_args(a, as_f(g_out), delta, as_f(g_q), ldg, as_f(g_k), as_f(g_v), ldg, part, g_bias);
+  if (int rc = sattn_check("rh_softmax_attn_half_bwd", a)) return rc;
+  RH_REQUIRE(out && lse && g_out && delta && g_q && g_k && g_v && (!bias || (part && g_bias)), RH_E_BADARG,
+             "rh_softmax_attn_half_bwd: null pointer");
+  RH_REQUIRE(ldg >= (int64_t)H * dh, RH_E_BADARG, "rh_softmax_attn_half_bwd: gradient row stride %lld too small",
+             (long long)ldg);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int nqt = (L + kT - 1) / kT;
+  if (B > 0) {
+    const int vec = half_vec(a, g_out, out);
+    if (is_bf16)
+      half_bwd_launch<TableBf16>(a, vec, nqt, st);
+    else
+      half_bwd_launch<TableF16>(a, vec, nqt, st);
+  }
+  if (bias) {
+    const int64_t n1 = (int64_t)H * L, n2 = (int64_t)nb * H;
+    hipLaunchKernelGGL(softmax_attn_diag_kernel, dim3((int)((n1 + RH_BLOCK - 1) / RH_BLOCK)), dim3(RH_BLOCK), 0, st, a, nqt);
+    hipLaunchKernelGGL(softmax_attn_bias_kernel<HllmRule>, dim3((int)((n2 + RH_BLOCK - 1) / RH_BLOCK)), dim3(RH_BLOCK), 0, st, a,
+                       nqt);
+  }
+  RH_LAUNCH_CHECK("rh_softmax_attn_half_bwd");
   return 0;
 }

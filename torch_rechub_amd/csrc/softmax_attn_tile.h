@@ -43,6 +43,10 @@ constexpr int kMaxDh = RH_ATTN_MAX_DH;
 constexpr int kNC = kMaxDh / kT;  // column chunks of a head
 constexpr int kMaxL = RH_ATTN_MAX_L;
 
+// The element pointers q, k, v, out, g_out, g_q, g_k, g_v are typed float for the f32 body of this file.  The half body
+// (softmax_attn_half_tile.h) fills the SAME fields with pointers to fp16 / bf16 elements and casts them back; the strides
+// count elements either way.  A rule therefore never dereferences them: it reads lengths, strides, mask, bias, bucket,
+// scale and the dropout state only, which are the same in every element type.
 struct AttnArgs {
   const float* q;         // (B, Lq, H, dh) view, row stride ldq
   int64_t ldq;

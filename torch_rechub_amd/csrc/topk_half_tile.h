@@ -25,11 +25,8 @@
 //   25 856 B of staging against the f32 scan's 33 280: the workgroups-per-CU bands of the f32 scan hold or improve.
 #pragma once
 
+#include "half_mfma.h"
 #include "topk_list.h"
-
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-typedef _Float16 v8h __attribute__((ext_vector_type(8)));
-typedef __bf16 v8b __attribute__((ext_vector_type(8)));
 
 constexpr int kHLdB = (kT + 8) * 2;                   // bytes of one row of an item buffer
 constexpr int kHBuf = kT * kHLdB;                     // one item buffer
@@ -51,24 +48,7 @@ inline int vec_flags(const TopkScanArgs& s) {
   return (xvec ? 1 : 0) | (qvec ? 2 : 0);
 }
 
-// the two table types: the bits of T(f), round to nearest even (NaN is out of scope), and the MFMA over 16 k
-struct TableF16 {
-  static __device__ __forceinline__ uint32_t round(float f) {
-    return __builtin_bit_cast(uint16_t, static_cast<_Float16>(f));
-  }
-  static __device__ __forceinline__ v16f mfma(v4u a, v4u b, v16f c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(v8h, a), __builtin_bit_cast(v8h, b), c, 0, 0, 0);
-  }
-};
-struct TableBf16 {
-  static __device__ __forceinline__ uint32_t round(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-  }
-  static __device__ __forceinline__ v16f mfma(v4u a, v4u b, v16f c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(v8b, a), __builtin_bit_cast(v8b, b), c, 0, 0, 0);
-  }
-};
+// the two table types, TableF16 and TableBf16, are half_mfma.h's
 
 // q[row][k .. k + 8) rounded to T, zero from D on (row = null: a tile row without a query); vec: 16-byte loads are legal
 template <typename T>

@@ -20,10 +20,17 @@ from ...utils.hstu_utils import RelPosBias
 
 
 class HLLMTransformerBlock(nn.Module):
-    """One pre-norm block: x + dropout(W_O attention(LN(x))), then x + FFN(LN(x)) (reference hllm.py:12-101)."""
+    """One pre-norm block: x + dropout(W_O attention(LN(x))), then x + FFN(LN(x)) (reference hllm.py:12-101).
 
-    def __init__(self, d_model=512, n_heads=8, dropout=0.1):
+    ``attn_dtype`` (not in the reference): None runs the attention in float32; torch.float16 / torch.bfloat16 casts the
+    three projections to that type, runs the half-precision attention kernel and casts its result back to float32 before
+    W_O.  Parameters and state_dict keys do not depend on it."""
+
+    def __init__(self, d_model=512, n_heads=8, dropout=0.1, attn_dtype=None):
         super().__init__()
+        if attn_dtype not in (None, torch.float16, torch.bfloat16):
+            raise ValueError(f"attn_dtype={attn_dtype} unsupported (None, torch.float16 or torch.bfloat16)")
+        self.attn_dtype = attn_dtype
         self.d_model = d_model
         self.n_heads = n_heads
         assert d_model % n_heads == 0, "d_model must be divisible by n_heads"
@@ -53,9 +60,12 @@ class HLLMTransformerBlock(nn.Module):
                 raise ValueError(f"seq_len ({x.shape[1]}) exceeds max_seq_len ({max_len}).")
         p = self.dropout.p
         h = self.norm1(x)
-        attn = ops.softmax_attention(self.W_Q(h), self.W_K(h), self.W_V(h), self.n_heads, max_len, bias_table=table,
-                                     dropout_p=p, training=self.training, scale=self.scale)
-        x = x + ops.dropout(self.W_O(attn), p, self.training)
+        q, k, v = self.W_Q(h), self.W_K(h), self.W_V(h)
+        if self.attn_dtype is not None:
+            q, k, v = q.to(self.attn_dtype), k.to(self.attn_dtype), v.to(self.attn_dtype)
+        attn = ops.softmax_attention(q, k, v, self.n_heads, max_len, bias_table=table, dropout_p=p, training=self.training,
+                                     scale=self.scale)
+        x = x + ops.dropout(self.W_O(attn.float()), p, self.training)
         h = self.norm2(x)
         h = ops.dropout(F.relu(self.ffn[0](h)), self.ffn[2].p, self.training)
         return x + ops.dropout(self.ffn[3](h), self.ffn[4].p, self.training)
@@ -65,7 +75,7 @@ class HLLMModel(nn.Module):
 
     def __init__(self, item_embeddings, vocab_size, d_model=512, n_heads=8, n_layers=4, max_seq_len=256, dropout=0.1,
                  use_rel_pos_bias=True, use_time_embedding=True, num_time_buckets=2048, time_bucket_fn='sqrt',
-                 temperature=0.07):
+                 temperature=0.07, attn_dtype=None):
         super().__init__()
         self.vocab_size = vocab_size
         self.d_model = d_model
@@ -91,7 +101,8 @@ class HLLMModel(nn.Module):
         if use_time_embedding:
             self.time_embedding = nn.Embedding(num_time_buckets + 1, d_model, padding_idx=0)
         self.transformer_blocks = nn.ModuleList(
-            [HLLMTransformerBlock(d_model=d_model, n_heads=n_heads, dropout=dropout) for _ in range(n_layers)])
+            [HLLMTransformerBlock(d_model=d_model, n_heads=n_heads, dropout=dropout, attn_dtype=attn_dtype)
+             for _ in range(n_layers)])
         self.use_rel_pos_bias = use_rel_pos_bias
         if use_rel_pos_bias:
             self.rel_pos_bias = RelPosBias(n_heads, max_seq_len)
